@@ -8,7 +8,7 @@ runtime-specialised quad kernel `okx_quad_solve_u`).  Every
 independent COLD START FROM THE DESIGN STATE — SURVEY.md section 8(d)'s start rule, the reference's own
 (`core/solver.py:710`) — and that launch is what `value`, `roofline` and `compute` describe.
 
-The same JSON line also carries, each measured in this run:
+A plain run measures that and nothing else.  With --full the same JSON line also carries, each measured in this run:
   own_first_pass the same launch with shared_first_step=0 (every problem evaluates the design state itself)
   pipelined      the same cold sweeps round-robin over three streams (throughput of independent sweeps)
   with_model     the same sweep with chain heads started from the fitted Chebyshev model (okx_program_fit_predictor),
@@ -19,12 +19,17 @@ The same JSON line also carries, each measured in this run:
   other_configs  BASELINE configs 3, 4, 5 at full size: cold independent solves and the product's chained mode
   downstream     tangents and the metric catalog on the solved states
   dropin         wall-clock of the drop-in `solve_sweep` on the reference's own benchmark workloads
+  sustained      the same launch 2000 times back to back on one stream
+  c5_sharded     BASELINE config 5 through the sharded pipeline of the same process group
+
+--dump-outputs DIR writes what the last timed step computed (records and info fields, float64) as DIR/<name>.npy.
 
 With N > 1 ranks the global sweep (N x 16384 steps) is sharded by index and the solved free coordinates are
 all-gathered over RCCL inside the timed step (`value` is exchange-inclusive; `solve_only` is reported beside it).
 `--config c5` runs BASELINE config 5 instead (4096 perturbed geometries x 256 steps, geometry-major shards).
 
   python bench.py --gpus 1 --steps 200 --warmup 10
+  python bench.py --gpus 1 --steps 200 --warmup 10 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
          --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
 """
@@ -109,6 +114,40 @@ def committed_traffic(tag: str) -> tuple:
         return float(summary["traffic_bytes_per_launch"]), os.path.relpath(path, REPO)
     except (OSError, KeyError, ValueError):
         return None, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """
+    ``--dump-outputs``: write ``name -> array / tensor`` (every one with the same leading row count) as ``directory/<name>.npy``
+    in float64.  Over ``DUMP_LIMIT_BYTES`` in all, the same fixed, seeded sample of rows is taken from every output and the
+    sorted row indices are written as ``rows.npy``; the inputs of a run are fixed by its arguments, so two builds give files
+    that compare output for output.
+    """
+    host = {name: (value.detach().cpu().numpy() if hasattr(value, "detach") else np.asarray(value)).astype(np.float64)
+            for name, value in outputs.items()}
+    n = {len(a) for a in host.values()}
+    if len(n) != 1:
+        raise ValueError(f"outputs to dump differ in their row count: { {k: a.shape for k, a in host.items()} }")
+    n = n.pop()
+    row_bytes = sum(a[:1].nbytes for a in host.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        # (8 B per kept row: its index in rows.npy; 4 KB for the .npy headers)
+        keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+def info_outputs(info_tensor) -> dict:
+    """The fields of the 40-byte info records a caller receives, one array per field (``info_<field>``)."""
+    host = info_tensor.cpu().numpy().view(INFO_FIELDS).reshape(-1)
+    return {f"info_{field}": host[field] for field in INFO_FIELDS.names if field != "reserved"}
 
 
 def time_launches(launch, steps: int, warmup: int, device) -> tuple:
@@ -842,6 +881,12 @@ def main() -> None:
                     help="one GPU: submit the K timed steps as K stream launches instead of ONE HIP graph of K kernel nodes "
                          "(measured on a quiet host: 16.09 against 16.30 us per step at K = 2000, no difference at K = 20; the graph "
                          "keeps 0.3 ms of GPU work independent of the host's launch loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (sustained, c5_sharded, one_shot, own_first_pass, pipelined, "
+                         "with_model, e2e, downstream, other_configs, dropin, cpu_baseline); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; outputs "
+                         "over 64 MB in all as a fixed, seeded sample of their rows, the row indices in DIR/rows.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5-sharded", action="store_true",
                     help="leave out the c5_sharded leg (BASELINE config 5 through dist.ShardedEnsemble in this process group)")
@@ -1124,11 +1169,15 @@ def run_c2(args, world: int, rank: int, device) -> dict:
         records = dp.solve(targets, **cold_kw).positions
         if not torch.equal(gathered, records):
             raise SystemExit("rccl-world-one: the gathered and re-expanded positions differ from the solver's own records")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records (with an exchange: the gathered block, every rank's solves) and this rank's info records
+        positions = pipe.drain() if pipe.exchange else pipe.solve_buffers[(args.steps - 1) % len(launches)]
+        dump_outputs(args.dump_outputs, {"positions": positions} if pipe.exchange else {"positions": positions, **info_outputs(info)})
     nfev_mean, ok = info_summary(info)
     # BASELINE config 5 through the sharded pipeline, in this process group (every rank takes part): the workload of north_star
     # that is "sharded across 8 x MI355X" rides in the default line at every N, beside the xGMI-bound per-step gather of C2
     c5_sharded = None
-    if not args.no_c5_sharded and not args.rccl_world_one:
+    if args.full and not args.no_c5_sharded and not args.rccl_world_one:
         # (under a deadline when ranks exchange: the headline above is measured; a point-to-point exchange that never
         #  completes on some node must cost this leg, not the line - main() then leaves without another collective)
         c5_sharded, timed_out = _with_deadline(lambda: measure_c5_sharded(world, rank, device), C5_LEG_DEADLINE_S if world > 1 else None, device)
@@ -1238,12 +1287,12 @@ def run_c2(args, world: int, rank: int, device) -> dict:
         }
         line["exchange"] = {"bytes_sent_per_rank_per_step": free_bytes, "bytes_received_per_rank_per_step": (world - 1) * free_bytes,
                             "collective": "all_gather_into_tensor (RCCL)" if not args.rehearse_on_one_gpu else "gloo (rehearsal)"}
-    if world == 1 and not args.rccl_world_one:
+    if args.full and world == 1 and not args.rccl_world_one:
         # Sustained figure: a few thousand back-to-back launches (the 20-step driver run times 0.6 ms of GPU work).
         sus_wall, sus_ms = time_launches(launches[0], 2000, 10, device)
         line["sustained"] = {"value": (hi - lo) / sus_wall, "kernel_ms": sus_ms, "launches": 2000,
                              "note": "the same launch 2000 times back to back on one stream, one HIP-event pair around them"}
-    if world == 1 and not args.no_extras and not args.rccl_world_one:
+    if args.full and world == 1 and not args.no_extras and not args.rccl_world_one:
         line["one_shot"] = measure_one_shot(program, targets, device, kernel_ms)
         extra_steps = max(5, min(args.steps, 50))
         own = dp.plan(targets, out=pipe.solve_buffers[0], info_out=info, chain_len=args.chain_len, predictor=False, shared_first_step=False)
@@ -1274,7 +1323,7 @@ def run_c2(args, world: int, rank: int, device) -> dict:
                            lambda: ensemble_problem(4096, 256), device, 20, 3, roles_geometry=geometry_path("geometry.yaml")),
         ]
         line["dropin"] = measure_dropin(device)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(STEPS_PER_RANK)
     # the figures a reader of the line's first 2000 characters should not miss, right behind the contract's own fields:
     # what the same launch gives without the amortised design-state pass, a fresh program's first launch, the evaluated rates
@@ -1483,11 +1532,13 @@ def run_c5(args, world: int, rank: int, device) -> dict:
                                info=args.c5_info, metric_columns=metric_columns,
                                chain_len=args.chain_len if args.chain_len != -1 else 1, predictor=False)
 
+    last = {}
+
     def step(k, start, end):
         if start is not None:
             start.record()
         if pipe is not None:
-            pipe.step()
+            last["out"] = pipe.step()
         else:
             launch()
         if end is not None:
@@ -1495,6 +1546,13 @@ def run_c5(args, world: int, rank: int, device) -> dict:
 
     elapsed, step_ms = timed_region(step, lambda: None, args.steps, args.warmup, world, device, per_launch_events=True)
     kernel_ms = step_ms
+    if args.dump_outputs and rank == 0:
+        if pipe is None:
+            dump_outputs(args.dump_outputs, {"positions": out, **info_outputs(info)})
+        else:   # what the pipeline's step returns (all ranks' rows) and the gathered info records or status bytes
+            name = "metric_columns" if metric_columns else "positions" if pipe.records else "free"
+            status = {"info_status": pipe.status_full} if pipe.status_only else info_outputs(pipe.info_full)
+            dump_outputs(args.dump_outputs, {name: last["out"], **status})
     if pipe is not None:  # the solve alone, for `solve_only`: the whole shard as one launch, outside the timed region
         if metric_columns:  # (the evaluated solve of the shard, no positions written)
             evb = torch.empty((n_local, 1 + program.n_targets, 24), dtype=torch.float64, device=device)

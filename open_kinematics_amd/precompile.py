@@ -57,8 +57,56 @@ def precompile_suspension(suspension, sweeps) -> list:
     return done
 
 
+def precompile_job(job) -> tuple:
+    """
+    One program of ``__graft_entry__.precompile_baseline_kernels`` (run in a worker process): ``(program arrays, line mode,
+    metric roles as bytes or None)`` -> ``(status, error text)``.
+    """
+    from . import _lib
+    from ._abi import HostProgram
+    from .metrics import AxleRoles, CornerRoles
+    from .program import ConstraintProgram
+
+    arrays, line_mode, roles = job
+    program = ConstraintProgram.from_arrays(arrays)
+    if program.line_mode != line_mode:
+        program = program.with_line_mode(line_mode)
+    host = HostProgram(program)
+    rc = _lib.load().okx_precompile(host.byref())
+    if rc == 0 and roles is not None:  # (after the plain modules: the evaluated lane module takes the plain one's arithmetic)
+        if len(roles) == C.sizeof(AxleRoles):
+            rc = _lib.load().okx_precompile_axle_evaluation(host.byref(), C.byref(AxleRoles.from_buffer_copy(roles)))
+            if rc == -2:
+                rc = 0  # (a program without a pair-mode kernel: its axle evaluates in separate launches)
+        else:
+            rc = _lib.load().okx_precompile_evaluation(host.byref(), C.byref(CornerRoles.from_buffer_copy(roles)))
+    return rc, (_lib.last_error() if rc else "")
+
+
+def _serve_jobs(path: str) -> int:
+    """``--jobs FILE``: a worker of ``__graft_entry__.build()``.  Reads job indices from stdin, one per line, compiles that job
+    of the pickled list and answers ``[index, status, error text]`` as one JSON line (anything else the compilers print goes
+    to stderr), until stdin closes."""
+    import json
+    import os
+    import pickle
+
+    with open(path, "rb") as fh:
+        jobs = pickle.load(fh)
+    answers = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    for line in iter(sys.stdin.readline, ""):
+        index = int(line)
+        rc, message = precompile_job(jobs[index])
+        answers.write(json.dumps([index, rc, message]) + "\n")
+        answers.flush()
+    return 0
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
+    if len(argv) == 2 and argv[0] == "--jobs":
+        return _serve_jobs(argv[1])
     if len(argv) < 2 or argv[0] in ("-h", "--help"):
         print(__doc__.strip())
         return 0 if argv and argv[0] in ("-h", "--help") else 2

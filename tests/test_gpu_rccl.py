@@ -45,7 +45,7 @@ def test_two_rank_bench_rehearsal_on_one_gpu():
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "10",
-                           "--warmup", "3", "--preheat-ms", "2", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True,
+                           "--warmup", "3", "--preheat-ms", "2", "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True,
                           text=True, timeout=600)
     assert proc.returncode == 0, (proc.stdout + proc.stderr)[-3000:]
     line = [json.loads(l) for l in proc.stdout.splitlines() if l.startswith("{")][-1]
@@ -92,7 +92,7 @@ def test_two_rank_c5_pipeline_rehearsal_on_one_gpu():
 
 
 def test_one_gpu_bench_line_keeps_the_contract():
-    """`python bench.py --steps 20 --warmup 5` as the driver runs it: one JSON line with the contract's fields, the roofline
+    """`python bench.py --steps 20 --warmup 5 --full`: one JSON line with the contract's fields, the roofline
     and cpu_baseline objects, the K timed steps as one HIP graph submitted through the HIP runtime directly - and the same
     through torch's own calls (--torch-submit)."""
     if not gpu_available():
@@ -101,7 +101,7 @@ def test_one_gpu_bench_line_keeps_the_contract():
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(key, None)
     for extra in ([], ["--torch-submit", "--no-cpu-baseline"]):
-        proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras"] + extra,
+        proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extras"] + extra,
                               env=env, capture_output=True, text=True, timeout=900)
         assert proc.returncode == 0, (proc.stdout + proc.stderr)[-3000:]
         lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
@@ -132,3 +132,34 @@ def test_one_gpu_bench_line_keeps_the_contract():
                 assert leg["all_converged"] and leg["value"] > 1e8 and leg["bytes_per_rank"] == 0 and leg["exchange_ms"] == 0.0
             assert list(line)[-1] == "summary" and line["summary"]["roofline"]["frac"] == roof["frac"]
             assert line["summary"]["cpu_baseline"]["value"] == base["value"]
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the contract's fields, K timed steps and no other
+    leg; DIR holds the last timed step's records and info fields, whose positions match the CPU oracle."""
+    if not gpu_available():
+        pytest.skip("no GPU")
+    import numpy as np
+
+    from open_kinematics_amd.workloads import bump_sweep_problem
+    from oracle.oracle import Oracle
+
+    env = dict(os.environ)
+    for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(key, None)
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                           "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, (proc.stdout + proc.stderr)[-3000:]
+    lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert abs(line["value"] - 16384 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert not {"sustained", "cpu_baseline", "c5_sharded", "one_shot", "other_configs", "dropin"} & set(line)
+    program, targets = bump_sweep_problem(16384)
+    pos = np.load(tmp_path / "positions.npy")
+    assert pos.dtype == np.float64 and pos.shape == (16384, program.n_out, 3)
+    assert np.all((np.load(tmp_path / "info_flags.npy").astype(np.int64) & 7) == 1)
+    rows = np.arange(0, 16384, 256)
+    orc = Oracle(program).sweep(targets[rows], 1e-15, 1e-15, 1e-15, warm_start=False)
+    assert np.max(np.abs(pos[rows] - orc.positions)) <= 1e-9

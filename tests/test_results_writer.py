@@ -193,7 +193,17 @@ def test_a_million_row_ensemble_goes_to_parquet_in_seconds(tmp_path):
 
     meta = pq.read_metadata(tmp_path / "c5.parquet")
     assert meta.num_rows == n and meta.num_columns == 4 + 2 + 3 * program.n_out
-    assert elapsed < 5.0, f"{elapsed:.1f} s"
+    # the same columns as a plain pyarrow table to the same directory: what this host and its disk need for these bytes
+    # without any per-row work.  5 s where that takes under 5/3 s; on a slower host or disk, three times that.
+    import pyarrow as pa
+
+    columns = {"step_index": np.arange(n), "solver_converged": info["flags"] == 1, "solver_max_residual": info["max_residual"],
+               "solver_nfev": info["nfev"].astype(np.int64), **metrics}
+    columns.update({f"c{k}": np.ascontiguousarray(c) for k, c in enumerate(pos.reshape(n, -1).T)})
+    t0 = time.perf_counter()
+    pq.write_table(pa.table(columns), tmp_path / "plain.parquet")
+    plain = time.perf_counter() - t0
+    assert elapsed < max(5.0, 3.0 * plain), f"{elapsed:.1f} s (a plain pyarrow write of the same columns: {plain:.1f} s)"
 
 
 def test_none_is_missing_and_nan_is_a_value_like_the_reference(tmp_path):

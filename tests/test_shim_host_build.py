@@ -23,7 +23,7 @@ def driver(tmp_path_factory):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not found")
     exe = str(tmp_path_factory.mktemp("shim_host") / "shim_host")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Wno-option-ignored", "-fsanitize=address,undefined",
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-Wno-option-ignored", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
            "-fno-sanitize-recover=undefined", "-o", exe, "-x", "hip", os.path.join(REPO, "tests", "cpu_harness", "shim_host.cpp")]
     subprocess.run(cmd, check=True, capture_output=True, timeout=600)
     return exe
