@@ -864,15 +864,25 @@ int32_t okx_program_lane_bodies(const okx_program* p) {
   return p && p->lane_fn_u ? (p->lane_cold_ok ? 1 : 0) | (p->lane_chain_ok ? 2 : 0) : 0;
 }
 
-/* Generated source of the lane kernel for a program (no device needed); same contract as okx_quad_source. */
-int64_t okx_lane_source(const okx_program_desc* desc, char* buf, int64_t buflen) {
+/* What okx_quad_source / okx_lane_source / okx_precompile share: the DevProgram of `desc`, handed to `use` (which returns
+   an okx_status and reports its own failures through fail()). */
+static int with_dev_program(const okx_program_desc* desc, const std::function<int(const okx::DevProgram&)>& use) {
   okx::DevProgram* tmp = new (std::nothrow) okx::DevProgram;
   if (!tmp) return fail(OKX_ERR_ALLOC, "out of host memory");
   int rc = okx::build_dev_program(desc, tmp, g_err, (int)sizeof(g_err));
-  std::string src, why;
-  if (rc == OKX_OK && !okx::lane_generate(*tmp, &src, &why))
-    rc = fail(OKX_ERR_LIMIT, "no lane kernel for this program: %s", why.c_str());
+  if (rc == OKX_OK) rc = use(*tmp);
   delete tmp;
+  return rc;
+}
+/* Generated source of a program's kernel of one family into the caller's buffer: the number of bytes the full text needs
+   (including the terminator) or a negative okx_status. */
+static int64_t generated_source(const okx_program_desc* desc, char* buf, int64_t buflen, const char* family,
+                                const std::function<bool(const okx::DevProgram&, std::string*, std::string*)>& generate) {
+  std::string src;
+  const int rc = with_dev_program(desc, [&](const okx::DevProgram& program) {
+    std::string why;
+    return generate(program, &src, &why) ? (int)OKX_OK : fail(OKX_ERR_LIMIT, "no %s kernel for this program: %s", family, why.c_str());
+  });
   if (rc != OKX_OK) return rc;
   if (buf && buflen > 0) {
     const size_t ncopy = src.size() < (size_t)buflen - 1 ? src.size() : (size_t)buflen - 1;
@@ -880,45 +890,39 @@ int64_t okx_lane_source(const okx_program_desc* desc, char* buf, int64_t buflen)
     buf[ncopy] = 0;
   }
   return (int64_t)src.size() + 1;
+}
+
+/* Generated source of the lane kernel for a program (no device needed); same contract as okx_quad_source. */
+int64_t okx_lane_source(const okx_program_desc* desc, char* buf, int64_t buflen) {
+  return generated_source(desc, buf, buflen, "lane", [](const okx::DevProgram& program, std::string* src, std::string* why) {
+    return okx::lane_generate(program, src, why);
+  });
 }
 
 /* Generated source of the quad kernel for a program (no device needed).  Returns the number of
    bytes the full text needs (including the terminator) or a negative okx_status. */
 int64_t okx_quad_source(const okx_program_desc* desc, char* buf, int64_t buflen) {
-  okx::DevProgram* tmp = new (std::nothrow) okx::DevProgram;
-  if (!tmp) return fail(OKX_ERR_ALLOC, "out of host memory");
-  int rc = okx::build_dev_program(desc, tmp, g_err, (int)sizeof(g_err));
-  std::string src, why;
-  if (rc == OKX_OK && !okx::quad_generate(*tmp, quad_waves_per_simd(), &src, &why))
-    rc = fail(OKX_ERR_LIMIT, "no quad kernel for this program: %s", why.c_str());
-  delete tmp;
-  if (rc != OKX_OK) return rc;
-  if (buf && buflen > 0) {
-    const size_t ncopy = src.size() < (size_t)buflen - 1 ? src.size() : (size_t)buflen - 1;
-    std::memcpy(buf, src.data(), ncopy);
-    buf[ncopy] = 0;
-  }
-  return (int64_t)src.size() + 1;
+  return generated_source(desc, buf, buflen, "quad", [](const okx::DevProgram& program, std::string* src, std::string* why) {
+    return okx::quad_generate(program, quad_waves_per_simd(), src, why);
+  });
 }
 
 /* Generates and compiles the quad kernel of a program into the on-disk cache (no device needed):
    what __graft_entry__.build() calls for the BASELINE topologies. */
 int32_t okx_precompile(const okx_program_desc* desc) {
-  okx::DevProgram* tmp = new (std::nothrow) okx::DevProgram;
-  if (!tmp) return fail(OKX_ERR_ALLOC, "out of host memory");
-  int rc = okx::build_dev_program(desc, tmp, g_err, (int)sizeof(g_err));
-  std::string src, why, code;
-  if (rc == OKX_OK && !okx::quad_build(*tmp, quad_waves_per_simd(), &src, &code, &why))
-    rc = fail(why.compare(0, 14, "compile failed") == 0 ? OKX_ERR_DEVICE : OKX_ERR_LIMIT, "no quad kernel for this program: %s", why.c_str());
-  if (rc == OKX_OK && tmp->n_free <= okx::kQuadMaxFree) {
-    // the lane kernel of the same program (programs it does not fit simply have none)
-    std::string lsrc, lwhy, lcode;
-    std::vector<okx::LaneOverride> overrides;  // (asked for so that the per-kernel choice is made and remembered)
-    if (okx::lane_generate(*tmp, &lsrc, &lwhy, 0) && !okx::lane_build(*tmp, &lsrc, &lcode, &lwhy, false, nullptr, 0, false, &overrides))
-      rc = fail(OKX_ERR_DEVICE, "lane kernel: %s", lwhy.c_str());
-  }
-  delete tmp;
-  return rc;
+  return with_dev_program(desc, [](const okx::DevProgram& program) {
+    std::string src, why, code;
+    if (!okx::quad_build(program, quad_waves_per_simd(), &src, &code, &why))
+      return fail(why.compare(0, 14, "compile failed") == 0 ? OKX_ERR_DEVICE : OKX_ERR_LIMIT, "no quad kernel for this program: %s", why.c_str());
+    if (program.n_free <= okx::kQuadMaxFree) {
+      // the lane kernel of the same program (programs it does not fit simply have none)
+      std::string lsrc, lwhy, lcode;
+      std::vector<okx::LaneOverride> overrides;  // (asked for so that the per-kernel choice is made and remembered)
+      if (okx::lane_generate(program, &lsrc, &lwhy, 0) && !okx::lane_build(program, &lsrc, &lcode, &lwhy, false, nullptr, 0, false, &overrides))
+        return fail(OKX_ERR_DEVICE, "lane kernel: %s", lwhy.c_str());
+    }
+    return (int)OKX_OK;
+  });
 }
 
 /* Scratch (private segment) bytes of the solve kernels okx_precompile / okx_program_create would use for this program:

@@ -1,0 +1,77 @@
+// okx_gen.cpp — the shared part of the kernel source generators (okx_gen.hpp).
+#include "okx_gen.hpp"
+
+#include <cstdarg>
+#include <cstdio>
+#include <set>
+
+namespace okx {
+
+std::vector<int> elimination_order(const DevProgram& P, int last_point) {
+  const int nf = P.n_free;
+  std::vector<std::set<int>> adj(nf);
+  for (int i = 0; i < P.m; ++i)
+    for (int a = 0; a < P.row_nblk[i]; ++a)
+      for (int b = 0; b < P.row_nblk[i]; ++b)
+        if (a != b) adj[P.row_blk[i][a]].insert(P.row_blk[i][b]);
+  std::vector<bool> gone(nf, false);
+  std::vector<int> perm;
+  int held_back = -1;
+  if (last_point >= 0)
+    for (int k = 0; k < nf; ++k)
+      if (P.free_point[k] == last_point) held_back = k;
+  for (int step = 0; step < nf; ++step) {
+    int best = -1;
+    for (int k = 0; k < nf; ++k)
+      if (!gone[k] && k != held_back && (best < 0 || adj[k].size() < adj[best].size())) best = k;
+    if (best < 0) best = held_back;
+    perm.push_back(best);
+    gone[best] = true;
+    for (int u : adj[best]) {
+      adj[u].erase(best);
+      for (int w : adj[best])
+        if (w != u) adj[u].insert(w);
+    }
+    adj[best].clear();
+  }
+  return perm;
+}
+
+GenBase::GenBase(const DevProgram& prog, int last_point) : P(prog), perm(elimination_order(prog, last_point)) {
+  blk_of_point.assign(P.n_points, -1);
+  dop_of_point.assign(P.n_points, -1);
+  for (int F = 0; F < P.n_free; ++F) blk_of_point[fp(F)] = F;
+  for (int e = 0; e < P.n_derived; ++e) dop_of_point[P.dop_out[e]] = e;
+}
+
+int GenBase::pin_leader(int i) const {
+  if (i >= P.n_crows || P.row_type[i] != OKX_ROW_LINE_PIN) return i;
+  for (int j = 0; j < i; ++j) {
+    if (P.row_type[j] != OKX_ROW_LINE_PIN || P.row_pts[j][0] != P.row_pts[i][0]) continue;
+    bool same = true;
+    for (int k = 0; k < 6; ++k) same = same && P.row_param[j][k] == P.row_param[i][k];
+    if (same) return j;
+  }
+  return i;
+}
+
+void GenBase::f(const char* fmt, ...) {
+  char buf[2048];
+  va_list ap, again;
+  va_start(ap, fmt);
+  va_copy(again, ap);
+  const int need = std::vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  if (need >= (int)sizeof(buf)) {  // a long combined expression: format again into an exact-size buffer
+    std::string big((size_t)need + 1, '\0');
+    std::vsnprintf(&big[0], big.size(), fmt, again);
+    big.resize((size_t)need);
+    out += big;
+  } else if (need > 0) {
+    out += buf;
+  }
+  va_end(again);
+  out += '\n';
+}
+
+}  // namespace okx

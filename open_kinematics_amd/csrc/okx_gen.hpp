@@ -1,0 +1,74 @@
+// okx_gen.hpp — what the two kernel source generators (okx_quadgen.cpp, okx_lanegen.cpp) have in common: the text
+// emitter, the block elimination order and the program lookups both use, and the device functions whose text is the same
+// in both generated modules.  Internal to csrc/.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "okx_plan.hpp"
+
+namespace okx {
+
+// Block F of the generated code (x{F}, rows 3F+c of J^T J, elimination step F of the LDL^T) is the program's free point
+// perm[F]: a greedy minimum-degree order on the block graph of J^T J (ties: program order), so that leaf chains (rack
+// pickup, pushrod / rocker / drop-link) are eliminated before the upright's clique and create no fill-in.
+// ONE function for every generator: the first-step table of okx_quad_head_u/_g is laid out in this block order and the
+// lane kernels read it, so the quad and the lane module of a program must number their blocks alike.
+// `last_point` >= 0: the block of that free point is held back and eliminated last (pair mode with one joining row,
+// okx_quadgen.cpp).
+std::vector<int> elimination_order(const DevProgram& P, int last_point = -1);
+
+// Base of a source generator specialised to one program: the text under construction and the lookups on `P`.
+class GenBase {
+ public:
+  explicit GenBase(const DevProgram& prog, int last_point = -1);
+
+  const DevProgram& P;
+  std::vector<int> perm;                        // elimination_order(P, last_point)
+  std::vector<int> blk_of_point, dop_of_point;  // point -> block of a free point / derived op that writes it, -1: neither
+  std::string out;                              // the text emitted so far
+  std::string why;                              // why an emission refused the program
+  int uid = 0;                                  // numbers the temporaries: the text depends on the ORDER of emission calls
+
+  int fp(int F) const { return P.free_point[perm[F]]; }
+  int target_of_row(int i) const { return (int)P.row_param[i][3]; }
+  // The three LINE_PIN rows that one point-on-line constraint flattens into (same point, same line in the program's own
+  // geometry, components 0/1/2) share their line parameters and their cross product: the first of them is the group's
+  // leader.  Per-geometry tables keep them equal (okx_rebind_design writes the same anchor for every pin of a point).
+  int pin_leader(int i) const;
+
+  void f(const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // one line of text (printf-style) + '\n'
+  std::string tmp(const char* base) { return "_" + std::string(base) + std::to_string(uid++); }
+};
+
+// Device functions both generated modules define with the same text; each generator splices them into its own prelude
+// where that prelude has always had them.  Everything else of the two preludes differs at least in its comments (the
+// `QArgs` mirror of QuadArgs among it) and stays with its generator: generated text is the kernel cache key.
+constexpr const char* kDevFastRcp = R"SRC(DEV double fast_rcp(double x) {
+  double r = __builtin_amdgcn_rcp(x);
+  double e = fma(-x, r, 1.0);
+  r = fma(e, r, r);
+  e = fma(-x, r, 1.0);
+  return fma(e, r, r);
+}
+)SRC";
+constexpr const char* kDevPivotRcp = R"SRC(DEV double pivot_rcp(double x) {
+  const double r = __builtin_amdgcn_rcp(x);
+  return fma(fma(-x, r, 1.0), r, r);
+}
+)SRC";
+constexpr const char* kDevFastSqrtRsqrt = R"SRC(DEV void fast_sqrt_rsqrt(double x, double* root, double* inv) {
+  const double y = __builtin_amdgcn_rsq(x);
+  double g = x * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  const double d = fma(-g, g, x);
+  g = fma(d, h, g);
+  *root = g;
+  *inv = h + h;
+}
+)SRC";
+
+}  // namespace okx

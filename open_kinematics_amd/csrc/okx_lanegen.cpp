@@ -21,9 +21,8 @@
 // problems always belong to one geometry (work units never straddle a span), so those values are read once per
 // wave unit and live in scalar registers; fp64 VALU instructions take them as scalar operands.
 //
-// The first-step tables are the quad module's (okx_quad_head_u/_g); this generator uses the same block
-// elimination order, so the table layout is shared.
-#include <cstdarg>
+// The first-step tables are the quad module's (okx_quad_head_u/_g); both generators take their block order from
+// elimination_order() (okx_gen.hpp), so the table layout is shared.
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -32,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "okx_gen.hpp"
 #include "okx_plan.hpp"
 #include "okx_quad.hpp"
 
@@ -56,73 +56,13 @@ struct LBlkTerm {
   int sg;
 };
 
-class LGen {
+class LGen : public GenBase {
  public:
-  explicit LGen(const DevProgram& prog) : P(prog) {
-    blk_of_point.assign(P.n_points, -1);
-    dop_of_point.assign(P.n_points, -1);
-    perm = lane_elimination_order(P);
-    layout_tables();
-    for (int F = 0; F < P.n_free; ++F) blk_of_point[fp(F)] = F;
-    for (int e = 0; e < P.n_derived; ++e) dop_of_point[P.dop_out[e]] = e;
-  }
+  explicit LGen(const DevProgram& prog) : GenBase(prog) { layout_tables(); }
 
-  // Same greedy minimum-degree order as the quad generator (okx_quadgen.cpp, Gen::elimination_order): the
-  // first-step table of okx_quad_head_* is laid out in that block order.
-  static std::vector<int> lane_elimination_order(const DevProgram& P) {
-    const int nf = P.n_free;
-    std::vector<std::set<int>> adj(nf);
-    for (int i = 0; i < P.m; ++i)
-      for (int a = 0; a < P.row_nblk[i]; ++a)
-        for (int b = 0; b < P.row_nblk[i]; ++b)
-          if (a != b) adj[P.row_blk[i][a]].insert(P.row_blk[i][b]);
-    std::vector<bool> gone(nf, false);
-    std::vector<int> perm;
-    for (int step = 0; step < nf; ++step) {
-      int best = -1;
-      for (int k = 0; k < nf; ++k)
-        if (!gone[k] && (best < 0 || adj[k].size() < adj[best].size())) best = k;
-      perm.push_back(best);
-      gone[best] = true;
-      for (int u : adj[best]) {
-        adj[u].erase(best);
-        for (int w : adj[best])
-          if (w != u) adj[u].insert(w);
-      }
-      adj[best].clear();
-    }
-    return perm;
-  }
-
-  const DevProgram& P;
-  std::vector<int> perm;
-  int fp(int F) const { return P.free_point[perm[F]]; }
-  std::string out, why;
-  std::vector<int> blk_of_point, dop_of_point;
-  int uid = 0;
   std::map<int, std::map<int, LBlk>> dblk;  // active derived op -> free block -> chain block
   bool nz[kMaxVars][kMaxVars] = {};         // scalar-level structure of the lower triangle (block-dense)
   bool fill[kMaxVars][kMaxVars] = {};       // ... after symbolic factorisation
-
-  void f(const char* fmt, ...) {
-    char buf[2048];
-    va_list ap, again;
-    va_start(ap, fmt);
-    va_copy(again, ap);
-    const int need = std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (need >= (int)sizeof(buf)) {
-      std::string big((size_t)need + 1, '\0');
-      std::vsnprintf(&big[0], big.size(), fmt, again);
-      big.resize((size_t)need);
-      out += big;
-    } else if (need > 0) {
-      out += buf;
-    }
-    va_end(again);
-    out += '\n';
-  }
-  std::string tmp(const char* base) { return "_" + std::string(base) + std::to_string(uid++); }
 
   // ---- scalar vector algebra on named doubles ----
   static S3 pt(int p) {
@@ -247,16 +187,6 @@ class LGen {
     hoisted_names[key] = name;
     return name;
   }
-  int pin_leader(int i) const {
-    if (i >= P.n_crows || P.row_type[i] != OKX_ROW_LINE_PIN) return i;
-    for (int j = 0; j < i; ++j) {
-      if (P.row_type[j] != OKX_ROW_LINE_PIN || P.row_pts[j][0] != P.row_pts[i][0]) continue;
-      bool same = true;
-      for (int k = 0; k < 6; ++k) same = same && P.row_param[j][k] == P.row_param[i][k];
-      if (same) return j;
-    }
-    return i;
-  }
   std::string rp(int i, int k) {
     i = pin_leader(i);
     auto key = std::make_pair(i, k);
@@ -273,7 +203,6 @@ class LGen {
     for (int k = 0; k < 3; ++k) v.c[k] = rp(i, k0 + k);
     return v;
   }
-  int target_of_row(int i) const { return (int)P.row_param[i][3]; }
   std::map<int, S3> pin_cross_;
 
   // ---- derived points ----
@@ -1120,7 +1049,9 @@ class LGen {
   }
 };
 
-const char* kLanePreamble = R"SRC(
+// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the `QArgs` mirror and the
+// comments around them differ between the two modules and are left as they are - the text is the kernel cache key)
+const std::string kLanePreamble = std::string(R"SRC(
 // Generated by okx_lanegen.cpp for one constraint program — do not edit.
 typedef struct { double max_residual, cost, last_step; int iterations, nfev, flags, reserved; } okx_info;
 // One wavefront per workgroup: its LDS instructions execute in program order, so what separates a lane's LDS writes from
@@ -1160,19 +1091,8 @@ DEV long long uni64(long long v) {
   const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
   return ((long long)hi << 32) | (unsigned int)lo;
 }
-DEV double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, r, 1.0);
-  r = fma(e, r, r);
-  e = fma(-x, r, 1.0);
-  return fma(e, r, r);
-}
-// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X, profiles/r02/README.md): one Newton step for a pivot.
-DEV double pivot_rcp(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-// a product / a sum that is rounded where it stands (never fused into a neighbour): the final state's squared norms are
+)SRC") + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X, profiles/r02/README.md): one Newton step for a pivot.
+)SRC" + kDevPivotRcp + R"SRC(// a product / a sum that is rounded where it stands (never fused into a neighbour): the final state's squared norms are
 // summed in the quad kernels' order with them
 DEV double okx_mul_rn(double a, double b) {
 #pragma clang fp contract(off)
@@ -1183,18 +1103,7 @@ DEV double okx_add_rn(double a, double b) {
   return a + b;
 }
 // sqrt(x) to the last bit or so and 1 / sqrt(x) to 4e-15: one Goldschmidt step, then the residual correction.
-DEV void fast_sqrt_rsqrt(double x, double* root, double* inv) {
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  const double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  *root = g;
-  *inv = h + h;
-}
-// atan2(y, x), y >= 0, result in [0, pi]: fdlibm-style reduction + odd polynomial (see okx_kernels.hip).
+)SRC" + kDevFastSqrtRsqrt + R"SRC(// atan2(y, x), y >= 0, result in [0, pi]: fdlibm-style reduction + odd polynomial (see okx_kernels.hip).
 DEV double lean_atan2_pos(double y, double x) {
   const double ax = fabs(x);
   if (!(y > 0.0)) return x >= 0.0 ? 0.0 : 3.14159265358979311600e+00;

@@ -1,5 +1,5 @@
-// okx_quad.hpp — runtime-specialised "quad" solve kernel: source generation (okx_quadgen.cpp)
-// and hiprtc compilation / caching / loading (okx_jit.cpp).
+// okx_quad.hpp — runtime-specialised "quad" and "lane" solve kernels: source generation (okx_quadgen.cpp,
+// okx_lanegen.cpp; their common base is okx_gen.hpp) and hiprtc compilation / caching / loading (okx_jit.cpp).
 #pragma once
 
 #include <string>
@@ -64,7 +64,8 @@ struct QuadHeadArgs {
   const double* dop_param;
 };
 // doubles per geometry in that table (0: the program has no quad kernel): Q[k][F][4] per half, M[j][k], N[j][k] for
-// k = constraint gradient + one column per program target, 8 scalars (okx_quadgen.cpp)
+// k = constraint gradient + one column per program target, 8 scalars, S[pair][F][4] per half - the generator's own
+// layout (`HeadLayout`, okx_quadgen.cpp), computed without generating a module
 int quad_head_stride(const DevProgram& program);
 
 // Arguments of the generated parity kernel `okx_quad_eval` (mirrors `struct QEvalArgs`).

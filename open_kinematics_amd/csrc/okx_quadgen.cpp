@@ -33,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "okx_gen.hpp"
 #include "okx_plan.hpp"
 #include "okx_quad.hpp"
 
@@ -58,59 +59,16 @@ struct BlkTerm {
   int sg;
 };
 
-class Gen {
+class Gen : public GenBase {
  public:
-  explicit Gen(const DevProgram& prog, const PairView* pair = nullptr) : P(prog), pv(pair) {
-    blk_of_point.assign(P.n_points, -1);
-    dop_of_point.assign(P.n_points, -1);
-    elimination_order();
-    for (int F = 0; F < P.n_free; ++F) blk_of_point[fp(F)] = F;
-    for (int e = 0; e < P.n_derived; ++e) dop_of_point[P.dop_out[e]] = e;
-  }
+  // Pair mode with ONE joining row: the joined point's block is eliminated LAST.  The right-hand side of the joining row's
+  // own system (D~ z = w) is then zero everywhere but in the last block, so z needs no substitution of its own: the
+  // coupling correction touches the last block only and rides on the backward substitution of the step itself
+  // (emit_substitute's `last_block_hook`; round 6 - a pass of the axle kernel: two substitutions -> one).
+  explicit Gen(const DevProgram& prog, const PairView* pair = nullptr)
+      : GenBase(prog, pair && pair->joins.size() == 1 ? pair->couple_point : -1), pv(pair) {}
 
-  // Block F of the generated code (x{F}, rows 3F+c of J^T J, elimination step F of the LDL^T) is
-  // the program's free point perm[F]: a greedy minimum-degree order on the block graph of J^T J
-  // (ties: program order), so that leaf chains (rack pickup, pushrod / rocker / drop-link) are
-  // eliminated before the upright's clique and create no fill-in.
-  std::vector<int> perm;
-  int fp(int F) const { return P.free_point[perm[F]]; }
-  void elimination_order() {
-    const int nf = P.n_free;
-    std::vector<std::set<int>> adj(nf);
-    for (int i = 0; i < P.m; ++i)
-      for (int a = 0; a < P.row_nblk[i]; ++a)
-        for (int b = 0; b < P.row_nblk[i]; ++b)
-          if (a != b) adj[P.row_blk[i][a]].insert(P.row_blk[i][b]);
-    std::vector<bool> gone(nf, false);
-    perm.clear();
-    // Pair mode with ONE joining row: the joined point's block is eliminated LAST.  The right-hand side of the joining row's
-    // own system (D~ z = w) is then zero everywhere but in the last block, so z needs no substitution of its own: the
-    // coupling correction touches the last block only and rides on the backward substitution of the step itself
-    // (emit_substitute's `last_block_hook`; round 6 - a pass of the axle kernel: two substitutions -> one).
-    int held_back = -1;
-    if (pv && pv->joins.size() == 1)
-      for (int k = 0; k < nf; ++k)
-        if (P.free_point[k] == pv->couple_point) held_back = k;
-    for (int step = 0; step < nf; ++step) {
-      int best = -1;
-      for (int k = 0; k < nf; ++k)
-        if (!gone[k] && k != held_back && (best < 0 || adj[k].size() < adj[best].size())) best = k;
-      if (best < 0) best = held_back;
-      perm.push_back(best);
-      gone[best] = true;
-      for (int u : adj[best]) {
-        adj[u].erase(best);
-        for (int w : adj[best])
-          if (w != u) adj[u].insert(w);
-      }
-      adj[best].clear();
-    }
-  }
-
-  const DevProgram& P;
   const PairView* pv;  // non-null: P is the side program of a two-sided problem (okx_pairview.cpp)
-  std::string out;
-  std::string why;
 
   // Index of program data as seen by a lane: one literal, or in pair mode a select on the side bit
   // q1 (all such accesses are chain-constant loads or record stores, never inside the LM passes).
@@ -127,7 +85,6 @@ class Gen {
   std::string crow8(int i, int k) const {  // constraint row parameter offset into gq
     return pv ? sel(8 * pv->row[0][i] + k, 8 * pv->row[1][i] + k) : std::to_string(8 * i + k);
   }
-  int target_of_row(int i) const { return (int)P.row_param[i][3]; }
   std::string trow8(int i, int k) const {  // target row parameter offset into a.row_param
     if (!pv) return std::to_string(8 * i + k);
     const int t = target_of_row(i);
@@ -150,31 +107,11 @@ class Gen {
     return e0 ? "(q1 ? 0.0 : 1.0)" : "(q1 ? 1.0 : 0.0)";
   }
   std::string dop_slot(int e) const { return pv ? sel(pv->dop[0][e], pv->dop[1][e]) : std::to_string(e); }
-  std::vector<int> blk_of_point, dop_of_point;
-  int uid = 0;
   std::map<std::string, std::string> rot1_, rot2_;
   std::map<std::string, std::vector<std::string>> bc_;
   std::map<int, std::map<int, Blk>> dblk;  // active derived op -> free block -> chain block
   bool nz[kMaxFree][kMaxFree] = {};
 
-  void f(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap, again;
-    va_start(ap, fmt);
-    va_copy(again, ap);
-    const int need = std::vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (need >= (int)sizeof(buf)) {  // a long combined expression: format again into an exact-size buffer
-      std::string big((size_t)need + 1, '\0');
-      std::vsnprintf(&big[0], big.size(), fmt, again);
-      big.resize((size_t)need);
-      out += big;
-    } else if (need > 0) {
-      out += buf;
-    }
-    va_end(again);
-    out += '\n';
-  }
   static std::string f_str(const char* fmt, ...) {
     char buf[256];
     va_list ap;
@@ -183,7 +120,6 @@ class Gen {
     va_end(ap);
     return buf;
   }
-  std::string tmp(const char* base) { return "_" + std::string(base) + std::to_string(uid++); }
   static std::string sx(const LV& v) { return (v.sg < 0 ? "-" : "") + v.n; }
   static std::string pn(int p) { return "p" + std::to_string(p); }
   void reset_caches() {
@@ -526,20 +462,6 @@ class Gen {
     hoisted += line;
     hoisted_names[key] = home;
     return home;
-  }
-  // The three LINE_PIN rows that one point-on-line constraint flattens into (same point, same
-  // line in the program's own geometry, components 0/1/2) share their line parameters and their
-  // cross product: the first of them is the group's leader.  Per-geometry tables keep them equal
-  // (okx_rebind_design writes the same anchor for every pin of a point).
-  int pin_leader(int i) const {
-    if (i >= P.n_crows || P.row_type[i] != OKX_ROW_LINE_PIN) return i;
-    for (int j = 0; j < i; ++j) {
-      if (P.row_type[j] != OKX_ROW_LINE_PIN || P.row_pts[j][0] != P.row_pts[i][0]) continue;
-      bool same = true;
-      for (int k = 0; k < 6; ++k) same = same && P.row_param[j][k] == P.row_param[i][k];
-      if (same) return j;
-    }
-    return i;
   }
   std::map<int, std::string> pin_cross_;  // leader row -> (p - line point) x line dir
 
@@ -1081,7 +1003,9 @@ class Gen {
   bool fillf[kMaxFree][kMaxFree] = {};
 };
 
-const char* kPreamble = R"SRC(
+// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the `QArgs` mirror and the
+// comments around them differ between the two modules and are left as they are - the text is the kernel cache key)
+const std::string kPreamble = std::string(R"SRC(
 // Generated by okx_quadgen.cpp for one constraint program — do not edit.
 typedef struct { double max_residual, cost, last_step; int iterations, nfev, flags, reserved; } okx_info;
 struct QArgs {
@@ -1138,34 +1062,12 @@ DEV double qsum(double v) {
 }
 DEV double qmax(double v) { v = fmax(v, qperm<0xB1>(v)); v = fmax(v, qperm<0x4E>(v)); return v; }
 
-DEV double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, r, 1.0);
-  r = fma(e, r, r);
-  e = fma(-x, r, 1.0);
-  return fma(e, r, r);
-}
-// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X over 2^20 arguments, profiles/r02/README.md).
+)SRC") + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X over 2^20 arguments, profiles/r02/README.md).
 // Reciprocal of a pivot: ONE Newton step (2^-48.6).  The factor only steers the Levenberg-Marquardt step (and the
 // tangents to 1e-9): a 2e-15 relative error in L is far inside what the damping already does to it.
-DEV double pivot_rcp(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-// sqrt(x) to the last bit or so and 1 / sqrt(x) to 4e-15: one Goldschmidt step (both to ~1.5 * 2^-48.4), then the
+)SRC" + kDevPivotRcp + R"SRC(// sqrt(x) to the last bit or so and 1 / sqrt(x) to 4e-15: one Goldschmidt step (both to ~1.5 * 2^-48.4), then the
 // residual correction of the root (x - g^2 is exact in the fma), which squares its error.
-DEV void fast_sqrt_rsqrt(double x, double* root, double* inv) {
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  const double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  *root = g;
-  *inv = h + h;
-}
-// sqrt(x), x > 0 and normal, to ~2^-48: one Goldschmidt step (values that are only reported).
+)SRC" + kDevFastSqrtRsqrt + R"SRC(// sqrt(x), x > 0 and normal, to ~2^-48: one Goldschmidt step (values that are only reported).
 DEV double lean_sqrt(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   const double g = x * y, h = 0.5 * y;
@@ -1212,19 +1114,61 @@ template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* 
 DEV bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 )SRC";
 
+// Layout of one geometry's first-step table (okx_quad_head_u/_g write it, the solve bodies and the lane kernels read
+// it, okx_api.hip allocates quad_head_stride() doubles per geometry), in doubles:
+// Q[k][F][4] (lane components, 0 in slot 3; pair mode: one such block per half), M[j][k] = Q_j . G_k, N[j][k] = Q_j . Q_k,
+// then dmax, min pivot, sum of squared constraint residuals, max |constraint residual|, ok, max pivot, pairs carried, 0.
+// Column k = 0 is the constraint rows' own gradient G_0 = Jc^T rc at the design state (the reference's distance
+// rows carry softnorm's -1e-6 offset there, constraints.py:125-134, so it is small but not zero) with weight 1;
+// column k = t + 1 belongs to target t: G_k = J^T e_t, weight = that target's residual.  Q_k = (J^T J + lambda I)^-1 G_k.
+// Pair mode carries the first-order table too.  Measured on the axle grid, round 3: cold starts 5.57 -> 4.72
+// evaluations, 0.483 -> 0.455 ms; chained grids unchanged (0.211 vs 0.212 ms) - in round 2 the block's registers still
+// cost the chained grid 3 %, before the LM scalars and constants had homes in LDS.
+struct HeadLayout {
+  // columns of the table: the constraint gradient, then one per PROGRAM target (pair mode: a side target stands for one
+  // program target per half that carries it; the column's weight is that half's residual, its Q spans both halves)
+  struct Col { int t, side, prog_t; };
+  std::vector<Col> cols;
+  // Second-order terms of the shared first step: S_st = (J^T J + lambda I)^-1 J^T r''(Q_s, Q_t) for the target
+  // columns s <= t, [pair][F][4] after the scalars (pair mode: one such block per half, the left half's first);
+  // scalar 6 says how many pairs the table carries.
+  std::vector<std::pair<int, int>> pairs;
+  int side;    // doubles of one half's Q block
+  int off;     // where the 8 scalars start
+  int s_off;   // where the S blocks start
+  int s_side;  // doubles of one half's S block (room for every pair, carried or not)
+  int stride;  // doubles per geometry
+
+  // `P`: the program the kernels are specialised to - in pair mode the side program of `pv`
+  HeadLayout(const DevProgram& P, const PairView* pv) {
+    const int nf = P.n_free, T = P.n_targets, prog_targets = pv ? pv->n_prog_targets : T;
+    cols.push_back({-1, -1, -1});
+    for (int pt = 0; pt < prog_targets; ++pt)
+      for (int t = 0; t < T; ++t) {
+        if (!pv) { if (t == pt) cols.push_back({t, -1, pt}); continue; }
+        for (int sd = 0; sd < 2; ++sd)
+          if (pv->tgt[sd][t] == pt) cols.push_back({t, sd, pt});
+      }
+    const int HK = (int)cols.size();
+    side = 4 * nf * HK;
+    off = (pv ? 2 : 1) * side + 2 * HK * HK;
+    if (!(pv && dev_switch("pair_first_order_head")))
+      for (int s2 = 1; s2 < HK; ++s2)
+        for (int t2 = s2; t2 < HK; ++t2) pairs.push_back({s2, t2});
+    s_off = off + 8;
+    s_side = 4 * nf * (HK - 1) * HK / 2;
+    stride = off + 8 + (pv ? 2 : 1) * s_side;
+  }
+};
+
 }  // namespace
 
 int quad_head_stride(const DevProgram& program) {
-  // mirrors the layout quad_generate() gives the first-step table (head_cols / head_off / head_stride there)
-  if (program.n_free <= kQuadMaxFree) {
-    const int k = program.n_targets + 1, pairs = program.n_targets * (program.n_targets + 1) / 2;
-    return 4 * program.n_free * k + 2 * k * k + 8 + 4 * program.n_free * pairs;  // Q, Gram matrices, scalars, second-order S
-  }
+  if (program.n_free <= kQuadMaxFree) return HeadLayout(program, nullptr).stride;
   PairView pv;
   std::string why;
   if (!build_pair_view(program, &pv, &why)) return 0;
-  const int k = pv.n_prog_targets + 1, pairs = pv.n_prog_targets * (pv.n_prog_targets + 1) / 2;
-  return 2 * 4 * pv.side.n_free * k + 2 * k * k + 8 + 2 * 4 * pv.side.n_free * pairs;  // both halves' Q and S blocks
+  return HeadLayout(pv.side, &pv).stride;
 }
 
 bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* src, std::string* why, bool lds_homes,
@@ -1317,41 +1261,10 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     light_src = lt.out;
   }
 
-  // Shared first step of the chain heads (single mode): layout of one geometry's table, in doubles:
-  // Q[k][F][4] (lane components, 0 in slot 3), M[j][k] = Q_j . G_k, N[j][k] = Q_j . Q_k, then
-  // dmax, min pivot, sum of squared constraint residuals, max |constraint residual|, ok, max pivot, 0, 0.
-  // Column k = 0 is the constraint rows' own gradient G_0 = Jc^T rc at the design state (the reference's distance
-  // rows carry softnorm's -1e-6 offset there, constraints.py:125-134, so it is small but not zero) with weight 1;
-  // column k = t + 1 belongs to target t: G_k = J^T e_t, weight = that target's residual.  Q_k = (J^T J + lambda I)^-1 G_k.
-  // Pair mode carries the first-order table (OKX_PAIR_NO_HEAD=1 leaves it out).  Measured on the axle grid, round 3:
-  // cold starts 5.57 -> 4.72 evaluations, 0.483 -> 0.455 ms; chained grids unchanged (0.211 vs 0.212 ms) - in round 2
-  // the block's registers still cost the chained grid 3 %, before the LM scalars and constants had homes in LDS.
+  // (OKX_PAIR_NO_HEAD=1 leaves the table out of a pair-mode module)
   const bool head_ok = T >= 1 && !dev_switch("quad_no_head") && (!pv || !dev_switch("pair_no_head"));
-  // columns of the table: the constraint gradient, then one per PROGRAM target (pair mode: a side target stands for one
-  // program target per half that carries it; the column's weight is that half's residual, its Q spans both halves)
-  struct HeadCol { int t, side, prog_t; };
-  std::vector<HeadCol> head_cols;
-  head_cols.push_back({-1, -1, -1});
-  for (int pt = 0; pt < prog_targets; ++pt)
-    for (int t = 0; t < T; ++t) {
-      if (!pv) { if (t == pt) head_cols.push_back({t, -1, pt}); continue; }
-      for (int sd = 0; sd < 2; ++sd)
-        if (pv->tgt[sd][t] == pt) head_cols.push_back({t, sd, pt});
-    }
-  const int HK = (int)head_cols.size();
-  const int head_side = 4 * nf * HK;                       // doubles of one half's Q block
-  const int head_off = (pv ? 2 : 1) * head_side + 2 * HK * HK;
-  // Second-order terms of the shared first step: S_st = (J^T J + lambda I)^-1 J^T r''(Q_s, Q_t) for the target
-  // columns s <= t, [pair][F][4] after the scalars (pair mode: one such block per half, the left half's first);
-  // scalar 6 says how many pairs the table carries.
-  std::vector<std::pair<int, int>> head_pairs;
-  if (!(pv && dev_switch("pair_first_order_head")))
-    for (int s2 = 1; s2 < HK; ++s2)
-      for (int t2 = s2; t2 < HK; ++t2) head_pairs.push_back({s2, t2});
-  const int NPAIR = (int)head_pairs.size();
-  const int head_s_off = head_off + 8;
-  const int head_s_side = 4 * nf * (HK - 1) * HK / 2;      // doubles of one half's S block
-  const int head_stride = head_off + 8 + (pv ? 2 : 1) * head_s_side;
+  const HeadLayout head(P, pv);
+  const int HK = (int)head.cols.size(), NPAIR = (int)head.pairs.size();
   bool has_atan = false;
   for (int i = 0; i < P.n_crows; ++i)
     has_atan = has_atan || P.row_type[i] == OKX_ROW_ANGLE || P.row_type[i] == OKX_ROW_THREE_POINT_ANGLE;
@@ -2110,7 +2023,7 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
   // staged into LDS with a handful of coalesced loads per lane and read from there.  Read directly, each of the ~85
   // values is a 64-lane load of 8 ... 32 distinct bytes: the four wavefronts of a CU queue ~330 of them on its one L1,
   // ~4000 cycles before the first pass starts (timeline stamps, tools/quad_timeline.py).
-  const int cs_head = 0, cs_pos = (head_stride + 1) / 2 * 2, cs_rp = cs_pos + (3 * prog_points + 1) / 2 * 2,
+  const int cs_head = 0, cs_pos = (head.stride + 1) / 2 * 2, cs_rp = cs_pos + (3 * prog_points + 1) / 2 * 2,
             cs_dp = cs_rp + 8 * (prog_crows + prog_targets), cs_end = cs_dp + (program.n_derived + 1) / 2 * 2 + 2;
   if (CD) {
     g.f("  __shared__ __attribute__((aligned(16))) double cst[%d];  // [first-step table | design positions | row parameters | derived-op parameters]", cs_end);
@@ -2125,7 +2038,7 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     // every load first (clamped indices: no branch), then the stores: one round trip
     struct Piece { const char* src; int n, off; };
     const Piece pieces[] = {{"a.design_pos", 3 * prog_points, cs_pos}, {"a.row_param", 8 * (prog_crows + prog_targets), cs_rp}, {"a.dop_param", program.n_derived, cs_dp}};  // (the PROGRAM's tables: both halves')
-    const int n2 = (head_stride + 1) / 2;  // (the table's allocation is rounded up to an even count of doubles)
+    const int n2 = (head.stride + 1) / 2;  // (the table's allocation is rounded up to an even count of doubles)
     for (int k = 0; 64 * k < n2; ++k) g.f("    double2 sh%d = h2[min(lane + %d, %d)];", k, 64 * k, n2 - 1);
     for (int q = 0; q < 3; ++q)
       for (int k = 0; 64 * k < pieces[q].n; ++k) g.f("    double sp%d_%d = %s[min(lane + %d, %d)];", q, k, pieces[q].src, 64 * k, pieces[q].n - 1);
@@ -2312,17 +2225,17 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     // barrier keeps the arithmetic below from being interleaved, which would issue the rest of the loads a round trip later)
     // (pair mode: each half reads its own Q and S blocks of the staged table where they are used - LDS reads, nothing to batch)
     g.f("    const double* hp = cst;");
-    g.f("    const double* hqb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head_side) + " : 0)").c_str() : "");
-    g.f("    const double* hsb = hp%s; (void)hsb;", pv ? (" + (q1 ? " + std::to_string(head_s_side) + " : 0)").c_str() : "");
+    g.f("    const double* hqb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head.side) + " : 0)").c_str() : "");
+    g.f("    const double* hsb = hp%s; (void)hsb;", pv ? (" + (q1 ? " + std::to_string(head.s_side) + " : 0)").c_str() : "");
     if (!pv)
     for (int k = 0; k < HK; ++k)
       for (int F = 0; F < nf; ++F) g.f("    const double hq%d_%d = hqb[%d + c];", k, F, 4 * (k * nf + F));
     for (int j = 0; j < HK; ++j)
-      for (int k = j; k < HK; ++k) g.f("    const double hm%d_%d = hp[%d];", j, k, head_off - 2 * HK * HK + j * HK + k);
-    for (int i = 0; i < 7; ++i) g.f("    const double hs%d = hp[%d];", i, head_off + i);
+      for (int k = j; k < HK; ++k) g.f("    const double hm%d_%d = hp[%d];", j, k, head.off - 2 * HK * HK + j * HK + k);
+    for (int i = 0; i < 7; ++i) g.f("    const double hs%d = hp[%d];", i, head.off + i);
     if (!pv)
     for (int pi = 0; pi < NPAIR; ++pi)
-      for (int F = 0; F < nf; ++F) g.f("    const double hS%d_%d = hsb[%d + c];", pi, F, head_s_off + 4 * (pi * nf + F));
+      for (int F = 0; F < nf; ++F) g.f("    const double hS%d_%d = hsb[%d + c];", pi, F, head.s_off + 4 * (pi * nf + F));
     g.f("    __builtin_amdgcn_sched_barrier(0);");
   }
   // The design state is a solved state too (of its own design targets): it seeds the chain's history, so the
@@ -2360,10 +2273,10 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     g.f("    if (a.head != nullptr && a.grad_tol == 0.0 && (PG || a.predictor == nullptr)) {");
     }
     if (!CD) {
-    g.f("      const double* hp = a.head + (PG ? geom * %d : 0);", head_stride);
+    g.f("      const double* hp = a.head + (PG ? geom * %d : 0);", head.stride);
     // pair mode: each half reads its own Q and S blocks; the Gram matrices and scalars belong to the whole problem
-    g.f("      const double* hqb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head_side) + " : 0)").c_str() : "");
-    g.f("      const double* hsb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head_s_side) + " : 0)").c_str() : "");
+    g.f("      const double* hqb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head.side) + " : 0)").c_str() : "");
+    g.f("      const double* hsb = hp%s;", pv ? (" + (q1 ? " + std::to_string(head.s_side) + " : 0)").c_str() : "");
     }
     // single mode: every table load issued at once (they travel with the prologue's other loads).  Pair mode: 2 x 100
     // values at once do not fit beside the chain's invariants (152 B of scratch); there the entries are read where they
@@ -2373,12 +2286,12 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
         for (int F = 0; F < nf; ++F) g.f("      const double hq%d_%d = hqb[%d + c];", k, F, 4 * (k * nf + F));
     if (!CD) {
     for (int j = 0; j < HK; ++j)
-      for (int k = j; k < HK; ++k) g.f("      const double hm%d_%d = hp[%d];", j, k, head_off - 2 * HK * HK + j * HK + k);
-    for (int i = 0; i < 6; ++i) g.f("      const double hs%d = hp[%d];", i, head_off + i);
+      for (int k = j; k < HK; ++k) g.f("      const double hm%d_%d = hp[%d];", j, k, head.off - 2 * HK * HK + j * HK + k);
+    for (int i = 0; i < 6; ++i) g.f("      const double hs%d = hp[%d];", i, head.off + i);
     }
     g.f("      const double hr0 = 1.0;  // weight of the constraint rows' own gradient");
     for (int k = 1; k < HK; ++k) {
-      const HeadCol& col = head_cols[k];
+      const HeadLayout::Col& col = head.cols[k];
       if (!pv)
         g.f("      const double hr%d = td%d - tn%d;  // target residual of the first problem at the design state", k, col.t, col.t);
       else  // the residual of the half that carries this program target, known to both halves
@@ -2388,23 +2301,23 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     if (NPAIR > 0) {
       // first-order step d1 and the second-order correction d2 = -1/2 sum_st w_s w_t S_st (see okx_quad_head_*); d2 is
       // taken while it is a correction, 2 |d2| <= 0.75 |d1| (Transtrum & Sethna's acceptance rule)
-      if (!CD) g.f("      const double hs6 = hp[%d];", head_off + 6);
+      if (!CD) g.f("      const double hs6 = hp[%d];", head.off + 6);
       g.f("      double hst1 = 0.0, hst2 = 0.0;");
       if (pv)
         for (int pi = 0; pi < NPAIR; ++pi)
-          g.f("      const double hv%d = %s * hr%d * hr%d;", pi, head_pairs[pi].first == head_pairs[pi].second ? "0.5" : "1.0",
-              head_pairs[pi].first, head_pairs[pi].second);
+          g.f("      const double hv%d = %s * hr%d * hr%d;", pi, head.pairs[pi].first == head.pairs[pi].second ? "0.5" : "1.0",
+              head.pairs[pi].first, head.pairs[pi].second);
       for (int F = 0; F < nf; ++F) {
         std::string e, e2;
         for (int k = 0; k < HK; ++k)
           e += (k ? " + hr" : "hr") + std::to_string(k) + " * " +
                (pv ? "hqb[" + std::to_string(4 * (k * nf + F)) + " + c]" : "hq" + std::to_string(k) + "_" + std::to_string(F));
         for (int pi = 0; pi < NPAIR; ++pi) {
-          const int s2 = head_pairs[pi].first, t2 = head_pairs[pi].second;
+          const int s2 = head.pairs[pi].first, t2 = head.pairs[pi].second;
           const std::string w = pv ? "hv" + std::to_string(pi)
                                    : std::string(s2 == t2 ? "0.5" : "1.0") + " * hr" + std::to_string(s2) + " * hr" + std::to_string(t2);
           e2 += (pi ? " + " : "") + w + (CD && !pv ? " * hS" + std::to_string(pi) + "_" + std::to_string(F)
-                                            : " * hsb[" + std::to_string(head_s_off + 4 * (pi * nf + F)) + " + c]");
+                                            : " * hsb[" + std::to_string(head.s_off + 4 * (pi * nf + F)) + " + c]");
         }
         g.f("      const double hxa%d = -(%s), hxb%d = -(%s);", F, e.c_str(), F, e2.c_str());
         g.f("      hst1 = fmax(hst1, fabs(hxa%d)); hst2 = fmax(hst2, fabs(hxb%d));", F, F);
@@ -3734,12 +3647,12 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
       g.f("    const double sm_g = qsum(cu * nz%d), sm_gp = xq(sm_g);", FU);
       g.f("    const double sm_det = 1.0 - sm_g * sm_gp;");
     }
-    g.f("    double* ho = a.head + geom * %d%s;", head_stride, pv ? (" + (q1 ? " + std::to_string(head_side) + " : 0)").c_str() : "");
-    g.f("    double* hs = a.head + geom * %d;  // Gram matrices and scalars (written once per geometry)", head_stride);
+    g.f("    double* ho = a.head + geom * %d%s;", head.stride, pv ? (" + (q1 ? " + std::to_string(head.side) + " : 0)").c_str() : "");
+    g.f("    double* hs = a.head + geom * %d;  // Gram matrices and scalars (written once per geometry)", head.stride);
     std::vector<std::vector<std::string>> rhs_of(HK, std::vector<std::string>(nf, "0.0"));
     for (int F = 0; F < nf; ++F) rhs_of[0][F] = "gn" + std::to_string(F);  // constraint rows' gradient (target rows vanish here)
     for (int k = 0; k < HK; ++k) {
-      const HeadCol& col = head_cols[k];
+      const HeadLayout::Col& col = head.cols[k];
       if (k > 0) {
         auto it = ev.target_j.find(col.t);
         if (it != ev.target_j.end())
@@ -3778,8 +3691,8 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
         }
         if (em.empty()) em = "0.0";
         g.f("    { const double vm = PSUM(%s), vn = PSUM(%s);", em.c_str(), en.c_str());
-        g.f("      if (valid && c == 0%s) { hs[%d] = vm; hs[%d] = vn; } }", pv ? " && !q1" : "", head_off - 2 * HK * HK + j * HK + k,
-            head_off - HK * HK + j * HK + k);
+        g.f("      if (valid && c == 0%s) { hs[%d] = vm; hs[%d] = vn; } }", pv ? " && !q1" : "", head.off - 2 * HK * HK + j * HK + k,
+            head.off - HK * HK + j * HK + k);
       }
     if (NPAIR > 0) {
       // ---- second-order terms of the first step (geodesic acceleration, Transtrum & Sethna 2012): the first step
@@ -3834,7 +3747,7 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
       };
       auto hd = [&](int d, int i) { return "hDl[" + std::to_string((d * fd_rows + i) * 16) + " + hdq]"; };
       auto pair_value = [&](int pi, int i) {
-        const int s2 = head_pairs[pi].first, t2 = head_pairs[pi].second;
+        const int s2 = head.pairs[pi].first, t2 = head.pairs[pi].second;
         char buf[256];
         if (s2 == t2)
           std::snprintf(buf, sizeof(buf), "%s * %.17g", hd(dir_of(s2, -1), i).c_str(), 1.0 / (0.25 * 0.25));
@@ -3908,21 +3821,21 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
           g.f("    {");
           g.out += ev.out;
           if (pv && NK > 1) {
-            g.f("    double* hso = hs + (q1 ? %d : 0);  // this half's S block", head_s_side);
+            g.f("    double* hso = hs + (q1 ? %d : 0);  // this half's S block", head.s_side);
             g.out += join_correct_src([&](int F) { return outn + std::to_string(F); }, [&](int F, const std::string& e) {
-              return sfmt("    if (valid) hso[%d + c] = c < 3 ? %s : 0.0;\n", head_s_off + 4 * (pi * nf + F), e.c_str());
+              return sfmt("    if (valid) hso[%d + c] = c < 3 ? %s : 0.0;\n", head.s_off + 4 * (pi * nf + F), e.c_str());
             });
           } else if (pv) {  // the coupling between the halves, as for the columns
             g.f("    const double sm_s = qsum(cu * %s%d);", outn.c_str(), FU);
             g.f("    const double sm_c = (xq(sm_s) - sm_gp * sm_s) / sm_det;");
-            g.f("    double* hso = hs + (q1 ? %d : 0);  // this half's S block", head_s_side);
+            g.f("    double* hso = hs + (q1 ? %d : 0);  // this half's S block", head.s_side);
             g.f("    if (valid) {");
             for (int F = 0; F < nf; ++F)
-              g.f("      hso[%d + c] = c < 3 ? fma(-nz%d, sm_c, %s%d) : 0.0;", head_s_off + 4 * (pi * nf + F), F, outn.c_str(), F);
+              g.f("      hso[%d + c] = c < 3 ? fma(-nz%d, sm_c, %s%d) : 0.0;", head.s_off + 4 * (pi * nf + F), F, outn.c_str(), F);
             g.f("    }");
           } else {
           g.f("    if (valid) {");
-          for (int F = 0; F < nf; ++F) g.f("      ho[%d + c] = c < 3 ? %s%d : 0.0;", head_s_off + 4 * (pi * nf + F), outn.c_str(), F);
+          for (int F = 0; F < nf; ++F) g.f("      ho[%d + c] = c < 3 ? %s%d : 0.0;", head.s_off + 4 * (pi * nf + F), outn.c_str(), F);
           g.f("    }");
           }
           g.f("    }");
@@ -3932,7 +3845,7 @@ bool quad_generate(const DevProgram& program, int waves_per_simd, std::string* s
     }
     g.f("    if (valid && c == 0%s) {", pv ? " && !q1" : "");
     g.f("      hs[%d] = diag; hs[%d] = pmin; hs[%d] = ss; hs[%d] = mres_new; hs[%d] = ok ? 1.0 : 0.0; hs[%d] = pmax; hs[%d] = %d.0; hs[%d] = 0.0;",
-        head_off, head_off + 1, head_off + 2, head_off + 3, head_off + 4, head_off + 5, head_off + 6, NPAIR, head_off + 7);
+        head.off, head.off + 1, head.off + 2, head.off + 3, head.off + 4, head.off + 5, head.off + 6, NPAIR, head.off + 7);
     g.f("    }");
     g.f("  }");
     g.f("}");
