@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define OKX_ABI_VERSION 6   /* 6: the evaluated solve of composed axles (okx_axle_roles, okx_program_enable_axle_evaluation, okx_precompile_axle_evaluation, okx_program_eval_columns).  5: the evaluated solve (okx_program_enable_evaluation, okx_solve_evaluated_batch, okx_evaluate_batch, okx_precompile_evaluation).  4: okx_rotation_role.kind / point_b (hardware metrics of composed axles), okx_program_has_cold_body, okx_program_ready.  3: okx_solve_opts.output (+ reserved); lane kernel entry points.  2: confirm_full_pass; diagnostics moved to okx_debug.h */
+#define OKX_ABI_VERSION 6   /* okx_diagnose_sweeps_batch (sweep diagnostics on device: okx_diag_roles, okx_diag_summary, okx_diag_issue) was ADDED UNDER 6 - nothing existing changed; a caller that must know whether a library has it looks the symbol up (dlsym).  6: the evaluated solve of composed axles (okx_axle_roles, okx_program_enable_axle_evaluation, okx_precompile_axle_evaluation, okx_program_eval_columns).  5: the evaluated solve (okx_program_enable_evaluation, okx_solve_evaluated_batch, okx_evaluate_batch, okx_precompile_evaluation).  4: okx_rotation_role.kind / point_b (hardware metrics of composed axles), okx_program_has_cold_body, okx_program_ready.  3: okx_solve_opts.output (+ reserved); lane kernel entry points.  2: confirm_full_pass; diagnostics moved to okx_debug.h */
 
 /* Hard limits of one problem (one wavefront owns one problem). */
 #define OKX_MAX_VARS 126     /* n = 3 * free points (one thread per variable: one wavefront up to 63, two beyond) */
@@ -426,7 +426,7 @@ int32_t okx_axle_metrics_batch(const okx_corner_roles* left, const okx_corner_ro
 
 /*
  * The EVALUATED solve (SURVEY.md section 8f.1-2 as ONE launch).  Replaces solve_evaluated_sweep / evaluate_solved_sweep
- * (core/sweep.py:217-270: solve -> compute_sweep_tangents -> compute_sweep_metrics; diagnostics excluded) for a batch:
+ * (core/sweep.py:217-270: solve -> compute_sweep_tangents -> compute_sweep_metrics; its sweep diagnostics are okx_diagnose_sweeps_batch) for a batch:
  * the generated solve kernels end every problem with an epilogue that, at the converged state still in registers,
  * evaluates the Jacobian once more, factors the undamped J^T J, substitutes once per target for the solution-manifold
  * tangent (sensitivity.py:57-143) and evaluates the corner metric catalog and its derivatives along every tangent
@@ -685,6 +685,82 @@ int64_t okx_program_lane_threshold(const okx_program* prog);   /* -1: no lane ke
  * allocation spills more than a little stays with the quad kernel (okx_solve_opts.kernel = 4 still runs it). */
 int32_t okx_program_lane_bodies(const okx_program* prog);
 int64_t okx_lane_source(const okx_program_desc* desc, char* buf, int64_t buflen);
+
+/*
+ * Sweep diagnostics on device: the reference's diagnose_sweep (core/diagnostics.py:114-226 and the U-bar's
+ * topology_diagnostics, axle/mechanisms.py:119-163, 432-549) for a batch of solved sweeps, one pass over the records in HBM.
+ * Sweep g is states [g * steps_per_sweep, (g + 1) * steps_per_sweep) - the convention of steps_per_geometry.  Per sweep:
+ *   convergence / residual   per step, from d_info (skipped when NULL): not converged; max_residual > residual_tolerance
+ *   jump                     per tracked point: a step displacement above max(5 mm, 4 x the median of its strictly positive
+ *                            step displacements); the median is exact (selection on the bit patterns, (a + b) / 2 at the end)
+ *   chirality                per U-bar side and step: |margin| <= 1e-6 (subject bit1 set, value = margin), else the sign of the
+ *                            signed volume differs from the design state's (value = the volume)
+ *   transmission             per U-bar side, step and joint: |link . tangent| defined and below 0.15
+ * All indices of okx_diag_roles are the PROGRAM's point indices.  The call maps them to the rows of the layout it is given
+ * (OKX_OUTPUT_RECORDS [B][n_out][3] or OKX_OUTPUT_FREE [B][n_free][3], read directly); a role point that is fixed (the bar
+ * axis, a rocker axis) is taken from the program's design positions or, with d_geom_pos [n_sweeps][n_points][3], from the
+ * sweep's own table - as is the design state whose volume sign the chirality check compares with.  A moving point the
+ * layout does not carry is OKX_ERR_INVALID.
+ * Findings are appended to d_issues in no particular order; *d_issue_count ends as the number FOUND, which may exceed
+ * capacity (nothing is written past it): size a second call from it.  The summaries are complete whatever the capacity.
+ * Summaries and the set of issue records are bit-identical from run to run and independent of the batch they were part of.
+ * Launch-only and stream-ordered (the call resets *d_issue_count on the stream itself); legal inside a stream capture.
+ * Sweeps too long for one workgroup's LDS (tracked points x (steps - 1) doubles beyond ~60 KiB) stage their displacements
+ * in ONE scratch buffer the program keeps, grown when a call needs more and then replaced in the order of that call's
+ * stream - the rule of the solve's geometry-table scratch.  For such shapes therefore:
+ *   - calls on one program are STREAM-ORDERED with each other: two of them on different streams at the same time would
+ *     write each other's displacements (use one stream, or one program per stream);
+ *   - run the shape once outside a stream capture first (a capture cannot grow the buffer: OKX_ERR_INVALID), and a
+ *     captured graph holds the buffer it was captured with: do not run a LARGER long shape on the program while such a
+ *     graph may still be replayed - growing frees the old buffer;
+ *   - a call on another stream than the one that grew the buffer must be ordered after that call (an event).
+ * Shapes that fit LDS (every ensemble of up to a few hundred steps) use no scratch and have none of these restrictions.
+ */
+enum { OKX_DIAG_CONVERGENCE = 0, OKX_DIAG_RESIDUAL = 1, OKX_DIAG_JUMP = 2, OKX_DIAG_CHIRALITY = 3, OKX_DIAG_TRANSMISSION = 4,
+       OKX_DIAG_COUNT = 5 };
+
+typedef struct okx_diag_side {
+  int32_t droplink_rocker, droplink_u_bar;                                   /* moving pickups                    */
+  int32_t rocker_axis_a, rocker_axis_b, pushrod_inboard, pushrod_outboard;   /* all -1: no rocker group           */
+} okx_diag_side;
+
+typedef struct okx_diag_roles {
+  int32_t n_points;                   /* continuity: how many points are tracked (<= OKX_MAX_VARS / 3)             */
+  int32_t point[OKX_MAX_VARS / 3];    /* ... and which, in suspension.free_points() order                          */
+  int32_t n_sides;                    /* 0: no U-bar checks; 2: LEFT, RIGHT                                        */
+  okx_diag_side side[2];
+  int32_t bar_axis_a, bar_axis_b;     /* the U-bar axis (fixed points)                                             */
+} okx_diag_roles;
+
+typedef struct okx_diag_summary {     /* one per sweep */
+  int32_t n_issues[OKX_DIAG_COUNT];
+  int32_t first_step[OKX_DIAG_COUNT]; /* -1: none                                                                  */
+  double worst[OKX_DIAG_COUNT];       /* over every step, issue or not: [1] largest max_residual, [2] largest step
+                                         displacement (0: nothing looked at), [3] smallest |chirality margin|,
+                                         [4] smallest transmission margin (+inf: nothing looked at); [0] unused      */
+} okx_diag_summary;
+
+typedef struct okx_diag_issue {       /* one per finding, the device form of DiagnosticIssue                       */
+  int64_t sweep;
+  int32_t step;
+  int32_t category;                   /* OKX_DIAG_*                                                                */
+  int32_t subject;                    /* jump: index into roles.point; chirality: side | boundary << 1;
+                                         transmission: side | joint << 1 (0 bar pickup, 1 pushrod, 2 rocker pickup) */
+  int32_t reserved;
+  double value, threshold;
+} okx_diag_issue;
+
+int32_t okx_diagnose_sweeps_batch(okx_program* prog, const okx_diag_roles* roles, int64_t n_sweeps, int64_t steps_per_sweep,
+                                  int32_t layout,               /* OKX_OUTPUT_RECORDS or OKX_OUTPUT_FREE            */
+                                  const double* d_pos,
+                                  const okx_info* d_info,       /* or NULL: no convergence / residual check         */
+                                  const double* d_geom_pos,     /* [n_sweeps][n_points][3] or NULL                  */
+                                  double residual_tolerance,
+                                  okx_diag_summary* d_summary,  /* [n_sweeps]                                       */
+                                  okx_diag_issue* d_issues,     /* [capacity] or NULL                               */
+                                  int64_t capacity,
+                                  int64_t* d_issue_count,       /* total found, may exceed capacity                 */
+                                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ EXPORTS = (
     "okx_program_enable_axle_evaluation",
     "okx_precompile_axle_evaluation",
     "okx_program_eval_columns",
+    "okx_diagnose_sweeps_batch",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -194,6 +195,8 @@ def load() -> C.CDLL:
     lib.okx_precompile_axle_evaluation.restype = i32
     lib.okx_program_eval_columns.argtypes = [vp]
     lib.okx_program_eval_columns.restype = i32
+    lib.okx_diagnose_sweeps_batch.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, C.c_double, vp, vp, i64, vp, vp]
+    lib.okx_diagnose_sweeps_batch.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -688,6 +688,59 @@ class DeviceProgram:
         _lib.check(rc, "okx_expand_positions_batch")
         return out
 
+    def diagnose(self, positions, info=None, *, steps_per_sweep: int, layout: str = "records", geom_pos=None, roles,
+                 capacity: int = 4096, residual_tolerance: float = 1e-3, out=None):
+        """
+        ``okx_diagnose_sweeps_batch``: the sweep diagnostics (``diagnostics.py``) of solved records in HBM.  ``positions``
+        ``[n_sweeps * steps_per_sweep, n_out, 3]`` (``layout="records"``) or ``[..., n_free, 3]`` (``"free"``); ``info`` the
+        solve's info tensor ``[B, 40]`` bytes or None (no convergence / residual check); ``roles`` a ``diagnostics.DiagRoles``
+        in this program's point indices (``diagnostics.diag_roles``); ``geom_pos [n_sweeps, P, 3]`` per-geometry design tables.
+        Returns ``(summary, issues, count)``, all on the device and nothing copied: ``summary`` uint8 ``[n_sweeps, 80]``
+        (``diagnostics.SUMMARY_DTYPE``), ``issues`` uint8 ``[capacity, 40]`` (``ISSUE_DTYPE``, the first ``min(count, capacity)``
+        rows valid, in no particular order) and ``count`` int64 ``[1]``, the number FOUND.  ``out``: such a triple to write
+        into (stream captures).  ``diagnose_host`` copies and sorts.
+        """
+        p = self.program
+        code = {"records": 0, "free": 1}[layout]
+        rows = p.n_out if code == 0 else p.n_free
+        positions = _as_f64(positions, self.device).reshape(-1, rows, 3)
+        b, s = positions.shape[0], int(steps_per_sweep)
+        if s < 1 or b % s:
+            raise ValueError("bad steps_per_sweep")
+        g = b // s
+        if info is not None and (info.device != positions.device or info.numel() * info.element_size() != 40 * b
+                                 or not info.is_contiguous()):
+            raise ValueError("info must be the contiguous device info tensor of these states")
+        if geom_pos is not None:
+            geom_pos = _as_f64(geom_pos, self.device).reshape(g, p.n_points, 3)
+        if out is None:
+            out = (torch.empty((g, 80), dtype=torch.uint8, device=self.device),
+                   torch.empty((max(int(capacity), 0), 40), dtype=torch.uint8, device=self.device),
+                   torch.empty(1, dtype=torch.int64, device=self.device))
+        summary, issues, count = out
+        c_roles = roles.to_c()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            rc = self.lib.okx_diagnose_sweeps_batch(self._handle, C.byref(c_roles), g, s, code, _ptr(positions), _ptr(info),
+                                                    _ptr(geom_pos), float(residual_tolerance), _ptr(summary),
+                                                    _ptr(issues) if issues.shape[0] else None, issues.shape[0], _ptr(count),
+                                                    C.c_void_p(stream))
+        _lib.check(rc, "okx_diagnose_sweeps_batch")
+        return summary, issues, count
+
+    def diagnose_host(self, positions, info=None, **kw):
+        """``diagnose`` copied to the host: ``(summaries [n_sweeps], issue records in the reference's order)``; a second launch
+        with a buffer of the reported size when the first one's was too small."""
+        from .diagnostics import ISSUE_DTYPE, SUMMARY_DTYPE, sort_records
+
+        summary, issues, count = self.diagnose(positions, info, **kw)
+        total = int(count.item())
+        if total > issues.shape[0]:
+            kw["capacity"] = total
+            summary, issues, count = self.diagnose(positions, info, **kw)
+        records = issues[:total].cpu().numpy().reshape(-1).view(ISSUE_DTYPE)
+        return summary.cpu().numpy().reshape(-1).view(SUMMARY_DTYPE), sort_records(records)
+
     def ensemble_targets(self, geom_pos: torch.Tensor, relative) -> torch.Tensor:
         """
         Absolute targets ``[G * S, T]`` of an ensemble from per-step RELATIVE displacements ``[S, T]``: every

@@ -520,6 +520,34 @@ class ShardedEnsemble:
                     self._expand_graphs[k] = graph
                 graph.replay()
 
+    def diagnose(self, roles, *, capacity: int = 4096, residual_tolerance: float = 1e-3):
+        """
+        The sweep diagnostics (``DeviceProgram.diagnose``, ``okx_diagnose_sweeps_batch``) of THIS RANK's shard after a
+        ``step()``, where its records lie - the free coordinates the solve wrote (or the records of a direct one-rank
+        ensemble), the shard's info records, every geometry's own design table - and an all-gather of the 80-byte summaries
+        (sweeps never straddle ranks: the partition is by whole geometries).  Returns ``(summary_full [G, 80] uint8,
+        issues, count)``: the summaries of every geometry on every rank; the issue records and their count stay this
+        rank's own, their ``sweep`` field counted from ``geometry_range[0]``.  Not for an evaluated ensemble
+        (``metric_columns``): it writes no positions.
+        """
+        if self.metric_index is not None:
+            raise ValueError("an evaluated ensemble (metric_columns) keeps no positions to diagnose")
+        glo, ghi = self.geometry_range
+        rows = self._rows((glo, ghi))
+        positions, layout = (self.positions[rows], "records") if self.direct else (self.free_full[rows], "free")
+        info = self.info_local if self.status_only else self.info_full[rows]
+        if ghi > glo:
+            summary, issues, count = self.dp.diagnose(positions, info, steps_per_sweep=self.steps, layout=layout, geom_pos=self.my_pos,
+                                                      roles=roles, capacity=capacity, residual_tolerance=residual_tolerance)
+        else:
+            summary = torch.empty((0, 80), dtype=torch.uint8, device=self.device)
+            issues = torch.empty((0, 40), dtype=torch.uint8, device=self.device)
+            count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if self.world > 1:
+            spans = [shard_range(self.n_geom, r, self.world) for r in range(self.world)]
+            summary = all_gather_rows(summary, self.n_geom, self.group, spans=spans)
+        return summary, issues, count
+
     def exchange_only(self):
         """The exchange stage alone (every chunk's grouped point-to-point call on whatever the buffers hold, waited for): what
         a step costs beyond its compute when nothing overlaps - a bench figure, not part of a step."""

@@ -497,8 +497,8 @@ class DerivativeIssue:
 class EvaluatedSweep:
     """
     ``core/sweep.py:91-113``: solved states, solver statistics and metric rows of one sweep, the same length each.
-    ``diagnostics`` carries the derivative advisories only: the reference's sweep diagnostics (``core/diagnostics.py``)
-    are outside this package's scope.
+    ``diagnostics`` carries the derivative advisories and, when the sweep was evaluated with ``diagnose=True``, the
+    reference's sweep diagnostics in front of them (``diagnostics.diagnose_sweep``; opt-in).
     """
 
     def __init__(self, states, solver_stats, metrics, diagnostics):
@@ -527,20 +527,41 @@ def _derivative_issues(result: SweepMetricsResult) -> list:
     return issues
 
 
-def evaluate_solved_sweep(suspension, sweep_config, states, solver_stats, *, device=None) -> EvaluatedSweep:
+def _sweep_issues(suspension, sweep_config, states, solver_stats, metrics, diagnose: bool, device, program=None) -> list:
+    """``EvaluatedSweep.diagnostics``: the derivative advisories, behind the sweep diagnostics when asked for - or behind the
+    one warning the reference leaves when their evaluation raised (``core/sweep.py:233-248``)."""
+    derivative = _derivative_issues(metrics)
+    if not diagnose:
+        return derivative
+    from . import diagnostics as dg
+
+    try:
+        if program is None and dg._want_device(device) and sweep_config.n_steps > 0:
+            program, _ = sweep_program(suspension, sweep_config)
+        issues = list(dg.diagnose_sweep(suspension, states, solver_stats, device=device, program=program).issues)
+    except Exception as error:  # noqa: BLE001 - diagnostics are advisory
+        issues = [dg.DiagnosticIssue(None, dg.DiagnosticCategory.DIAGNOSTICS, dg.DiagnosticSeverity.WARNING,
+                                     f"Sweep diagnostics unavailable: diagnostic evaluation failed ({type(error).__name__}: {error}).",
+                                     None)]
+    return issues + derivative
+
+
+def evaluate_solved_sweep(suspension, sweep_config, states, solver_stats, *, device=None, diagnose: bool = False) -> EvaluatedSweep:
     """
     Drop-in for ``kinematics.core.sweep.evaluate_solved_sweep`` (``core/sweep.py:217-245``): metric rows and the
     derivative advisories of an already solved sweep.  For a corner the tangents, the catalog and its derivative columns
-    are ONE kernel launch on the given states (``okx_evaluate_batch``).
+    are ONE kernel launch on the given states (``okx_evaluate_batch``).  ``diagnose=True`` puts the reference's sweep
+    diagnostics (``diagnostics.diagnose_sweep``: one more launch on the records) in front of the derivative advisories.
     """
     if len(states) != len(solver_stats):
         raise ValueError(f"Solved state and solver-stat counts must match: {len(states)} states, {len(solver_stats)} solver stats.")
     metrics = compute_sweep_metrics(suspension, sweep_config, states, device=device)
-    return EvaluatedSweep(states, solver_stats, metrics, _derivative_issues(metrics))
+    return EvaluatedSweep(states, solver_stats, metrics,
+                          _sweep_issues(suspension, sweep_config, states, solver_stats, metrics, diagnose, device))
 
 
 def solve_evaluated_sweep(suspension, sweep_config, solver_config: SolverConfig = SolverConfig(), *, device=None,
-                          fused: bool | None = None) -> EvaluatedSweep:
+                          fused: bool | None = None, diagnose: bool = False) -> EvaluatedSweep:
     """
     Drop-in for ``kinematics.core.sweep.solve_evaluated_sweep`` (``core/sweep.py:248-270``): solve one sweep and compute
     its metric rows.  For a corner whose program has evaluated kernels the whole of it - every step's solve, its
@@ -553,6 +574,7 @@ def solve_evaluated_sweep(suspension, sweep_config, solver_config: SolverConfig 
     more is first solved as) take the one fused launch; a warm-started CHAIN (shorter sweeps, the fallback when the cold
     starts are not the sequential path) is solved as such and then evaluated by ONE more launch on the records in HBM (every
     step side by side); no host round trip either way.  Same states, same error behaviour as ``solve_sweep``.
+    ``diagnose``: see ``evaluate_solved_sweep``.
     """
     from .metrics import axis_rotation_metrics, axle_evaluation_roles, corner_roles, topology_rotation_roles
     from .sensitivity import solve_infos_from_records
@@ -578,7 +600,7 @@ def solve_evaluated_sweep(suspension, sweep_config, solver_config: SolverConfig 
             program, evaluated = extra
             rows = _axle_rows_from_evaluated(suspension, program, evaluated, *axle_parts)
             metrics = SweepMetricsResult(rows, None, solve_infos_from_records(evaluated.tangent_info(), program.n_vars))
-            return EvaluatedSweep(states, stats, metrics, _derivative_issues(metrics))
+            return EvaluatedSweep(states, stats, metrics, _sweep_issues(suspension, sweep_config, states, stats, metrics, diagnose, device, program))
         if extra is not None:
             program, evaluated = extra
             names, roles = topology_rotation_roles(suspension, program)
@@ -589,7 +611,7 @@ def solve_evaluated_sweep(suspension, sweep_config, solver_config: SolverConfig 
             rows = _corner_rows(suspension, program, positions, evaluated.tangents, None, (names, rot_values, rot_derivs),
                                 evaluated=evaluated)
             metrics = SweepMetricsResult(rows, None, solve_infos_from_records(evaluated.tangent_info(), program.n_vars))
-            return EvaluatedSweep(states, stats, metrics, _derivative_issues(metrics))
+            return EvaluatedSweep(states, stats, metrics, _sweep_issues(suspension, sweep_config, states, stats, metrics, diagnose, device, program))
     else:
         states, stats = solve_sweep(suspension, sweep_config, solver_config, device=device)
-    return evaluate_solved_sweep(suspension, sweep_config, states, stats, device=device)
+    return evaluate_solved_sweep(suspension, sweep_config, states, stats, device=device, diagnose=diagnose)
