@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <set>
 
+#include "okx_quad.hpp"
+
 namespace okx {
 
 std::vector<int> elimination_order(const DevProgram& P, int last_point) {
@@ -72,6 +74,26 @@ void GenBase::f(const char* fmt, ...) {
   }
   va_end(again);
   out += '\n';
+}
+
+HeadLayout::HeadLayout(const DevProgram& P, const PairView* pv) {
+  const int nf = P.n_free, T = P.n_targets, prog_targets = pv ? pv->n_prog_targets : T;
+  cols.push_back({-1, -1, -1});
+  for (int pt = 0; pt < prog_targets; ++pt)
+    for (int t = 0; t < T; ++t) {
+      if (!pv) { if (t == pt) cols.push_back({t, -1, pt}); continue; }
+      for (int sd = 0; sd < 2; ++sd)
+        if (pv->tgt[sd][t] == pt) cols.push_back({t, sd, pt});
+    }
+  const int HK = (int)cols.size();
+  side = 4 * nf * HK;
+  off = (pv ? 2 : 1) * side + 2 * HK * HK;
+  if (!(pv && dev_switch("pair_first_order_head")))
+    for (int s2 = 1; s2 < HK; ++s2)
+      for (int t2 = s2; t2 < HK; ++t2) pairs.push_back({s2, t2});
+  s_off = off + 8;
+  s_side = 4 * nf * (HK - 1) * HK / 2;
+  stride = off + 8 + (pv ? 2 : 1) * s_side;
 }
 
 }  // namespace okx

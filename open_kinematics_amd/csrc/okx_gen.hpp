@@ -4,11 +4,14 @@
 #pragma once
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "okx_plan.hpp"
 
 namespace okx {
+
+struct PairView;  // okx_quad.hpp
 
 // Block F of the generated code (x{F}, rows 3F+c of J^T J, elimination step F of the LDL^T) is the program's free point
 // perm[F]: a greedy minimum-degree order on the block graph of J^T J (ties: program order), so that leaf chains (rack
@@ -40,6 +43,35 @@ class GenBase {
 
   void f(const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // one line of text (printf-style) + '\n'
   std::string tmp(const char* base) { return "_" + std::string(base) + std::to_string(uid++); }
+};
+
+// Layout of one geometry's first-step table (okx_quad_head_u/_g write it, the solve bodies and the lane kernels read
+// it, okx_api.hip allocates quad_head_stride() doubles per geometry), in doubles:
+// Q[k][F][4] (lane components, 0 in slot 3; pair mode: one such block per half), M[j][k] = Q_j . G_k, N[j][k] = Q_j . Q_k,
+// then dmax, min pivot, sum of squared constraint residuals, max |constraint residual|, ok, max pivot, pairs carried, 0.
+// Column k = 0 is the constraint rows' own gradient G_0 = Jc^T rc at the design state (the reference's distance
+// rows carry softnorm's -1e-6 offset there, constraints.py:125-134, so it is small but not zero) with weight 1;
+// column k = t + 1 belongs to target t: G_k = J^T e_t, weight = that target's residual.  Q_k = (J^T J + lambda I)^-1 G_k.
+// Pair mode carries the first-order table too.  Measured on the axle grid, round 3: cold starts 5.57 -> 4.72
+// evaluations, 0.483 -> 0.455 ms; chained grids unchanged (0.211 vs 0.212 ms) - in round 2 the block's registers still
+// cost the chained grid 3 %, before the LM scalars and constants had homes in LDS.
+struct HeadLayout {
+  // columns of the table: the constraint gradient, then one per PROGRAM target (pair mode: a side target stands for one
+  // program target per half that carries it; the column's weight is that half's residual, its Q spans both halves)
+  struct Col { int t, side, prog_t; };
+  std::vector<Col> cols;
+  // Second-order terms of the shared first step: S_st = (J^T J + lambda I)^-1 J^T r''(Q_s, Q_t) for the target
+  // columns s <= t, [pair][F][4] after the scalars (pair mode: one such block per half, the left half's first);
+  // scalar 6 says how many pairs the table carries.
+  std::vector<std::pair<int, int>> pairs;
+  int side;    // doubles of one half's Q block
+  int off;     // where the 8 scalars start
+  int s_off;   // where the S blocks start
+  int s_side;  // doubles of one half's S block (room for every pair, carried or not)
+  int stride;  // doubles per geometry
+
+  // `P`: the program the kernels are specialised to - in pair mode the side program of `pv`
+  HeadLayout(const DevProgram& P, const PairView* pv);
 };
 
 // Device functions both generated modules define with the same text; each generator splices them into its own prelude

@@ -23,6 +23,7 @@
 //
 // The first-step tables are the quad module's (okx_quad_head_u/_g); both generators take their block order from
 // elimination_order() (okx_gen.hpp), so the table layout is shared.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
@@ -1146,7 +1147,8 @@ namespace {
 // Emission variants: the same arithmetic, differing only in hints to the compiler (opaque uses after each row, a
 // redefinition of the factorisation's inputs at its top, where the scheduling barriers of the factorisation sit) - except
 // `late_diag`, which assembles the diagonal of J^T J in another order (other rounding).
-const struct { bool pin, launder, late_diag; int col_fence; } kVariants[12] = {
+struct Variant { bool pin, launder, late_diag; int col_fence; };
+const Variant kVariants[12] = {
     {false, false, false, 3}, {true, true, false, 3}, {false, true, false, 3}, {true, false, false, 3},
     {false, false, false, 1}, {false, false, false, 6}, {false, false, true, 3}, {false, false, false, 0},
     {false, false, false, 2}, {false, false, true, 1}, {false, true, true, 3}, {true, false, true, 6}};
@@ -1163,52 +1165,70 @@ bool lane_chain_is_flat(int n_vars) {
   return 80 - 4 * n_vars < 16;  // fewer than 16 of the 80 LDS slots left for the factor's rows beside x, dx, xp, xq
 }
 
-bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int variant, const EvalSpec* es) {
+namespace {
+
+struct PassSrc { std::string eval, factor, subst; };  // a pass as text: rows, factorisation, substitution(s)
+struct Piece { const char* src; int src_off, count, dst; };  // `count` doubles of table `src` from `src_off` on, to gl[dst ...]
+
+// One body per start mode.  COLD: every problem is an independent solve from the design state (chain_len 1): no
+// chain loop, no history, 36 LDS slots.  CHAIN: consecutive problems of a lane form a chain with secant / quadratic
+// extrapolation: the history xp / xq takes another 36 slots.
+// `ch`: the chain loop inside the body, history in LDS.  `fl` (flat chain, see okx_quad.hpp lane_chain_is_flat): the
+// independent-solve body walked over (wave unit, chain step) pairs, chain state in the launch's global scratch.
+// `gb`: the independent-solve body of per-geometry launches (tables and first-step table staged in LDS, see split_g)
+// `ns` (with `fl`): the NESTED start mode - the warm-started form of a sweep for a kernel whose lanes run in lockstep.
+// A lane owns four consecutive steps of its span, as in a flat chain of four, and a wave unit therefore 256 consecutive
+// steps of one geometry; but the four are solved in the order 0, 2, 1, 3, and every one after the first starts from the
+// Lagrange interpolant (in the step index) of the up to six nearest steps the wave unit has already solved - its own and
+// its neighbour lanes', read from the launch's scratch [step of four][slot][lane].  Step 0 of every lane is a cold start
+// (first-step table); steps 2, 1 and 3 start ~1e-8 mm from their solutions instead of a secant's ~1e-4: one full pass
+// and one confirming evaluation.  What a chain carries beside the point - the damping it ended with, the contraction
+// constant it observed - comes from the lane's own step 0.
+// Coarse-to-fine start (developer switch lane_refine; okx_api.hip solve_impl): two more instantiations of the
+// independent-solve bodies with a compile-time STRIDE - SUB = 4: lane l of a wave unit solves step 4 l + offset of its
+// span (offset = a.chain_len, 0 .. 3) - one as it is (the coarse launch: every fourth step, cold from the first-step
+// table) and one WARM: the start is the cubic Lagrange interpolant, in the step index, of the four nearest coarse steps,
+// read from the OUTPUT buffer the coarse launch wrote; no first-step table, the first pass evaluates the guess.
+struct LaneBody {
+  const bool ch, fl, gb, ns;
+  LGen& gen;            // the generator whose pass the body runs: evc, or evg for `gb`
+  const PassSrc& pass;  // ... and that pass (the looping chain body runs pass_chain instead)
+  // the LDS plan and what follows from the flags (LaneModule::plan_body)
+  bool cold = false, sc = false, tl = false, reg_state = false, sub_body = false;
+  int lds_doubles = 0, head_l0 = 0, gl_doubles = 0;
+  std::string state_decl, refresh_kz;
+};
+
+// Everything lane_generate knows about one module: the program, the variant, the LDS budget, the generators with their
+// passes as text, and `g`, the module's text.  Its emitters are called by lane_generate in the order of the text.
+class LaneModule {
+ public:
+  LaneModule(const DevProgram& program, const EvalSpec* spec, int variant)
+      : P(program), es(spec), V(kVariants[variant % 12]), small_in_registers(3 * program.n_free <= 15 && variant < 12) {}
+
+  const DevProgram& P;
+  const EvalSpec* const es;
   // EV: the lane form of the evaluated module (okx_solve_evaluated_batch): the independent-solve bodies end every wave
   // unit with the tangent / metric epilogue (see the quad form in okx_quadgen.cpp; here a lane holds a whole problem, so the
   // catalog runs on duals with ALL the targets' directions at once, its role points straight from the lane's registers)
   const bool EV = es != nullptr;
-  // Emission variants (kVariants above): the register allocator's result for an 18-unknown program sits at the edge of the
-  // 512-register file and is not monotonic in any of the hints (0 ... 250 B of scratch across them for the double
-  // wishbone, and not the same variant for every kernel of the module), so lane_build (okx_jit.cpp) compiles them in this
-  // order, keeps the first one whose independent-solve kernels do not spill - or, after a full search, the one that spills
-  // least, with single kernels taken from other variants of the same arithmetic.
-  if (variant < 0 || variant >= lane_variant_count()) variant = 0;
-  const auto& V = kVariants[variant % 12];
+  const Variant& V;
   // Programs of up to 15 variables (the MacPherson corner) have registers to spare: variants 0 .. 11 keep the accepted
   // point, the step in hand and the whole factor of their independent-solve body in registers, variants 12 .. 23 are the
   // same hints with the LDS layout every larger program has (a 15-variable program with one row of each class spills
   // 272 B in registers and nothing in LDS).  For larger programs the second dozen would repeat the first: not generated.
-  const bool small_in_registers = 3 * P.n_free <= 15 && variant < 12;
-  if (3 * P.n_free > 15 && variant >= 12) {
-    *why = "variant " + std::to_string(variant) + " is variant " + std::to_string(variant - 12) + " for this program";
-    return false;
-  }
-  if (P.n_free > kLaneMaxFree) {
-    *why = "more than " + std::to_string(kLaneMaxFree) + " free points: the lower triangle of J^T J does not fit one lane's registers";
-    return false;
-  }
-  if (P.n_targets > kMaxTargets || P.n_targets < 1) {
-    *why = "needs 1.." + std::to_string(kMaxTargets) + " targets";
-    return false;
-  }
+  const bool small_in_registers;
   const int nf = P.n_free, n = 3 * nf, NP = P.n_points, T = P.n_targets;
-  // The pass (rows, factorisation, backward substitution) is generated once per body: the independent-solve body has
-  // LDS slots to spare for the rows' gradients, the chain body has not.  `ev` is the chain body's generator (no LDS
-  // homes) and the owner of the chain constants; `evc` the independent-solve body's.
   const int kColdStateSlots = 2 * n;                               // x, dx
-  // first-step table layout (shared with okx_quadgen.cpp: quad_head_stride)
-  const int HK = T + 1;
-  const int head_off = 4 * nf * HK + 2 * HK * HK;
-  const int head_s_off = head_off + 8;                                   // second-order vectors S_st, [pair][F][4]
-  const int head_stride = head_s_off + 4 * nf * (HK - 1) * HK / 2;
+  // first-step table layout: the quad head kernel writes the table, the bodies here read it
+  const HeadLayout head{P, nullptr};
+  const int HK = (int)head.cols.size(), head_off = head.off, head_s_off = head.s_off, head_stride = head.stride;
   // The geometry's tables are read through the scalar cache where they are used (see the chain constants above); the
   // developer switch lane_lds_tables brings back round 3's staging into LDS (and takes its share of the 40 KiB).
   const bool scalar_tables = !dev_switch("lane_lds_tables");
   const int all_table_doubles = 3 * P.n_points + 8 * (P.n_crows + P.n_targets) + (P.n_derived > 0 ? P.n_derived : 1);
   const int table_doubles = scalar_tables ? 0 : all_table_doubles;
-  int cold_j_slots = (40 * 1024 - 8 * table_doubles - 256) / 512 - kColdStateSlots;
-  if (cold_j_slots < 0) cold_j_slots = 0;
+  int cold_j_slots = std::max(0, (40 * 1024 - 8 * table_doubles - 256) / 512 - kColdStateSlots), cold_l_slots = 0;
   // Independent solves on PER-GEOMETRY tables get a body of their own: every wave unit (or every few) has another
   // geometry, the wavefronts of a CU read 3 KB each of different tables, and those reads miss the 16 KB scalar cache - a
   // round trip to L2 per batch of reads, in every pass (measured: the scalar tables gave the ensemble kernel 2.5 % where
@@ -1216,10 +1236,26 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
   // LDS once per geometry, every load of the batch in flight together, and a wavefront takes a contiguous block of wave
   // units (developer switch lane_g_scalar: one body for both, as for the chains).
   const bool split_g = scalar_tables && !dev_switch("lane_g_scalar");
-  int g_l_slots = (40 * 1024 - 8 * (all_table_doubles + head_stride) - 256) / 512 - kColdStateSlots;
-  if (g_l_slots < 0) g_l_slots = 0;
-  struct PassSrc { std::string eval, factor, subst; };
-  auto make_pass = [&](LGen& gen, PassSrc* out) -> bool {
+  const int g_l_slots = std::max(0, (40 * 1024 - 8 * (all_table_doubles + head_stride) - 256) / 512 - kColdStateSlots);
+  LGen ev{P}, evc{P}, evg{P}, epc{P}, epg{P};
+  PassSrc pass_chain, pass_cold, pass_g, epi_cold, epi_g;
+  bool light_ok = true;
+  std::string light_src, final_src;
+  std::vector<bool> used;  // points some row, derived op or output reads
+  int gl_size = 0;
+  const bool marks = dev_switch("lane_mark");  // `s_nop 11..16` between the sections of a pass (tools/lane_isa.sh)
+  // developer build: every wave unit of the independent-solve body stamps the shader clock into a.trace[16 wu + k] - 0 unit
+  // start, 1 tables staged, 16 state set up, 2 first step in hand, 3 passes done (4 / 5: full / confirming passes it ran,
+  // 6 ... 11: cycles of its last full pass by section), 13 final state, 14 info stored, 17 records in LDS, 15 records
+  // stored; 32 slots per wave unit (tools/lane_timeline.py)
+  const bool timeline = dev_switch("lane_timeline");
+  LGen g{P};
+  const bool flat_chain = lane_chain_is_flat(n);
+  const bool refine = !EV && dev_switch("lane_refine");
+  std::string why;  // why an emitter refused
+  static constexpr const char* kRefreshKz = "asm volatile(\"\" : \"+v\"(kz));";
+
+  bool make_pass(LGen& gen, PassSrc* out) {
     // (measured on the double wishbone, scratch bytes of the independent-solve bodies _u / _g: pins + launder 0 / 188, pins
     //  only 160 / -, launder only 96 / 96, neither 0 / 0: the register allocator's result is not monotonic in anything)
     gen.pin_acc = V.pin;
@@ -1241,51 +1277,52 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     out->subst = gen.out;
     gen.out.clear();
     return true;
-  };
-  LGen ev(P);
-  PassSrc pass_chain, pass_cold;
-  if (!make_pass(ev, &pass_chain)) {
-    *why = ev.why;
-    return false;
   }
-  LGen evc(P);
-  evc.hoisted_names = ev.hoisted_names;
-  // Measured on the double wishbone (scratch bytes of okx_lane_solve_u): the spare slots given to the factor's rows
-  // 104 B, to the rows' gradients 432 B, hand-parked AGPR rows on top of either 250 - 1000 B (the allocator needs the
-  // accumulation registers for its own spilling).  So: the factor's first rows in LDS, nothing parked by hand.
-  // (a program of up to 15 variables - the MacPherson corner - holds its whole factor in registers: 369 of 512 without a
-  //  parked row; C4 cold 0.105 -> 0.097 ms: what a parked row costs a lone wavefront is its round trip, not its instruction)
-  int cold_l_slots = small_in_registers ? 0 : cold_j_slots;
-  cold_j_slots -= cold_l_slots;
-  if (small_in_registers) cold_j_slots = 0;  // (... nor a gradient)
-  evc.j_lds_base = kColdStateSlots;
-  evc.j_lds_slots = cold_j_slots;
-  evc.l_lds_base = kColdStateSlots + cold_j_slots;
-  evc.l_lds_slots = cold_l_slots;
-  evc.late_diag = V.late_diag;
-  if (!make_pass(evc, &pass_cold)) {
-    *why = evc.why;
-    return false;
-  }
-  LGen evg(P);
-  PassSrc pass_g;
-  if (split_g) {
-    evg.hoisted_names = ev.hoisted_names;
-    evg.j_lds_base = kColdStateSlots;
-    evg.j_lds_slots = 0;
-    evg.l_lds_base = kColdStateSlots;
-    evg.l_lds_slots = small_in_registers ? 0 : g_l_slots;  // (a small program's factor stays in registers here too)
-    evg.late_diag = V.late_diag;
-    if (!make_pass(evg, &pass_g)) {
-      *why = evg.why;
+
+  // The pass (rows, factorisation, backward substitution) is generated once per body: the independent-solve body has
+  // LDS slots to spare for the rows' gradients, the chain body has not.  `ev` is the chain body's generator (no LDS
+  // homes) and the owner of the chain constants; `evc` the independent-solve body's.
+  bool make_passes() {
+    if (!make_pass(ev, &pass_chain)) {
+      why = ev.why;
       return false;
     }
+    evc.hoisted_names = ev.hoisted_names;
+    // Measured on the double wishbone (scratch bytes of okx_lane_solve_u): the spare slots given to the factor's rows
+    // 104 B, to the rows' gradients 432 B, hand-parked AGPR rows on top of either 250 - 1000 B (the allocator needs the
+    // accumulation registers for its own spilling).  So: the factor's first rows in LDS, nothing parked by hand.
+    // (a program of up to 15 variables - the MacPherson corner - holds its whole factor in registers: 369 of 512 without a
+    //  parked row; C4 cold 0.105 -> 0.097 ms: what a parked row costs a lone wavefront is its round trip, not its instruction)
+    cold_l_slots = small_in_registers ? 0 : cold_j_slots;
+    cold_j_slots -= cold_l_slots;
+    if (small_in_registers) cold_j_slots = 0;  // (... nor a gradient)
+    evc.j_lds_base = kColdStateSlots;
+    evc.j_lds_slots = cold_j_slots;
+    evc.l_lds_base = kColdStateSlots + cold_j_slots;
+    evc.l_lds_slots = cold_l_slots;
+    evc.late_diag = V.late_diag;
+    if (!make_pass(evc, &pass_cold)) {
+      why = evc.why;
+      return false;
+    }
+    if (split_g) {
+      evg.hoisted_names = ev.hoisted_names;
+      evg.j_lds_base = kColdStateSlots;
+      evg.j_lds_slots = 0;
+      evg.l_lds_base = kColdStateSlots;
+      evg.l_lds_slots = small_in_registers ? 0 : g_l_slots;  // (a small program's factor stays in registers here too)
+      evg.late_diag = V.late_diag;
+      if (!make_pass(evg, &pass_g)) {
+        why = evg.why;
+        return false;
+      }
+    }
+    return true;
   }
 
   // evaluated module: the epilogue's pass - J at the solved state, the undamped LDL^T with one forward substitution per
   // target (right-hand side J^T e_t, the target row's gradient), one backward substitution each: tq{t}_{i} = d x_i / d target t
-  struct EpiSrc { std::string eval, factor, subst; };
-  auto make_epilogue_pass = [&](LGen& gen, const LGen& like, EpiSrc* out) -> bool {
+  bool make_epilogue_pass(LGen& gen, const LGen& like, PassSrc* out) {
     gen.uid = 700000;
     gen.hoisted_names = ev.hoisted_names;
     gen.j_lds_base = like.j_lds_base;
@@ -1321,83 +1358,90 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     out->subst = gen.out;
     gen.out.clear();
     return true;
-  };
-  LGen epc(P), epg(P);
-  EpiSrc epi_cold, epi_g;
-  if (EV) {
-    std::vector<int> oi(NP, -1);
-    for (int k = 0; k < P.n_out; ++k) oi[P.out_point[k]] = k;
-    for (int F = 0; F < nf; ++F)
-      if (oi[ev.fp(F)] < 0) {
-        *why = "an evaluated module needs every free point among the output points";
+  }
+
+  bool make_epilogue_passes() {
+    if (EV) {
+      std::vector<int> oi(NP, -1);
+      for (int k = 0; k < P.n_out; ++k) oi[P.out_point[k]] = k;
+      for (int F = 0; F < nf; ++F)
+        if (oi[ev.fp(F)] < 0) {
+          why = "an evaluated module needs every free point among the output points";
+          return false;
+        }
+      if (!make_epilogue_pass(epc, evc, &epi_cold) || (split_g && !make_epilogue_pass(epg, evg, &epi_g))) {
+        why = epc.why.empty() ? epg.why : epc.why;
         return false;
       }
-    if (!make_epilogue_pass(epc, evc, &epi_cold) || (split_g && !make_epilogue_pass(epg, evg, &epi_g))) {
-      *why = epc.why.empty() ? epg.why : epc.why;
-      return false;
     }
+    return true;
   }
 
-  // confirming evaluation (residuals only); not for programs with the reference's zero-gradient point-on-line row
-  bool light_ok = true;
-  for (int i = 0; i < P.n_crows; ++i) light_ok = light_ok && P.row_type[i] != OKX_ROW_POINT_ON_LINE;
-  std::string light_src;
-  if (light_ok) {
-    LGen lt(P);
-    lt.uid = 300000;
-    lt.hoisted_names = ev.hoisted_names;
-    for (int idx = 0; idx < P.n_active; ++idx)
-      if (!lt.derived_op(P.active_op[idx], false)) light_ok = false;
-    if (light_ok && !lt.emit_rows_residual_only()) light_ok = false;
-    light_src = lt.out;
-  }
-  // final state: every derived point
-  LGen fin(P);
-  fin.quad_order = true;
-  fin.uid = 100000;
-  fin.hoisted_names = ev.hoisted_names;
-  for (int e = 0; e < P.n_derived; ++e)
-    if (!fin.derived_op(e, false)) {
-      *why = fin.why;
-      return false;
+  bool make_light_and_final() {
+    // confirming evaluation (residuals only); not for programs with the reference's zero-gradient point-on-line row
+    for (int i = 0; i < P.n_crows; ++i) light_ok = light_ok && P.row_type[i] != OKX_ROW_POINT_ON_LINE;
+    if (light_ok) {
+      LGen lt(P);
+      lt.uid = 300000;
+      lt.hoisted_names = ev.hoisted_names;
+      for (int idx = 0; idx < P.n_active; ++idx)
+        if (!lt.derived_op(P.active_op[idx], false)) light_ok = false;
+      if (light_ok && !lt.emit_rows_residual_only()) light_ok = false;
+      light_src = lt.out;
     }
-  const std::string final_src = fin.out;
-
-  std::vector<bool> used(NP, false);
-  for (int k = 0; k < P.n_out; ++k) used[P.out_point[k]] = true;
-  for (int i = 0; i < P.m; ++i)
-    for (int s = 0; s < 4; ++s)
-      if (P.row_pts[i][s] >= 0) used[P.row_pts[i][s]] = true;
-  for (int e = 0; e < P.n_derived; ++e) {
-    used[P.dop_out[e]] = true;
-    for (int s = 0; s < 4; ++s)
-      if (P.dop_pts[e][s] >= 0) used[P.dop_pts[e][s]] = true;
-  }
-  for (int k = 0; k < nf; ++k) used[P.free_point[k]] = true;
-  auto is_fixed = [&](int p) { return ev.blk_of_point[p] < 0 && ev.dop_of_point[p] < 0; };
-
-  // the fixed points are chain constants too (macros p{k}_{c} -> cl[...])
-  for (int p = 0; p < NP; ++p)
-    if (used[p] && is_fixed(p))
-      for (int c = 0; c < 3; ++c) {
-        char name[32];
-        std::snprintf(name, sizeof(name), "p%d_%d", p, c);
-        ev.add_const(name, ev.gl_gp0 + 3 * p + c);
+    // final state: every derived point
+    LGen fin(P);
+    fin.quad_order = true;
+    fin.uid = 100000;
+    fin.hoisted_names = ev.hoisted_names;
+    for (int e = 0; e < P.n_derived; ++e)
+      if (!fin.derived_op(e, false)) {
+        why = fin.why;
+        return false;
       }
-  const int gl_size = ev.gl_size;
+    final_src = fin.out;
+    return true;
+  }
+
+  bool is_fixed(int p) const { return ev.blk_of_point[p] < 0 && ev.dop_of_point[p] < 0; }
+
+  void collect_chain_constants() {
+    used.assign(NP, false);
+    for (int k = 0; k < P.n_out; ++k) used[P.out_point[k]] = true;
+    for (int i = 0; i < P.m; ++i)
+      for (int s = 0; s < 4; ++s)
+        if (P.row_pts[i][s] >= 0) used[P.row_pts[i][s]] = true;
+    for (int e = 0; e < P.n_derived; ++e) {
+      used[P.dop_out[e]] = true;
+      for (int s = 0; s < 4; ++s)
+        if (P.dop_pts[e][s] >= 0) used[P.dop_pts[e][s]] = true;
+    }
+    for (int k = 0; k < nf; ++k) used[P.free_point[k]] = true;
+
+    // the fixed points are chain constants too (macros p{k}_{c} -> cl[...])
+    for (int p = 0; p < NP; ++p)
+      if (used[p] && is_fixed(p))
+        for (int c = 0; c < 3; ++c) {
+          char name[32];
+          std::snprintf(name, sizeof(name), "p%d_%d", p, c);
+          ev.add_const(name, ev.gl_gp0 + 3 * p + c);
+        }
+    gl_size = ev.gl_size;
+  }
+
   // coalesced staging of the geometry's tables (and, in the solve bodies, of its first-step table) into LDS
-  auto stage_tables = [&](LGen& gg, const char* indent) {
+  void stage_tables(LGen& gg, const char* indent) {
     gg.f("%sfor (int k = lane; k < %d; k += 64) gl[%d + k] = gp[k];", indent, 3 * NP, ev.gl_gp0);
     gg.f("%sfor (int k = lane; k < %d; k += 64) gl[%d + k] = gq[k];", indent, 8 * P.n_crows, ev.gl_gq0);
     gg.f("%sif (lane < %d) gl[%d + lane] = a.row_param[%d + lane];", indent, 8 * T, ev.gl_tq0, 8 * P.n_crows);
     gg.f("%sif (lane < %d) gl[%d + lane] = a.dop_param[lane];", indent, P.n_derived, ev.gl_dp0);
-  };
+  }
+
   // The same as ONE batch: every load first (lane k fetching entries k, k + 64, ... of each table, the index clamped so
   // that no load sits under a branch), then the LDS writes; the first-step table too (under `with_head`), to gl[head_into].
   // (a `for` with a load and an LDS store per trip is compiled to one memory round trip per trip: seven to HBM-resident
   //  tables were 13 900 cycles per wave unit of the ensemble kernel)
-  struct Piece { const char* src; int src_off, count, dst; };
-  auto stage_pieces = [&](LGen& gg, const char* indent, const std::vector<Piece>& pieces, int id) -> std::string {
+  std::string stage_pieces(LGen& gg, const char* indent, const std::vector<Piece>& pieces, int id) {
     std::string stores;
     char line[160];
     for (const Piece& pc : pieces)
@@ -1413,8 +1457,9 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
         stores += line;
       }
     return stores;
-  };
-  auto stage_tables_batched = [&](LGen& gg, const char* indent, int head_into) {
+  }
+
+  void stage_tables_batched(LGen& gg, const char* indent, int head_into) {
     const std::string stores = stage_pieces(gg, indent, {{"gp", 0, 3 * NP, ev.gl_gp0}, {"gq", 0, 8 * P.n_crows, ev.gl_gq0},
                                                          {"a.row_param", 8 * P.n_crows, 8 * T, ev.gl_tq0}, {"a.dop_param", 0, P.n_derived, ev.gl_dp0}}, 0);
     gg.f("%sif (with_head) {", indent);
@@ -1422,116 +1467,92 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     gg.out += stage_pieces(gg, deeper.c_str(), {{"hsrc", 0, head_stride, head_into}}, 100);
     gg.f("%s}", indent);
     gg.out += stores;
-  };
-  const bool marks = dev_switch("lane_mark");  // `s_nop 11..16` between the sections of a pass (tools/lane_isa.sh)
-  // developer build: every wave unit of the independent-solve body stamps the shader clock into a.trace[16 wu + k] - 0 unit
-  // start, 1 tables staged, 16 state set up, 2 first step in hand, 3 passes done (4 / 5: full / confirming passes it ran,
-  // 6 ... 11: cycles of its last full pass by section), 13 final state, 14 info stored, 17 records in LDS, 15 records
-  // stored; 32 slots per wave unit (tools/lane_timeline.py)
-  const bool timeline = dev_switch("lane_timeline");
-
-  LGen g(P);
-  g.out += kLanePreamble;
-  g.f("");
-  if (EV) {
-    g.out += eval_metrics_source(*es);
-    g.f("struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; };");
   }
-  {
-    // every table entry a constant's name can stand for (unused macros cost nothing)
-    std::set<std::string> defs;
-    for (LGen* gen : {&ev, &evc, &evg, &epc, &epg}) defs.insert(gen->defines.begin(), gen->defines.end());
-    char line[96];
-    for (int i = 0; i < P.m; ++i)
-      for (int k = 0; k < 8; ++k) {
-        std::snprintf(line, sizeof(line), "#define hs%d_%d GL(%d)\n", i, k,
-                      i < P.n_crows ? ev.gl_gq0 + 8 * i + k : ev.gl_tq0 + 8 * (i - P.n_crows) + k);
+
+  void emit_prelude() {
+    g.out += kLanePreamble;
+    g.f("");
+    if (EV) {
+      g.out += eval_metrics_source(*es);
+      g.f("struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; };");
+    }
+    {
+      // every table entry a constant's name can stand for (unused macros cost nothing)
+      std::set<std::string> defs;
+      for (LGen* gen : {&ev, &evc, &evg, &epc, &epg}) defs.insert(gen->defines.begin(), gen->defines.end());
+      char line[96];
+      for (int i = 0; i < P.m; ++i)
+        for (int k = 0; k < 8; ++k) {
+          std::snprintf(line, sizeof(line), "#define hs%d_%d GL(%d)\n", i, k,
+                        i < P.n_crows ? ev.gl_gq0 + 8 * i + k : ev.gl_tq0 + 8 * (i - P.n_crows) + k);
+          defs.insert(line);
+        }
+      for (int e = 0; e < P.n_derived; ++e) {
+        std::snprintf(line, sizeof(line), "#define hd%d GL(%d)\n", e, ev.gl_dp0 + e);
         defs.insert(line);
       }
-    for (int e = 0; e < P.n_derived; ++e) {
-      std::snprintf(line, sizeof(line), "#define hd%d GL(%d)\n", e, ev.gl_dp0 + e);
-      defs.insert(line);
+      for (const std::string& d : defs) g.out += d;
     }
-    for (const std::string& d : defs) g.out += d;
   }
-  auto PF = [&](int i) { return "p" + std::to_string(ev.fp(i / 3)) + "_" + std::to_string(i % 3); };
-  const char* refresh_kz = "asm volatile(\"\" : \"+v\"(kz));";
 
-  // One body per start mode.  COLD: every problem is an independent solve from the design state (chain_len 1): no
-  // chain loop, no history, 36 LDS slots.  CHAIN: consecutive problems of a lane form a chain with secant / quadratic
-  // extrapolation: the history xp / xq takes another 36 slots.
-  std::string lds_why;
-  const bool flat_chain = lane_chain_is_flat(n);
-  // `ch`: the chain loop inside the body, history in LDS.  `fl` (flat chain, see okx_quad.hpp lane_chain_is_flat): the
-  // independent-solve body walked over (wave unit, chain step) pairs, chain state in the launch's global scratch.
-  LGen& evc_ = evc;
-  const PassSrc& pass_cold_ = pass_cold;
-  // `gb`: the independent-solve body of per-geometry launches (tables and first-step table staged in LDS, see split_g)
-  // `ns` (with `fl`): the NESTED start mode - the warm-started form of a sweep for a kernel whose lanes run in lockstep.
-  // A lane owns four consecutive steps of its span, as in a flat chain of four, and a wave unit therefore 256 consecutive
-  // steps of one geometry; but the four are solved in the order 0, 2, 1, 3, and every one after the first starts from the
-  // Lagrange interpolant (in the step index) of the up to six nearest steps the wave unit has already solved - its own and
-  // its neighbour lanes', read from the launch's scratch [step of four][slot][lane].  Step 0 of every lane is a cold start
-  // (first-step table); steps 2, 1 and 3 start ~1e-8 mm from their solutions instead of a secant's ~1e-4: one full pass
-  // and one confirming evaluation.  What a chain carries beside the point - the damping it ended with, the contraction
-  // constant it observed - comes from the lane's own step 0.
-  // Coarse-to-fine start (developer switch lane_refine; okx_api.hip solve_impl): two more instantiations of the
-  // independent-solve bodies with a compile-time STRIDE - SUB = 4: lane l of a wave unit solves step 4 l + offset of its
-  // span (offset = a.chain_len, 0 .. 3) - one as it is (the coarse launch: every fourth step, cold from the first-step
-  // table) and one WARM: the start is the cubic Lagrange interpolant, in the step index, of the four nearest coarse steps,
-  // read from the OUTPUT buffer the coarse launch wrote; no first-step table, the first pass evaluates the guess.
-  const bool refine = !EV && dev_switch("lane_refine");
-  auto body = [&](bool ch, bool fl, bool gb, bool ns = false) -> bool {
-    LGen& evc = gb ? evg : evc_;
-    const PassSrc& pass_cold = gb ? pass_g : pass_cold_;
+  std::string PF(int i) const { return "p" + std::to_string(ev.fp(i / 3)) + "_" + std::to_string(i % 3); }
+
+  // The LDS layout of a body: state slots, the staging area of the records, the staged first-step table, the tables.
+  bool plan_body(LaneBody& b) {
     int n_slots = 0;
     auto slot_ref = [&](const std::string& name) { return "double& " + name + " = lds[" + std::to_string(64 * n_slots++) + " + lane];"; };
     // A program of up to 15 variables (the MacPherson corner) keeps the accepted point and the step in hand in registers
     // too: 30 LDS slots less, and - what counts for a lone wavefront - their round trips out of the passes.  7 % more
     // instructions (a value parked in accumulation registers costs two moves, one in LDS one access) and C4 cold
     // 0.0973 -> 0.0889 ms; with the factor's rows out of LDS as well (below) 2.46e9 -> 2.85e9 solves/s.
-    const bool reg_state = !ch && !fl && small_in_registers;  // (the chain body, its history on top, spills 56 B with it)
-    std::string state_decl;
+    b.reg_state = !b.ch && !b.fl && small_in_registers;  // (the chain body, its history on top, spills 56 B with it)
     for (int i = 0; i < n; ++i) {
-      if (reg_state) state_decl += "    double x" + std::to_string(i) + ", dx" + std::to_string(i) + ";";
-      else state_decl += "    " + slot_ref("x" + std::to_string(i)) + " " + slot_ref("dx" + std::to_string(i));
-      if (ch) state_decl += " " + slot_ref("xp" + std::to_string(i)) + " " + slot_ref("xq" + std::to_string(i));
-      state_decl += "\n";
+      if (b.reg_state) b.state_decl += "    double x" + std::to_string(i) + ", dx" + std::to_string(i) + ";";
+      else b.state_decl += "    " + slot_ref("x" + std::to_string(i)) + " " + slot_ref("dx" + std::to_string(i));
+      if (b.ch) b.state_decl += " " + slot_ref("xp" + std::to_string(i)) + " " + slot_ref("xq" + std::to_string(i));
+      b.state_decl += "\n";
     }
     const int state_doubles_before_l = 64 * n_slots;  // x, dx (and the chain history): live from the prologue on
-    if (!ch) n_slots = evc.l_lds_base + evc.l_lds_slots > n_slots + (int)evc.j_home.size() ? evc.l_lds_base + evc.l_lds_slots : n_slots + (int)evc.j_home.size();  // + the rows' gradients / the factor's first rows
+    if (!b.ch) n_slots = b.gen.l_lds_base + b.gen.l_lds_slots > n_slots + (int)b.gen.j_home.size() ? b.gen.l_lds_base + b.gen.l_lds_slots : n_slots + (int)b.gen.j_home.size();  // + the rows' gradients / the factor's first rows
     const int state_doubles = 64 * n_slots;
-    const int stage_doubles = (ch || fl) && !ns ? 0 : 64 * 3 * P.n_out;
-    int lds_doubles = state_doubles > stage_doubles ? state_doubles : stage_doubles;
-    if (EV && lds_doubles < 64 * ((3 * P.n_out) | 1)) lds_doubles = 64 * ((3 * P.n_out) | 1);  // (tangent rows [lane][record | 1]; result rows [lane][25])
-    if (EV && lds_doubles < 64 * 25) lds_doubles = 64 * 25;
+    const int stage_doubles = (b.ch || b.fl) && !b.ns ? 0 : 64 * 3 * P.n_out;
+    b.lds_doubles = state_doubles > stage_doubles ? state_doubles : stage_doubles;
+    if (EV && b.lds_doubles < 64 * ((3 * P.n_out) | 1)) b.lds_doubles = 64 * ((3 * P.n_out) | 1);  // (tangent rows [lane][record | 1]; result rows [lane][25])
+    if (EV && b.lds_doubles < 64 * 25) b.lds_doubles = 64 * 25;
     // the first-step table of the wave unit's geometry is staged behind the state (the area the factor's rows are parked
     // in later): the prologue's 100-odd table reads are LDS broadcasts instead of same-address global loads
-    const int head_l0 = state_doubles_before_l;
-    const bool cold = !ch && !fl;
-    const bool sc = scalar_tables && !gb;  // no tables in LDS at all: read where they are used through the scalar cache
-    if (!sc && !gb && lds_doubles < head_l0 + head_stride) lds_doubles = head_l0 + head_stride;
-    const int gl_doubles = sc ? 0 : gl_size + (gb ? head_stride : 0);
-    const std::string refresh_s = sc ? std::string(refresh_kz) + " asm volatile(\"\" : \"+s\"(kzs));" : std::string(refresh_kz);
-    const char* const refresh_kz = refresh_s.c_str();  // (shadows the LDS-only form: this body's passes refresh both opaque zeros)
-    if ((lds_doubles + gl_doubles) * 8 > 40 * 1024) {
-      lds_why = "per-wavefront LDS state exceeds 40 KiB";
+    b.head_l0 = state_doubles_before_l;
+    b.cold = !b.ch && !b.fl;
+    b.sc = scalar_tables && !b.gb;  // no tables in LDS at all: read where they are used through the scalar cache
+    if (!b.sc && !b.gb && b.lds_doubles < b.head_l0 + head_stride) b.lds_doubles = b.head_l0 + head_stride;
+    b.gl_doubles = b.sc ? 0 : gl_size + (b.gb ? head_stride : 0);
+    // (this body's passes refresh both opaque zeros where it reads its tables through the scalar cache)
+    b.refresh_kz = b.sc ? std::string(kRefreshKz) + " asm volatile(\"\" : \"+s\"(kzs));" : std::string(kRefreshKz);
+    if ((b.lds_doubles + b.gl_doubles) * 8 > 40 * 1024) {
+      why = "per-wavefront LDS state exceeds 40 KiB";
       return false;
     }
-    const bool tl = timeline && ((!ch && !fl) || ns);  // (nested mode: one row per unit-step, `it`)
-    auto stamp = [&](int slot) {
-      if (tl) g.f("    if (a.trace && lane == 0) a.trace[%s * 32 + %d] = (double)__builtin_readcyclecounter();", ns ? "it" : "wu", slot);
-    };
-    auto mark = [&](int k) {
-      if (marks && !ch && !fl) g.f("    __builtin_amdgcn_sched_barrier(0); asm volatile(\"s_nop %d\"); __builtin_amdgcn_sched_barrier(0);", 10 + k);
-      // (scheduling barriers on both sides: without them the compiler moves a section's arithmetic across the clock read)
-      if (tl) g.f("    __builtin_amdgcn_sched_barrier(0); { const long long tl_now = __builtin_readcyclecounter(); tl_sec%d = (double)(tl_now - tl_at); tl_at = tl_now; } __builtin_amdgcn_sched_barrier(0);", k);
-    };
+    b.tl = timeline && (b.cold || b.ns);  // (nested mode: one row per unit-step, `it`)
+    b.sub_body = refine && b.cold;  // (the independent-solve bodies carry the stride / warm-start parameters)
+    return true;
+  }
+
+  void stamp(const LaneBody& b, int slot) {
+    if (b.tl) g.f("    if (a.trace && lane == 0) a.trace[%s * 32 + %d] = (double)__builtin_readcyclecounter();", b.ns ? "it" : "wu", slot);
+  }
+
+  void mark(const LaneBody& b, int k) {
+    if (marks && !b.ch && !b.fl) g.f("    __builtin_amdgcn_sched_barrier(0); asm volatile(\"s_nop %d\"); __builtin_amdgcn_sched_barrier(0);", 10 + k);
+    // (scheduling barriers on both sides: without them the compiler moves a section's arithmetic across the clock read)
+    if (b.tl) g.f("    __builtin_amdgcn_sched_barrier(0); { const long long tl_now = __builtin_readcyclecounter(); tl_sec%d = (double)(tl_now - tl_at); tl_at = tl_now; } __builtin_amdgcn_sched_barrier(0);", k);
+  }
+
+  void body_signature(const LaneBody& b) {
     // FULL: the kernel that writes full records (okx_solve_opts.output = 0) is compiled on its own, exactly as it was
     // before the compact outputs existed: the register allocator's result for the double wishbone is that fragile
     // (the same body with the output mode as a run-time switch: 0 -> 248 B of scratch).
     g.f("#undef GL");
-    if (sc) {
+    if (b.sc) {
       // a table entry by its place in the (former) LDS image: positions, constraint-row parameters, target-row parameters,
       // derived-op parameters - the offset is a literal, the chain of conditions folds to one array
       g.f("#define GL(o) ((o) < %d ? gpc[(o) + kzs] : (o) < %d ? gqc[(o) - %d + kzs] : (o) < %d ? rpc[(o) - %d + kzs] : dpc[(o) - %d + kzs])",
@@ -1540,22 +1561,21 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("#define GL(o) gl[(o) + kz]");
     // (evaluated module: GIVEN = the wave unit's states are read from records - a.targets points at them - instead of solved;
     //  the body is then its final state and the epilogue: okx_evaluate_batch's lane form)
-    const bool sub_body = refine && !ch && !fl;  // (the independent-solve bodies carry the stride / warm-start parameters)
-    g.f("template <bool PG, bool FULL%s> DEV void okx_lane_body_%s(const QArgs& a%s) {", EV ? ", bool GIVEN" : sub_body ? ", int SUB, bool WARM" : "",
-        ns ? (gb ? "nestg" : "nest") : ch || fl ? "chain" : gb ? "coldg" : "cold", EV ? ", const QEvArgs& ea" : "");
+    g.f("template <bool PG, bool FULL%s> DEV void okx_lane_body_%s(const QArgs& a%s) {", EV ? ", bool GIVEN" : b.sub_body ? ", int SUB, bool WARM" : "",
+        b.ns ? (b.gb ? "nestg" : "nest") : b.ch || b.fl ? "chain" : b.gb ? "coldg" : "cold", EV ? ", const QEvArgs& ea" : "");
     if (!EV) g.f("  constexpr bool GIVEN = false;");
-    if (!sub_body) g.f("  constexpr int SUB = 1; constexpr bool WARM = false;");
+    if (!b.sub_body) g.f("  constexpr int SUB = 1; constexpr bool WARM = false;");
     g.f("  const int lane = threadIdx.x;");
-    g.f("  __shared__ double lds[%d];", lds_doubles);
-    if (sc) g.f("  int kzs = 0;  // an opaque zero in a scalar register: a table read inside a pass is a load of that pass, not a loop invariant");
+    g.f("  __shared__ double lds[%d];", b.lds_doubles);
+    if (b.sc) g.f("  int kzs = 0;  // an opaque zero in a scalar register: a table read inside a pass is a load of that pass, not a loop invariant");
     else
-    g.f("  __shared__ double gl[%d];  // the wave unit's geometry tables: positions, row parameters, derived-op parameters%s", gl_doubles,
-        gb ? ", first-step table" : "");
+    g.f("  __shared__ double gl[%d];  // the wave unit's geometry tables: positions, row parameters, derived-op parameters%s", b.gl_doubles,
+        b.gb ? ", first-step table" : "");
     g.f("  int kz = 0;");
     g.f("  const long long spg = a.steps_per_geometry;");
     g.f("  const long long span = spg > 0 ? spg : a.n_problems;");
     g.f("  const long long n_spans = spg > 0 ? a.n_problems / span : 1;");
-    if (ch || fl) {
+    if (b.ch || b.fl) {
       g.f("  const long long unit_len = a.chain_len;");
       g.f("  const long long chains_per_span = (span + unit_len - 1) / unit_len;");
     } else {
@@ -1565,27 +1585,30 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     }
     g.f("  const long long waves_per_span = (chains_per_span + 63) / 64;");
     g.f("  const long long n_wave_units = n_spans * waves_per_span;");
-    if (fl) {
+  }
+
+  void body_wave_unit_loop(const LaneBody& b) {
+    if (b.fl) {
       // every wavefront owns a contiguous block of wave units and walks (wave unit, step) pairs in order: the steps of a
       // lane's chain are consecutive iterations of ONE loop whose body carries nothing from one iteration to the next
       g.f("  const long long wu_per_wave = (n_wave_units + gridDim.x - 1) / gridDim.x;");
       g.f("  const long long wu_lo = blockIdx.x * wu_per_wave, wu_hi = wu_lo + wu_per_wave < n_wave_units ? wu_lo + wu_per_wave : n_wave_units;");
-      g.f("  double* const ring = const_cast<double*>(a.predictor) + (long long)blockIdx.x * %lld + lane;  // [entry][slot][lane]", ns ? lane_nest_doubles(n) : lane_flat_chain_doubles(n));
+      g.f("  double* const ring = const_cast<double*>(a.predictor) + (long long)blockIdx.x * %lld + lane;  // [entry][slot][lane]", b.ns ? lane_nest_doubles(n) : lane_flat_chain_doubles(n));
       g.f("  long long staged_span = -1;");
-      if (gb) g.f("  const bool with_head_all = a.head != nullptr && a.grad_tol == 0.0;");
+      if (b.gb) g.f("  const bool with_head_all = a.head != nullptr && a.grad_tol == 0.0;");
       g.f("  for (long long it = wu_lo * unit_len; it < wu_hi * unit_len; ++it) {");
       g.f("    const long long wu = uni64(it / unit_len);");
       g.f("    const int step = (int)uni64(it - wu * unit_len);  // wave-uniform: every lane of the wave unit is at this step of its chain");
-      if (ns) g.f("    const int sidx = step == 1 ? 2 : step == 2 ? 1 : step;  // which of its four steps a lane solves now: 0, 2, 1, 3");
+      if (b.ns) g.f("    const int sidx = step == 1 ? 2 : step == 2 ? 1 : step;  // which of its four steps a lane solves now: 0, 2, 1, 3");
       else g.f("    const int sidx = step;");
-    } else if (cold) {
+    } else if (b.cold) {
       // Own geometry: the tables are staged once per wavefront, the wave units dealt out round-robin (a unit's cost goes with
       // its place in the sweep: neighbours to different wavefronts).  Per-geometry tables: every wavefront takes a contiguous
       // block of wave units, so that the units of one geometry follow each other and its tables are staged once.
       g.f("  const long long wu_per_wave = (n_wave_units + gridDim.x - 1) / gridDim.x;");
       g.f("  const long long wu_lo = PG ? blockIdx.x * wu_per_wave : blockIdx.x, wu_step = PG ? 1 : gridDim.x;");
       g.f("  const long long wu_hi = PG ? (wu_lo + wu_per_wave < n_wave_units ? wu_lo + wu_per_wave : n_wave_units) : n_wave_units;");
-      if (gb) {
+      if (b.gb) {
         g.f("  const bool with_head = !GIVEN && !WARM && a.head != nullptr && a.grad_tol == 0.0;");
         g.f("  long long staged_span = -1;");
       }
@@ -1598,8 +1621,11 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       }
     } else
     g.f("  for (long long wu = blockIdx.x; wu < n_wave_units; wu += gridDim.x) {");
-    stamp(0);
-    if (tl) g.f("    long long tl_at = 0; double tl_sec1 = 0.0, tl_sec2 = 0.0, tl_sec3 = 0.0, tl_sec4 = 0.0, tl_sec5 = 0.0, tl_sec6 = 0.0, tl_full = 0.0, tl_light = 0.0;");
+  }
+
+  void body_unit_start(const LaneBody& b) {
+    stamp(b, 0);
+    if (b.tl) g.f("    long long tl_at = 0; double tl_sec1 = 0.0, tl_sec2 = 0.0, tl_sec3 = 0.0, tl_sec4 = 0.0, tl_sec5 = 0.0, tl_sec6 = 0.0, tl_full = 0.0, tl_light = 0.0;");
     // (the 64-bit division runs on the vector ALU; its result goes to scalar registers so that every table address
     //  derived from it is scalar arithmetic, not a pair of vector registers kept alive through the solve)
     g.f("    const long long span_idx = uni64(n_spans > 1 ? wu / waves_per_span : 0);  // wave-uniform: one geometry per wave unit");
@@ -1607,30 +1633,33 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("    long long chain_in_span = wave_in_span * 64 + lane;");
     g.f("    const bool have = chain_in_span < chains_per_span;");
     g.f("    if (!have) chain_in_span = chains_per_span - 1;");
-    if (!ch && !fl) g.f("    const long long first_b = span_idx * span + (SUB == 1 ? chain_in_span : chain_in_span * SUB + sub_off);");
+    if (!b.ch && !b.fl) g.f("    const long long first_b = span_idx * span + (SUB == 1 ? chain_in_span : chain_in_span * SUB + sub_off);");
     else
     g.f("    const long long first_b = span_idx * span + chain_in_span * unit_len;");
-    if (ch || fl) g.f("    const long long last_b = first_b + unit_len < (span_idx + 1) * span ? first_b + unit_len : (span_idx + 1) * span;");
+    if (b.ch || b.fl) g.f("    const long long last_b = first_b + unit_len < (span_idx + 1) * span ? first_b + unit_len : (span_idx + 1) * span;");
     g.f("    const double* gp = PG ? a.geom_pos + span_idx * %d : a.design_pos;", 3 * NP);
     g.f("    const double* gq = PG ? a.geom_row_param + span_idx * %d : a.row_param;", 8 * P.n_crows);
     g.f("    (void)gq;");
-    if (ch)
+    if (b.ch)
       for (int t = 0; t < T; ++t) g.f("    double tn%d = a.targets[first_b * %d + %d], tp%d = 0.0, tq%d = 0.0, tr%d = 0.0;", t, T, t, t, t, t);
-    else if (fl) {
+    else if (b.fl) {
       g.f("    const bool valid = have && first_b + sidx < last_b;");
       g.f("    const long long bb = valid ? first_b + sidx : last_b - 1;");
       for (int t = 0; t < T; ++t) g.f("    const double tn%d = a.targets[bb * %d + %d];", t, T, t);
     } else
       for (int t = 0; t < T; ++t) g.f("    const double tn%d = GIVEN ? 0.0 : a.targets[first_b * %d + %d];", t, T, t);
-    if (sc) {
+  }
+
+  void body_staging(const LaneBody& b) {
+    if (b.sc) {
       g.f("    const okx_cptr gpc = (okx_cptr)gp, gqc = (okx_cptr)gq, rpc = (okx_cptr)a.row_param, dpc = (okx_cptr)a.dop_param;");
       g.f("    (void)gqc; (void)rpc; (void)dpc;");
-      g.f("    const bool with_head = !GIVEN && !WARM && a.head != nullptr && a.grad_tol == 0.0%s;", fl ? " && step == 0" : "");
+      g.f("    const bool with_head = !GIVEN && !WARM && a.head != nullptr && a.grad_tol == 0.0%s;", b.fl ? " && step == 0" : "");
       g.f("    WAVE_SYNC();  // (the previous wave unit's last LDS reads are done)");
     } else {
     g.f("    // the geometry's tables (and its first-step table) into LDS, lane k fetching entry k");
     g.f("    WAVE_SYNC();  // (the previous wave unit's last reads of these areas are done)");
-    if (fl && gb) {  // (the nested mode's per-geometry kernels: tables and first-step table staged once per geometry, like coldg)
+    if (b.fl && b.gb) {  // (the nested mode's per-geometry kernels: tables and first-step table staged once per geometry, like coldg)
       g.f("    if (span_idx != staged_span) {  // wave-uniform: the tables stay while the geometry does");
       g.f("      const bool with_head = with_head_all;");
       g.f("      const double* hsrc = a.head + span_idx * %d;", head_stride);
@@ -1638,12 +1667,12 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("      staged_span = span_idx;");
       g.f("    }");
       g.f("    const bool with_head = with_head_all && step == 0;");
-    } else if (fl) {
+    } else if (b.fl) {
       g.f("    if (span_idx != staged_span) {  // wave-uniform: the tables stay while the geometry does");
       stage_tables(g, "      ");
       g.f("      staged_span = span_idx;");
       g.f("    }");
-    } else if (gb) {
+    } else if (b.gb) {
       g.f("    if (span_idx != staged_span) {  // wave-uniform: the tables stay while the geometry does");
       g.f("      const double* hsrc = a.head + span_idx * %d;", head_stride);
       stage_tables_batched(g, "      ", gl_size);
@@ -1651,29 +1680,32 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("    }");
     } else
     stage_tables(g, "    ");
-    if (!gb) {
-    g.f("    const bool with_head = !GIVEN && !WARM && a.head != nullptr && a.grad_tol == 0.0%s;", fl ? " && step == 0" : "");
+    if (!b.gb) {
+    g.f("    const bool with_head = !GIVEN && !WARM && a.head != nullptr && a.grad_tol == 0.0%s;", b.fl ? " && step == 0" : "");
     g.f("    if (with_head) {");
     g.f("      const double* hp = a.head + (PG ? span_idx * %d : 0);", head_stride);
-    g.f("      for (int k = lane; k < %d; k += 64) lds[%d + k] = hp[k];", head_stride, head_l0);
+    g.f("      for (int k = lane; k < %d; k += 64) lds[%d + k] = hp[k];", head_stride, b.head_l0);
     g.f("    }");
     }
     g.f("    WAVE_SYNC();");
     }
-    stamp(1);
-    g.f("    %s", refresh_kz);
+    stamp(b, 1);
+  }
+
+  void body_state(const LaneBody& b) {
+    g.f("    %s", b.refresh_kz.c_str());
     for (int p = 0; p < NP; ++p) {
       if (!used[p] || is_fixed(p)) continue;
       for (int c = 0; c < 3; ++c)
-        if (sc || gb) g.f("    double p%d_%d = GL(%d);", p, c, ev.gl_gp0 + 3 * p + c);
+        if (b.sc || b.gb) g.f("    double p%d_%d = GL(%d);", p, c, ev.gl_gp0 + 3 * p + c);
         else g.f("    double p%d_%d = gp[%d];", p, c, 3 * p + c);
     }
-    g.out += state_decl;
+    g.out += b.state_decl;
     for (int i = 0; i < n; ++i) {
       g.f("    x%d = %s; dx%d = 0.0;", i, PF(i).c_str(), i);
-      if (ch) g.f("    xp%d = %s; xq%d = %s;", i, PF(i).c_str(), i, PF(i).c_str());
+      if (b.ch) g.f("    xp%d = %s; xq%d = %s;", i, PF(i).c_str(), i, PF(i).c_str());
     }
-    if (EV && !ch && !fl) {
+    if (EV && !b.ch && !b.fl) {
       // given states: the free coordinates from the lane's record (18 loads in flight; the wave unit's records are one
       // contiguous block, so every line fetched is used by the unit)
       std::vector<int> oi(NP, -1);
@@ -1689,7 +1721,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
         g.f("    static_assert(!GIVEN, \"a free point is not among the output points\");");
       }
     }
-    if (sub_body) {
+    if (b.sub_body) {
       // warm start: cubic Lagrange through the four nearest coarse steps (steps 4 m of this span, already in the output
       // buffer), the stencil shifted inwards at the ends of the span; loads unconditional, from clamped node indices
       std::vector<int> oi(NP, -1);
@@ -1710,7 +1742,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       }
       g.f("    }");
     }
-    stamp(16);
+    stamp(b, 16);
     // the design state is a solved state of its own design targets: it seeds the chain's history
     for (int i = P.n_crows; i < P.m; ++i) {
       const int t = ev.target_of_row(i);
@@ -1719,15 +1751,18 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("    const double td%d = fma(%s, %s, fma(%s, %s, %s * %s));", t, q.c[0].c_str(), dir.c[0].c_str(), q.c[1].c_str(),
           dir.c[1].c_str(), q.c[2].c_str(), dir.c[2].c_str());
     }
-    if (ch)
+    if (b.ch)
       for (int t = 0; t < T; ++t) g.f("    tp%d = td%d;", t, t);
+  }
+
     // shared first step of the unit's first problem, table of okx_quad_head_u/_g
+  void body_head_step(const LaneBody& b) {
     g.f("    bool head_ready = false;");
     g.f("    double hstep = 0.0, hN = 0.0, hM = 0.0, hss = 0.0, hmr = 0.0, hs0 = 0.0, hs1 = 0.0, hs4 = 0.0, hs5 = 0.0;");
     g.f("    if (with_head) {");
-    if (sc) g.f("      const okx_cptr hp = (okx_cptr)(a.head + (PG ? span_idx * %d : 0)) + kzs;", head_stride);
-    else if (gb) g.f("      const double* hp = gl + %d + kz;  // the staged table", gl_size);
-    else g.f("      const double* hp = lds + %d + kz;  // the staged table", head_l0);
+    if (b.sc) g.f("      const okx_cptr hp = (okx_cptr)(a.head + (PG ? span_idx * %d : 0)) + kzs;", head_stride);
+    else if (b.gb) g.f("      const double* hp = gl + %d + kz;  // the staged table", gl_size);
+    else g.f("      const double* hp = lds + %d + kz;  // the staged table", b.head_l0);
     g.f("      const double hr0 = 1.0;");
     for (int k = 1; k < HK; ++k) g.f("      const double hr%d = td%d - tn%d;", k, k - 1, k - 1);
     // first-order step d1 and, when the table carries them (scalar 6), the second-order correction
@@ -1756,180 +1791,190 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("      hs0 = hp[%d]; hs1 = hp[%d]; hs4 = hp[%d]; hs5 = hp[%d];", head_off, head_off + 1, head_off + 4, head_off + 5);
     g.f("      head_ready = true;");
     g.f("    }");
-    if (ch) {
-      g.f("    int hist = 1;");
-      g.f("    double lambda_carry = 0.0;");
-      g.f("    for (long long b = first_b; wave_any(have && b < last_b); ++b) {");
-      g.f("      const bool valid = have && b < last_b;");
-      g.f("      const long long bb = valid ? b : last_b - 1;");
-      g.f("      const long long nb = b + 1 < last_b ? b + 1 : last_b - 1;");
-      for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
-      for (int t = 0; t < T; ++t) g.f("      tn%d = a.targets[nb * %d + %d];", t, T, t);
-      // extrapolation along the chain: secant / quadratic through the last solved states
-      g.f("      if (hist >= 2) {");
-      g.f("        double num = 0.0, den = 0.0, nn = 0.0, num2 = 0.0, den2 = 0.0;");
-      for (int t = 0; t < T; ++t) {
-        g.f("        { const double dn = tv%d - tp%d, dold = tp%d - tq%d, dolder = tq%d - tr%d;", t, t, t, t, t, t);
-        g.f("          num = fma(dn, dold, num); den = fma(dold, dold, den); nn = fma(dn, dn, nn);");
-        g.f("          num2 = fma(dold, dolder, num2); den2 = fma(dolder, dolder, den2); }");
-      }
-      g.f("        double alpha = den > 0.0 ? num * fast_rcp(den) : 0.0;");
-      g.f("        alpha = fmin(fmax(alpha, 0.0), 2.0);");
-      g.f("        const double beta = den2 > 0.0 ? num2 * fast_rcp(den2) : 0.0;");
-      g.f("        const bool line = hist >= 3 && alpha > 0.0 && beta >= 1e-3 && beta <= 2.0 && num * num >= 0.98 * nn * den && num2 * num2 >= 0.98 * den * den2;");
-      g.f("        const double bq = line ? fast_rcp(beta) : 1.0;");
-      g.f("        const double r1q = fast_rcp(1.0 + bq);");
-      g.f("        const double l0 = line ? (alpha + 1.0) * (alpha + 1.0 + bq) * r1q : 1.0 + alpha;");
-      g.f("        const double l1 = line ? -alpha * (alpha + 1.0 + bq) * beta : -alpha;");
-      g.f("        const double l2 = line ? alpha * (alpha + 1.0) * r1q * beta : 0.0;");
-      for (int i = 0; i < n; ++i)
-        g.f("        { const double xo = x%d, xpo = xp%d; const double xn = fma(l0, xo, fma(l1, xpo, l2 * xq%d)); xq%d = xpo; xp%d = xo; x%d = xn; }", i, i, i, i, i, i);
-      g.f("      } else {");
-      for (int i = 0; i < n; ++i) g.f("        { const double xo = x%d; xq%d = xp%d; xp%d = xo; }", i, i, i, i);
-      g.f("      }");
-    } else if (fl && ns) {
-      // Nested start: the Lagrange interpolant, in the step index, of the nearest steps this wave unit has solved (own and
-      // neighbour lanes'), over whichever of eight candidates exist - four on either side inside the wave unit, so that the
-      // lanes at its ends still have four or five on one side: a unit-step takes the passes of its slowest lane.  Entry
-      // [step of four]: n coordinates, converged?, damping, contraction constant.  No candidate (a neighbourhood that
-      // failed): the design state, like a chain that restarts.
-      const int E = (n + 3) * 64, K = 8;
-      struct Cand { int dl, q, o; };
-      const Cand cand[3][K] = {
-          {{-3, 0, -14}, {-2, 0, -10}, {-1, 0, -6}, {0, 0, -2}, {1, 0, 2}, {2, 0, 6}, {3, 0, 10}, {4, 0, 14}},          // second step (third of the four)
-          {{-2, 0, -9}, {-2, 1, -7}, {-1, 0, -5}, {-1, 1, -3}, {0, 0, -1}, {0, 1, 1}, {1, 0, 3}, {1, 1, 5}},            // third step (second of the four)
-          {{-1, 2, -6}, {-1, 1, -5}, {0, 0, -3}, {0, 2, -2}, {0, 1, -1}, {1, 0, 1}, {1, 2, 2}, {1, 1, 3}}};             // fourth step
-      g.f("    {");
-      for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
-      g.f("      double lambda_carry = 0.0, cq_carry = 0.0;");
-      g.f("      if (step > 0) {");
-      // (entries stored by other lanes of THIS wavefront, through the same L1: its vector-memory instructions execute in
-      //  order, so what separates the stores from these loads is an ordering for the compiler - an agent-scope release
-      //  would wait for every record store in flight)
-      g.f("        WAVE_SYNC();");
-      // (opaque: derived from a loop invariant, every candidate address of every coordinate would be hoisted out of the
-      //  unit-step loop, kept alive across the passes and spilled - a kilobyte of scratch, read back at memory latency)
-      g.f("        const double* rb = ring - lane;  // this wavefront's entries [step][slot][lane]");
-      g.f("        asm volatile(\"\" : \"+v\"(rb));");
-      // Few round trips per unit-step: the lane's own first entry (damping, contraction constant), the candidates' flags and
-      // their coordinates - half of the coordinates at a time - are loaded unconditionally (clamped lane indices: every
-      // address is a valid entry) and pinned as a batch; flags, weights and selects afterwards.  (As written first - flags,
-      // then per coordinate the loads under `v ? load : 0` - the compiler issued 20-odd dependent round trips to the
-      // Infinity Cache: 14 us per unit-step, tools/lane_timeline.py c5nest.)
-      g.f("        const double own_ok = rb[%d + lane], own_lambda = rb[%d + lane], own_cq = rb[%d + lane];", 64 * n, 64 * (n + 1), 64 * (n + 2));
-      g.f("        bool v0 = false, v1 = false, v2 = false, v3 = false, v4 = false, v5 = false, v6 = false, v7 = false;");
-      g.f("        double w0 = 0.0, w1 = 0.0, w2 = 0.0, w3 = 0.0, w4 = 0.0, w5 = 0.0, w6 = 0.0, w7 = 0.0;");
-      for (int q = 1; q <= 3; ++q) {
-        g.f("        %sif (step == %d) {", q > 1 ? "else " : "", q);
-        std::string fpin = "          asm volatile(\"\" : ";
-        for (int j = 0; j < K; ++j) {
-          const Cand& c = cand[q - 1][j];
-          g.f("          const int lc%d = lane + (%d) < 0 ? 0 : (lane + (%d) > 63 ? 63 : lane + (%d));", j, c.dl, c.dl, c.dl);
-          g.f("          const double* en%d = rb + %d + lc%d;", j, c.q * E, j);
-          g.f("          double f%d = en%d[%d];", j, j, 64 * n);
-          fpin += std::string(j ? ", " : "") + "\"+v\"(f" + std::to_string(j) + ")";
-        }
-        for (int half = 0; half < 2; ++half) {
-          const int i0 = half * ((n + 1) / 2), i1 = half ? n : (n + 1) / 2;
-          g.f("          __builtin_amdgcn_sched_barrier(0);");
-          g.f("          {");
-          for (int i = i0; i < i1; ++i)
-            for (int j = 0; j < K; ++j) g.f("            double t%d_%d = en%d[%d];", j, i, j, 64 * i);
-          if (half == 0) g.out += fpin + ");\n";
-          for (int i = i0; i < i1; i += 3) {  // (an asm statement takes 30 operands)
-            std::string pin = "            asm volatile(\"\" : ";
-            bool first = true;
-            for (int k = i; k < i + 3 && k < i1; ++k)
-              for (int j = 0; j < K; ++j) {
-                pin += std::string(first ? "" : ", ") + "\"+v\"(t" + std::to_string(j) + "_" + std::to_string(k) + ")";
-                first = false;
-              }
-            g.out += pin + ");\n";
-          }
-          if (half == 0) {
-            for (int j = 0; j < K; ++j) {
-              const Cand& c = cand[q - 1][j];
-              g.f("            v%d = lane + (%d) >= 0 && lane + (%d) < 64 && f%d > 0.5;", j, c.dl, c.dl, j);
-            }
-            for (int j = 0; j < K; ++j) {
-              std::string w = "1.0";
-              for (int k = 0; k < K; ++k) {
-                if (k == j) continue;
-                char buf[96];
-                std::snprintf(buf, sizeof(buf), " * (v%d ? %.17g : 1.0)", k, (0.0 - cand[q - 1][k].o) / (double)(cand[q - 1][j].o - cand[q - 1][k].o));
-                w += buf;
-              }
-              g.f("            w%d = v%d ? %s : 0.0;", j, j, w.c_str());
-            }
-          }
-          g.f("            if (v0 || v1 || v2 || v3 || v4 || v5 || v6 || v7) {");
-          for (int i = i0; i < i1; ++i) {
-            std::string e;
-            for (int j = 0; j < K; ++j) e += std::string(j ? " + " : "") + "w" + std::to_string(j) + " * (v" + std::to_string(j) + " ? t" + std::to_string(j) + "_" + std::to_string(i) + " : 0.0)";
-            g.f("              x%d = %s;", i, e.c_str());
-          }
-          g.f("            }");
-          g.f("          }");
-          if (half == 0) continue;
-        }
-        g.f("        }");
-      }
-      g.f("        if (own_ok > 0.5) { lambda_carry = own_lambda; cq_carry = own_cq; }  // (the lane's own first step)");
-      g.f("      }");
-    } else if (fl) {
-      // Start of a chain step: from the ring of this lane's chain - the last three steps' solutions, whether each
-      // converged, the damping the last one ended with - exactly what the looping chain body keeps in x / xp / xq, hist
-      // and lambda_carry (the design state stands in for solutions the chain does not have yet; a predecessor that did
-      // not converge restarts the chain from the design state).
-      const int E = (n + 2) * 64;
-      g.f("    {");
-      for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
-      g.f("      double lambda_carry = 0.0;");
-      g.f("      if (step > 0) {");
-      g.f("        const double* r1 = ring + ((step + 2) %% 3) * %d;", E);
-      g.f("        const double* r2 = ring + ((step + 1) %% 3) * %d;", E);
-      g.f("        const double* r3 = ring + (step %% 3) * %d;", E);
-      g.f("        const bool ok1 = r1[%d] > 0.5, ok2 = ok1 && step >= 2 && r2[%d] > 0.5, ok3 = ok2 && step >= 3 && r3[%d] > 0.5;", 64 * n, 64 * n, 64 * n);
-      g.f("        if (ok1) {");
-      g.f("          lambda_carry = r1[%d];", 64 * (n + 1));
-      g.f("          const long long b2 = step >= 2 ? bb - 2 : bb, b3 = step >= 3 ? bb - 3 : bb;");
-      for (int t = 0; t < T; ++t)
-        g.f("          const double tp%d = a.targets[(bb - 1) * %d + %d], tq%d = ok2 ? a.targets[b2 * %d + %d] : td%d, tr%d = ok3 ? a.targets[b3 * %d + %d] : td%d;",
-            t, T, t, t, T, t, t, t, T, t, t);
-      g.f("          double num = 0.0, den = 0.0, nn = 0.0, num2 = 0.0, den2 = 0.0;");
-      for (int t = 0; t < T; ++t) {
-        g.f("          { const double dn = tv%d - tp%d, dold = tp%d - tq%d, dolder = tq%d - tr%d;", t, t, t, t, t, t);
-        g.f("            num = fma(dn, dold, num); den = fma(dold, dold, den); nn = fma(dn, dn, nn);");
-        g.f("            num2 = fma(dold, dolder, num2); den2 = fma(dolder, dolder, den2); }");
-      }
-      g.f("          double alpha = den > 0.0 ? num * fast_rcp(den) : 0.0;");
-      g.f("          alpha = fmin(fmax(alpha, 0.0), 2.0);");
-      g.f("          const double beta = den2 > 0.0 ? num2 * fast_rcp(den2) : 0.0;");
-      g.f("          const bool line = ok2 && alpha > 0.0 && beta >= 1e-3 && beta <= 2.0 && num * num >= 0.98 * nn * den && num2 * num2 >= 0.98 * den * den2;");
-      g.f("          const double bq = line ? fast_rcp(beta) : 1.0;");
-      g.f("          const double r1q = fast_rcp(1.0 + bq);");
-      g.f("          const double l0 = line ? (alpha + 1.0) * (alpha + 1.0 + bq) * r1q : 1.0 + alpha;");
-      g.f("          const double l1 = line ? -alpha * (alpha + 1.0 + bq) * beta : -alpha;");
-      g.f("          const double l2 = line ? alpha * (alpha + 1.0) * r1q * beta : 0.0;");
-      for (int i = 0; i < n; ++i)
-        g.f("          { const double xd = x%d, xo = r1[%d], xpo = ok2 ? r2[%d] : xd, xqo = ok3 ? r3[%d] : xd; x%d = fma(l0, xo, fma(l1, xpo, l2 * xqo)); }",
-            i, 64 * i, 64 * i, 64 * i, i);
-      g.f("        }");
-      g.f("      }");
-    } else {
-      g.f("    {");
-      g.f("      const bool valid = have;");
-      g.f("      const long long bb = first_b;");
-      for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
+  }
+
+  void body_chain_start(const LaneBody& b) {
+    g.f("    int hist = 1;");
+    g.f("    double lambda_carry = 0.0;");
+    g.f("    for (long long b = first_b; wave_any(have && b < last_b); ++b) {");
+    g.f("      const bool valid = have && b < last_b;");
+    g.f("      const long long bb = valid ? b : last_b - 1;");
+    g.f("      const long long nb = b + 1 < last_b ? b + 1 : last_b - 1;");
+    for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
+    for (int t = 0; t < T; ++t) g.f("      tn%d = a.targets[nb * %d + %d];", t, T, t);
+    // extrapolation along the chain: secant / quadratic through the last solved states
+    g.f("      if (hist >= 2) {");
+    g.f("        double num = 0.0, den = 0.0, nn = 0.0, num2 = 0.0, den2 = 0.0;");
+    for (int t = 0; t < T; ++t) {
+      g.f("        { const double dn = tv%d - tp%d, dold = tp%d - tq%d, dolder = tq%d - tr%d;", t, t, t, t, t, t);
+      g.f("          num = fma(dn, dold, num); den = fma(dold, dold, den); nn = fma(dn, dn, nn);");
+      g.f("          num2 = fma(dold, dolder, num2); den2 = fma(dolder, dolder, den2); }");
     }
+    g.f("        double alpha = den > 0.0 ? num * fast_rcp(den) : 0.0;");
+    g.f("        alpha = fmin(fmax(alpha, 0.0), 2.0);");
+    g.f("        const double beta = den2 > 0.0 ? num2 * fast_rcp(den2) : 0.0;");
+    g.f("        const bool line = hist >= 3 && alpha > 0.0 && beta >= 1e-3 && beta <= 2.0 && num * num >= 0.98 * nn * den && num2 * num2 >= 0.98 * den * den2;");
+    g.f("        const double bq = line ? fast_rcp(beta) : 1.0;");
+    g.f("        const double r1q = fast_rcp(1.0 + bq);");
+    g.f("        const double l0 = line ? (alpha + 1.0) * (alpha + 1.0 + bq) * r1q : 1.0 + alpha;");
+    g.f("        const double l1 = line ? -alpha * (alpha + 1.0 + bq) * beta : -alpha;");
+    g.f("        const double l2 = line ? alpha * (alpha + 1.0) * r1q * beta : 0.0;");
+    for (int i = 0; i < n; ++i)
+      g.f("        { const double xo = x%d, xpo = xp%d; const double xn = fma(l0, xo, fma(l1, xpo, l2 * xq%d)); xq%d = xpo; xp%d = xo; x%d = xn; }", i, i, i, i, i, i);
+    g.f("      } else {");
+    for (int i = 0; i < n; ++i) g.f("        { const double xo = x%d; xq%d = xp%d; xp%d = xo; }", i, i, i, i);
+    g.f("      }");
+  }
+
+  void body_nested_start(const LaneBody& b) {
+    // Nested start: the Lagrange interpolant, in the step index, of the nearest steps this wave unit has solved (own and
+    // neighbour lanes'), over whichever of eight candidates exist - four on either side inside the wave unit, so that the
+    // lanes at its ends still have four or five on one side: a unit-step takes the passes of its slowest lane.  Entry
+    // [step of four]: n coordinates, converged?, damping, contraction constant.  No candidate (a neighbourhood that
+    // failed): the design state, like a chain that restarts.
+    const int E = (n + 3) * 64, K = 8;
+    struct Cand { int dl, q, o; };
+    const Cand cand[3][K] = {
+        {{-3, 0, -14}, {-2, 0, -10}, {-1, 0, -6}, {0, 0, -2}, {1, 0, 2}, {2, 0, 6}, {3, 0, 10}, {4, 0, 14}},          // second step (third of the four)
+        {{-2, 0, -9}, {-2, 1, -7}, {-1, 0, -5}, {-1, 1, -3}, {0, 0, -1}, {0, 1, 1}, {1, 0, 3}, {1, 1, 5}},            // third step (second of the four)
+        {{-1, 2, -6}, {-1, 1, -5}, {0, 0, -3}, {0, 2, -2}, {0, 1, -1}, {1, 0, 1}, {1, 2, 2}, {1, 1, 3}}};             // fourth step
+    g.f("    {");
+    for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
+    g.f("      double lambda_carry = 0.0, cq_carry = 0.0;");
+    g.f("      if (step > 0) {");
+    // (entries stored by other lanes of THIS wavefront, through the same L1: its vector-memory instructions execute in
+    //  order, so what separates the stores from these loads is an ordering for the compiler - an agent-scope release
+    //  would wait for every record store in flight)
+    g.f("        WAVE_SYNC();");
+    // (opaque: derived from a loop invariant, every candidate address of every coordinate would be hoisted out of the
+    //  unit-step loop, kept alive across the passes and spilled - a kilobyte of scratch, read back at memory latency)
+    g.f("        const double* rb = ring - lane;  // this wavefront's entries [step][slot][lane]");
+    g.f("        asm volatile(\"\" : \"+v\"(rb));");
+    // Few round trips per unit-step: the lane's own first entry (damping, contraction constant), the candidates' flags and
+    // their coordinates - half of the coordinates at a time - are loaded unconditionally (clamped lane indices: every
+    // address is a valid entry) and pinned as a batch; flags, weights and selects afterwards.  (As written first - flags,
+    // then per coordinate the loads under `v ? load : 0` - the compiler issued 20-odd dependent round trips to the
+    // Infinity Cache: 14 us per unit-step, tools/lane_timeline.py c5nest.)
+    g.f("        const double own_ok = rb[%d + lane], own_lambda = rb[%d + lane], own_cq = rb[%d + lane];", 64 * n, 64 * (n + 1), 64 * (n + 2));
+    g.f("        bool v0 = false, v1 = false, v2 = false, v3 = false, v4 = false, v5 = false, v6 = false, v7 = false;");
+    g.f("        double w0 = 0.0, w1 = 0.0, w2 = 0.0, w3 = 0.0, w4 = 0.0, w5 = 0.0, w6 = 0.0, w7 = 0.0;");
+    for (int q = 1; q <= 3; ++q) {
+      g.f("        %sif (step == %d) {", q > 1 ? "else " : "", q);
+      std::string fpin = "          asm volatile(\"\" : ";
+      for (int j = 0; j < K; ++j) {
+        const Cand& c = cand[q - 1][j];
+        g.f("          const int lc%d = lane + (%d) < 0 ? 0 : (lane + (%d) > 63 ? 63 : lane + (%d));", j, c.dl, c.dl, c.dl);
+        g.f("          const double* en%d = rb + %d + lc%d;", j, c.q * E, j);
+        g.f("          double f%d = en%d[%d];", j, j, 64 * n);
+        fpin += std::string(j ? ", " : "") + "\"+v\"(f" + std::to_string(j) + ")";
+      }
+      for (int half = 0; half < 2; ++half) {
+        const int i0 = half * ((n + 1) / 2), i1 = half ? n : (n + 1) / 2;
+        g.f("          __builtin_amdgcn_sched_barrier(0);");
+        g.f("          {");
+        for (int i = i0; i < i1; ++i)
+          for (int j = 0; j < K; ++j) g.f("            double t%d_%d = en%d[%d];", j, i, j, 64 * i);
+        if (half == 0) g.out += fpin + ");\n";
+        for (int i = i0; i < i1; i += 3) {  // (an asm statement takes 30 operands)
+          std::string pin = "            asm volatile(\"\" : ";
+          bool first = true;
+          for (int k = i; k < i + 3 && k < i1; ++k)
+            for (int j = 0; j < K; ++j) {
+              pin += std::string(first ? "" : ", ") + "\"+v\"(t" + std::to_string(j) + "_" + std::to_string(k) + ")";
+              first = false;
+            }
+          g.out += pin + ");\n";
+        }
+        if (half == 0) {
+          for (int j = 0; j < K; ++j) {
+            const Cand& c = cand[q - 1][j];
+            g.f("            v%d = lane + (%d) >= 0 && lane + (%d) < 64 && f%d > 0.5;", j, c.dl, c.dl, j);
+          }
+          for (int j = 0; j < K; ++j) {
+            std::string w = "1.0";
+            for (int k = 0; k < K; ++k) {
+              if (k == j) continue;
+              char buf[96];
+              std::snprintf(buf, sizeof(buf), " * (v%d ? %.17g : 1.0)", k, (0.0 - cand[q - 1][k].o) / (double)(cand[q - 1][j].o - cand[q - 1][k].o));
+              w += buf;
+            }
+            g.f("            w%d = v%d ? %s : 0.0;", j, j, w.c_str());
+          }
+        }
+        g.f("            if (v0 || v1 || v2 || v3 || v4 || v5 || v6 || v7) {");
+        for (int i = i0; i < i1; ++i) {
+          std::string e;
+          for (int j = 0; j < K; ++j) e += std::string(j ? " + " : "") + "w" + std::to_string(j) + " * (v" + std::to_string(j) + " ? t" + std::to_string(j) + "_" + std::to_string(i) + " : 0.0)";
+          g.f("              x%d = %s;", i, e.c_str());
+        }
+        g.f("            }");
+        g.f("          }");
+        if (half == 0) continue;
+      }
+      g.f("        }");
+    }
+    g.f("        if (own_ok > 0.5) { lambda_carry = own_lambda; cq_carry = own_cq; }  // (the lane's own first step)");
+    g.f("      }");
+  }
+
+  void body_flat_start(const LaneBody& b) {
+    // Start of a chain step: from the ring of this lane's chain - the last three steps' solutions, whether each
+    // converged, the damping the last one ended with - exactly what the looping chain body keeps in x / xp / xq, hist
+    // and lambda_carry (the design state stands in for solutions the chain does not have yet; a predecessor that did
+    // not converge restarts the chain from the design state).
+    const int E = (n + 2) * 64;
+    g.f("    {");
+    for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
+    g.f("      double lambda_carry = 0.0;");
+    g.f("      if (step > 0) {");
+    g.f("        const double* r1 = ring + ((step + 2) %% 3) * %d;", E);
+    g.f("        const double* r2 = ring + ((step + 1) %% 3) * %d;", E);
+    g.f("        const double* r3 = ring + (step %% 3) * %d;", E);
+    g.f("        const bool ok1 = r1[%d] > 0.5, ok2 = ok1 && step >= 2 && r2[%d] > 0.5, ok3 = ok2 && step >= 3 && r3[%d] > 0.5;", 64 * n, 64 * n, 64 * n);
+    g.f("        if (ok1) {");
+    g.f("          lambda_carry = r1[%d];", 64 * (n + 1));
+    g.f("          const long long b2 = step >= 2 ? bb - 2 : bb, b3 = step >= 3 ? bb - 3 : bb;");
+    for (int t = 0; t < T; ++t)
+      g.f("          const double tp%d = a.targets[(bb - 1) * %d + %d], tq%d = ok2 ? a.targets[b2 * %d + %d] : td%d, tr%d = ok3 ? a.targets[b3 * %d + %d] : td%d;",
+          t, T, t, t, T, t, t, t, T, t, t);
+    g.f("          double num = 0.0, den = 0.0, nn = 0.0, num2 = 0.0, den2 = 0.0;");
+    for (int t = 0; t < T; ++t) {
+      g.f("          { const double dn = tv%d - tp%d, dold = tp%d - tq%d, dolder = tq%d - tr%d;", t, t, t, t, t, t);
+      g.f("            num = fma(dn, dold, num); den = fma(dold, dold, den); nn = fma(dn, dn, nn);");
+      g.f("            num2 = fma(dold, dolder, num2); den2 = fma(dolder, dolder, den2); }");
+    }
+    g.f("          double alpha = den > 0.0 ? num * fast_rcp(den) : 0.0;");
+    g.f("          alpha = fmin(fmax(alpha, 0.0), 2.0);");
+    g.f("          const double beta = den2 > 0.0 ? num2 * fast_rcp(den2) : 0.0;");
+    g.f("          const bool line = ok2 && alpha > 0.0 && beta >= 1e-3 && beta <= 2.0 && num * num >= 0.98 * nn * den && num2 * num2 >= 0.98 * den * den2;");
+    g.f("          const double bq = line ? fast_rcp(beta) : 1.0;");
+    g.f("          const double r1q = fast_rcp(1.0 + bq);");
+    g.f("          const double l0 = line ? (alpha + 1.0) * (alpha + 1.0 + bq) * r1q : 1.0 + alpha;");
+    g.f("          const double l1 = line ? -alpha * (alpha + 1.0 + bq) * beta : -alpha;");
+    g.f("          const double l2 = line ? alpha * (alpha + 1.0) * r1q * beta : 0.0;");
+    for (int i = 0; i < n; ++i)
+      g.f("          { const double xd = x%d, xo = r1[%d], xpo = ok2 ? r2[%d] : xd, xqo = ok3 ? r3[%d] : xd; x%d = fma(l0, xo, fma(l1, xpo, l2 * xqo)); }",
+          i, 64 * i, 64 * i, 64 * i, i);
+    g.f("        }");
+    g.f("      }");
+  }
+
+  void body_plain_start(const LaneBody& b) {
+    g.f("    {");
+    g.f("      const bool valid = have;");
+    g.f("      const long long bb = first_b;");
+    for (int t = 0; t < T; ++t) g.f("      const double tv%d = tn%d;", t, t);
+  }
+
+  void body_lm_open(const LaneBody& b) {
     g.f("      double Fc = 0.0, lambda = 0.0, nu = 2.0, dmax = 0.0, step_len = 0.0, last_step = 0.0, mres = 0.0, pred = 0.0;");
     g.f("      int nfev = 0, iters = 0, flags = 0, nfail = 0;");
     g.f("      int mode = 0;  // 0 first evaluation, 1 trial point, 2 re-evaluation of the accepted point");
     g.f("      bool done = GIVEN || !valid, want_light = false;");
     g.f("      double prev_sl = 0.0, piv_lo = 0.0, piv_hi = 0.0;");
-    if (ns) g.f("      double cq_seen = 0.0;");
-    g.f("      if (head_ready%s) {", ch ? " && b == first_b" : "");
-    g.f("        const bool at_design = valid%s && hs4 > 0.5;", ch ? " && hist == 1" : "");
+    if (b.ns) g.f("      double cq_seen = 0.0;");
+    g.f("      if (head_ready%s) {", b.ch ? " && b == first_b" : "");
+    g.f("        const bool at_design = valid%s && hs4 > 0.5;", b.ch ? " && hist == 1" : "");
     g.f("        if (at_design) {");
     g.f("          Fc = 0.5 * hss; mres = hmr; dmax = hs0; lambda = a.lambda0 * dmax;");
     g.f("          step_len = hstep; pred = 0.5 * fma(lambda, hN, hM); iters = 1; mode = 1;");
@@ -1942,21 +1987,20 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("        } else {");
     for (int i = 0; i < n; ++i) g.f("          dx%d = 0.0;", i);
     g.f("        }");
-    g.f("      }%s", ch ? " else {" : "");
-    if (ch) {
+    g.f("      }%s", b.ch ? " else {" : "");
+    if (b.ch) {
       for (int i = 0; i < n; ++i) g.f("        dx%d = 0.0;", i);
       g.f("      }");
     }
     // Two nested loops: the inner one runs full passes while any lane needs one; when every active lane only has a step to
     // confirm, the outer loop takes the residual-only pass and comes back (a lane whose step is not confirmed goes on with
     // full passes).  Same order of evaluations as one loop with the confirming pass as a branch at its top.
-    const bool nested = light_ok;
-    stamp(2);
-    if (nested) {
+    stamp(b, 2);
+    if (light_ok) {
       g.f("      while (wave_any(!done)) {");
-      g.f("    %s", refresh_kz);
+      g.f("    %s", b.refresh_kz.c_str());
       g.f("    if (a.confirm == 0 && !wave_any(!done && !want_light)) {");
-      if (tl) g.f("      tl_light += 1.0;");
+      if (b.tl) g.f("      tl_light += 1.0;");
       for (int i = 0; i < n; ++i) g.f("      %s = x%d + dx%d;", PF(i).c_str(), i, i);
       g.out += light_src;
       g.f("      const double Fl = 0.5 * ss;");
@@ -1971,35 +2015,20 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("      }");
       g.f("    }");
       g.f("    while (wave_any(!done) && (a.confirm != 0 || wave_any(!done && !want_light))) {");
-      g.f("    %s", refresh_kz);
+      g.f("    %s", b.refresh_kz.c_str());
       g.f("    want_light = false;");
-      if (tl) g.f("    __builtin_amdgcn_sched_barrier(0); tl_full += 1.0; tl_at = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);");
+      if (b.tl) g.f("    __builtin_amdgcn_sched_barrier(0); tl_full += 1.0; tl_at = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);");
     } else {
     g.f("      while (wave_any(!done)) {");
-    g.f("    %s", refresh_kz);
-    if (light_ok) {
-      g.f("    if (a.confirm == 0 && !wave_any(!done && !want_light)) {");
-      for (int i = 0; i < n; ++i) g.f("      %s = x%d + dx%d;", PF(i).c_str(), i, i);
-      g.out += light_src;
-      g.f("      const double Fl = 0.5 * ss;");
-      g.f("      if (!done) {");
-      g.f("        ++nfev;");
-      g.f("        if (Fl == Fl && Fl <= Fc * (1.0 + 1e-6) + 1e-28) {");
-      for (int i = 0; i < n; ++i) g.f("          x%d = %s;", i, PF(i).c_str());
-      g.f("          Fc = Fl; mres = mres_new; last_step = step_len; flags |= INFO_CONVERGED; done = true;");
-      g.f("        } else {");
-      g.f("          want_light = false;");
-      g.f("        }");
-      g.f("      }");
-      g.f("      continue;");
-      g.f("    }");
-      g.f("    want_light = false;");
+    g.f("    %s", b.refresh_kz.c_str());
     }
-    }
-    mark(1);
+  }
+
+  void body_lm_pass(const LaneBody& b) {
+    mark(b, 1);
     for (int i = 0; i < n; ++i) g.f("    %s = mode == 2 ? x%d : x%d + dx%d;", PF(i).c_str(), i, i, i);
-    g.out += (ch ? pass_chain : pass_cold).eval;  // (the flat chain body runs the independent-solve body's pass)
-    mark(2);
+    g.out += (b.ch ? pass_chain : b.pass).eval;  // (the flat chain body runs the independent-solve body's pass)
+    mark(b, 2);
     g.f("    const double Ft = 0.5 * ss;");
     g.f("    bool accept = true, stop = false, compromise = false;");
     g.f("    double rho = 1.0;");
@@ -2013,9 +2042,9 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("    }");
     g.f("    double diag = 0.0, gm = 0.0;");
     g.f("    if (wave_any(mode == 0)) {");
-    if (!ch && evc.late_diag) {
+    if (!b.ch && b.gen.late_diag) {
       auto same = [](const std::string& nm) { return nm; };
-      for (int i = 0; i < n; ++i) g.f("      diag = fmax(diag, %s);", evc.diag_expr(i, same).c_str());
+      for (int i = 0; i < n; ++i) g.f("      diag = fmax(diag, %s);", b.gen.diag_expr(i, same).c_str());
     } else {
       for (int i = 0; i < n; ++i) g.f("      diag = fmax(diag, %s);", LGen::A(i, i).c_str());
     }
@@ -2027,7 +2056,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("    } else if (a.grad_tol < 0.0) {");
     g.f("      const double rr = 2.0 * Ft;");
     for (int i = 0; i < n; ++i) {
-      const std::string aii = (!ch && evc.late_diag) ? evc.diag_expr(i, [](const std::string& nm) { return nm; }) : LGen::A(i, i);
+      const std::string aii = (!b.ch && b.gen.late_diag) ? b.gen.diag_expr(i, [](const std::string& nm) { return nm; }) : LGen::A(i, i);
       g.f("      { const double cn = %s * rr; gm = fmax(gm, cn > 0.0 ? fabs(%s) * __builtin_amdgcn_rsq(cn) : 0.0); }", aii.c_str(), LGen::gn(i).c_str());
     }
     g.f("    }");
@@ -2046,7 +2075,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("        if (!stop) {");
     g.f("          if (mode == 0) {");
     g.f("            dmax = diag; lambda = a.lambda0 * dmax;");
-    if (ch || fl) g.f("            if (lambda_carry > 0.0) lambda = fmin(lambda, lambda_carry);");
+    if (b.ch || b.fl) g.f("            if (lambda_carry > 0.0) lambda = fmin(lambda, lambda_carry);");
     g.f("          }");
     g.f("          else if (mode == 1 && rho > 1e-4) {");
     g.f("            const double t = 2.0 * rho - 1.0;");
@@ -2062,11 +2091,11 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("    const bool solve_now = !done && accept;");
     g.f("    if (!done && !accept) mode = 2;");
     g.f("    if (wave_any(solve_now)) {");
-    mark(3);
-    g.out += (ch ? pass_chain : pass_cold).factor;
-    mark(4);
-    g.out += (ch ? pass_chain : pass_cold).subst;
-    mark(5);
+    mark(b, 3);
+    g.out += (b.ch ? pass_chain : b.pass).factor;
+    mark(b, 4);
+    g.out += (b.ch ? pass_chain : b.pass).subst;
+    mark(b, 5);
     g.f("    double sl = 0.0, pr = 0.0, dd = 0.0;");
     for (int i = 0; i < n; ++i) g.f("    sl = fmax(sl, fabs(nx%d));", i);
     for (int i = 0; i < n; ++i) g.f("    pr = fma(nx%d, fma(lambda, nx%d, -%s), pr); dd = fma(nx%d, nx%d, dd);", i, i, LGen::gn(i).c_str(), i, i);
@@ -2082,7 +2111,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("        step_len = sl; pred = pr;");
     g.f("        if (sl <= a.step_tol) { flags |= INFO_CONVERGED; last_step = sl; done = true; }");
     g.f("        else {");
-    if (ns) {
+    if (b.ns) {
       // (a warm-started step has no earlier step of its own to read the quadratic contraction from: the constant its lane
       //  observed on the first of its four steps - same mechanism, same place on the solution manifold - stands in for
       //  the 1 / mm a cold problem's first step is given)
@@ -2092,7 +2121,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("          const double cq = prev_sl > 0.0 ? fmax(3.0 * sl * fast_rcp(prev_sl * prev_sl), 1e-3) : 1.0;");
     g.f("          const double rho_lin = 100.0 * lambda * fast_rcp(pmin);");
     g.f("          want_light = sl <= 1e-3 && (rho_lin + cq * sl) * sl <= a.step_tol;");
-    if (ns) {
+    if (b.ns) {
       // Nested mode, interpolated starts: the start is ~1e-8 mm from the solution and this Gauss-Newton step lands within
       // a THOUSANDTH of step_tol of it by the same prediction that otherwise asks for a confirming evaluation.  With that
       // margin the step is taken as it is - one pass per step instead of a pass and a confirming pass (which costs a lone
@@ -2113,18 +2142,21 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("        mode = 2;");
     g.f("      }");
     g.f("    }");
-    mark(6);
+    mark(b, 6);
     g.f("    }  // any lane solves");
-    if (nested) g.f("    }  // full passes");
+    if (light_ok) g.f("    }  // full passes");
     g.f("      }  // LM passes");
-    stamp(3);
-    if (tl) {
-      g.f("    if (a.trace && lane == 0) { double* tr = a.trace + %s * 32; tr[4] = tl_full; tr[5] = tl_light; tr[6] = tl_sec1; tr[7] = tl_sec2;", ns ? "it" : "wu");
+    stamp(b, 3);
+    if (b.tl) {
+      g.f("    if (a.trace && lane == 0) { double* tr = a.trace + %s * 32; tr[4] = tl_full; tr[5] = tl_light; tr[6] = tl_sec1; tr[7] = tl_sec2;", b.ns ? "it" : "wu");
       g.f("      tr[8] = tl_sec3; tr[9] = tl_sec4; tr[10] = tl_sec5; tr[11] = tl_sec6; }");
     }
+  }
+
+  void body_final_state(const LaneBody& b) {
     // final state and output
     g.f("      {");
-    g.f("    %s", refresh_kz);
+    g.f("    %s", b.refresh_kz.c_str());
     for (int i = 0; i < n; ++i) g.f("    %s = x%d;", PF(i).c_str(), i);
     if (EV) g.f("    {  // (the evaluated module needs every derived point: records or not)");
     else
@@ -2133,12 +2165,12 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
     g.f("    }");
     g.f("    if (mres > a.residual_tolerance) flags |= INFO_RESIDUAL_EXCEEDED;");
     g.f("    if (piv_hi > 0.0 && piv_lo <= ILL_CONDITIONED_PIVOT_RATIO * piv_hi) flags |= INFO_ILL_CONDITIONED;");
-    if (ch) {
+    if (b.ch) {
       // chain bookkeeping
       for (int t = 0; t < T; ++t) g.f("    tr%d = tq%d; tq%d = tp%d; tp%d = tv%d;", t, t, t, t, t, t);
       g.f("    if (!(flags & INFO_CONVERGED) || (flags & INFO_FAILED)) {");
       for (int i = 0; i < n; ++i)
-        if (sc) g.f("      x%d = GL(%d);", i, ev.gl_gp0 + 3 * ev.fp(i / 3) + i % 3);
+        if (b.sc) g.f("      x%d = GL(%d);", i, ev.gl_gp0 + 3 * ev.fp(i / 3) + i % 3);
         else g.f("      x%d = gp[%d];", i, 3 * ev.fp(i / 3) + i % 3);
       g.f("      hist = 1; lambda_carry = 0.0;");
       for (int t = 0; t < T; ++t) g.f("      tp%d = td%d;", t, t);
@@ -2147,252 +2179,400 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
       g.f("      lambda_carry = lambda;");
       g.f("    }");
     }
-    if (fl && ns) {
+    if (b.fl && b.ns) {
       g.f("    { double* r0 = ring + step * %d;  // this step's entry: solution, converged?, damping, contraction constant", (n + 3) * 64);
       g.f("      _Pragma(\"unroll 6\")");
       g.f("      for (int i = 0; i < %d; ++i) r0[64 * i] = lds[128 * i + lane];  // (x{i})", n);
       g.f("      r0[%d] = ((flags & INFO_CONVERGED) && !(flags & INFO_FAILED)) ? 1.0 : 0.0; r0[%d] = lambda; r0[%d] = cq_seen > 0.0 ? cq_seen : cq_carry;", 64 * n, 64 * (n + 1), 64 * (n + 2));
       g.f("      WAVE_SYNC(); }");
-    } else if (fl) {
+    } else if (b.fl) {
       g.f("    { double* r0 = ring + (step %% 3) * %d;  // this step's entry: solution, converged?, damping", (n + 2) * 64);
       for (int i = 0; i < n; ++i) g.f("      r0[%d] = x%d;", 64 * i, i);
       g.f("      r0[%d] = ((flags & INFO_CONVERGED) && !(flags & INFO_FAILED)) ? 1.0 : 0.0; r0[%d] = lambda; }", 64 * n, 64 * (n + 1));
     }
-    stamp(13);
+    stamp(b, 13);
     g.f("    if (valid && !GIVEN) {");
     g.f("      okx_info inf; inf.max_residual = mres; inf.cost = Fc; inf.last_step = last_step;");
     g.f("      inf.iterations = iters; inf.nfev = nfev; inf.flags = flags; inf.reserved = 0;");
     g.f("      a.info[bb] = inf;");
     g.f("    }");
-    stamp(14);
-    if (!ch && !fl) {
-      // Records of independent solves: the 64 problems of a wave unit are consecutive, their records one contiguous
-      // block: transposed through LDS (which the state no longer needs) and written as full 16-byte-per-lane rows.
-      // (okx_solve_opts.output: the full record, the free points alone in the program's free_point order, or nothing)
-      if (EV) {  // (the evaluated module's kernels take the output mode at run time)
-        g.f("      const bool full_rec = a.out_mode == 0;");
-        g.f("      if (a.out_mode != 2) {");
-        g.f("      const int rec = full_rec ? %d : %d;", 3 * P.n_out, n);
-        g.f("      WAVE_SYNC();");
-        g.f("      if (full_rec) {");
-      } else {
-      g.f("      if (FULL || a.out_mode == 1) {");
-      g.f("      const int rec = FULL ? %d : %d;", 3 * P.n_out, n);
+    stamp(b, 14);
+  }
+
+  void body_cold_records(const LaneBody& b) {
+    // Records of independent solves: the 64 problems of a wave unit are consecutive, their records one contiguous
+    // block: transposed through LDS (which the state no longer needs) and written as full 16-byte-per-lane rows.
+    // (okx_solve_opts.output: the full record, the free points alone in the program's free_point order, or nothing)
+    if (EV) {  // (the evaluated module's kernels take the output mode at run time)
+      g.f("      const bool full_rec = a.out_mode == 0;");
+      g.f("      if (a.out_mode != 2) {");
+      g.f("      const int rec = full_rec ? %d : %d;", 3 * P.n_out, n);
       g.f("      WAVE_SYNC();");
-      g.f("      if (FULL) {");
-      }
-      g.f("      double* st = lds + lane * %d;", 3 * P.n_out);
-      for (int k = 0; k < P.n_out; ++k)
-        for (int c = 0; c < 3; ++c) g.f("      st[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
-      g.f("      } else {");
-      g.f("      double* st = lds + lane * %d;", n);
-      for (int i = 0; i < n; ++i) g.f("      st[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
-      g.f("      }");
-      g.f("      WAVE_SYNC();");
-      stamp(17);
-      if (sub_body) {
-        // strided bodies: the wave unit's records lie SUB problems apart - lane = column of a record, pointer bumps
-        g.f("      if (SUB != 1) {");
-        g.f("        const int per = 64 / rec > 0 ? 64 / rec : 1;");
-        g.f("        const int sub = lane / rec, col = lane - sub * rec;");
-        g.f("        const long long sb = span_idx * span + wave_in_span * 64 * SUB + sub_off, sl_ = (span_idx + 1) * span;");
-        g.f("        const long long n_rows = (sl_ - sb + SUB - 1) / SUB;");
-        g.f("        const int rows = (int)(n_rows < 64 ? (n_rows > 0 ? n_rows : 0) : 64);");
-        g.f("        double* op = a.out_pos + (sb + (long long)sub * SUB) * rec + col;");
-        g.f("        const double* ip = lds + sub * rec + col;");
-        g.f("        if (sub < per) {");
-        g.f("          _Pragma(\"unroll 8\")");
-        g.f("          for (int r = sub; r < rows; r += per) { *op = *ip; op += (long long)per * SUB * rec; ip += per * rec; }");
-        g.f("        }");
-        g.f("      } else {");
-      }
-      g.f("      const long long base_b = span_idx * span + wave_in_span * 64;");
-      g.f("      const long long rem = (span_idx + 1) * span - base_b;");
-      g.f("      const int n_doubles = (int)(rem < 64 ? rem : 64) * rec;");
-      g.f("      double* dst = a.out_pos + base_b * rec;");
-      g.f("      double2* dst2 = reinterpret_cast<double2*>(dst);");
-      g.f("      const double2* src2 = reinterpret_cast<const double2*>(lds);");
-      // (measured: the same copy with a fixed trip count, unrolled - the compiler hoists its 23 store addresses out of the
-      //  wave-unit loop and spills them; no faster where it did not)
-      g.f("      if ((reinterpret_cast<unsigned long long>(dst) & 15ull) == 0ull) {");
-      g.f("        for (int i = lane; i < n_doubles / 2; i += 64) dst2[i] = src2[i];");
-      g.f("        if ((n_doubles & 1) && lane == 0) dst[n_doubles - 1] = lds[n_doubles - 1];");
-      g.f("      } else {");
-      g.f("        for (int i = lane; i < n_doubles; i += 64) dst[i] = lds[i];");
-      g.f("      }");
-      if (sub_body) g.f("      }");
-      g.f("      WAVE_SYNC();");
-      g.f("      }");
-      stamp(15);
-      if (EV) {
-        // ---- evaluated epilogue (see okx_quadgen.cpp for the quad form): J at the solved state, undamped LDL^T with one
-        // substitution per target, the points' velocities in forward mode, then the metric catalog on duals with all T
-        // directions - role points and their velocities straight from this lane's registers.  Rows leave through LDS
-        // ([lane][25]: an odd stride) as 192-byte fragments of the [problem][1 + T][24] records.
-        LGen& eg = gb ? epg : epc;
-        const EpiSrc& ep = gb ? epi_g : epi_cold;
-        const int REC = 3 * P.n_out, RS = REC | 1, EVC = OKX_EVAL_COLUMNS;
-        g.f("      {");
-        g.f("      WAVE_SYNC();  // (the record copy's last LDS reads are done)");
-        g.f("      %s", refresh_kz);
-        g.out += ep.eval;
-        g.f("      const double lambda = 0.0;  // (an undamped factorisation; shadows the solve's damping)");
-        g.out += ep.factor;
-        g.out += ep.subst;
-        eg.out.clear();
-        std::vector<std::vector<S3>> vel(T, std::vector<S3>(NP));
-        for (int t = 0; t < T; ++t)
-          for (int F = 0; F < nf; ++F)
-            for (int c = 0; c < 3; ++c) vel[t][eg.fp(F)].c[c] = "tq" + std::to_string(t) + "_" + std::to_string(3 * F + c);
-        for (int e = 0; e < P.n_derived; ++e)
-          if (!eg.derived_jvp(e, vel)) {
-            lds_why = eg.why;
-            return false;
-          }
-        const std::string jvp_src = eg.out;
-        eg.out.clear();
-        g.f("      const double ev_flags = (ok ? 1.0 : 0.0) + ((!ok || pmin <= %d * 2.220446049250313e-16 * pmax) ? 2.0 : 0.0);", n);
-        g.f("      const long long ev_base = span_idx * span + wave_in_span * 64;");
-        g.f("      const long long ev_rem = (span_idx + 1) * span - ev_base;");
-        g.f("      const int ev_rows = (int)(ev_rem < 64 ? ev_rem : 64);");
-        g.f("      if (ea.tan != nullptr) {  // the tangents themselves: [problem][target][record], one target at a time through LDS");
-        g.out += jvp_src;
-        for (int t = 0; t < T; ++t) {
-          g.f("        WAVE_SYNC();");
-          g.f("        { double* st = lds + lane * %d;", RS);
-          for (int k = 0; k < P.n_out; ++k)
-            for (int c = 0; c < 3; ++c) {
-              const std::string& nm = vel[t][P.out_point[k]].c[c];
-              if (nm.empty()) g.f("          st[%d] = ok ? 0.0 : __builtin_nan(\"\");", 3 * k + c);
-              else g.f("          st[%d] = ok ? %s : __builtin_nan(\"\");", 3 * k + c, nm.c_str());
-            }
-          g.f("        }");
-          g.f("        WAVE_SYNC();");
-          g.f("        for (int i = lane; i < ev_rows * %d; i += 64) { const int j = i / %d, col = i - j * %d; ea.tan[((ev_base + j) * %d + %d) * %d + col] = lds[j * %d + col]; }",
-              REC, REC, REC, T, t, REC, RS);
-        }
-        g.f("        WAVE_SYNC();");
-        g.f("      }");
-        g.f("      if (ea.ev != nullptr) {");
-        g.out += jvp_src;
-        g.f("        EvCfg cfg = ea.cfg;");
-        g.f("        if (PG) {  // an ensemble's design references are its geometry's own");
-        g.f("          cfg.design_wheel_center_z = GL(%d); cfg.design_contact_patch_z = GL(%d);", ev.gl_gp0 + 3 * P.out_point[es->wheel_center] + 2,
-            ev.gl_gp0 + 3 * P.out_point[es->contact_patch] + 2);
-        if (es->rack >= 0) g.f("          cfg.design_rack_y = GL(%d);", ev.gl_gp0 + 3 * P.out_point[es->rack] + 1);
-        g.f("        }");
-        g.f("        DV<%d> RP[EV_SLOTS];", T);
-        for (int sl = 0; sl < kEvalSlots; ++sl) {
-          const int k = eval_slot_point(*es, sl);
-          for (int c = 0; c < 3; ++c) {
-            if (k < 0) {
-              g.f("        RP[%d].%c = du_const<%d>(0.0);", sl, "xyz"[c], T);
-              continue;
-            }
-            const int pnt = P.out_point[k];
-            g.f("        RP[%d].%c.v = p%d_%d;", sl, "xyz"[c], pnt, c);
-            for (int t = 0; t < T; ++t) {
-              const std::string& nm = vel[t][pnt].c[c];
-              g.f("        RP[%d].%c.d[%d] = %s;", sl, "xyz"[c], t, nm.empty() ? "0.0" : ("(ok ? " + nm + " : __builtin_nan(\"\"))").c_str());
-            }
-          }
-        }
-        g.f("        Du<%d> em[%d];", T, OKX_METRIC_COUNT);
-        g.f("        ev_corner_metrics<%d>(cfg, RP, em);", T);
-        for (int r = 0; r <= T; ++r) {
-          g.f("        WAVE_SYNC();");
-          g.f("        { double* st = lds + lane * 25;");
-          if (r == 0) {
-            for (int k = 0; k < OKX_METRIC_COUNT; ++k) g.f("          st[%d] = em[%d].v;", k, k);
-            g.f("          st[19] = pmin; st[20] = pmax; st[21] = ev_flags; st[22] = 0.0; st[23] = 0.0;");
-          } else {
-            for (int k = 0; k < OKX_METRIC_COUNT; ++k) g.f("          st[%d] = em[%d].d[%d];", k, k, r - 1);
-            g.f("          st[19] = RP[EV_SLOT_WHEEL_CENTER].x.d[%d]; st[20] = RP[EV_SLOT_WHEEL_CENTER].y.d[%d]; st[21] = RP[EV_SLOT_WHEEL_CENTER].z.d[%d];", r - 1, r - 1, r - 1);
-            if (es->rack >= 0) g.f("          st[22] = RP[EV_SLOT_RACK].y.d[%d]; st[23] = 0.0;", r - 1);
-            else g.f("          st[22] = __builtin_nan(\"\"); st[23] = 0.0;");
-          }
-          g.f("        }");
-          g.f("        WAVE_SYNC();");
-          g.f("        for (int i = lane; i < ev_rows * %d; i += 64) { const int j = i / %d, c2 = i - j * %d;", EVC / 2, EVC / 2, EVC / 2);
-          g.f("          double2 v2; v2.x = lds[j * 25 + 2 * c2]; v2.y = lds[j * 25 + 2 * c2 + 1];");
-          g.f("          reinterpret_cast<double2*>(ea.ev + ((ev_base + j) * %d + %d) * %d)[c2] = v2; }", 1 + T, r, EVC);
-        }
-        g.f("        WAVE_SYNC();");
-        g.f("      }");
-        g.f("      }");
-      }
-    } else if (ns) {
-      // nested mode: the wave unit's records of this step lie four problems apart - each one a contiguous run of `rec`
-      // doubles: through LDS (which the state no longer needs), every record written by consecutive lanes
-      g.f("    if (FULL || a.out_mode == 1) {");
-      g.f("      constexpr int rec = FULL ? %d : %d;", 3 * P.n_out, n);
-      g.f("      WAVE_SYNC();");
-      g.f("      if (FULL) {");
-      g.f("      double* st = lds + lane * %d;", 3 * P.n_out);
-      for (int k = 0; k < P.n_out; ++k)
-        for (int c = 0; c < 3; ++c) g.f("      st[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
-      g.f("      } else {");
-      g.f("      double* st = lds + lane * %d;", n);
-      for (int i = 0; i < n; ++i) g.f("      st[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
-      g.f("      }");
-      g.f("      WAVE_SYNC();");
-      stamp(17);
-      g.f("      const long long base_b = span_idx * span + wave_in_span * 64 * unit_len + sidx, lim_b = (span_idx + 1) * span;");
-      // lane l copies column l % rec of record (l / rec) of every group of 64 / rec records: one LDS read, one store and a
-      // pointer bump per group (no division, no address arithmetic inside the loop); a record leaves as one contiguous run
-      g.f("      constexpr int per = 64 / rec > 0 ? 64 / rec : 1;  // records per group");
-      g.f("      const int sub = lane / rec, col = lane - sub * rec;");
-      g.f("      const long long n_rows = (lim_b - base_b + unit_len - 1) / unit_len;  // records of this step inside the span");
-      g.f("      const int rows = (int)(n_rows < 64 ? (n_rows > 0 ? n_rows : 0) : 64);");
-      g.f("      double* op = a.out_pos + (base_b + (long long)sub * unit_len) * rec + col;");
-      g.f("      const double* ip = lds + sub * rec + col;");
-      g.f("      if (sub < per) {");
-      g.f("        _Pragma(\"unroll 8\")");
-      g.f("        for (int r = sub; r < rows; r += per) { *op = *ip; op += (long long)per * unit_len * rec; ip += per * rec; }");
-      g.f("      }");
-      g.f("      WAVE_SYNC();");
-      g.f("    }");
-      stamp(15);
+      g.f("      if (full_rec) {");
     } else {
-      // chains: a lane's problems are far apart in memory, every lane stores its own record
-      g.f("    if (valid && FULL) {");
-      g.f("      double* o = a.out_pos + bb * %d;", 3 * P.n_out);
-      for (int k = 0; k < P.n_out; ++k)
-        for (int c = 0; c < 3; ++c) g.f("      o[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
-      g.f("    } else if (valid && !FULL && a.out_mode == 1) {");
-      g.f("      double* o = a.out_pos + bb * %d;", n);
-      for (int i = 0; i < n; ++i) g.f("      o[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
-      g.f("    }");
+    g.f("      if (FULL || a.out_mode == 1) {");
+    g.f("      const int rec = FULL ? %d : %d;", 3 * P.n_out, n);
+    g.f("      WAVE_SYNC();");
+    g.f("      if (FULL) {");
     }
+    g.f("      double* st = lds + lane * %d;", 3 * P.n_out);
+    for (int k = 0; k < P.n_out; ++k)
+      for (int c = 0; c < 3; ++c) g.f("      st[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
+    g.f("      } else {");
+    g.f("      double* st = lds + lane * %d;", n);
+    for (int i = 0; i < n; ++i) g.f("      st[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
+    g.f("      }");
+    g.f("      WAVE_SYNC();");
+    stamp(b, 17);
+    if (b.sub_body) {
+      // strided bodies: the wave unit's records lie SUB problems apart - lane = column of a record, pointer bumps
+      g.f("      if (SUB != 1) {");
+      g.f("        const int per = 64 / rec > 0 ? 64 / rec : 1;");
+      g.f("        const int sub = lane / rec, col = lane - sub * rec;");
+      g.f("        const long long sb = span_idx * span + wave_in_span * 64 * SUB + sub_off, sl_ = (span_idx + 1) * span;");
+      g.f("        const long long n_rows = (sl_ - sb + SUB - 1) / SUB;");
+      g.f("        const int rows = (int)(n_rows < 64 ? (n_rows > 0 ? n_rows : 0) : 64);");
+      g.f("        double* op = a.out_pos + (sb + (long long)sub * SUB) * rec + col;");
+      g.f("        const double* ip = lds + sub * rec + col;");
+      g.f("        if (sub < per) {");
+      g.f("          _Pragma(\"unroll 8\")");
+      g.f("          for (int r = sub; r < rows; r += per) { *op = *ip; op += (long long)per * SUB * rec; ip += per * rec; }");
+      g.f("        }");
+      g.f("      } else {");
+    }
+    g.f("      const long long base_b = span_idx * span + wave_in_span * 64;");
+    g.f("      const long long rem = (span_idx + 1) * span - base_b;");
+    g.f("      const int n_doubles = (int)(rem < 64 ? rem : 64) * rec;");
+    g.f("      double* dst = a.out_pos + base_b * rec;");
+    g.f("      double2* dst2 = reinterpret_cast<double2*>(dst);");
+    g.f("      const double2* src2 = reinterpret_cast<const double2*>(lds);");
+    // (measured: the same copy with a fixed trip count, unrolled - the compiler hoists its 23 store addresses out of the
+    //  wave-unit loop and spills them; no faster where it did not)
+    g.f("      if ((reinterpret_cast<unsigned long long>(dst) & 15ull) == 0ull) {");
+    g.f("        for (int i = lane; i < n_doubles / 2; i += 64) dst2[i] = src2[i];");
+    g.f("        if ((n_doubles & 1) && lane == 0) dst[n_doubles - 1] = lds[n_doubles - 1];");
+    g.f("      } else {");
+    g.f("        for (int i = lane; i < n_doubles; i += 64) dst[i] = lds[i];");
+    g.f("      }");
+    if (b.sub_body) g.f("      }");
+    g.f("      WAVE_SYNC();");
+    g.f("      }");
+    stamp(b, 15);
+  }
+
+  bool body_epilogue(const LaneBody& b) {
+    // ---- evaluated epilogue (see okx_quadgen.cpp for the quad form): J at the solved state, undamped LDL^T with one
+    // substitution per target, the points' velocities in forward mode, then the metric catalog on duals with all T
+    // directions - role points and their velocities straight from this lane's registers.  Rows leave through LDS
+    // ([lane][25]: an odd stride) as 192-byte fragments of the [problem][1 + T][24] records.
+    LGen& eg = b.gb ? epg : epc;
+    const PassSrc& ep = b.gb ? epi_g : epi_cold;
+    const int REC = 3 * P.n_out, RS = REC | 1, EVC = OKX_EVAL_COLUMNS;
+    g.f("      {");
+    g.f("      WAVE_SYNC();  // (the record copy's last LDS reads are done)");
+    g.f("      %s", b.refresh_kz.c_str());
+    g.out += ep.eval;
+    g.f("      const double lambda = 0.0;  // (an undamped factorisation; shadows the solve's damping)");
+    g.out += ep.factor;
+    g.out += ep.subst;
+    eg.out.clear();
+    std::vector<std::vector<S3>> vel(T, std::vector<S3>(NP));
+    for (int t = 0; t < T; ++t)
+      for (int F = 0; F < nf; ++F)
+        for (int c = 0; c < 3; ++c) vel[t][eg.fp(F)].c[c] = "tq" + std::to_string(t) + "_" + std::to_string(3 * F + c);
+    for (int e = 0; e < P.n_derived; ++e)
+      if (!eg.derived_jvp(e, vel)) {
+        why = eg.why;
+        return false;
+      }
+    const std::string jvp_src = eg.out;
+    eg.out.clear();
+    g.f("      const double ev_flags = (ok ? 1.0 : 0.0) + ((!ok || pmin <= %d * 2.220446049250313e-16 * pmax) ? 2.0 : 0.0);", n);
+    g.f("      const long long ev_base = span_idx * span + wave_in_span * 64;");
+    g.f("      const long long ev_rem = (span_idx + 1) * span - ev_base;");
+    g.f("      const int ev_rows = (int)(ev_rem < 64 ? ev_rem : 64);");
+    g.f("      if (ea.tan != nullptr) {  // the tangents themselves: [problem][target][record], one target at a time through LDS");
+    g.out += jvp_src;
+    for (int t = 0; t < T; ++t) {
+      g.f("        WAVE_SYNC();");
+      g.f("        { double* st = lds + lane * %d;", RS);
+      for (int k = 0; k < P.n_out; ++k)
+        for (int c = 0; c < 3; ++c) {
+          const std::string& nm = vel[t][P.out_point[k]].c[c];
+          if (nm.empty()) g.f("          st[%d] = ok ? 0.0 : __builtin_nan(\"\");", 3 * k + c);
+          else g.f("          st[%d] = ok ? %s : __builtin_nan(\"\");", 3 * k + c, nm.c_str());
+        }
+      g.f("        }");
+      g.f("        WAVE_SYNC();");
+      g.f("        for (int i = lane; i < ev_rows * %d; i += 64) { const int j = i / %d, col = i - j * %d; ea.tan[((ev_base + j) * %d + %d) * %d + col] = lds[j * %d + col]; }",
+          REC, REC, REC, T, t, REC, RS);
+    }
+    g.f("        WAVE_SYNC();");
+    g.f("      }");
+    g.f("      if (ea.ev != nullptr) {");
+    g.out += jvp_src;
+    g.f("        EvCfg cfg = ea.cfg;");
+    g.f("        if (PG) {  // an ensemble's design references are its geometry's own");
+    g.f("          cfg.design_wheel_center_z = GL(%d); cfg.design_contact_patch_z = GL(%d);", ev.gl_gp0 + 3 * P.out_point[es->wheel_center] + 2,
+        ev.gl_gp0 + 3 * P.out_point[es->contact_patch] + 2);
+    if (es->rack >= 0) g.f("          cfg.design_rack_y = GL(%d);", ev.gl_gp0 + 3 * P.out_point[es->rack] + 1);
+    g.f("        }");
+    g.f("        DV<%d> RP[EV_SLOTS];", T);
+    for (int sl = 0; sl < kEvalSlots; ++sl) {
+      const int k = eval_slot_point(*es, sl);
+      for (int c = 0; c < 3; ++c) {
+        if (k < 0) {
+          g.f("        RP[%d].%c = du_const<%d>(0.0);", sl, "xyz"[c], T);
+          continue;
+        }
+        const int pnt = P.out_point[k];
+        g.f("        RP[%d].%c.v = p%d_%d;", sl, "xyz"[c], pnt, c);
+        for (int t = 0; t < T; ++t) {
+          const std::string& nm = vel[t][pnt].c[c];
+          g.f("        RP[%d].%c.d[%d] = %s;", sl, "xyz"[c], t, nm.empty() ? "0.0" : ("(ok ? " + nm + " : __builtin_nan(\"\"))").c_str());
+        }
+      }
+    }
+    g.f("        Du<%d> em[%d];", T, OKX_METRIC_COUNT);
+    g.f("        ev_corner_metrics<%d>(cfg, RP, em);", T);
+    for (int r = 0; r <= T; ++r) {
+      g.f("        WAVE_SYNC();");
+      g.f("        { double* st = lds + lane * 25;");
+      if (r == 0) {
+        for (int k = 0; k < OKX_METRIC_COUNT; ++k) g.f("          st[%d] = em[%d].v;", k, k);
+        g.f("          st[19] = pmin; st[20] = pmax; st[21] = ev_flags; st[22] = 0.0; st[23] = 0.0;");
+      } else {
+        for (int k = 0; k < OKX_METRIC_COUNT; ++k) g.f("          st[%d] = em[%d].d[%d];", k, k, r - 1);
+        g.f("          st[19] = RP[EV_SLOT_WHEEL_CENTER].x.d[%d]; st[20] = RP[EV_SLOT_WHEEL_CENTER].y.d[%d]; st[21] = RP[EV_SLOT_WHEEL_CENTER].z.d[%d];", r - 1, r - 1, r - 1);
+        if (es->rack >= 0) g.f("          st[22] = RP[EV_SLOT_RACK].y.d[%d]; st[23] = 0.0;", r - 1);
+        else g.f("          st[22] = __builtin_nan(\"\"); st[23] = 0.0;");
+      }
+      g.f("        }");
+      g.f("        WAVE_SYNC();");
+      g.f("        for (int i = lane; i < ev_rows * %d; i += 64) { const int j = i / %d, c2 = i - j * %d;", EVC / 2, EVC / 2, EVC / 2);
+      g.f("          double2 v2; v2.x = lds[j * 25 + 2 * c2]; v2.y = lds[j * 25 + 2 * c2 + 1];");
+      g.f("          reinterpret_cast<double2*>(ea.ev + ((ev_base + j) * %d + %d) * %d)[c2] = v2; }", 1 + T, r, EVC);
+    }
+    g.f("        WAVE_SYNC();");
+    g.f("      }");
+    g.f("      }");
+    return true;
+  }
+
+  void body_nested_records(const LaneBody& b) {
+    // nested mode: the wave unit's records of this step lie four problems apart - each one a contiguous run of `rec`
+    // doubles: through LDS (which the state no longer needs), every record written by consecutive lanes
+    g.f("    if (FULL || a.out_mode == 1) {");
+    g.f("      constexpr int rec = FULL ? %d : %d;", 3 * P.n_out, n);
+    g.f("      WAVE_SYNC();");
+    g.f("      if (FULL) {");
+    g.f("      double* st = lds + lane * %d;", 3 * P.n_out);
+    for (int k = 0; k < P.n_out; ++k)
+      for (int c = 0; c < 3; ++c) g.f("      st[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
+    g.f("      } else {");
+    g.f("      double* st = lds + lane * %d;", n);
+    for (int i = 0; i < n; ++i) g.f("      st[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
+    g.f("      }");
+    g.f("      WAVE_SYNC();");
+    stamp(b, 17);
+    g.f("      const long long base_b = span_idx * span + wave_in_span * 64 * unit_len + sidx, lim_b = (span_idx + 1) * span;");
+    // lane l copies column l % rec of record (l / rec) of every group of 64 / rec records: one LDS read, one store and a
+    // pointer bump per group (no division, no address arithmetic inside the loop); a record leaves as one contiguous run
+    g.f("      constexpr int per = 64 / rec > 0 ? 64 / rec : 1;  // records per group");
+    g.f("      const int sub = lane / rec, col = lane - sub * rec;");
+    g.f("      const long long n_rows = (lim_b - base_b + unit_len - 1) / unit_len;  // records of this step inside the span");
+    g.f("      const int rows = (int)(n_rows < 64 ? (n_rows > 0 ? n_rows : 0) : 64);");
+    g.f("      double* op = a.out_pos + (base_b + (long long)sub * unit_len) * rec + col;");
+    g.f("      const double* ip = lds + sub * rec + col;");
+    g.f("      if (sub < per) {");
+    g.f("        _Pragma(\"unroll 8\")");
+    g.f("        for (int r = sub; r < rows; r += per) { *op = *ip; op += (long long)per * unit_len * rec; ip += per * rec; }");
+    g.f("      }");
+    g.f("      WAVE_SYNC();");
+    g.f("    }");
+    stamp(b, 15);
+  }
+
+  void body_chain_records(const LaneBody& b) {
+    // chains: a lane's problems are far apart in memory, every lane stores its own record
+    g.f("    if (valid && FULL) {");
+    g.f("      double* o = a.out_pos + bb * %d;", 3 * P.n_out);
+    for (int k = 0; k < P.n_out; ++k)
+      for (int c = 0; c < 3; ++c) g.f("      o[%d] = p%d_%d;", 3 * k + c, P.out_point[k], c);
+    g.f("    } else if (valid && !FULL && a.out_mode == 1) {");
+    g.f("      double* o = a.out_pos + bb * %d;", n);
+    for (int i = 0; i < n; ++i) g.f("      o[%d] = %s;", 3 * ev.perm[i / 3] + i % 3, PF(i).c_str());
+    g.f("    }");
+  }
+
+  bool body(bool ch, bool fl, bool gb, bool ns = false) {
+    LaneBody b{ch, fl, gb, ns, gb ? evg : evc, gb ? pass_g : pass_cold};
+    if (!plan_body(b)) return false;
+    body_signature(b);
+    body_wave_unit_loop(b);
+    body_unit_start(b);
+    body_staging(b);
+    body_state(b);
+    body_head_step(b);
+    if (ch) body_chain_start(b);
+    else if (fl && ns) body_nested_start(b);
+    else if (fl) body_flat_start(b);
+    else body_plain_start(b);
+    body_lm_open(b);
+    body_lm_pass(b);
+    body_final_state(b);
+    if (b.cold) {
+      body_cold_records(b);
+      if (EV && !body_epilogue(b)) return false;
+    } else if (ns) body_nested_records(b);
+    else body_chain_records(b);
     g.f("      }");
     g.f("    }  // chain steps");
     g.f("  }  // wave units");
     g.f("}");
     g.f("");
     return true;
-  };
-  if (EV) {
-    if (!body(false, false, false) || (split_g && !body(false, false, true))) {
-      *why = lds_why;
+  }
+
+  void emit_evaluated_entries() {
+      g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evsolve_u(QEvArgs ea) { okx_lane_body_cold<false, true, false>(ea.q, ea); }");
+      g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evsolve_g(QEvArgs ea) { okx_lane_body_%s<true, true, false>(ea.q, ea); }", split_g ? "coldg" : "cold");
+      {  // okx_evaluate_batch's lane form (reference core/sweep.py:217-245 evaluate_solved_sweep): the epilogue on given states
+        bool all_out = true;
+        std::vector<bool> is_out(NP, false);
+        for (int k = 0; k < P.n_out; ++k) is_out[P.out_point[k]] = true;
+        for (int F = 0; F < nf; ++F) all_out = all_out && is_out[evc.fp(F)];
+        if (all_out) {
+          g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evaluate_u(QEvArgs ea) { okx_lane_body_cold<false, true, true>(ea.q, ea); }");
+          g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evaluate_g(QEvArgs ea) { okx_lane_body_%s<true, true, true>(ea.q, ea); }", split_g ? "coldg" : "cold");
+        }
+      }
+  }
+
+  // ---- parity / debug kernel: r, J^T J, J^T r at given x, and the damped step for a given lambda ----
+  void emit_eval_kernel() {
+    g.f("struct QEvalArgs { const double* x; const double* targets; double* r; double* ata; double* atr; double* dx;");
+    g.f("  double lambda; long long n_problems; const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.f("#undef GL\n#define GL(o) gl[(o) + kz]");
+    g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_eval(QEvalArgs a) {");
+    g.f("  const double* gp = a.design_pos; const double* gq = a.row_param; (void)gq;");
+    g.f("  __shared__ double gl[%d];", gl_size);
+    g.f("  const int lane = threadIdx.x;");
+    g.f("  int kz = 0;");
+    stage_tables(g, "  ");
+    g.f("  __syncthreads();");
+    g.f("  %s", kRefreshKz);
+    g.f("  for (long long wu = blockIdx.x; wu * 64 < a.n_problems; wu += gridDim.x) {");
+    g.f("    long long bb = wu * 64 + threadIdx.x; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;");
+    for (int p = 0; p < NP; ++p)
+      if (used[p] && !is_fixed(p))
+        for (int c = 0; c < 3; ++c) g.f("    double p%d_%d = gp[%d];", p, c, 3 * p + c);
+    for (int i = 0; i < n; ++i) g.f("    %s = a.x[bb * %d + %d];", PF(i).c_str(), n, 3 * ev.perm[i / 3] + i % 3);
+    for (int t = 0; t < T; ++t) g.f("    const double tv%d = a.targets[bb * %d + %d];", t, T, t);
+    {
+      // the parity kernel additionally accumulates the whole lower triangle of J^T J where the rows are (E{i}_{j}): the
+      // solve kernels never hold it in that form
+      LGen ee(P);
+      ee.uid = 500000;
+      ee.early_ata = true;
+      ee.pin_acc = false;
+      ee.hoisted_names = ev.hoisted_names;
+      for (int idx = 0; idx < P.n_active; ++idx) (void)ee.derived_op(P.active_op[idx], true);
+      (void)ee.emit_rows();
+      g.out += ee.out;
+      ee.out.clear();
+      g.f("    if (valid) {");
+      for (int i = 0; i < P.m; ++i) g.f("      a.r[bb * %d + %d] = r%d;", P.m, i, i);
+      for (int i = 0; i < n; ++i) {
+        const int pi = 3 * ev.perm[i / 3] + i % 3;
+        g.f("      a.atr[bb * %d + %d] = %s;", n, pi, LGen::gn(i).c_str());
+        g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pi, n, pi, LGen::A(i, i).c_str());
+        for (int j = 0; j < i; ++j)
+          if (ee.nz[i][j] && ee.early_ata) {
+            const int pj = 3 * ev.perm[j / 3] + j % 3;
+            g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pi, n, pj, LGen::E(i, j).c_str());
+            if (i / 3 == j / 3) g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pj, n, pi, LGen::E(i, j).c_str());
+          }
+      }
+      g.f("    }");
+      g.f("    const double lambda = a.lambda;");
+      std::vector<std::string> rhs;
+      for (int i = 0; i < n; ++i) rhs.push_back("-" + LGen::gn(i));
+      ee.col_fence = ev.col_fence;
+      ee.resident_rows = ev.resident_rows;
+      ee.emit_factor(rhs);
+      ee.emit_backward("nx");
+      g.out += ee.out;
+    }
+    g.f("    if (valid) {");
+    for (int i = 0; i < n; ++i) g.f("      a.dx[bb * %d + %d] = ok ? nx%d : __builtin_nan(\"\");", n, 3 * ev.perm[i / 3] + i % 3, i);
+    g.f("    }");
+    g.f("  }");
+    g.f("}");
+    g.f("");
+  }
+
+  void emit_entry_points(bool nested) {
+    for (const char* mode : {"solve", "chain"})
+      for (const char* geo : {"u", "g"})
+        for (const char* out : {"", "_c"})   // _c: compact outputs (free coordinates or nothing)
+          g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_%s_%s%s(QArgs a) { okx_lane_body_%s<%s, %s%s>(a); }", mode, geo,
+              out, mode[0] != 's' ? "chain" : (split_g && geo[0] == 'g') ? "coldg" : "cold", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true",
+              refine && mode[0] == 's' ? ", 1, false" : "");
+    if (refine)
+      for (const char* kind : {"refc", "refw"})   // coarse launch (every fourth step, cold) / warm launches (the steps between)
+        for (const char* geo : {"u", "g"})
+          for (const char* out : {"", "_c"})
+            g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_%s_%s%s(QArgs a) { okx_lane_body_%s<%s, %s, 4, %s>(a); }", kind, geo, out,
+                (split_g && geo[0] == 'g') ? "coldg" : "cold", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true", kind[3] == 'w' ? "true" : "false");
+    if (nested)
+      for (const char* geo : {"u", "g"})
+        for (const char* out : {"", "_c"})
+          g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_nest_%s%s(QArgs a) { okx_lane_body_%s<%s, %s>(a); }", geo, out,
+              split_g && geo[0] == 'g' ? "nestg" : "nest", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true");
+    (void)ev.undefs;  // (the macros live to the end of the translation unit: one program per module)
+  }
+};
+
+}  // namespace
+
+bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int variant, const EvalSpec* es) {
+  // Emission variants (kVariants above): the register allocator's result for an 18-unknown program sits at the edge of the
+  // 512-register file and is not monotonic in any of the hints (0 ... 250 B of scratch across them for the double
+  // wishbone, and not the same variant for every kernel of the module), so lane_build (okx_jit.cpp) compiles them in this
+  // order, keeps the first one whose independent-solve kernels do not spill - or, after a full search, the one that spills
+  // least, with single kernels taken from other variants of the same arithmetic.
+  if (variant < 0 || variant >= lane_variant_count()) variant = 0;
+  if (3 * P.n_free > 15 && variant >= 12) {
+    *why = "variant " + std::to_string(variant) + " is variant " + std::to_string(variant - 12) + " for this program";
+    return false;
+  }
+  if (P.n_free > kLaneMaxFree) {
+    *why = "more than " + std::to_string(kLaneMaxFree) + " free points: the lower triangle of J^T J does not fit one lane's registers";
+    return false;
+  }
+  if (P.n_targets > kMaxTargets || P.n_targets < 1) {
+    *why = "needs 1.." + std::to_string(kMaxTargets) + " targets";
+    return false;
+  }
+  LaneModule m(P, es, variant);
+  if (!m.make_passes() || !m.make_epilogue_passes() || !m.make_light_and_final()) {
+    *why = m.why;
+    return false;
+  }
+  m.collect_chain_constants();
+  m.emit_prelude();
+  if (m.EV) {
+    if (!m.body(false, false, false) || (m.split_g && !m.body(false, false, true))) {
+      *why = m.why;
       return false;
     }
-    g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evsolve_u(QEvArgs ea) { okx_lane_body_cold<false, true, false>(ea.q, ea); }");
-    g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evsolve_g(QEvArgs ea) { okx_lane_body_%s<true, true, false>(ea.q, ea); }", split_g ? "coldg" : "cold");
-    {  // okx_evaluate_batch's lane form (reference core/sweep.py:217-245 evaluate_solved_sweep): the epilogue on given states
-      bool all_out = true;
-      std::vector<bool> is_out(NP, false);
-      for (int k = 0; k < P.n_out; ++k) is_out[P.out_point[k]] = true;
-      for (int F = 0; F < nf; ++F) all_out = all_out && is_out[evc.fp(F)];
-      if (all_out) {
-        g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evaluate_u(QEvArgs ea) { okx_lane_body_cold<false, true, true>(ea.q, ea); }");
-        g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_evaluate_g(QEvArgs ea) { okx_lane_body_%s<true, true, true>(ea.q, ea); }", split_g ? "coldg" : "cold");
-      }
-    }
-    *src = g.out;
+    m.emit_evaluated_entries();
+    *src = m.g.out;
     return true;
   }
-  if (!body(false, false, false) || (split_g && !body(false, false, true)) || !(flat_chain ? body(false, true, false) : body(true, false, false))) {
-    *why = lds_why;
+  if (!m.body(false, false, false) || (m.split_g && !m.body(false, false, true)) || !(m.flat_chain ? m.body(false, true, false) : m.body(true, false, false))) {
+    *why = m.why;
     return false;
   }
   // The nested start mode is generated on request only (developer switch lane_nested): measured on BASELINE config 5 it
@@ -2400,92 +2580,16 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
   // the pace of its slowest lane, a confirming pass costs a lone wavefront most of a full one, and every unit-step carries
   // ~19 k cycles that are not passes (profiles/r05/EXPERIMENTS.md section 5).  chain_len = -1 keeps resolving to
   // independent solves on the lane kernel.
-  const bool nested = light_ok && dev_switch("lane_nested");
+  const bool nested = m.light_ok && dev_switch("lane_nested");
   // (two bodies: own geometry reads its tables through the scalar cache; per-geometry launches stage each geometry's tables
   //  and first-step table in LDS once per wave unit - its four unit-steps share them - like the independent-solve body)
-  if (nested && (!body(false, true, false, true) || (split_g && !body(false, true, true, true)))) {
-    *why = lds_why;
+  if (nested && (!m.body(false, true, false, true) || (m.split_g && !m.body(false, true, true, true)))) {
+    *why = m.why;
     return false;
   }
-  // ---- parity / debug kernel: r, J^T J, J^T r at given x, and the damped step for a given lambda ----
-  g.f("struct QEvalArgs { const double* x; const double* targets; double* r; double* ata; double* atr; double* dx;");
-  g.f("  double lambda; long long n_problems; const double* design_pos; const double* row_param; const double* dop_param; };");
-  g.f("#undef GL\n#define GL(o) gl[(o) + kz]");
-  g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_eval(QEvalArgs a) {");
-  g.f("  const double* gp = a.design_pos; const double* gq = a.row_param; (void)gq;");
-  g.f("  __shared__ double gl[%d];", gl_size);
-  g.f("  const int lane = threadIdx.x;");
-  g.f("  int kz = 0;");
-  stage_tables(g, "  ");
-  g.f("  __syncthreads();");
-  g.f("  %s", refresh_kz);
-  g.f("  for (long long wu = blockIdx.x; wu * 64 < a.n_problems; wu += gridDim.x) {");
-  g.f("    long long bb = wu * 64 + threadIdx.x; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;");
-  for (int p = 0; p < NP; ++p)
-    if (used[p] && !is_fixed(p))
-      for (int c = 0; c < 3; ++c) g.f("    double p%d_%d = gp[%d];", p, c, 3 * p + c);
-  for (int i = 0; i < n; ++i) g.f("    %s = a.x[bb * %d + %d];", PF(i).c_str(), n, 3 * ev.perm[i / 3] + i % 3);
-  for (int t = 0; t < T; ++t) g.f("    const double tv%d = a.targets[bb * %d + %d];", t, T, t);
-  {
-    // the parity kernel additionally accumulates the whole lower triangle of J^T J where the rows are (E{i}_{j}): the
-    // solve kernels never hold it in that form
-    LGen ee(P);
-    ee.uid = 500000;
-    ee.early_ata = true;
-    ee.pin_acc = false;
-    ee.hoisted_names = ev.hoisted_names;
-    for (int idx = 0; idx < P.n_active; ++idx) (void)ee.derived_op(P.active_op[idx], true);
-    (void)ee.emit_rows();
-    g.out += ee.out;
-    ee.out.clear();
-    g.f("    if (valid) {");
-    for (int i = 0; i < P.m; ++i) g.f("      a.r[bb * %d + %d] = r%d;", P.m, i, i);
-    for (int i = 0; i < n; ++i) {
-      const int pi = 3 * ev.perm[i / 3] + i % 3;
-      g.f("      a.atr[bb * %d + %d] = %s;", n, pi, LGen::gn(i).c_str());
-      g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pi, n, pi, LGen::A(i, i).c_str());
-      for (int j = 0; j < i; ++j)
-        if (ee.nz[i][j] && ee.early_ata) {
-          const int pj = 3 * ev.perm[j / 3] + j % 3;
-          g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pi, n, pj, LGen::E(i, j).c_str());
-          if (i / 3 == j / 3) g.f("      a.ata[(bb * %d + %d) * %d + %d] = %s;", n, pj, n, pi, LGen::E(i, j).c_str());
-        }
-    }
-    g.f("    }");
-    g.f("    const double lambda = a.lambda;");
-    std::vector<std::string> rhs;
-    for (int i = 0; i < n; ++i) rhs.push_back("-" + LGen::gn(i));
-    ee.col_fence = ev.col_fence;
-    ee.resident_rows = ev.resident_rows;
-    ee.emit_factor(rhs);
-    ee.emit_backward("nx");
-    g.out += ee.out;
-  }
-  g.f("    if (valid) {");
-  for (int i = 0; i < n; ++i) g.f("      a.dx[bb * %d + %d] = ok ? nx%d : __builtin_nan(\"\");", n, 3 * ev.perm[i / 3] + i % 3, i);
-  g.f("    }");
-  g.f("  }");
-  g.f("}");
-  g.f("");
-  for (const char* body : {"solve", "chain"})
-    for (const char* geo : {"u", "g"})
-      for (const char* out : {"", "_c"})   // _c: compact outputs (free coordinates or nothing)
-        g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_%s_%s%s(QArgs a) { okx_lane_body_%s<%s, %s%s>(a); }", body, geo,
-            out, body[0] != 's' ? "chain" : (split_g && geo[0] == 'g') ? "coldg" : "cold", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true",
-            refine && body[0] == 's' ? ", 1, false" : "");
-  if (refine)
-    for (const char* kind : {"refc", "refw"})   // coarse launch (every fourth step, cold) / warm launches (the steps between)
-      for (const char* geo : {"u", "g"})
-        for (const char* out : {"", "_c"})
-          g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_%s_%s%s(QArgs a) { okx_lane_body_%s<%s, %s, 4, %s>(a); }", kind, geo, out,
-              (split_g && geo[0] == 'g') ? "coldg" : "cold", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true", kind[3] == 'w' ? "true" : "false");
-  if (nested)
-    for (const char* geo : {"u", "g"})
-      for (const char* out : {"", "_c"})
-        g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_nest_%s%s(QArgs a) { okx_lane_body_%s<%s, %s>(a); }", geo, out,
-            split_g && geo[0] == 'g' ? "nestg" : "nest", geo[0] == 'g' ? "true" : "false", out[0] ? "false" : "true");
-  (void)ev.undefs;  // (the macros live to the end of the translation unit: one program per module)
-  *src = g.out;
+  m.emit_eval_kernel();
+  m.emit_entry_points(nested);
+  *src = m.g.out;
   return true;
 }
 

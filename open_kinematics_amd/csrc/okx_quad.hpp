@@ -65,7 +65,7 @@ struct QuadHeadArgs {
 };
 // doubles per geometry in that table (0: the program has no quad kernel): Q[k][F][4] per half, M[j][k], N[j][k] for
 // k = constraint gradient + one column per program target, 8 scalars, S[pair][F][4] per half - the generator's own
-// layout (`HeadLayout`, okx_quadgen.cpp), computed without generating a module
+// layout (`HeadLayout`, okx_gen.hpp), computed without generating a module
 int quad_head_stride(const DevProgram& program);
 
 // Arguments of the generated parity kernel `okx_quad_eval` (mirrors `struct QEvalArgs`).

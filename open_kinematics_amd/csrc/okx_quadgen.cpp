@@ -1114,53 +1114,6 @@ template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* 
 DEV bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 )SRC";
 
-// Layout of one geometry's first-step table (okx_quad_head_u/_g write it, the solve bodies and the lane kernels read
-// it, okx_api.hip allocates quad_head_stride() doubles per geometry), in doubles:
-// Q[k][F][4] (lane components, 0 in slot 3; pair mode: one such block per half), M[j][k] = Q_j . G_k, N[j][k] = Q_j . Q_k,
-// then dmax, min pivot, sum of squared constraint residuals, max |constraint residual|, ok, max pivot, pairs carried, 0.
-// Column k = 0 is the constraint rows' own gradient G_0 = Jc^T rc at the design state (the reference's distance
-// rows carry softnorm's -1e-6 offset there, constraints.py:125-134, so it is small but not zero) with weight 1;
-// column k = t + 1 belongs to target t: G_k = J^T e_t, weight = that target's residual.  Q_k = (J^T J + lambda I)^-1 G_k.
-// Pair mode carries the first-order table too.  Measured on the axle grid, round 3: cold starts 5.57 -> 4.72
-// evaluations, 0.483 -> 0.455 ms; chained grids unchanged (0.211 vs 0.212 ms) - in round 2 the block's registers still
-// cost the chained grid 3 %, before the LM scalars and constants had homes in LDS.
-struct HeadLayout {
-  // columns of the table: the constraint gradient, then one per PROGRAM target (pair mode: a side target stands for one
-  // program target per half that carries it; the column's weight is that half's residual, its Q spans both halves)
-  struct Col { int t, side, prog_t; };
-  std::vector<Col> cols;
-  // Second-order terms of the shared first step: S_st = (J^T J + lambda I)^-1 J^T r''(Q_s, Q_t) for the target
-  // columns s <= t, [pair][F][4] after the scalars (pair mode: one such block per half, the left half's first);
-  // scalar 6 says how many pairs the table carries.
-  std::vector<std::pair<int, int>> pairs;
-  int side;    // doubles of one half's Q block
-  int off;     // where the 8 scalars start
-  int s_off;   // where the S blocks start
-  int s_side;  // doubles of one half's S block (room for every pair, carried or not)
-  int stride;  // doubles per geometry
-
-  // `P`: the program the kernels are specialised to - in pair mode the side program of `pv`
-  HeadLayout(const DevProgram& P, const PairView* pv) {
-    const int nf = P.n_free, T = P.n_targets, prog_targets = pv ? pv->n_prog_targets : T;
-    cols.push_back({-1, -1, -1});
-    for (int pt = 0; pt < prog_targets; ++pt)
-      for (int t = 0; t < T; ++t) {
-        if (!pv) { if (t == pt) cols.push_back({t, -1, pt}); continue; }
-        for (int sd = 0; sd < 2; ++sd)
-          if (pv->tgt[sd][t] == pt) cols.push_back({t, sd, pt});
-      }
-    const int HK = (int)cols.size();
-    side = 4 * nf * HK;
-    off = (pv ? 2 : 1) * side + 2 * HK * HK;
-    if (!(pv && dev_switch("pair_first_order_head")))
-      for (int s2 = 1; s2 < HK; ++s2)
-        for (int t2 = s2; t2 < HK; ++t2) pairs.push_back({s2, t2});
-    s_off = off + 8;
-    s_side = 4 * nf * (HK - 1) * HK / 2;
-    stride = off + 8 + (pv ? 2 : 1) * s_side;
-  }
-};
-
 }  // namespace
 
 int quad_head_stride(const DevProgram& program) {

@@ -55,6 +55,7 @@ GENERATOR_SWITCHES = [
     ("lane_lds_tables", "c1_dw_corner", "okx_lane_source", "-okx_cptr gpc"),
     ("lane_nested", "c1_dw_corner", "okx_lane_source", "+okx_lane_nest_u"),
     ("lane_refine", "c1_dw_corner", "okx_lane_source", "+okx_lane_refw_u"),
+    ("lane_g_scalar", "c1_dw_corner", "okx_lane_source", "-okx_lane_body_coldg"),
 ]
 
 
