@@ -27,6 +27,7 @@
 #ifndef OKX_H
 #define OKX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -761,6 +762,43 @@ int32_t okx_diagnose_sweeps_batch(okx_program* prog, const okx_diag_roles* roles
                                   int64_t capacity,
                                   int64_t* d_issue_count,       /* total found, may exceed capacity                 */
                                   void* stream);
+
+/*
+ * Ensemble reduction on device: per (step, column) entry of a table of metric columns, over its geometries, the raw
+ * accumulators a tolerance / sensitivity study finalizes on the host (open_kinematics_amd/ensemble_stats.py).
+ * d_values is [n_geometries * steps][ld] with the n_columns columns in front of every row (ld >= n_columns: the gathered
+ * column table of an evaluated ensemble, or a view of its evaluation rows); geometry g is rows [g * steps, (g + 1) * steps).
+ * A state counts when its status byte (d_status[row * status_stride], the low byte of okx_info.flags; NULL: every state)
+ * says converged, not residual-exceeded, not failed, and its value is finite; anything else is REJECTED.
+ * d_acc [steps][n_columns][OKX_ENS_FIELDS + n_factors], every field a double:
+ *   OKX_ENS_COUNT, OKX_ENS_REJECTED   states that count / do not
+ *   OKX_ENS_SUM, OKX_ENS_SUMSQ        sum d, sum d^2 with d = value - d_shift[step][column] over the states that count
+ *   OKX_ENS_MIN, OKX_ENS_MAX          +inf / -inf when nothing counts
+ *   OKX_ENS_ARGMIN, OKX_ENS_ARGMAX    geometry_offset + g of the extreme, ties to the LOWEST index, -1 when nothing counts
+ *   OKX_ENS_FIELDS + p                sum f_p d over the states that count, f = d_factors [n_geometries][n_factors]
+ * d_factor_acc (or NULL) [n_factors + n_factors (n_factors + 1) / 2 + 1]: sum f_p, sum f_p f_q (q <= p, lower triangle
+ * row by row) and the geometry count, over EVERY geometry of the call.
+ * accumulate = 1 merges into what d_acc / d_factor_acc hold (additions and comparisons only: every partial that is ever
+ * merged must have been taken with the same d_shift); 0 overwrites.  n_columns = 0 computes the factor moments alone.
+ * No floating-point atomics: two launches, partial accumulators per slab of geometries in d_scratch
+ * (okx_ensemble_scratch_bytes of the same sizes), merged in ascending slab order.  The slab count depends on the sizes
+ * alone, so the result is bit-identical from run to run and from device to device.  Launch-only, stream-ordered, legal
+ * inside a stream capture; calls that share d_scratch must be stream-ordered with each other.
+ */
+enum { OKX_ENS_COUNT = 0, OKX_ENS_REJECTED = 1, OKX_ENS_SUM = 2, OKX_ENS_SUMSQ = 3, OKX_ENS_MIN = 4, OKX_ENS_MAX = 5,
+       OKX_ENS_ARGMIN = 6, OKX_ENS_ARGMAX = 7, OKX_ENS_FIELDS = 8, OKX_ENS_MAX_FACTORS = 1024 };
+
+int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                            const double* d_values, int64_t ld,
+                            const uint8_t* d_status, int64_t status_stride, /* or NULL                                  */
+                            const double* d_factors, int32_t n_factors,     /* or NULL, 0                               */
+                            const double* d_shift,                          /* [steps][n_columns]                       */
+                            int64_t geometry_offset,                        /* global index of geometry 0 of this call  */
+                            int32_t accumulate,
+                            double* d_acc,
+                            double* d_factor_acc,                           /* or NULL                                  */
+                            void* d_scratch, size_t scratch_bytes, void* stream);
+size_t okx_ensemble_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_factors);
 
 #ifdef __cplusplus
 }

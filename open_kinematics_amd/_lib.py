@@ -58,6 +58,8 @@ EXPORTS = (
     "okx_precompile_axle_evaluation",
     "okx_program_eval_columns",
     "okx_diagnose_sweeps_batch",
+    "okx_ensemble_reduce",
+    "okx_ensemble_scratch_bytes",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -197,6 +199,10 @@ def load() -> C.CDLL:
     lib.okx_program_eval_columns.restype = i32
     lib.okx_diagnose_sweeps_batch.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, C.c_double, vp, vp, i64, vp, vp]
     lib.okx_diagnose_sweeps_batch.restype = i32
+    lib.okx_ensemble_reduce.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_reduce.restype = i32
+    lib.okx_ensemble_scratch_bytes.argtypes = [i64, i64, i32, i32]
+    lib.okx_ensemble_scratch_bytes.restype = C.c_size_t
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -741,6 +741,72 @@ class DeviceProgram:
         records = issues[:total].cpu().numpy().reshape(-1).view(ISSUE_DTYPE)
         return summary.cpu().numpy().reshape(-1).view(SUMMARY_DTYPE), sort_records(records)
 
+    def reduce_ensemble(self, values, *, steps_per_geometry: int, status=None, factors=None, shift=None, geometry_offset: int = 0,
+                        out=None, accumulate: bool = False, factor_moments: bool = True):
+        """
+        ``okx_ensemble_reduce``: the statistics accumulator (``ensemble_stats.EnsembleAccumulator``, device tensors) of a
+        column table in HBM over its geometries.  ``values [G * S, K]`` float64 with unit column stride - the gathered
+        ``metric_full`` of an evaluated ensemble, or a strided view of its evaluation rows (``eval[:, 0, :]``: nothing is
+        copied, the row stride is passed on); ``status [G * S]`` uint8, the low byte of ``okx_info.flags`` (``info_raw[:, 32]``
+        is fine), or None: every state accepted; ``factors [G, P]`` per-geometry factors or None; ``shift [S, K]`` the common
+        shift of the sums (None: the table's own geometry 0, undefined entries 0 - partial accumulators that are merged
+        later need ONE shift, pass it); ``geometry_offset`` the global index of the table's geometry 0.  ``out``: an
+        accumulator to write (``accumulate=False``) or merge into (``True``); with it and a table shape seen before, the call
+        allocates nothing and is legal inside a stream capture.  ``factor_moments=False`` skips the factor moments (a caller
+        that merges chunks of fixed factors takes them once).
+        """
+        from .ensemble_stats import ENS_FIELDS, EnsembleAccumulator, factor_moment_count
+
+        s = int(steps_per_geometry)
+        if values.dim() != 2 or values.dtype != torch.float64 or values.device != self.device or (values.shape[1] > 1 and values.stride(1) != 1):
+            raise ValueError("values must be a float64 [G * S, K] device tensor with unit column stride")
+        b, k = values.shape
+        if s < 1 or b % s:
+            raise ValueError("bad steps_per_geometry")
+        g = b // s
+        ld = values.stride(0) if b > 1 else max(k, values.stride(0))
+        if ld < k:
+            raise ValueError("rows of values overlap")
+        stride = 0
+        if status is not None:
+            if status.dtype != torch.uint8 or status.dim() != 1 or status.shape[0] != b or status.device != self.device:
+                raise ValueError("status must be a uint8 [G * S] device tensor")
+            stride = status.stride(0) if b > 1 else 1
+        p = 0
+        if factors is not None:
+            factors = _as_f64(factors, self.device)
+            if factors.dim() != 2 or factors.shape[0] != g:
+                raise ValueError("factors must be [G, P]")
+            factors = factors.contiguous()
+            p = factors.shape[1]
+        if out is None:
+            if shift is None:
+                shift = torch.nan_to_num(values[:s], nan=0.0, posinf=0.0, neginf=0.0) if g else torch.zeros((s, k), dtype=torch.float64, device=self.device)
+            shift = _as_f64(shift, self.device).reshape(s, k).contiguous()
+            out = EnsembleAccumulator(torch.empty((s, k, ENS_FIELDS + p), dtype=torch.float64, device=self.device), shift,
+                                      torch.empty(factor_moment_count(p), dtype=torch.float64, device=self.device) if p and factor_moments else None)
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+        elif shift is not None:
+            raise ValueError("out= carries its own shift")
+        if tuple(out.acc.shape) != (s, k, ENS_FIELDS + p) or not out.acc.is_contiguous() or not out.shift.is_contiguous() \
+                or out.acc.device != self.device or out.shift.device != self.device:
+            raise ValueError(f"out must hold contiguous device tables [S, K, {ENS_FIELDS + p}] and [S, K]")
+        factor_acc = out.factor_acc if factor_moments and p else None
+        need = int(self.lib.okx_ensemble_scratch_bytes(g, s, k, p))
+        scratch = getattr(self, "_ens_scratch", None)
+        if scratch is None or scratch.numel() < need:  # grow-only; a captured graph keeps the buffer it was captured with alive
+            scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            self._ens_keep = getattr(self, "_ens_keep", []) + [scratch]
+            self._ens_scratch = scratch
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            rc = self.lib.okx_ensemble_reduce(g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(factors), p, _ptr(out.shift),
+                                              int(geometry_offset), 1 if accumulate else 0, _ptr(out.acc), _ptr(factor_acc),
+                                              _ptr(scratch), scratch.numel(), C.c_void_p(stream))
+        _lib.check(rc, "okx_ensemble_reduce")
+        return out
+
     def ensemble_targets(self, geom_pos: torch.Tensor, relative) -> torch.Tensor:
         """
         Absolute targets ``[G * S, T]`` of an ensemble from per-step RELATIVE displacements ``[S, T]``: every

@@ -250,11 +250,28 @@ class ShardedEnsemble:
     ``t``.  ``step()`` then returns ``metric_full [G * S, K]``; the rank's own complete evaluation rows stay in
     ``eval_local [n_local, 1 + T, 24]``.  This is the form of the sharded ensemble that scales: a sensitivity study wants
     camber gain and bump steer of every perturbed geometry, not 144 bytes of coordinates per state on every rank.
+
+    ``reduce=True`` (with ``metric_columns``) ends the ensemble in an ANSWER instead of a table: every chunk's columns are
+    reduced on the device right after its evaluated solve (``okx_ensemble_reduce``: count, sums, extremes and which geometry
+    produced them, cross sums with the factors) and merged into the rank's accumulator; nothing per state is exchanged - no
+    ``metric_full``, no status bytes - and ``step()`` ends with ONE all-gather of the accumulators, merged on every rank in
+    rank order (fixed order, extremes travel with their indices: every rank ends with the same bits).  ``step()`` returns
+    the ``ensemble_stats.EnsembleAccumulator``; ``stats()`` finalizes it.  ``factors``: None (moments and extremes only),
+    ``[G, P]`` per-geometry factors of the WHOLE ensemble, or ``"hardpoints"``: ``hardpoints - hardpoints.mean(0)``
+    restricted to the coordinates of authored points that vary (``factor_names`` says which).  ``shift``: the common shift
+    of the sums ``[S, K]``; None: the evaluation of global geometry 0 on the kernel the ensemble is pinned to (rank 0 solves
+    its S states once, here, and broadcasts the table), undefined entries 0.  The unmasked factor moments of a rank's
+    geometries never change: they are summed once, here, on the host in ascending geometry order - so ``factor_acc`` repeats
+    bit for bit from step to step, rank to rank and chunking to chunking, but agrees with a direct
+    ``reduce_ensemble(factor_moments=True)`` of the same table (summed per slab on the device) to rounding only.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
-                 metric_columns=None, **solve_kw):
+                 metric_columns=None, reduce: bool = False, factors=None, shift=None, **solve_kw):
+        if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
+            raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
+        self.reduce = bool(reduce)
         if metric_columns is not None:
             records, info = False, "status"   # nothing of the positions travels or is written
         self.dp = device_program
@@ -328,7 +345,7 @@ class ShardedEnsemble:
                 raise ValueError("metric_columns is empty")
             self.metric_index = torch.tensor(flat, dtype=torch.int64, device=device)
 
-        self.status_only = info == "status" and self.world > 1  # (one rank exchanges nothing: full records, a view of their flag byte)
+        self.status_only = info == "status" and (self.world > 1 or self.reduce)  # (one rank exchanges nothing: full records, a view of their flag byte)
         # ONE rank that wants records has nothing to exchange: its solves write the records themselves (`direct`; the gathered
         # free coordinates are then not kept - direct=False keeps the two-stage form, e.g. to compare the stages' bits)
         self.direct = (self.world == 1 and self.records and not self.status_only) if direct is None else bool(direct)
@@ -339,12 +356,14 @@ class ShardedEnsemble:
                 raise ValueError("direct records and metric_columns exclude each other")
             n_local = (ghi - glo) * self.steps
             self.eval_local = torch.empty((n_local, 1 + program.n_targets, self.eval_columns), dtype=torch.float64, device=device)
-            self.metric_full = torch.empty((self.n_total, len(self.metric_index)), dtype=torch.float64, device=device)
+            # (reduced: the chosen columns of the rank's own states only, the table the reduction reads)
+            self.metric_full = None if self.reduce else torch.empty((self.n_total, len(self.metric_index)), dtype=torch.float64, device=device)
+            self.metric_local = torch.empty((n_local, len(self.metric_index)), dtype=torch.float64, device=device) if self.reduce else None
         self.free_full = None if self.metric_index is not None else torch.empty((self.n_total, program.n_free, 3), dtype=torch.float64, device=device)
         # what travels beside the coordinates: the 40-byte info records, or one status byte per solve (then the records of
         # this rank's own shard are kept in `info_local`)
         self.info_full = None if self.status_only else torch.empty((self.n_total, 40), dtype=torch.uint8, device=device)
-        self.status_full = torch.empty((self.n_total,), dtype=torch.uint8, device=device) if self.status_only else None
+        self.status_full = torch.empty((self.n_total,), dtype=torch.uint8, device=device) if self.status_only and not self.reduce else None
         self.info_local = torch.empty(((ghi - glo) * self.steps, 40), dtype=torch.uint8, device=device) if self.status_only else None
         self.positions = torch.empty((self.n_total, program.n_out, 3), dtype=torch.float64, device=device) if self.records else None
         self.expand_stream = torch.cuda.Stream(device=device) if device.type == "cuda" and self.records and not self.direct else None
@@ -360,6 +379,131 @@ class ShardedEnsemble:
         self._expand_graphs = {}
         self.use_graphs = device.type == "cuda"
         self.p2p_groups = self.p2p_ops = 0  # grouped point-to-point calls / operations issued so far
+        if self.reduce:
+            self._init_reduction(hardpoints, targets, relative_targets, factors, shift)
+
+    # ---- reduce=True: the accumulators of ensemble_stats.py instead of a gathered table ----
+
+    def _init_reduction(self, hardpoints, targets, relative_targets, factors, shift) -> None:
+        import numpy as np
+
+        from .ensemble_stats import ENS_FIELDS, EnsembleAccumulator, clean_shift, factor_moment_count, hardpoint_factors
+
+        glo, ghi = self.geometry_range
+        device, k = self.device, len(self.metric_index)
+        self.factor_names = None
+        if isinstance(factors, str):
+            if factors != "hardpoints":
+                raise ValueError("factors must be None, 'hardpoints' or a [G, P] table")
+            program = self.dp.program
+            table = torch.as_tensor(hardpoints).detach().cpu().numpy()
+            # (derived points are recomputed from the authored ones by rebind: their coordinates are no factors)
+            from .program import key_name
+
+            authored = np.setdiff1d(np.arange(table.shape[1]), np.asarray(program.dop_out, dtype=np.int64))
+            names = [key_name(program.point_keys[i]).lower() for i in authored]
+            factors, self.factor_names = hardpoint_factors(table[:, authored], names)
+        if factors is not None:
+            factors = np.ascontiguousarray(torch.as_tensor(factors).detach().cpu().numpy(), dtype=np.float64).reshape(self.n_geom, -1)
+        p = 0 if factors is None else factors.shape[1]
+        self.n_factors = p
+        self.my_factors = torch.as_tensor(factors[glo:ghi], device=device).contiguous() if p else None
+        # the shift: ONE table for every partial that is ever merged
+        if shift is None:
+            shift = torch.zeros((self.steps, k), dtype=torch.float64, device=device)
+            if self.rank == 0 and self.n_geom > 0:
+                gpos, gparam = self.dp.rebind(torch.as_tensor(hardpoints)[:1])
+                first = self.dp.ensemble_targets(gpos, targets) if relative_targets else targets[: self.steps]
+                res = self.dp.solve_evaluated(first, geom_pos=gpos, geom_row_param=gparam, steps_per_geometry=self.steps,
+                                              output="none", **self.solve_kw)
+                rows = res.eval.reshape(self.steps, -1).to(device)
+                shift = torch.nan_to_num(torch.index_select(rows, 1, self.metric_index), nan=0.0, posinf=0.0, neginf=0.0)
+            if self.world > 1:
+                shift = self._broadcast_from_rank_zero(shift.contiguous())
+        else:
+            shift = torch.as_tensor(clean_shift(torch.as_tensor(shift).detach().cpu().numpy()), device=device)
+        shift = shift.reshape(self.steps, k).contiguous()
+        # the unmasked factor moments of this rank's geometries, once: the factors never change (ascending order, as the device sums)
+        factor_acc = None
+        if p:
+            mine = factors[glo:ghi]
+            rows, cols = np.tril_indices(p)
+            moments = np.zeros(factor_moment_count(p))
+            if ghi > glo:
+                moments[:p] = np.cumsum(mine, axis=0)[-1]
+                moments[p:-1] = np.cumsum(mine[:, rows] * mine[:, cols], axis=0)[-1]
+            moments[-1] = ghi - glo
+            factor_acc = torch.as_tensor(moments, device=device)
+        self.local_accumulator = EnsembleAccumulator(torch.empty((self.steps, k, ENS_FIELDS + p), dtype=torch.float64, device=device),
+                                                     shift, factor_acc, self.factor_names)
+        self.accumulator = self.local_accumulator
+        words = self.local_accumulator.acc.numel() + (factor_acc.numel() if p else 0)
+        self._acc_send = torch.empty(words, dtype=torch.float64, device=device) if self.world > 1 else None
+        self._acc_recv = torch.empty((self.world, words), dtype=torch.float64, device=device) if self.world > 1 else None
+        self.exchange_bytes_per_rank = 8 * words if self.world > 1 else 0
+        self._reduced_any = False
+
+    def _broadcast_from_rank_zero(self, tensor: torch.Tensor) -> torch.Tensor:
+        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        if tensor.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
+            host = tensor.cpu()
+            dist.broadcast(host, src, group=self.group)
+            return host.to(tensor.device)
+        dist.broadcast(tensor, src, group=self.group)
+        return tensor
+
+    def _reduce_rows(self, a: int, b: int, local) -> None:
+        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's accumulator."""
+        glo = self.geometry_range[0]
+        acc = self.local_accumulator
+        values = self.metric_local[local]
+        status = self.info_local[local][:, 32]
+        factors = self.my_factors[a - glo : b - glo] if self.n_factors else None
+        if values.is_cuda:  # (no quiet host reduction of device tables: a program without the device pass is an error)
+            self.dp.reduce_ensemble(values, steps_per_geometry=self.steps, status=status, factors=factors, geometry_offset=a, out=acc,
+                                    accumulate=self._reduced_any, factor_moments=False)
+        else:  # the CPU tests' stand-in: the NumPy accumulator, merged the same way
+            from .ensemble_stats import EnsembleAccumulator, reduce_host
+
+            part = reduce_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
+                               None if factors is None else factors.cpu().numpy(), acc.shift.cpu().numpy(), a)
+            part = EnsembleAccumulator(torch.as_tensor(part.acc, device=self.device), acc.shift, None)
+            if self._reduced_any:
+                part = EnsembleAccumulator(acc.acc, acc.shift, None).merge(part)
+            acc.acc.copy_(part.acc)
+        self._reduced_any = True
+
+    def _exchange_accumulators(self):
+        """ONE all-gather of the ranks' accumulators and their merge in rank order: the same bits on every rank."""
+        from .ensemble_stats import EnsembleAccumulator
+
+        mine = self.local_accumulator
+        if self.world == 1:
+            self.accumulator = mine
+            return mine
+        n_acc = mine.acc.numel()
+        self._acc_send[:n_acc] = mine.acc.reshape(-1)
+        if self.n_factors:
+            self._acc_send[n_acc:] = mine.factor_acc
+        if self._acc_send.is_cuda and dist.get_backend(self.group) == "gloo":
+            host = torch.empty(self._acc_recv.numel(), dtype=torch.float64)
+            dist.all_gather_into_tensor(host, self._acc_send.cpu(), group=self.group)
+            self._acc_recv.view(-1).copy_(host)
+        else:
+            dist.all_gather_into_tensor(self._acc_recv.view(-1), self._acc_send, group=self.group)
+        merged = None
+        for r in range(self.world):
+            part = EnsembleAccumulator(self._acc_recv[r, :n_acc].reshape(mine.acc.shape), mine.shift,
+                                       self._acc_recv[r, n_acc:] if self.n_factors else None, self.factor_names)
+            merged = part if merged is None else merged.merge(part)
+        self.accumulator = merged
+        return merged
+
+    def stats(self):
+        """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
+        if not self.reduce:
+            raise ValueError("stats() needs reduce=True")
+        return self.accumulator.finalize()
 
     def _rows(self, span):
         return slice(span[0] * self.steps, span[1] * self.steps)
@@ -420,12 +564,16 @@ class ShardedEnsemble:
                 ev.copy_(res.eval)
             if res.info_raw.data_ptr() != info.data_ptr():
                 info.copy_(res.info_raw)
+        if self.reduce:
+            torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_local[local])
+            self._reduce_rows(a, b, local)
+            return
         torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_full[rows])
         if self.status_only:
             self.status_full[rows] = info[:, 32]
 
     def _exchange_chunk(self, k: int) -> list:
-        if self.world == 1:
+        if self.world == 1 or self.reduce:  # (reduced: nothing per state travels; the accumulators go once, at the end of the step)
             return []
         if self.device.type == "cuda" and dist.get_backend(self.group) == "gloo":
             return self._exchange_chunk_through_the_host(k)
@@ -560,6 +708,8 @@ class ShardedEnsemble:
     def step(self):
         """One pass over the whole ensemble: returns ``positions`` (``records=True``) or the gathered free coordinates."""
         pending = []
+        if self.reduce:
+            self._reduced_any = False
         for k in range(self.chunks):
             self._solve_chunk(k)
             works = self._exchange_chunk(k)
@@ -571,6 +721,11 @@ class ShardedEnsemble:
             w.wait()
         if self.expand_stream is not None:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
+        if self.reduce:
+            if not self._reduced_any:  # a rank without a geometry contributes the neutral accumulator
+                glo = self.geometry_range[0]
+                self._reduce_rows(glo, glo, slice(0, 0))
+            return self._exchange_accumulators()
         if self.metric_index is not None:
             return self.metric_full
         return self.positions if self.records else self.free_full

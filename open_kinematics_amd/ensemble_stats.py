@@ -1,0 +1,268 @@
+"""
+Statistics of an evaluated ensemble: per (sweep step, metric column), over the geometries, how many states were accepted,
+mean, spread, the extremes and WHICH geometry produced them, and the least-squares slopes of the column on per-geometry
+factors (hardpoint perturbations).
+
+Three layers, the same accumulator in each (``include/okx.h``, ``okx_ensemble_reduce``):
+
+* ``reduce_host``: NumPy over ``values [G, S, K]``; the fallback without a GPU and the cross-check of the device pass;
+* ``DeviceProgram.reduce_ensemble`` (``batch.py``): the device pass over a column table in HBM;
+* ``dist.ShardedEnsemble(reduce=True)``: every rank reduces its own shard chunk by chunk and the ranks exchange the
+  accumulators alone.
+
+``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
+comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+ENS_COUNT, ENS_REJECTED, ENS_SUM, ENS_SUMSQ, ENS_MIN, ENS_MAX, ENS_ARGMIN, ENS_ARGMAX = range(8)
+ENS_FIELDS = 8  # OKX_ENS_FIELDS
+
+STATUS_ACCEPT_MASK = 7  # okx_info.flags: converged (1) set, residual exceeded (2) and failed (4) clear - BatchResult.accepted
+
+
+def factor_moment_count(n_factors: int) -> int:
+    """Length of the factor-moment table: ``sum f_p``, the lower triangle of ``sum f_p f_q`` row by row, the geometry count."""
+    return n_factors + n_factors * (n_factors + 1) // 2 + 1 if n_factors > 0 else 0
+
+
+def _is_tensor(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+@dataclass
+class EnsembleStats:
+    """
+    What ``EnsembleAccumulator.finalize`` returns, every table ``[S, K]`` (NumPy, host):
+    ``count`` accepted finite values, ``rejected`` the others, ``mean``, ``variance`` (unbiased; NaN for ``count < 2``),
+    ``std``, ``min`` / ``max`` (NaN for ``count == 0``), ``argmin`` / ``argmax`` (global geometry index, ties to the lowest;
+    ``-1`` for ``count == 0``).  With factors: ``sensitivity [S, K, P]`` - the least-squares slopes of the column on the
+    factors with an intercept -, ``intercept`` and ``r2`` ``[S, K]``.  The fit uses the UNMASKED factor moments, so it is
+    defined where ``rejected == 0`` for that entry and NaN elsewhere (and where fewer than ``P + 2`` geometries were seen);
+    ``r2`` is NaN where the column does not vary.
+    """
+
+    count: np.ndarray
+    rejected: np.ndarray
+    mean: np.ndarray
+    variance: np.ndarray
+    std: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    argmin: np.ndarray
+    argmax: np.ndarray
+    sensitivity: np.ndarray | None = None
+    intercept: np.ndarray | None = None
+    r2: np.ndarray | None = None
+    factor_names: list | None = None
+
+
+class EnsembleAccumulator:
+    """
+    The raw tables of ``okx_ensemble_reduce``: ``acc [S, K, ENS_FIELDS + P]`` float64, ``shift [S, K]`` and, with factors,
+    ``factor_acc [P + P (P + 1) / 2 + 1]`` - NumPy arrays or torch tensors (host or device), whatever produced them.
+    """
+
+    def __init__(self, acc, shift, factor_acc=None, factor_names=None):
+        self.acc = acc
+        self.shift = shift
+        self.factor_acc = factor_acc
+        self.factor_names = list(factor_names) if factor_names is not None else None
+        if acc.ndim != 3 or acc.shape[2] < ENS_FIELDS or tuple(shift.shape) != tuple(acc.shape[:2]):
+            raise ValueError("acc must be [S, K, ENS_FIELDS + P] and shift [S, K]")
+        if factor_acc is not None and factor_acc.shape[0] != factor_moment_count(self.n_factors):
+            raise ValueError("factor_acc does not fit the accumulator's factor count")
+
+    @property
+    def n_factors(self) -> int:
+        return int(self.acc.shape[2]) - ENS_FIELDS
+
+    @classmethod
+    def empty(cls, steps: int, n_columns: int, n_factors: int, shift, factor_names=None) -> "EnsembleAccumulator":
+        """The accumulator of no geometry at all (the neutral element of ``merge``), NumPy."""
+        acc = np.zeros((steps, n_columns, ENS_FIELDS + n_factors))
+        acc[..., ENS_MIN], acc[..., ENS_MAX] = np.inf, -np.inf
+        acc[..., ENS_ARGMIN] = acc[..., ENS_ARGMAX] = -1.0
+        shift = np.asarray(shift, dtype=np.float64).reshape(steps, n_columns)
+        return cls(acc, shift, np.zeros(factor_moment_count(n_factors)) if n_factors else None, factor_names)
+
+    def numpy(self) -> "EnsembleAccumulator":
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(self.acc):
+            return self
+        host = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
+        return EnsembleAccumulator(host(self.acc), host(self.shift), host(self.factor_acc), self.factor_names)
+
+    def to(self, device) -> "EnsembleAccumulator":
+        """The tables as torch tensors on ``device``."""
+        import torch
+
+        move = lambda t: None if t is None else torch.as_tensor(t).to(device)  # noqa: E731
+        return EnsembleAccumulator(move(self.acc), move(self.shift), move(self.factor_acc), self.factor_names)
+
+    def merge(self, other: "EnsembleAccumulator") -> "EnsembleAccumulator":
+        """
+        ``self`` then ``other`` as one accumulator (a new one; both stay): sums add, an extreme that is strictly better
+        wins and a tie goes to the LOWER geometry index.  Both must have been taken with the same shift - that is what
+        makes a merge additions and comparisons only.  Works on NumPy arrays and on torch tensors alike.
+        """
+        a, b = self.acc, other.acc
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError("accumulators of different shapes")
+        xp = __import__("torch") if _is_tensor(a) else np
+        # (one table object on both sides - the sharded exchange - needs no comparison: on a device that would be a sync)
+        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
+        if not bool(same):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        out = a + b
+        for value, arg, better in ((ENS_MIN, ENS_ARGMIN, lambda x, y: x < y), (ENS_MAX, ENS_ARGMAX, lambda x, y: x > y)):
+            av, ai, bv, bi = a[..., value], a[..., arg], b[..., value], b[..., arg]
+            take = (bi >= 0) & ((ai < 0) | better(bv, av) | ((bv == av) & (bi < ai)))
+            out[..., value] = xp.where(take, bv, av)
+            out[..., arg] = xp.where(take, bi, ai)
+        fa = None
+        if self.factor_acc is not None and other.factor_acc is not None:
+            fa = self.factor_acc + other.factor_acc
+        return EnsembleAccumulator(out, self.shift, fa, self.factor_names)
+
+    def finalize(self) -> EnsembleStats:
+        """Moments, extremes and (with factors) the least-squares fit, on the host in fp64."""
+        h = self.numpy()
+        acc, shift = np.asarray(h.acc, dtype=np.float64), np.asarray(h.shift, dtype=np.float64)
+        n = acc[..., ENS_COUNT]
+        count, rejected = n.astype(np.int64), acc[..., ENS_REJECTED].astype(np.int64)
+        s1, s2 = acc[..., ENS_SUM], acc[..., ENS_SUMSQ]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_d = np.where(n > 0, s1 / n, np.nan)
+            mean = shift + mean_d
+            # sum (d - mean_d)^2 = s2 - s1^2 / n, about a shift that lies inside the data
+            variance = np.where(n > 1, np.maximum(s2 - s1 * mean_d, 0.0) / (n - 1), np.nan)
+        std = np.sqrt(variance)
+        some = n > 0
+        stats = EnsembleStats(count, rejected, mean, variance, std, np.where(some, acc[..., ENS_MIN], np.nan),
+                              np.where(some, acc[..., ENS_MAX], np.nan), acc[..., ENS_ARGMIN].astype(np.int64),
+                              acc[..., ENS_ARGMAX].astype(np.int64), factor_names=self.factor_names)
+        p = self.n_factors
+        if p and h.factor_acc is not None:
+            stats.sensitivity, stats.intercept, stats.r2 = _fit(acc, shift, np.asarray(h.factor_acc, dtype=np.float64), p)
+        return stats
+
+
+def _fit(acc, shift, factor_acc, p: int):
+    """Slopes, intercept and R^2 of every entry from the normal equations of the accumulated moments."""
+    g = factor_acc[-1]
+    s_f = factor_acc[:p]
+    tri = np.zeros((p, p))
+    tri[np.tril_indices(p)] = factor_acc[p:-1]
+    s_ff = tri + np.tril(tri, -1).T
+    steps, cols = acc.shape[:2]
+    nan = np.full((steps, cols), np.nan)
+    if g < 1:
+        return np.full((steps, cols, p), np.nan), nan, nan.copy()
+    # centred: C = sum (f - fbar)(f - fbar)^T; the intercept separates exactly
+    fbar = s_f / g
+    c = s_ff - g * np.outer(fbar, fbar)
+    scale = np.sqrt(np.maximum(np.diag(c), 0.0))
+    scale[scale == 0.0] = 1.0
+    rank = int(np.linalg.matrix_rank(c / np.outer(scale, scale), tol=1e-10)) if g > 1 else 0
+    if rank < p:
+        raise ValueError(f"the factor matrix is rank-deficient: rank {rank + 1} of {p + 1} columns [1 | factors]")
+    n = acc[..., ENS_COUNT]
+    s1, s2 = acc[..., ENS_SUM], acc[..., ENS_SUMSQ]
+    cross = acc[..., ENS_FIELDS:]                                  # sum f_p d
+    rhs = cross - fbar[None, None, :] * s1[..., None]              # sum (f_p - fbar_p) d
+    slopes = np.linalg.solve(c, rhs.reshape(-1, p).T).T.reshape(steps, cols, p)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_d = s1 / g
+        intercept = shift + mean_d - slopes @ fbar
+        total = s2 - s1 * mean_d                                   # sum (d - mean_d)^2
+        explained = np.einsum("skp,skp->sk", slopes, rhs)
+        r2 = np.where(total > 0.0, explained / total, np.nan)
+    defined = (acc[..., ENS_REJECTED] == 0) & (n == g) & (g >= p + 2)
+    slopes = np.where(defined[..., None], slopes, np.nan)
+    return slopes, np.where(defined, intercept, np.nan), np.where(defined, r2, np.nan)
+
+
+def clean_shift(shift) -> np.ndarray:
+    """A shift table with its undefined entries (NaN / inf: a metric the state does not have) replaced by 0."""
+    shift = np.array(shift, dtype=np.float64, copy=True)
+    shift[~np.isfinite(shift)] = 0.0
+    return shift
+
+
+def reduce_host(values, status=None, factors=None, shift=None, geometry_offset: int = 0, factor_names=None) -> EnsembleAccumulator:
+    """
+    The accumulator of ``okx_ensemble_reduce`` in NumPy.  ``values [G, S, K]``; ``status [G, S]`` uint8 (the low byte of
+    ``okx_info.flags``) or None (every state accepted); ``factors [G, P]`` or None; ``shift [S, K]`` (None: the values of
+    geometry 0, undefined entries 0).  Sums run over the geometries in ascending order, one after the other.
+    """
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim != 3:
+        raise ValueError("values must be [G, S, K]")
+    g, s, k = v.shape
+    if shift is None:
+        shift = clean_shift(v[0]) if g else np.zeros((s, k))
+    shift = np.asarray(shift, dtype=np.float64).reshape(s, k)
+    if not np.all(np.isfinite(shift)):
+        raise ValueError("the shift must be finite (clean_shift replaces undefined entries)")
+    ok = np.isfinite(v)
+    if status is not None:
+        st = np.asarray(status).reshape(g, s).astype(np.uint8)
+        ok &= ((st & STATUS_ACCEPT_MASK) == 1)[:, :, None]
+    f = None if factors is None else np.asarray(factors, dtype=np.float64)
+    if f is not None and (f.ndim != 2 or f.shape[0] != g):
+        raise ValueError("factors must be [G, P]")
+    p = 0 if f is None else f.shape[1]
+    acc = np.zeros((s, k, ENS_FIELDS + p))
+    with np.errstate(invalid="ignore"):
+        d = np.where(ok, v - shift[None], 0.0)
+    acc[..., ENS_COUNT] = ok.sum(axis=0)
+    acc[..., ENS_REJECTED] = g - ok.sum(axis=0)
+    for i in range(g):  # ascending geometry order, as the device walks a slab
+        acc[..., ENS_SUM] += d[i]
+        acc[..., ENS_SUMSQ] += d[i] * d[i]
+        if p:
+            acc[..., ENS_FIELDS:] += d[i][..., None] * f[i][None, None, :]
+    some = ok.any(axis=0)
+    lo = np.where(ok, v, np.inf)
+    hi = np.where(ok, v, -np.inf)
+    acc[..., ENS_MIN], acc[..., ENS_MAX] = lo.min(axis=0) if g else np.inf, hi.max(axis=0) if g else -np.inf
+    # (argmin / argmax return the FIRST extreme: the lowest geometry index)
+    acc[..., ENS_ARGMIN] = np.where(some, geometry_offset + lo.argmin(axis=0), -1.0) if g else -1.0
+    acc[..., ENS_ARGMAX] = np.where(some, geometry_offset + hi.argmax(axis=0), -1.0) if g else -1.0
+    factor_acc = None
+    if p:
+        factor_acc = np.zeros(factor_moment_count(p))
+        rows, cols = np.tril_indices(p)
+        for i in range(g):
+            factor_acc[:p] += f[i]
+            factor_acc[p:-1] += f[i][rows] * f[i][cols]
+        factor_acc[-1] = g
+    return EnsembleAccumulator(acc, shift, factor_acc, factor_names)
+
+
+def hardpoint_factors(hardpoints, point_names=None, atol: float = 0.0):
+    """
+    ``factors="hardpoints"``: ``hardpoints [G, P, 3]`` minus their mean over the geometries, restricted to the
+    coordinates that vary (a derived or unperturbed point's do not).  Returns ``(factors [G, F], names)`` with names like
+    ``"upper_wishbone_outboard.x"`` (``"point7.x"`` without ``point_names``).
+    """
+    hp = np.asarray(hardpoints, dtype=np.float64)
+    g = hp.shape[0]
+    flat = hp.reshape(g, -1)
+    varies = (flat.max(axis=0) - flat.min(axis=0)) > atol if g else np.zeros(flat.shape[1], dtype=bool)
+    centred = flat[:, varies] - flat[:, varies].mean(axis=0)
+    names = []
+    for j in np.flatnonzero(varies):
+        point = point_names[j // 3] if point_names is not None else f"point{j // 3}"
+        names.append(f"{point}.{'xyz'[j % 3]}")
+    return np.ascontiguousarray(centred), names
+
+
+__all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
+           "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX"]

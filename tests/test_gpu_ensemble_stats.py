@@ -1,0 +1,405 @@
+"""
+GPU: okx_ensemble_reduce (DeviceProgram.reduce_ensemble) and ShardedEnsemble(reduce=True) - against the statistics the
+fixture generator took from the REFERENCE's metrics (tests/golden/ensemble_stats_dw.npz), against the NumPy accumulator
+on the copied tables, at full size (BASELINE config 5), in chunks, over two ranks rehearsed on one GPU, inside a captured
+graph and on strided views of evaluation rows.  The bounds are those derived in tests/test_ensemble_stats.py.
+"""
+
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO, gpu_available
+from test_ensemble_stats import (U, check_against_generator, check_fit_against_lstsq, check_same_accumulator, cross_bound,
+                                 load_fixture, sum_bounds)
+from test_gpu_metrics import _roles
+from test_metrics_oracle import derivative_plan, load_metrics_golden
+
+pytestmark = pytest.mark.gpu
+
+EVAL_RATE_WHEEL_CENTER_X = 19
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not gpu_available():
+        pytest.skip("no GPU")
+
+
+def _fixture_program(fx):
+    """The fixture's base program with evaluated kernels (roles: those of the same geometry's metrics golden)."""
+    from open_kinematics_amd.batch import DeviceProgram
+    from open_kinematics_amd.program import ConstraintProgram
+
+    program = ConstraintProgram.from_arrays(fx, prefix="prog_").with_line_mode("pinned")
+    mg = load_metrics_golden("c1_dw_corner")
+    roles, _ = _roles(program, mg)
+    dp = DeviceProgram(program, "cuda:0")
+    dp.enable_evaluation(roles)
+    assert dp.evaluation & 1, dp.evaluation_note
+    return dp, program
+
+
+def _fixture_columns(program, fx):
+    """The 15 columns of the fixture as ShardedEnsemble's ``metric_columns``."""
+    from open_kinematics_amd.metrics import METRIC_NAMES
+
+    cols = [(METRIC_NAMES.index(str(n)), None) for n in fx["value_names"]]
+    plan = derivative_plan(program, fx["deriv_names"])
+    assert len(plan) == len(fx["deriv_names"]) == 8
+    for j in range(8):
+        what, t = plan[j]
+        cols.append((EVAL_RATE_WHEEL_CENTER_X if isinstance(what, tuple) else what, t))
+    return cols
+
+
+def _flat_index(cols, eval_columns=24):
+    return torch.tensor([(0 if t is None else 1 + t) * eval_columns + c for c, t in cols], dtype=torch.int64, device="cuda:0")
+
+
+def test_kernel_reproduces_the_reference_statistics():
+    """The fixture's reference values uploaded as they are: the kernel against the reference's numbers, nothing of the
+    project's solver between."""
+    fx = load_fixture()
+    dp, _ = _fixture_program(fx)
+    g, s, k = fx["table"].shape
+    values = torch.as_tensor(fx["table"].reshape(g * s, k), device="cuda:0")
+    acc = dp.reduce_ensemble(values, steps_per_geometry=s, factors=fx["factors"])
+    torch.cuda.synchronize()
+    st = check_against_generator(acc, fx)
+    check_fit_against_lstsq(st, fx)
+    fa = acc.numpy().factor_acc
+    from open_kinematics_amd.ensemble_stats import reduce_host
+
+    want = reduce_host(fx["table"], None, fx["factors"])
+    assert fa[-1] == g and np.allclose(fa, want.factor_acc, rtol=0, atol=2 * (g + 1) * U * np.abs(want.factor_acc).max())
+    # no factors, all-accepted status bytes, an offset: same moments, shifted indices
+    lean = dp.reduce_ensemble(values, steps_per_geometry=s, status=torch.ones(g * s, dtype=torch.uint8, device="cuda:0"), geometry_offset=1000)
+    torch.cuda.synchronize()
+    a, b = lean.numpy().acc, acc.numpy().acc
+    assert np.array_equal(a[..., :6], b[..., :6]) and np.array_equal(a[..., 6:8], b[..., 6:8] + 1000)
+    with pytest.raises(ValueError, match="unit column stride"):
+        dp.reduce_ensemble(values.t(), steps_per_geometry=s)
+
+
+def test_reference_states_to_statistics():
+    """(i) okx_evaluate_batch at the reference's own states, reduced on the device, against the reference's statistics with
+    the per-state tolerances of tests/test_gpu_evaluated.py carried through; (ii) the ensemble solved AND evaluated on the
+    device against the NumPy accumulator of the same run's evaluation rows."""
+    import open_kinematics_amd.dist as okd
+    from open_kinematics_amd.ensemble_stats import reduce_host
+
+    fx = load_fixture()
+    dp, program = _fixture_program(fx)
+    g, s, k = fx["table"].shape
+    cols = _fixture_columns(program, fx)
+    hard = torch.as_tensor(fx["hardpoints"], device="cuda:0")
+    gpos, grow = dp.rebind(hard)
+    res = dp.evaluate(fx["pos"].reshape(g * s, -1, 3), geom_pos=gpos, geom_row_param=grow, steps_per_geometry=s)
+    table = torch.index_select(res.eval.reshape(g * s, -1), 1, _flat_index(cols))
+    acc = dp.reduce_ensemble(table, steps_per_geometry=s, factors=fx["factors"])
+    torch.cuda.synchronize()
+    st = acc.finalize()
+    # per-state tolerance of the evaluation against the reference: 1e-9 (values), 1e-7 max(1, |v|) (derivative columns)
+    eps = np.concatenate([np.full((s, 7), 1e-9), 1e-7 * np.maximum(1.0, np.abs(fx["deriv"]).max(axis=0))], axis=1)
+    per_state = np.abs(table.cpu().numpy().reshape(g, s, k) - fx["table"])
+    print("evaluate vs reference, worst per-state error / eps:", float((per_state.max(axis=0) / eps).max()))
+    assert np.array_equal(st.count, fx["stat_count"]) and np.all(st.rejected == 0)
+    err = {"mean": np.abs(st.mean - fx["stat_mean"]), "std": np.abs(st.std - np.sqrt(fx["stat_variance"])),
+           "min": np.abs(st.min - fx["stat_min"]), "max": np.abs(st.max - fx["stat_max"])}
+    for name, e in err.items():
+        print(f"{name}: worst error / eps = {float((e / eps).max()):.3e}")
+    for name, e in err.items():
+        assert np.all(e <= eps), name
+    assert np.array_equal(st.argmin, fx["stat_argmin"]) and np.array_equal(st.argmax, fx["stat_argmax"])
+    design = np.concatenate([np.ones((g, 1)), fx["factors"]], axis=1)
+    amplification = np.sqrt(g) * np.linalg.norm(np.linalg.pinv(design), 2)
+    slope_err = np.abs(st.sensitivity - fx["stat_sensitivity"]).max(axis=2)
+    print("sensitivity: worst error / (eps sqrt(G) ||pinv||) =", float((slope_err / (eps * amplification)).max()))
+    assert np.all(slope_err <= eps * amplification)
+
+    # (ii) solved and evaluated on the device
+    rel = np.stack([np.zeros(s), fx["bump"]], axis=1)
+    pipe = okd.ShardedEnsemble(dp, hard, rel, s, metric_columns=cols, reduce=True, factors="hardpoints")
+    got = pipe.step()
+    torch.cuda.synchronize()
+    assert pipe.metric_full is None and pipe.status_full is None and pipe.exchange_bytes_per_rank == 0
+    status = pipe.info_local[:, 32].cpu().numpy().reshape(g, s)
+    assert np.all((status & 7) == 1)  # every solve accepted
+    want_names = [str(n) for n in fx["factor_names"]]
+    assert sorted(pipe.factor_names) == sorted(want_names)
+    mine = pipe.my_factors.cpu().numpy()
+    centred = fx["factors"] - fx["factors"].mean(axis=0)
+    for j, n in enumerate(pipe.factor_names):
+        assert np.max(np.abs(mine[:, j] - centred[:, want_names.index(n)])) <= 1e-12, n
+    values = torch.index_select(pipe.eval_local.reshape(g * s, -1), 1, _flat_index(cols)).cpu().numpy().reshape(g, s, k)
+    shift = got.numpy().shift
+    assert np.array_equal(shift, np.nan_to_num(values[0]))
+    want = reduce_host(values, status, mine, shift, 0)
+    ok = np.isfinite(values)
+    e1, e2 = sum_bounds(values, ok, shift)
+    check_same_accumulator(got, want, e1, e2, cross_bound(values, ok, shift, mine))
+    assert np.allclose(got.numpy().factor_acc, want.factor_acc, rtol=0, atol=2 * (g + 1) * U * np.abs(want.factor_acc).max())
+    full = pipe.stats()
+    assert np.all(full.count == g) and np.all(full.r2 > 0.999) and full.sensitivity.shape == (s, k, 30)
+
+
+def _c5(n_geom=4096, steps=256):
+    from open_kinematics_amd.batch import DeviceProgram
+    from open_kinematics_amd.input import load_geometry
+    from open_kinematics_amd.metrics import corner_roles
+    from open_kinematics_amd.workloads import ensemble_problem, geometry_path
+
+    program, table, rel = ensemble_problem(n_geom, steps)
+    dp = DeviceProgram(program, "cuda:0")
+    dp.enable_evaluation(corner_roles(load_geometry(geometry_path("geometry.yaml")), program))
+    bump = program.n_targets - 1
+    columns = [("camber", None), ("camber", bump), ("roadwheel_angle", bump), (21, bump)]  # bench.py's c5 metrics form
+    return dp, program, torch.as_tensor(table, device="cuda:0"), rel, columns
+
+
+def test_full_size_ensemble():
+    """BASELINE config 5: 1 048 576 states, 4 columns, 30 factors."""
+    import open_kinematics_amd.dist as okd
+    from open_kinematics_amd.ensemble_stats import EnsembleAccumulator, reduce_host
+
+    g, s = 4096, 256
+    dp, program, table, rel, columns = _c5(g, s)
+    kw = dict(chain_len=1, predictor=False)
+    pipe = okd.ShardedEnsemble(dp, table, rel, s, metric_columns=columns, reduce=True, factors="hardpoints", **kw)
+    whole = pipe.step()
+    torch.cuda.synchronize()
+    k, p = 4, pipe.n_factors
+    assert p == 30 and tuple(whole.acc.shape) == (s, k, 8 + p)
+    first_bits = whole.acc.clone()
+    assert torch.equal(pipe.step().acc, first_bits)  # a second step starts from nothing: the same bits
+    torch.cuda.synchronize()
+    values_dev = pipe.metric_local.clone()
+    status_dev = pipe.info_local[:, 32].clone()
+    factors = pipe.my_factors
+    shift = whole.shift
+    # seeded tampering: 1000 status bytes, 1000 values, ties planted at the extremes
+    rng = np.random.default_rng(17)
+    status_dev[torch.as_tensor(rng.integers(0, g * s, 1000), device="cuda:0")] = torch.as_tensor(
+        rng.choice(np.array([0, 2, 3, 4, 5, 9], dtype=np.uint8), 1000), device="cuda:0")
+    flat = values_dev.view(-1)
+    where = torch.as_tensor(rng.integers(0, g * s * k, 1000), device="cuda:0")
+    flat[where] = torch.as_tensor(rng.choice(np.array([np.nan, np.inf, -np.inf, 1e6]), 1000), device="cuda:0")
+    host = values_dev.cpu().numpy().reshape(g, s, k)
+    st_host = status_dev.cpu().numpy().reshape(g, s)
+    ok = np.isfinite(host) & ((st_host & 7) == 1)[:, :, None]
+    for step, col in ((0, 0), (100, 1), (255, 3)):
+        column = np.where(ok[:, step, col], host[:, step, col], np.nan)
+        for geometry, v in ((3000, np.nanmin(column)), (4000, np.nanmin(column)), (3500, np.nanmax(column)), (4095, np.nanmax(column))):
+            values_dev[geometry * s + step, col] = float(v)
+            status_dev[geometry * s + step] = 1
+    host = values_dev.cpu().numpy().reshape(g, s, k)
+    st_host = status_dev.cpu().numpy().reshape(g, s)
+    ok = np.isfinite(host) & ((st_host & 7) == 1)[:, :, None]
+    want = reduce_host(host, st_host, factors.cpu().numpy(), shift.cpu().numpy(), 0)
+    e1, e2 = sum_bounds(host, ok, shift.cpu().numpy())
+    fe = cross_bound(host, ok, shift.cpu().numpy(), factors.cpu().numpy())
+
+    def run(chunks=1, out=None):
+        acc = out
+        edges = np.linspace(0, g, chunks + 1).round().astype(int)
+        for i, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
+            acc = dp.reduce_ensemble(values_dev[a * s : b * s], steps_per_geometry=s, status=status_dev[a * s : b * s],
+                                     factors=factors[a:b], shift=shift if acc is None else None, geometry_offset=int(a), out=acc,
+                                     accumulate=i > 0)
+        torch.cuda.synchronize()
+        return acc
+
+    first = run()
+    check_same_accumulator(first, want, e1, e2, fe)
+    assert np.allclose(first.numpy().factor_acc, want.factor_acc, rtol=0, atol=2 * (g + 1) * U * np.abs(want.factor_acc).max())
+    assert first.numpy().acc[0, 0, 6] <= 3000 and first.numpy().acc[0, 0, 7] <= 3500  # ties went to the lowest index
+    second = run()
+    assert torch.equal(first.acc, second.acc) and torch.equal(first.factor_acc, second.factor_acc)  # bit for bit, run to run
+    for chunks in (2, 8):
+        check_same_accumulator(run(chunks), first, e1, e2, fe)
+    # a captured graph replays to the same bits
+    out = EnsembleAccumulator(torch.zeros_like(first.acc), shift, torch.zeros_like(first.factor_acc))
+    run(out=out)  # (warm: the scratch buffer exists)
+    out.acc.zero_()
+    stream = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        dp.reduce_ensemble(values_dev, steps_per_geometry=s, status=status_dev, factors=factors, out=out)
+    out.acc.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out.acc, first.acc) and torch.equal(out.factor_acc, first.factor_acc)
+    # the sharded ensemble in chunks: counts, extremes and indices exactly, sums within the bound
+    whole_host = reduce_host(pipe.metric_local.cpu().numpy().reshape(g, s, k), pipe.info_local[:, 32].cpu().numpy().reshape(g, s),
+                             factors.cpu().numpy(), shift.cpu().numpy(), 0)
+    clean = pipe.metric_local.cpu().numpy().reshape(g, s, k)
+    ok_clean = np.isfinite(clean) & ((pipe.info_local[:, 32].cpu().numpy().reshape(g, s) & 7) == 1)[:, :, None]
+    c1, c2 = sum_bounds(clean, ok_clean, shift.cpu().numpy())
+    cf = cross_bound(clean, ok_clean, shift.cpu().numpy(), factors.cpu().numpy())
+    check_same_accumulator(whole, whole_host, c1, c2, cf)
+    for chunks in (2, 8):
+        other = okd.ShardedEnsemble(dp, table, rel, s, chunks=chunks, metric_columns=columns, reduce=True, factors="hardpoints", **kw)
+        got = other.step()
+        torch.cuda.synchronize()
+        assert torch.equal(got.shift, shift)
+        check_same_accumulator(got, whole, c1, c2, cf)
+    # reduce=False: what it was
+    plain = okd.ShardedEnsemble(dp, table, rel, s, metric_columns=columns, **kw)
+    full = plain.step()
+    torch.cuda.synchronize()
+    assert torch.equal(torch.nan_to_num(full), torch.nan_to_num(pipe.metric_local))
+
+
+def _rehearse(tmp_path, world, g, s):
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "tools", "ensemble_reduce_rate.py"), "--rehearse", str(world), "--geometries", str(g),
+                           "--steps-per-geometry", str(s), "--out", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
+    got = [torch.load(os.path.join(tmp_path, f"rank{r}.pt")) for r in range(world)]
+    for r in range(1, world):  # the same bits on every rank
+        for key in ("acc", "factor_acc", "shift"):
+            assert torch.equal(got[0][key], got[r][key]), (key, r)
+    return got
+
+
+def test_two_ranks_rehearsed_on_one_gpu(tmp_path):
+    """BASELINE config 5 at full size, both ranks on cuda:0, gloo in place of RCCL (fresh child processes, as
+    tests/test_gpu_rccl.py rehearses): the same accumulator bits on both ranks, equal to the one-process reduction of the
+    whole ensemble within the bound and exactly in counts, extremes and indices."""
+    import open_kinematics_amd.dist as okd
+    from open_kinematics_amd.ensemble_stats import EnsembleAccumulator
+
+    g, s = 4096, 256
+    got = _rehearse(tmp_path, 2, g, s)
+    assert got[0]["sent"] == 8 * (s * 4 * 38 + 30 + 465 + 1) and got[0]["range"] == (0, g // 2) and got[1]["range"] == (g // 2, g)
+    dp, program, table, rel, columns = _c5(g, s)
+    pipe = okd.ShardedEnsemble(dp, table, rel, s, metric_columns=columns, reduce=True, factors="hardpoints", chain_len=1, predictor=False)
+    alone = pipe.step()
+    torch.cuda.synchronize()
+    values = pipe.metric_local.cpu().numpy().reshape(g, s, 4)
+    ok = np.isfinite(values) & ((pipe.info_local[:, 32].cpu().numpy().reshape(g, s) & 7) == 1)[:, :, None]
+    shift = alone.shift.cpu().numpy()
+    assert np.array_equal(got[0]["shift"].numpy(), shift)
+    e1, e2 = sum_bounds(values, ok, shift)
+    check_same_accumulator(EnsembleAccumulator(got[0]["acc"].numpy(), shift), alone, e1, e2, cross_bound(values, ok, shift, pipe.my_factors.cpu().numpy()))
+    fa = alone.factor_acc.cpu().numpy()
+    assert np.allclose(got[0]["factor_acc"].numpy(), fa, rtol=0, atol=2 * (g + 1) * U * np.abs(fa).max())
+
+
+def test_a_rank_without_a_geometry_on_the_device(tmp_path):
+    """The neutral accumulator of an empty table with an empty factor table, and three ranks rehearsed on one GPU over two
+    geometries: rank 2 owns none and takes the device path with nothing to reduce."""
+    import open_kinematics_amd.dist as okd
+    from open_kinematics_amd.ensemble_stats import EnsembleAccumulator
+
+    dp, program, table, rel, columns = _c5(2, 16)
+    s, k, p = 16, 4, 30
+    shift = torch.zeros((s, k), dtype=torch.float64, device="cuda:0")
+    empty = dp.reduce_ensemble(torch.empty((0, k), dtype=torch.float64, device="cuda:0"), steps_per_geometry=s,
+                               status=torch.empty(0, dtype=torch.uint8, device="cuda:0"),
+                               factors=torch.empty((0, p), dtype=torch.float64, device="cuda:0"), shift=shift)
+    torch.cuda.synchronize()
+    want = EnsembleAccumulator.empty(s, k, p, np.zeros((s, k)))
+    assert np.array_equal(empty.numpy().acc, want.acc) and np.array_equal(empty.numpy().factor_acc, want.factor_acc)
+    with pytest.raises(ValueError, match=r"\[G, P\]"):
+        dp.reduce_ensemble(torch.zeros((s, k), dtype=torch.float64, device="cuda:0"), steps_per_geometry=s, factors=torch.zeros(p, device="cuda:0"))
+    got = _rehearse(tmp_path, 3, 2, s)
+    assert [g["range"] for g in got] == [(0, 1), (1, 2), (2, 2)]
+    pipe = okd.ShardedEnsemble(dp, table, rel, s, metric_columns=columns, reduce=True, factors="hardpoints", chain_len=1, predictor=False)
+    alone = pipe.step()
+    torch.cuda.synchronize()
+    values = pipe.metric_local.cpu().numpy().reshape(2, s, k)
+    ok = np.isfinite(values) & ((pipe.info_local[:, 32].cpu().numpy().reshape(2, s) & 7) == 1)[:, :, None]
+    shift = alone.shift.cpu().numpy()
+    e1, e2 = sum_bounds(values, ok, shift)
+    check_same_accumulator(EnsembleAccumulator(got[0]["acc"].numpy(), shift), alone, e1, e2, cross_bound(values, ok, shift, pipe.my_factors.cpu().numpy()))
+
+
+@pytest.mark.parametrize("p", [1, 2, 3, 7, 9, 17, 33])
+def test_few_factors_at_the_end_of_their_allocation(p):
+    """Blocks of 8 / 16 / 32 factors with fewer factors than half a block (and one factor past a block): the wide factor reads
+    must end inside the [G][P] table.  The factor table is the tail of its allocation; the accumulators against NumPy's."""
+    from open_kinematics_amd.batch import DeviceProgram
+    from open_kinematics_amd.ensemble_stats import reduce_host
+    from open_kinematics_amd.workloads import bump_sweep_problem
+
+    program, _ = bump_sweep_problem(4)
+    dp = DeviceProgram(program, "cuda:0")
+    rng = np.random.default_rng(40 + p)
+    g, s, k = 37, 5, 3
+    values = rng.normal(size=(g, s, k))
+    status = np.ones((g, s), dtype=np.uint8)
+    status[rng.integers(0, g, 9), rng.integers(0, s, 9)] = 2
+    factors = rng.normal(size=(g, p))
+    block = torch.empty(32 * 1024 * 1024 // 8, dtype=torch.float64, device="cuda:0")  # (large enough to be an allocation of its own)
+    tail = block[block.numel() - g * p :].view(g, p)
+    tail.copy_(torch.as_tensor(factors))
+    assert tail.data_ptr() + 8 * g * p == block.data_ptr() + 8 * block.numel()
+    shift = values[0].copy()
+    acc = dp.reduce_ensemble(torch.as_tensor(values.reshape(g * s, k), device="cuda:0"), steps_per_geometry=s,
+                             status=torch.as_tensor(status.reshape(-1), device="cuda:0"), factors=tail, shift=shift, geometry_offset=5)
+    torch.cuda.synchronize()
+    want = reduce_host(values, status, factors, shift, 5)
+    ok = np.broadcast_to(((status & 7) == 1)[:, :, None], values.shape)
+    e1, e2 = sum_bounds(values, ok, shift)
+    check_same_accumulator(acc, want, e1, e2, cross_bound(values, ok, shift, factors))
+    assert np.allclose(acc.numpy().factor_acc, want.factor_acc, rtol=0, atol=2 * (g + 1) * U * max(1.0, np.abs(want.factor_acc).max()))
+
+
+@pytest.mark.parametrize("kind", ["corner", "axle"])
+def test_strided_views_of_evaluation_rows(golden, kind):
+    """Row 0 of a corner (24 columns) and of an axle (64 columns) evaluation passed as a strided view (ld = row length x
+    (1 + T)): the same accumulators as the packed copy, bit for bit."""
+    from open_kinematics_amd.batch import DeviceProgram
+
+    rng = np.random.default_rng(2)
+    if kind == "corner":
+        arrays, program = golden("c1_dw_corner")
+        program = program.with_line_mode("pinned")
+        dp = DeviceProgram(program, "cuda:0")
+        roles, _ = _roles(program, load_metrics_golden("c1_dw_corner"))
+        dp.enable_evaluation(roles)
+        targets = arrays["targets_abs"][:96]
+        ev = dp.solve_evaluated(targets, output="none").eval
+    else:
+        import yaml
+
+        from open_kinematics_amd.input import build_suspension, build_sweep
+        from open_kinematics_amd.metrics import axle_evaluation_roles
+        from open_kinematics_amd.sweep import sweep_program
+
+        arrays, _ = golden("c3_axle_grid")
+        axle = build_suspension(yaml.safe_load(str(arrays["geometry_yaml"])))
+        program, table = sweep_program(axle, build_sweep(yaml.safe_load(str(arrays["sweep_yaml"])), axle))
+        dp = DeviceProgram(program, "cuda:0")
+        dp.enable_evaluation(axle_evaluation_roles(axle, program)[0])
+        ev = dp.solve_evaluated(np.asarray(table)[:96], output="none").eval
+    torch.cuda.synchronize()
+    b, rows, width = ev.shape
+    assert width == (24 if kind == "corner" else 64) and b == 96
+    s = 8
+    g = b // s
+    view = ev[:, 0, :]
+    assert view.stride(0) == rows * width and not view.is_contiguous()
+    factors = rng.normal(size=(g, 5))
+    status = torch.ones(b, dtype=torch.uint8, device="cuda:0")
+    status[::7] = 2
+    shift = torch.nan_to_num(view[:s].clone(), nan=0.0, posinf=0.0, neginf=0.0)
+    a = dp.reduce_ensemble(view, steps_per_geometry=s, status=status, factors=factors, shift=shift)
+    packed = dp.reduce_ensemble(view.contiguous(), steps_per_geometry=s, status=status, factors=factors, shift=shift)
+    torch.cuda.synchronize()
+    assert torch.equal(a.acc, packed.acc) and torch.equal(a.factor_acc, packed.factor_acc)
+    count = a.acc[..., 0].cpu().numpy()
+    finite = torch.isfinite(view).cpu().numpy().reshape(g, s, width) & ((status.cpu().numpy().reshape(g, s) & 7) == 1)[:, :, None]
+    assert np.array_equal(count, finite.sum(axis=0))
+    # the info records' flag byte as a strided status view
+    info = torch.zeros((b, 40), dtype=torch.uint8, device="cuda:0")
+    info[:, 32] = status
+    c = dp.reduce_ensemble(view, steps_per_geometry=s, status=info[:, 32], factors=factors, shift=shift)
+    torch.cuda.synchronize()
+    assert torch.equal(c.acc, a.acc)
