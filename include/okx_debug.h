@@ -60,6 +60,37 @@ int32_t okx_debug_kernel_scratch(const okx_program_desc* desc, int32_t* scratch_
  * variant kept by the build). */
 int32_t okx_debug_lane_scratch(const okx_program_desc* desc, int32_t* out3);
 
+/* What the launch planner (csrc/okx_launch.hpp) reads from a program: every launching entry point fills one from its
+ * okx_program and plans from it alone, so a test can plan from hand-made capabilities without a device.  Flags are 0 / 1. */
+typedef struct okx_launch_caps {
+  int64_t lane_min_problems;    /* batch size from which auto selection looks at the lane kernel */
+  int32_t n_cu, n, nreg, n_targets;
+  int32_t blocks_per_cu, packed_blocks_per_cu, groups, has_packed;        /* interpreter kernels */
+  int32_t has_quad, quad_ppw, quad_waves_per_cu, has_head, has_cold;      /* quad kernel, first-step tables, cold body */
+  int32_t has_lane, lane_cold_ok, lane_chain_ok, has_nest, has_refine;    /* lane kernel and its start modes */
+  int32_t ev_enabled, ev_lane, ev_cold, ev_lane_pos;                      /* evaluated modules */
+  int32_t line_row;             /* the program has the zero-gradient point-on-line row */
+  int32_t trace, predictor;     /* okx_debug_quad_trace hook set, okx_program_fit_predictor model present */
+  int32_t lane_timeline, quad_timeline, no_cold, evaluate_quad, evaluate_lane;  /* developer switches, sampled by the caller */
+} okx_launch_caps;
+
+/* The planner on caller-made capabilities (no device, no program): out6 = (family as okx_plan_launch reports it,
+ * chain length with okx_plan_launch's -1 for the nested start mode, start mode 0 cold / 1 chain / 2 nested / 3 refined,
+ * 1 when chain_len = -1 was resolved to independent solves on the lane kernel, confirm, grid size).  Returns the
+ * okx_status of the plan; okx_last_error() has its message. */
+int32_t okx_debug_plan_launch(const okx_launch_caps* caps, const okx_solve_opts* opts, int64_t n_problems,
+                              int32_t geometry_tables, int32_t evaluated, int32_t* out6);
+
+/* The notes okx_debug_plan_launch passes where a launch passes its program's quad_note, lane_note and ev_note (per thread;
+ * null or never set: empty, as on a program whose kernels all attached). */
+void okx_debug_plan_notes(const char* quad_note, const char* lane_note, const char* ev_note);
+
+/* okx_evaluate_batch's choice on caller-made capabilities: out2 = (1 lane form / 0 quad form, the lane form's wave units). */
+int32_t okx_debug_plan_evaluate(const okx_launch_caps* caps, int64_t n_problems, int64_t steps_per_geometry, int32_t* out2);
+
+/* The capabilities the launch path itself fills for this program (developer switches as the environment has them now). */
+int32_t okx_debug_program_caps(okx_program* prog, okx_launch_caps* caps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,19 @@ class SolveOpts(C.Structure):
     ]
 
 
+class LaunchCaps(C.Structure):
+    """``okx_launch_caps`` (include/okx_debug.h): what the launch planner reads of a program."""
+
+    _fields_ = [("lane_min_problems", C.c_int64)] + [(name, C.c_int32) for name in (
+        "n_cu", "n", "nreg", "n_targets",
+        "blocks_per_cu", "packed_blocks_per_cu", "groups", "has_packed",
+        "has_quad", "quad_ppw", "quad_waves_per_cu", "has_head", "has_cold",
+        "has_lane", "lane_cold_ok", "lane_chain_ok", "has_nest", "has_refine",
+        "ev_enabled", "ev_lane", "ev_cold", "ev_lane_pos",
+        "line_row", "trace", "predictor",
+        "lane_timeline", "quad_timeline", "no_cold", "evaluate_quad", "evaluate_lane")]
+
+
 class Info(C.Structure):
     _fields_ = [
         ("max_residual", C.c_double),

@@ -13,7 +13,7 @@ import ctypes as C
 import os
 import subprocess
 
-from ._abi import ABI_VERSION, Info, ProgramDesc, SolveOpts
+from ._abi import ABI_VERSION, Info, LaunchCaps, ProgramDesc, SolveOpts
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libokx.so")
@@ -72,6 +72,10 @@ DEBUG_EXPORTS = (
     "okx_debug_plan_stats",
     "okx_debug_kernel_scratch",
     "okx_debug_lane_scratch",
+    "okx_debug_plan_launch",
+    "okx_debug_plan_notes",
+    "okx_debug_plan_evaluate",
+    "okx_debug_program_caps",
 )
 
 _lib = None
@@ -131,6 +135,14 @@ def load() -> C.CDLL:
     lib.okx_debug_kernel_scratch.restype = i32
     lib.okx_debug_lane_scratch.argtypes = [C.POINTER(ProgramDesc), C.POINTER(i32)]
     lib.okx_debug_lane_scratch.restype = i32
+    lib.okx_debug_plan_launch.argtypes = [C.POINTER(LaunchCaps), C.POINTER(SolveOpts), i64, i32, i32, C.POINTER(i32 * 6)]
+    lib.okx_debug_plan_launch.restype = i32
+    lib.okx_debug_plan_notes.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+    lib.okx_debug_plan_notes.restype = None
+    lib.okx_debug_plan_evaluate.argtypes = [C.POINTER(LaunchCaps), i64, i64, C.POINTER(i32 * 2)]
+    lib.okx_debug_plan_evaluate.restype = i32
+    lib.okx_debug_program_caps.argtypes = [vp, C.POINTER(LaunchCaps)]
+    lib.okx_debug_program_caps.restype = i32
     lib.okx_debug_quad_trace.argtypes = [vp, vp, i64]
     lib.okx_debug_quad_trace.restype = i32
     lib.okx_debug_phase_profile.argtypes = [vp, C.POINTER(SolveOpts), i64, vp, vp, vp, vp, vp]

@@ -1184,7 +1184,7 @@ struct Piece { const char* src; int src_off, count, dst; };  // `count` doubles 
 // (first-step table); steps 2, 1 and 3 start ~1e-8 mm from their solutions instead of a secant's ~1e-4: one full pass
 // and one confirming evaluation.  What a chain carries beside the point - the damping it ended with, the contraction
 // constant it observed - comes from the lane's own step 0.
-// Coarse-to-fine start (developer switch lane_refine; okx_api.hip solve_impl): two more instantiations of the
+// Coarse-to-fine start (developer switch lane_refine; okx_launch.cpp plan_launch, okx_api.hip launch_lane): two more instantiations of the
 // independent-solve bodies with a compile-time STRIDE - SUB = 4: lane l of a wave unit solves step 4 l + offset of its
 // span (offset = a.chain_len, 0 .. 3) - one as it is (the coarse launch: every fourth step, cold from the first-step
 // table) and one WARM: the start is the cubic Lagrange interpolant, in the step index, of the four nearest coarse steps,
