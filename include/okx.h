@@ -800,6 +800,70 @@ int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_colum
                             void* d_scratch, size_t scratch_bytes, void* stream);
 size_t okx_ensemble_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_factors);
 
+/*
+ * Ensemble selection on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): per (step, column)
+ * entry of the same table, over the states that count by the rule of okx_ensemble_reduce, EXACT order statistics and
+ * spec-limit counts - what quantiles and yield are finalized from on the host (open_kinematics_amd/ensemble_stats.py).
+ * d_probs [n_probs] probabilities in [0, 1]; d_limits (or NULL) [steps][n_columns][2] = (lo, hi), -inf / +inf leaves a side
+ * open.  With n the number of states that count and h = (n - 1) * p in fp64:
+ *   d_order   [steps][n_columns][n_probs][2]  x[floor(h)], x[ceil(h)] of the sorted accepted values (0-based) - the bits
+ *                                             of values in the table; NaN when n = 0 (or p is not in [0, 1])
+ *   d_count   [steps][n_columns]              n, int64
+ *   d_outside [steps][n_columns][2] or NULL   accepted values < lo, > hi (strictly), int64
+ * The quantile x_lo + (h - floor(h)) (x_hi - x_lo) (NumPy's method="linear") and the yield 1 - (below + above) / n are
+ * host arithmetic; p = 0 / 1 give OKX_ENS_MIN / OKX_ENS_MAX of the reduce pass bit for bit.
+ *
+ * A radix select on order-preserving keys: key = bits ^ (sign ? ~0 : 1 << 63) (-0.0 sorts before +0.0), and
+ * okx_ensemble_select_rounds() = 64 / OKX_ENS_SELECT_BITS rounds fix OKX_ENS_SELECT_BITS key bits each, from the top.
+ * Selection j = 2 q + side of an entry carries a prefix (the bits fixed so far) and the rank wanted among the values that
+ * share it.  Per round: a COUNT pass adds into d_hist, int64 [steps][n_columns][2 n_probs][1 << OKX_ENS_SELECT_BITS]
+ * (okx_ensemble_select_hist_len words): hist[s][k][j][b] += accepted values whose fixed bits equal selection j's prefix and
+ * whose next bits are b; a DESCEND picks the bin that holds the rank, extends the prefix, subtracts what lies below and
+ * re-zeroes the histogram.  Round 0 has no prefix: hist[s][k][0][:] is the histogram all selections of the entry share,
+ * hist[s][k][1][0] / [1][1] count the values below lo / above hi, the rest stays zero; its descend sums n and turns the
+ * probabilities into ranks.  Integer atomics only (LDS, then global) - no floating-point operation but the rank's product.
+ * The histogram is ALL that depends on the data: a table that arrives in chunks counts every chunk into the same d_hist
+ * before the round's descend, and ranks that hold parts of it sum their histograms (an integer all-reduce) before each
+ * descends its own copy of the state - integer sums in any order, so the result is bit-identical across chunks, slabs,
+ * runs, devices and ranks.  d_state (okx_ensemble_select_state_bytes) is opaque.  Launch-only, stream-ordered, legal inside
+ * a stream capture: no host read-back between rounds, and begin zeroes state and histogram on the stream.
+ *   okx_ensemble_select          one device, one table: begin, every round's count + descend, finish; d_scratch holds
+ *                                state and histogram (okx_ensemble_select_scratch_bytes).  n_geometries = 0 is legal.
+ *   okx_ensemble_select_begin    zeroes d_state and d_hist
+ *   okx_ensemble_select_count    round `round` over one chunk of geometries, adds into d_hist (d_limits is read in round 0)
+ *   okx_ensemble_select_descend  consumes d_hist, advances d_state, re-zeroes d_hist (d_probs is read in round 0)
+ *   okx_ensemble_select_finish   writes d_order / d_count / d_outside from d_state
+ * The launches cannot read d_probs / d_limits on the host: okx_ensemble_select_check validates HOST copies of them
+ * (p outside [0, 1] or NaN, NaN limits, lo > hi: OKX_ERR_INVALID with okx_last_error text) before they are uploaded.
+ */
+#ifndef OKX_ENS_SELECT_BITS
+#define OKX_ENS_SELECT_BITS 4
+#endif
+enum { OKX_ENS_SELECT_MAX_PROBS = 64 };
+
+int32_t okx_ensemble_select(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                            const double* d_values, int64_t ld,
+                            const uint8_t* d_status, int64_t status_stride, /* or NULL                                  */
+                            const double* d_probs, int32_t n_probs,
+                            const double* d_limits,                         /* or NULL                                  */
+                            double* d_order, int64_t* d_count,
+                            int64_t* d_outside,                             /* or NULL                                  */
+                            void* d_scratch, size_t scratch_bytes, void* stream);
+int32_t okx_ensemble_select_begin(int64_t steps, int32_t n_columns, int32_t n_probs, void* d_state, int64_t* d_hist, void* stream);
+int32_t okx_ensemble_select_count(int32_t round, int64_t n_geometries, int64_t steps, int32_t n_columns,
+                                  const double* d_values, int64_t ld, const uint8_t* d_status, int64_t status_stride,
+                                  int32_t n_probs, const double* d_limits, const void* d_state, int64_t* d_hist, void* stream);
+int32_t okx_ensemble_select_descend(int32_t round, int64_t steps, int32_t n_columns, const double* d_probs, int32_t n_probs,
+                                    void* d_state, int64_t* d_hist, void* stream);
+int32_t okx_ensemble_select_finish(int64_t steps, int32_t n_columns, int32_t n_probs, const void* d_state,
+                                   double* d_order, int64_t* d_count, int64_t* d_outside, void* stream);
+/* host only */
+int32_t okx_ensemble_select_rounds(void);
+int64_t okx_ensemble_select_hist_len(int64_t steps, int32_t n_columns, int32_t n_probs);
+size_t okx_ensemble_select_state_bytes(int64_t steps, int32_t n_columns, int32_t n_probs);
+size_t okx_ensemble_select_scratch_bytes(int64_t steps, int32_t n_columns, int32_t n_probs);
+int32_t okx_ensemble_select_check(const double* probs, int32_t n_probs, const double* limits /* or NULL */, int64_t n_limits /* (lo, hi) pairs */);
+
 #ifdef __cplusplus
 }
 #endif

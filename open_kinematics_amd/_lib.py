@@ -60,6 +60,16 @@ EXPORTS = (
     "okx_diagnose_sweeps_batch",
     "okx_ensemble_reduce",
     "okx_ensemble_scratch_bytes",
+    "okx_ensemble_select",
+    "okx_ensemble_select_begin",
+    "okx_ensemble_select_count",
+    "okx_ensemble_select_descend",
+    "okx_ensemble_select_finish",
+    "okx_ensemble_select_rounds",
+    "okx_ensemble_select_hist_len",
+    "okx_ensemble_select_state_bytes",
+    "okx_ensemble_select_scratch_bytes",
+    "okx_ensemble_select_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -215,6 +225,26 @@ def load() -> C.CDLL:
     lib.okx_ensemble_reduce.restype = i32
     lib.okx_ensemble_scratch_bytes.argtypes = [i64, i64, i32, i32]
     lib.okx_ensemble_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_select.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_select.restype = i32
+    lib.okx_ensemble_select_begin.argtypes = [i64, i32, i32, vp, vp, vp]
+    lib.okx_ensemble_select_begin.restype = i32
+    lib.okx_ensemble_select_count.argtypes = [i32, i64, i64, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp]
+    lib.okx_ensemble_select_count.restype = i32
+    lib.okx_ensemble_select_descend.argtypes = [i32, i64, i32, vp, i32, vp, vp, vp]
+    lib.okx_ensemble_select_descend.restype = i32
+    lib.okx_ensemble_select_finish.argtypes = [i64, i32, i32, vp, vp, vp, vp, vp]
+    lib.okx_ensemble_select_finish.restype = i32
+    lib.okx_ensemble_select_rounds.argtypes = []
+    lib.okx_ensemble_select_rounds.restype = i32
+    lib.okx_ensemble_select_hist_len.argtypes = [i64, i32, i32]
+    lib.okx_ensemble_select_hist_len.restype = i64
+    lib.okx_ensemble_select_state_bytes.argtypes = [i64, i32, i32]
+    lib.okx_ensemble_select_state_bytes.restype = C.c_size_t
+    lib.okx_ensemble_select_scratch_bytes.argtypes = [i64, i32, i32]
+    lib.okx_ensemble_select_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_select_check.argtypes = [vp, i32, vp, i64]
+    lib.okx_ensemble_select_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

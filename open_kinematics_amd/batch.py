@@ -127,6 +127,37 @@ class EvaluatedResult(BatchResult):
         return out
 
 
+@dataclass
+class EnsembleSelection:
+    """
+    What ``DeviceProgram.select_ensemble`` returns and its round-level calls work on, device tensors: ``probs [Q]`` and
+    ``limits [S, K, 2]`` (or None) as uploaded, ``order [S, K, Q, 2]`` the order statistics below / above every quantile,
+    ``count [S, K]`` and ``outside [S, K, 2]`` (or None) int64; ``state`` / ``hist`` (``select_prepare(rounds=True)``) the
+    opaque state and the int64 histogram ``[S, K, 2 Q, bins]`` of ``okx_ensemble_select_count``.
+    """
+
+    probs_host: np.ndarray
+    probs: torch.Tensor
+    limits: torch.Tensor | None
+    order: torch.Tensor
+    count: torch.Tensor
+    outside: torch.Tensor | None
+    state: torch.Tensor | None = None
+    hist: torch.Tensor | None = None
+
+    @property
+    def shape(self) -> tuple:
+        """``(S, K, Q)``."""
+        return tuple(self.order.shape[:3])
+
+    def finalize(self):
+        """Host copy, interpolated: ``ensemble_stats.EnsembleQuantiles``."""
+        from .ensemble_stats import quantiles_from_order
+
+        return quantiles_from_order(self.probs_host, self.order.cpu().numpy(), self.count.cpu().numpy(),
+                                    None if self.outside is None else self.outside.cpu().numpy())
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -805,6 +836,123 @@ class DeviceProgram:
                                               int(geometry_offset), 1 if accumulate else 0, _ptr(out.acc), _ptr(factor_acc),
                                               _ptr(scratch), scratch.numel(), C.c_void_p(stream))
         _lib.check(rc, "okx_ensemble_reduce")
+        return out
+
+    # ---- okx_ensemble_select: exact order statistics and spec-limit counts (ensemble_stats.EnsembleQuantiles) ----
+
+    def _ensemble_table(self, values, status, steps_per_geometry: int):
+        """``(G, S, K, ld, status stride)`` of a column table view - the rules and words of ``reduce_ensemble``."""
+        s = int(steps_per_geometry)
+        if values.dim() != 2 or values.dtype != torch.float64 or values.device != self.device or (values.shape[1] > 1 and values.stride(1) != 1):
+            raise ValueError("values must be a float64 [G * S, K] device tensor with unit column stride")
+        b, k = values.shape
+        if s < 1 or b % s:
+            raise ValueError("bad steps_per_geometry")
+        ld = values.stride(0) if b > 1 else max(k, values.stride(0))
+        if ld < k:
+            raise ValueError("rows of values overlap")
+        stride = 0
+        if status is not None:
+            if status.dtype != torch.uint8 or status.dim() != 1 or status.shape[0] != b or status.device != self.device:
+                raise ValueError("status must be a uint8 [G * S] device tensor")
+            stride = status.stride(0) if b > 1 else 1
+        return b // s, s, k, ld, stride
+
+    def select_prepare(self, steps: int, n_columns: int, probs, limits=None, *, rounds: bool = False) -> "EnsembleSelection":
+        """
+        The tables of a select over ``[steps, n_columns]`` entries: ``probs`` (``[Q]`` in [0, 1]) and ``limits`` (``[S, K, 2]``,
+        ``[K, 2]`` or ``[2]`` = (lo, hi), -inf / +inf leaves a side open; None: no limit counts) are validated by
+        ``okx_ensemble_select_check`` on the host and uploaded ONCE; outputs are allocated.  ``rounds=True`` adds the state and
+        the histogram the round-level calls (``select_begin`` / ``select_count`` / ``select_descend`` / ``select_finish``) work on.
+        """
+        from .ensemble_stats import SELECT_MAX_PROBS
+
+        s, k = int(steps), int(n_columns)
+        host = lambda t: np.array(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64)  # noqa: E731  (a copy, in fp64 from the start)
+        p = np.ascontiguousarray(np.atleast_1d(host(probs)).reshape(-1))
+        lim = None
+        if limits is not None:
+            lim = host(limits)
+            if lim.shape[-1:] != (2,) or lim.size not in (2, 2 * k, 2 * s * k):
+                raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
+            lim = np.array(np.broadcast_to(lim.reshape(s, k, 2) if lim.size == 2 * s * k else lim.reshape(-1, 2), (s, k, 2)), order="C")
+        rc = self.lib.okx_ensemble_select_check(p.ctypes.data_as(C.c_void_p), min(p.size, SELECT_MAX_PROBS + 1),
+                                                None if lim is None else lim.ctypes.data_as(C.c_void_p), 0 if lim is None else s * k)
+        _lib.check(rc, "okx_ensemble_select")
+        q, dev = p.size, self.device
+        run = EnsembleSelection(p, torch.as_tensor(p, device=dev), None if lim is None else torch.as_tensor(lim, device=dev),
+                                torch.empty((s, k, q, 2), dtype=torch.float64, device=dev), torch.empty((s, k), dtype=torch.int64, device=dev),
+                                None if lim is None else torch.empty((s, k, 2), dtype=torch.int64, device=dev))
+        if rounds:
+            run.state = torch.empty(max(1, int(self.lib.okx_ensemble_select_state_bytes(s, k, q))), dtype=torch.uint8, device=dev)
+            run.hist = torch.empty((s, k, 2 * q, int(self.lib.okx_ensemble_select_hist_len(s, k, q)) // max(1, s * k * 2 * q)),
+                                   dtype=torch.int64, device=dev)
+        return run
+
+    @property
+    def select_rounds(self) -> int:
+        return int(self.lib.okx_ensemble_select_rounds())
+
+    def _select_call(self, name: str, *args) -> None:
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(*args, C.c_void_p(stream))
+        _lib.check(rc, name)
+
+    def select_begin(self, run: "EnsembleSelection") -> None:
+        """State and histogram of ``run`` zeroed on the stream (``okx_ensemble_select_begin``)."""
+        s, k, q = run.shape
+        self._select_call("okx_ensemble_select_begin", s, k, q, _ptr(run.state), _ptr(run.hist))
+
+    def select_count(self, run: "EnsembleSelection", rnd: int, values, *, steps_per_geometry: int, status=None) -> None:
+        """Round ``rnd`` over one chunk of geometries ``values [G' * S, K]``, added into ``run.hist`` (``okx_ensemble_select_count``)."""
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if (s, k) != run.shape[:2]:
+            raise ValueError(f"the select was prepared for [S, K] = {list(run.shape[:2])}")
+        self._select_call("okx_ensemble_select_count", int(rnd), g, s, k, _ptr(values), ld, _ptr(status), stride, run.shape[2],
+                          _ptr(run.limits), _ptr(run.state), _ptr(run.hist))
+
+    def select_descend(self, run: "EnsembleSelection", rnd: int) -> None:
+        """``run.hist`` consumed and re-zeroed, the state advanced by one round (``okx_ensemble_select_descend``)."""
+        s, k, q = run.shape
+        self._select_call("okx_ensemble_select_descend", int(rnd), s, k, _ptr(run.probs), q, _ptr(run.state), _ptr(run.hist))
+
+    def select_finish(self, run: "EnsembleSelection") -> "EnsembleSelection":
+        """``run.order`` / ``count`` / ``outside`` written from the state (``okx_ensemble_select_finish``)."""
+        s, k, q = run.shape
+        self._select_call("okx_ensemble_select_finish", s, k, q, _ptr(run.state), _ptr(run.order), _ptr(run.count), _ptr(run.outside))
+        return run
+
+    def select_ensemble(self, values, *, steps_per_geometry: int, probs=None, status=None, limits=None, out=None):
+        """
+        ``okx_ensemble_select``: per (step, column) entry of a column table in HBM, over the geometries whose state counts
+        (the rule of ``reduce_ensemble``), the two order statistics around every probability of ``probs`` - exact bits of
+        table values - the count, and with ``limits`` the counts of values strictly below ``lo`` / above ``hi``.  ``values``
+        and ``status`` as ``reduce_ensemble`` takes them (unit column stride; strided rows and a strided status byte are
+        passed on, nothing is copied).  Returns an ``EnsembleSelection`` of device tensors (``order [S, K, Q, 2]``, ``count
+        [S, K]``, ``outside [S, K, 2]`` or None); ``.finalize()`` copies it to the host and interpolates
+        (``ensemble_stats.EnsembleQuantiles``).  ``out``: the selection of an earlier call or of ``select_prepare`` - it carries
+        its own probabilities and limits; with it and a table shape seen before, the call uploads and allocates nothing and
+        is legal inside a stream capture.  Bit-identical from run to run: integer counting only.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if out is None:
+            if probs is None:
+                raise ValueError("probs is needed (or out=, which carries its own)")
+            out = self.select_prepare(s, k, probs, limits)
+        elif probs is not None or limits is not None:
+            raise ValueError("out= carries its own probabilities and limits")
+        if out.shape[:2] != (s, k) or out.order.device != self.device:
+            raise ValueError(f"out was prepared for [S, K] = {list(out.shape[:2])} on {out.order.device}")
+        q = out.shape[2]
+        need = int(self.lib.okx_ensemble_select_scratch_bytes(s, k, q))
+        scratch = getattr(self, "_sel_scratch", None)
+        if scratch is None or scratch.numel() < need:  # grow-only; a captured graph keeps the buffer it was captured with alive
+            scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+            self._sel_keep = getattr(self, "_sel_keep", []) + [scratch]
+            self._sel_scratch = scratch
+        self._select_call("okx_ensemble_select", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.probs), q, _ptr(out.limits),
+                          _ptr(out.order), _ptr(out.count), _ptr(out.outside), _ptr(scratch), scratch.numel())
         return out
 
     def ensemble_targets(self, geom_pos: torch.Tensor, relative) -> torch.Tensor:

@@ -264,13 +264,23 @@ class ShardedEnsemble:
     geometries never change: they are summed once, here, on the host in ascending geometry order - so ``factor_acc`` repeats
     bit for bit from step to step, rank to rank and chunking to chunking, but agrees with a direct
     ``reduce_ensemble(factor_moments=True)`` of the same table (summed per slab on the device) to rounding only.
+
+    ``quantiles=(p, ...)`` (with ``reduce=True``; ``limits`` optional, ``[S, K, 2]`` / ``[K, 2]`` / ``[2]`` = (lo, hi)) adds the
+    band and the yield: after the last chunk of a step the rank runs the select rounds (``okx_ensemble_select_count`` /
+    ``_descend``) over its ``metric_local``, and per round the ranks SUM their int64 histograms (one ``all_reduce``; over
+    gloo on a GPU through host tensors) before each descends its own copy of the state - integer sums, so every rank ends
+    with the same bits whatever the world size and chunking.  ``quantiles()`` returns ``ensemble_stats.EnsembleQuantiles``;
+    the traffic is ``select_exchange_bytes_per_rank`` (``exchange_bytes_per_rank`` stays the accumulators').  A rank
+    without a geometry contributes a zero histogram.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
-                 metric_columns=None, reduce: bool = False, factors=None, shift=None, **solve_kw):
+                 metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, **solve_kw):
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
+        if (quantiles is not None or limits is not None) and (not reduce or quantiles is None):
+            raise ValueError("quantiles / limits select over the reduced ensemble: they need reduce=True (and limits need quantiles)")
         self.reduce = bool(reduce)
         if metric_columns is not None:
             records, info = False, "status"   # nothing of the positions travels or is written
@@ -381,6 +391,10 @@ class ShardedEnsemble:
         self.p2p_groups = self.p2p_ops = 0  # grouped point-to-point calls / operations issued so far
         if self.reduce:
             self._init_reduction(hardpoints, targets, relative_targets, factors, shift)
+        self.select_probs = None
+        self.select_exchange_bytes_per_rank = 0
+        if quantiles is not None:
+            self._init_selection(quantiles, limits)
 
     # ---- reduce=True: the accumulators of ensemble_stats.py instead of a gathered table ----
 
@@ -498,6 +512,70 @@ class ShardedEnsemble:
             merged = part if merged is None else merged.merge(part)
         self.accumulator = merged
         return merged
+
+    # ---- quantiles=...: the select rounds of ensemble_stats.py over the rank's shard, histograms summed over the ranks ----
+
+    def _init_selection(self, quantiles, limits) -> None:
+        from .ensemble_stats import SELECT_BINS, SELECT_ROUNDS, check_select_arguments
+
+        k = len(self.metric_index)
+        self.select_probs, self.select_limits = check_select_arguments(quantiles, limits, self.steps, k)
+        self._selection = self._quantiles = None
+        self._selected = False
+        if self.device.type == "cuda":  # (no quiet host selection of device tables: a program without the device pass is an error)
+            self._selection = self.dp.select_prepare(self.steps, k, self.select_probs, self.select_limits, rounds=True)
+            rounds, words = self.dp.select_rounds, self._selection.hist.numel()
+        else:
+            rounds, words = SELECT_ROUNDS, self.steps * k * 2 * len(self.select_probs) * SELECT_BINS
+        self.select_exchange_bytes_per_rank = rounds * 8 * words if self.world > 1 else 0
+
+    def _sum_histograms(self, hist: torch.Tensor) -> None:
+        if self.world == 1:
+            return
+        if hist.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
+            host = hist.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
+            hist.copy_(host)
+        else:
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=self.group)
+
+    def _run_selection(self) -> None:
+        """Every round: count this rank's shard, sum the histograms over the ranks, descend."""
+        glo, ghi = self.geometry_range
+        values, status = self.metric_local, self.info_local[:, 32]
+        if self._selection is not None:
+            run, dp = self._selection, self.dp
+            dp.select_begin(run)
+            for rnd in range(dp.select_rounds):
+                if ghi > glo:
+                    dp.select_count(run, rnd, values, steps_per_geometry=self.steps, status=status)
+                self._sum_histograms(run.hist)
+                dp.select_descend(run, rnd)
+            dp.select_finish(run)
+            self._quantiles, self._selected = None, True
+            return
+        # the CPU tests' stand-in: the same protocol by the NumPy rounds
+        from .ensemble_stats import SELECT_ROUNDS, select_begin, select_count_round, select_descend_round, select_finish
+
+        k = values.shape[1]
+        v = values.numpy().reshape(ghi - glo, self.steps, k)
+        st = status.numpy().reshape(ghi - glo, self.steps)
+        state, hist = select_begin(self.steps, k, len(self.select_probs))
+        for rnd in range(SELECT_ROUNDS):
+            select_count_round(rnd, v, st, state, hist, self.select_limits)
+            self._sum_histograms(torch.from_numpy(hist))
+            select_descend_round(rnd, state, hist, self.select_probs)
+        self._quantiles = select_finish(state, self.select_probs, self.select_limits is not None)
+
+    def quantiles(self):
+        """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""
+        if self.select_probs is None:
+            raise ValueError("quantiles() needs quantiles=(p, ...)")
+        if self._quantiles is None:
+            if not self._selected:
+                raise RuntimeError("no step() yet")
+            self._quantiles = self._selection.finalize()
+        return self._quantiles
 
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
@@ -725,7 +803,10 @@ class ShardedEnsemble:
             if not self._reduced_any:  # a rank without a geometry contributes the neutral accumulator
                 glo = self.geometry_range[0]
                 self._reduce_rows(glo, glo, slice(0, 0))
-            return self._exchange_accumulators()
+            merged = self._exchange_accumulators()
+            if self.select_probs is not None:
+                self._run_selection()
+            return merged
         if self.metric_index is not None:
             return self.metric_full
         return self.positions if self.records else self.free_full

@@ -264,5 +264,221 @@ def hardpoint_factors(hardpoints, point_names=None, atol: float = 0.0):
     return np.ascontiguousarray(centred), names
 
 
+# ---- quantiles and spec-limit yield: exact order statistics by a radix select on integer keys (okx_ensemble_select) ----
+
+SELECT_BITS = 4  # OKX_ENS_SELECT_BITS: key bits a round fixes
+SELECT_BINS = 1 << SELECT_BITS
+SELECT_ROUNDS = 64 // SELECT_BITS
+SELECT_MAX_PROBS = 64  # OKX_ENS_SELECT_MAX_PROBS
+
+
+@dataclass
+class EnsembleQuantiles:
+    """
+    Per (step, column) entry over the states that count (NumPy, host): ``count [S, K]``; for every probability of ``probs [Q]``
+    the two order statistics ``lower`` / ``upper [S, K, Q]`` = ``x[floor(h)]``, ``x[ceil(h)]`` with ``h = (count - 1) p`` of the
+    sorted accepted values - bits of values in the table, NaN for ``count == 0`` - and ``quantile``, their interpolation
+    ``lower + (h - floor(h)) (upper - lower)`` (``numpy.quantile(..., method="linear")``).  With limits: ``below`` / ``above
+    [S, K]`` accepted values strictly under ``lo`` / over ``hi`` and ``yield_ = 1 - (below + above) / count`` (NaN for
+    ``count == 0``).
+    """
+
+    probs: np.ndarray
+    count: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    quantile: np.ndarray
+    below: np.ndarray | None = None
+    above: np.ndarray | None = None
+    yield_: np.ndarray | None = None
+
+
+def check_select_arguments(probs, limits=None, steps: int | None = None, n_columns: int | None = None):
+    """``(probs [Q], limits [S, K, 2] or None)`` as float64 arrays, or ValueError in the words of ``okx_ensemble_select_check``."""
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+    if not 1 <= p.size <= SELECT_MAX_PROBS:
+        raise ValueError(f"okx_ensemble_select: 1 to {SELECT_MAX_PROBS} probabilities")
+    bad = np.flatnonzero(~((p >= 0.0) & (p <= 1.0)))
+    if bad.size:
+        raise ValueError(f"okx_ensemble_select: probability {int(bad[0])} is {p[bad[0]]:g}, outside [0, 1]")
+    if limits is None:
+        return p, None
+    lim = np.asarray(limits, dtype=np.float64)
+    if steps is not None:
+        if lim.shape[-1:] != (2,) or lim.size not in (2, n_columns * 2, steps * n_columns * 2):
+            raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
+        lim = np.ascontiguousarray(np.broadcast_to(lim.reshape((-1, 2)) if lim.size != steps * n_columns * 2 else lim.reshape(steps, n_columns, 2),
+                                                   (steps, n_columns, 2)))
+    flat = lim.reshape(-1, 2)
+    nan = np.flatnonzero(np.isnan(flat).any(axis=1))
+    if nan.size:
+        raise ValueError(f"okx_ensemble_select: limit {int(nan[0])} is NaN (an open side is -inf / +inf)")
+    bad = np.flatnonzero(flat[:, 0] > flat[:, 1])
+    if bad.size:
+        raise ValueError(f"okx_ensemble_select: limit {int(bad[0])} has lo > hi ({flat[bad[0], 0]:g} > {flat[bad[0], 1]:g})")
+    return p, lim
+
+
+def quantiles_from_order(probs, order, count, outside=None) -> EnsembleQuantiles:
+    """The host's share of ``okx_ensemble_select``: ``order [S, K, Q, 2]``, ``count [S, K]``, ``outside [S, K, 2]`` or None."""
+    probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+    order = np.asarray(order, dtype=np.float64)
+    count = np.asarray(count, dtype=np.int64)
+    lower, upper = order[..., 0].copy(), order[..., 1].copy()
+    h = np.maximum(count - 1, 0).astype(np.float64)[..., None] * probs
+    frac = h - np.floor(h)
+    with np.errstate(invalid="ignore", over="ignore"):
+        quantile = np.where((frac == 0.0) | (lower == upper), lower, lower + frac * (upper - lower))
+    out = EnsembleQuantiles(probs, count, lower, upper, quantile)
+    if outside is not None:
+        outside = np.asarray(outside, dtype=np.int64)
+        out.below, out.above = outside[..., 0].copy(), outside[..., 1].copy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out.yield_ = np.where(count > 0, 1.0 - (out.below + out.above) / count, np.nan)
+    return out
+
+
+def _accepted(values, status):
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim != 3:
+        raise ValueError("values must be [G, S, K]")
+    ok = np.isfinite(v)
+    if status is not None:
+        st = np.asarray(status).reshape(v.shape[0], v.shape[1]).astype(np.uint8)
+        ok &= ((st & STATUS_ACCEPT_MASK) == 1)[:, :, None]
+    return v, ok
+
+
+def select_host(values, status=None, probs=(0.5,), limits=None) -> EnsembleQuantiles:
+    """The plain answer by ``np.sort``: ``values [G, S, K]``, ``status [G, S]`` or None, ``limits [S, K, 2]`` (lo, hi) or None."""
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    p, lim = check_select_arguments(probs, limits, s, k)
+    n = ok.sum(axis=0).astype(np.int64)
+    order = np.full((s, k, p.size, 2), np.nan)
+    if g:
+        ranked = np.sort(np.where(ok, v, np.inf), axis=0)  # the accepted values are finite: they come first
+        h = np.maximum(n - 1, 0).astype(np.float64)[..., None] * p
+        for side, index in enumerate((np.floor(h), np.ceil(h))):
+            picked = np.take_along_axis(ranked, np.moveaxis(index.astype(np.int64), 2, 0), axis=0)  # [Q, S, K]
+            order[..., side] = np.where((n > 0)[..., None], np.moveaxis(picked, 0, 2), np.nan)
+    outside = None
+    if lim is not None:
+        outside = np.stack([(ok & (v < lim[None, ..., 0])).sum(axis=0), (ok & (v > lim[None, ..., 1])).sum(axis=0)], axis=2).astype(np.int64)
+    return quantiles_from_order(p, order, n, outside)
+
+
+def select_keys(values) -> np.ndarray:
+    """Order-preserving uint64 keys of finite doubles: ``bits ^ (sign ? ~0 : 1 << 63)``; -0.0 sorts before +0.0."""
+    bits = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+    return bits ^ np.where(bits >> np.uint64(63), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(1 << 63))
+
+
+def select_values(keys) -> np.ndarray:
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    return np.where(keys >> np.uint64(63), keys ^ np.uint64(1 << 63), ~keys).view(np.float64)
+
+
+@dataclass
+class SelectState:
+    """State of the select rounds, per selection ``j = 2 q + side``: ``prefix`` (key bits fixed so far) and ``rank`` (still
+    wanted among the values that share them; < 0: nothing to select) ``[S, K, 2 Q]``, ``count [S, K]``, ``outside [S, K, 2]``."""
+
+    prefix: np.ndarray
+    rank: np.ndarray
+    count: np.ndarray
+    outside: np.ndarray
+
+
+def select_begin(steps: int, n_columns: int, n_probs: int):
+    """``(state, hist)`` of a select that has seen nothing: ``hist`` int64 ``[S, K, 2 Q, SELECT_BINS]`` (``okx.h``'s layout), zero."""
+    j = 2 * n_probs
+    state = SelectState(np.zeros((steps, n_columns, j), dtype=np.uint64), np.zeros((steps, n_columns, j), dtype=np.int64),
+                        np.zeros((steps, n_columns), dtype=np.int64), np.zeros((steps, n_columns, 2), dtype=np.int64))
+    return state, np.zeros((steps, n_columns, j, SELECT_BINS), dtype=np.int64)
+
+
+def select_count_round(rnd: int, values, status, state: SelectState, hist, limits=None) -> None:
+    """The count pass of round ``rnd`` over one chunk ``values [G, S, K]``: adds into ``hist`` (round 0: the shared histogram in
+    selection 0, the limit counts in ``hist[s, k, 1, 0:2]``)."""
+    v, ok = _accepted(values, status)
+    if v.shape[0] == 0:
+        return
+    keys = select_keys(v)
+    bins = np.arange(SELECT_BINS, dtype=np.uint64)
+    digit = (keys >> np.uint64(64 - SELECT_BITS * (rnd + 1))) & np.uint64(SELECT_BINS - 1)
+    hot = digit[..., None] == bins  # [G, S, K, bins]
+    if rnd == 0:
+        hist[:, :, 0, :] += (hot & ok[..., None]).sum(axis=0)
+        if limits is not None:
+            lim = np.asarray(limits, dtype=np.float64)
+            hist[:, :, 1, 0] += (ok & (v < lim[None, ..., 0])).sum(axis=0)
+            hist[:, :, 1, 1] += (ok & (v > lim[None, ..., 1])).sum(axis=0)
+        return
+    fixed = np.uint64(64 - SELECT_BITS * rnd)
+    head = keys >> fixed
+    for j in range(state.prefix.shape[2]):
+        match = ok & (head == (state.prefix[None, :, :, j] >> fixed))
+        hist[:, :, j, :] += (hot & match[..., None]).sum(axis=0)
+
+
+def select_descend_round(rnd: int, state: SelectState, hist, probs) -> None:
+    """The descend of round ``rnd``: the bin that holds every selection's rank, prefix and rank advanced, ``hist`` re-zeroed.
+    Round 0 sums ``count``, takes the limit counts and turns the probabilities into ranks (``h = (n - 1) p`` in fp64)."""
+    if rnd == 0:
+        p = np.asarray(probs, dtype=np.float64).reshape(-1)
+        n = hist[:, :, 0, :].sum(axis=-1)
+        state.count[...] = n
+        state.outside[...] = hist[:, :, 1, 0:2]
+        h = (n - 1).astype(np.float64)[..., None] * p
+        with np.errstate(invalid="ignore"):
+            rank = np.stack([np.floor(h), np.ceil(h)], axis=-1)
+            valid = (n > 0)[..., None] & (p >= 0.0) & (p <= 1.0)
+        rank = np.where(valid[..., None], rank, -1.0).astype(np.int64)
+        state.rank[...] = rank.reshape(state.rank.shape)
+        state.prefix[...] = 0
+        source = np.broadcast_to(hist[:, :, 0:1, :], hist.shape)
+    else:
+        source = hist
+    above = np.cumsum(source, axis=-1)  # values in bins <= b
+    holds = above > state.rank[..., None]
+    pick = holds.argmax(axis=-1)
+    found = holds.any(axis=-1) & (state.rank >= 0)
+    below = np.take_along_axis(above - source, pick[..., None], axis=-1)[..., 0]
+    shift = np.uint64(64 - SELECT_BITS * (rnd + 1))
+    state.prefix[...] = np.where(found, state.prefix | (pick.astype(np.uint64) << shift), state.prefix)
+    state.rank[...] = np.where(found, state.rank - below, -1)
+    hist[...] = 0
+
+
+def select_finish(state: SelectState, probs, with_limits: bool = False) -> EnsembleQuantiles:
+    s, k, j = state.prefix.shape
+    order = np.where(state.rank >= 0, select_values(state.prefix), np.nan).reshape(s, k, j // 2, 2)
+    return quantiles_from_order(probs, order, state.count, state.outside if with_limits else None)
+
+
+def select_rounds_host(values, status=None, probs=(0.5,), limits=None, chunks: int = 1, on_round=None) -> EnsembleQuantiles:
+    """
+    The device's protocol in NumPy: ``SELECT_ROUNDS`` rounds of count (the geometries cut into ``chunks`` runs, every run added
+    into the round's one histogram) and descend.  ``on_round(rnd, hist)`` sees every round's histogram before its descend.
+    """
+    v = np.asarray(values, dtype=np.float64)
+    g, s, k = v.shape
+    p, lim = check_select_arguments(probs, limits, s, k)
+    st = None if status is None else np.asarray(status).reshape(g, s)
+    state, hist = select_begin(s, k, p.size)
+    edges = [g * i // chunks for i in range(chunks + 1)]
+    for rnd in range(SELECT_ROUNDS):
+        for a, b in zip(edges[:-1], edges[1:]):
+            select_count_round(rnd, v[a:b], None if st is None else st[a:b], state, hist, lim)
+        if on_round is not None:
+            on_round(rnd, hist)
+        select_descend_round(rnd, state, hist, p)
+    return select_finish(state, p, lim is not None)
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
-           "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX"]
+           "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
+           "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
+           "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "SELECT_BITS", "SELECT_BINS",
+           "SELECT_ROUNDS", "SELECT_MAX_PROBS"]
