@@ -864,6 +864,49 @@ size_t okx_ensemble_select_state_bytes(int64_t steps, int32_t n_columns, int32_t
 size_t okx_ensemble_select_scratch_bytes(int64_t steps, int32_t n_columns, int32_t n_probs);
 int32_t okx_ensemble_select_check(const double* probs, int32_t n_probs, const double* limits /* or NULL */, int64_t n_limits /* (lo, hi) pairs */);
 
+/*
+ * Ensemble screening on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): the JOINT verdict of
+ * every geometry of the same table against d_limits [steps][n_columns][2] = (lo, hi) - what the per-entry yields of
+ * okx_ensemble_select cannot give, the columns of one geometry being correlated along the sweep.  An entry is LOOKED AT
+ * when at least one of its limits is finite; it COUNTS by the rule of okx_ensemble_reduce.  d_scale (or NULL: 1)
+ * [steps][n_columns], finite and > 0, is the unit in which margins are compared across entries.  Per geometry of THIS call:
+ *   d_flags  [n_geometries] uint8   OKX_SCREEN_OUTSIDE: a looked-at entry that counts is < lo or > hi (strictly);
+ *                                   OKX_SCREEN_UNRESOLVED: a looked-at entry does not count.  0: the geometry passes.
+ *   d_margin [n_geometries] double  min over the looked-at entries that count of m = min((v - lo) / scale, (hi - v) / scale),
+ *                                   every operation rounded on its own (m = y < x ? y : x with x the lo side); +inf when
+ *                                   nothing qualifies
+ *   d_entry  [n_geometries] int32   s * n_columns + k of that minimum, the lowest on ties; -1 when nothing qualifies
+ * Per ensemble, int64:
+ *   d_tally  [4]                    geometries seen, passed, outside, unresolved
+ *   d_blame  [steps][n_columns][2]  per OUTSIDE geometry one count at its d_entry: side 0 its value is below lo, side 1 not
+ *   d_pass_index [capacity] or NULL geometry_offset + g of the passing geometries, ascending; slots at or beyond capacity
+ *                                   and beyond the count are never written
+ *   d_pass_count [1]                survivors found (may exceed capacity)
+ * accumulate = 0 overwrites d_tally, d_blame and d_pass_count; accumulate = 1 adds into tally and blame and appends the
+ * survivors after the *d_pass_count already there (read on the device, stream-ordered): chunks passed in ascending order
+ * give one ascending list.  Integer atomics only, and no atomic decides a survivor's slot: the result is bit-identical
+ * across chunks, launch geometries, runs, devices and ranks.  Launch-only, stream-ordered, no host read-back, legal inside
+ * a stream capture; n_geometries = 0 is legal.  d_scratch: okx_ensemble_screen_scratch_bytes.  The launch cannot read
+ * d_limits / d_scale on the host: okx_ensemble_screen_check validates HOST copies of them (NaN limits, lo > hi, a scale
+ * that is not finite and > 0: OKX_ERR_INVALID with okx_last_error text) before they are uploaded.
+ */
+enum { OKX_SCREEN_OUTSIDE = 1, OKX_SCREEN_UNRESOLVED = 2 };
+
+int32_t okx_ensemble_screen(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                            const double* d_values, int64_t ld,
+                            const uint8_t* d_status, int64_t status_stride, /* or NULL                                  */
+                            const double* d_limits,
+                            const double* d_scale,                          /* or NULL                                  */
+                            int64_t geometry_offset, int32_t accumulate,
+                            uint8_t* d_flags, double* d_margin, int32_t* d_entry,
+                            int64_t* d_tally, int64_t* d_blame,
+                            int64_t* d_pass_index, int64_t capacity,        /* or NULL                                  */
+                            int64_t* d_pass_count,
+                            void* d_scratch, size_t scratch_bytes, void* stream);
+/* host only */
+size_t okx_ensemble_screen_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns);
+int32_t okx_ensemble_screen_check(const double* limits, const double* scale /* or NULL */, int64_t n_entries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,41 @@ class EnsembleSelection:
                                     None if self.outside is None else self.outside.cpu().numpy())
 
 
+@dataclass
+class EnsembleScreening:
+    """
+    What ``DeviceProgram.screen_ensemble`` returns, device tensors: ``limits [S, K, 2]`` and ``scale [S, K]`` (or None) as
+    uploaded; per geometry ``flags [G]`` uint8, ``margin [G]`` float64 and ``entry [G]`` int32; per ensemble ``tally [4]`` and
+    ``blame [S, K, 2]`` int64, ``pass_index [capacity]`` int64 (the ascending global indices of the geometries that pass;
+    slots beyond ``min(pass_count, capacity)`` are never written) and ``pass_count [1]`` int64, the survivors found.
+    """
+
+    limits: torch.Tensor
+    scale: torch.Tensor | None
+    flags: torch.Tensor
+    margin: torch.Tensor
+    entry: torch.Tensor
+    tally: torch.Tensor
+    blame: torch.Tensor
+    pass_index: torch.Tensor
+    pass_count: torch.Tensor
+
+    @property
+    def shape(self) -> tuple:
+        """``(S, K)``."""
+        return tuple(self.blame.shape[:2])
+
+    def finalize(self):
+        """Host copy: ``ensemble_stats.EnsembleScreen`` (``passed`` holds the survivors that fit the capacity)."""
+        from .ensemble_stats import EnsembleScreen
+
+        tally = self.tally.cpu().numpy()
+        n = min(int(self.pass_count.item()), self.pass_index.shape[0])
+        seen = min(int(tally[0]), self.flags.shape[0])  # (accumulated chunks fill the tables from the front)
+        return EnsembleScreen(self.flags[:seen].cpu().numpy(), self.margin[:seen].cpu().numpy(), self.entry[:seen].cpu().numpy(), tally,
+                              self.blame.cpu().numpy(), self.pass_index[:n].cpu().numpy())
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -953,6 +988,82 @@ class DeviceProgram:
             self._sel_scratch = scratch
         self._select_call("okx_ensemble_select", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.probs), q, _ptr(out.limits),
                           _ptr(out.order), _ptr(out.count), _ptr(out.outside), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_screen: the joint spec-limit verdict of every geometry (ensemble_stats.EnsembleScreen) ----
+
+    def screen_prepare(self, steps: int, n_columns: int, limits, scale=None, n_geometries: int = 0, capacity: int | None = None) -> "EnsembleScreening":
+        """
+        The tables of a screen over ``[steps, n_columns]`` entries and ``n_geometries`` geometries: ``limits`` (``[S, K, 2]``,
+        ``[K, 2]`` or ``[2]`` = (lo, hi), -inf / +inf leaves a side open) and ``scale`` (``[S, K]``, ``[K]`` or a scalar, finite
+        and > 0; None: 1) are validated by ``okx_ensemble_screen_check`` on the host and uploaded ONCE; the outputs are
+        allocated, the survivor list with ``capacity`` slots (None: one per geometry).
+        """
+        s, k, g = int(steps), int(n_columns), int(n_geometries)
+        host = lambda t: np.array(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64)  # noqa: E731
+        if limits is None:
+            raise ValueError("limits are needed: [S, K, 2], [K, 2] or [2] (lo, hi)")
+        lim = host(limits)
+        if lim.shape[-1:] != (2,) or lim.size not in (2, 2 * k, 2 * s * k):
+            raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
+        lim = np.array(np.broadcast_to(lim.reshape(s, k, 2) if lim.size == 2 * s * k else lim.reshape(-1, 2), (s, k, 2)), order="C")
+        sc = None
+        if scale is not None:
+            sc = host(scale)
+            if sc.size not in (1, k, s * k):
+                raise ValueError("scale must be [S, K], [K] or a scalar")
+            sc = np.array(np.broadcast_to(sc.reshape(s, k) if sc.size == s * k else sc.reshape(-1), (s, k)), order="C")
+        rc = self.lib.okx_ensemble_screen_check(lim.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p), s * k)
+        _lib.check(rc, "okx_ensemble_screen")
+        if g < 0 or (capacity is not None and int(capacity) < 0):
+            raise ValueError("negative geometry count or capacity")
+        dev = self.device
+        cap = g if capacity is None else int(capacity)
+        return EnsembleScreening(torch.as_tensor(lim, device=dev), None if sc is None else torch.as_tensor(sc, device=dev),
+                                 torch.empty(g, dtype=torch.uint8, device=dev), torch.empty(g, dtype=torch.float64, device=dev),
+                                 torch.empty(g, dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int64, device=dev),
+                                 torch.zeros((s, k, 2), dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
+                                 torch.zeros(1, dtype=torch.int64, device=dev))
+
+    def screen_ensemble(self, values, *, steps_per_geometry: int, limits=None, status=None, scale=None, geometry_offset: int = 0,
+                        capacity: int | None = None, out=None, accumulate: bool = False, first_row: int | None = None):
+        """
+        ``okx_ensemble_screen``: per GEOMETRY of a column table in HBM, whether it meets every limit at every step
+        (``flags``), its worst margin in units of ``scale`` and the entry that holds it; per ensemble the tally, the blame
+        counts and the ascending list of the geometries that pass.  ``values`` and ``status`` as ``select_ensemble`` takes them
+        (unit column stride; strided rows and a strided status byte are passed on, nothing is copied).  Returns an
+        ``EnsembleScreening`` of device tensors - ``margin`` and ``pass_index`` stay in HBM for whatever follows -;
+        ``.finalize()`` copies it to the host (``ensemble_stats.EnsembleScreen``).  ``out``: the screening of an earlier call or
+        of ``screen_prepare`` - it carries its own limits and scale; with it and a table shape seen before, the call uploads
+        and allocates nothing and is legal inside a stream capture.  ``accumulate=True`` (with ``out``) adds this chunk to
+        what ``out`` holds: tally and blame add and the survivors are appended.  The call's per-geometry verdicts are written
+        from row ``first_row`` of ``out``'s tables on (None: ``geometry_offset`` with ``out=``, else 0).  Bit-identical from
+        run to run.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        row = int(first_row) if first_row is not None else (0 if out is None else int(geometry_offset))
+        if out is None:
+            if limits is None:
+                raise ValueError("limits are needed (or out=, which carries its own)")
+            if accumulate:
+                raise ValueError("accumulate=True adds to out=")
+            out = self.screen_prepare(s, k, limits, scale, row + g, capacity)
+        elif limits is not None or scale is not None or capacity is not None:
+            raise ValueError("out= carries its own limits, scale and capacity")
+        if out.shape != (s, k) or out.blame.device != self.device:
+            raise ValueError(f"out was prepared for [S, K] = {list(out.shape)} on {out.blame.device}")
+        if row < 0 or row + g > out.flags.shape[0]:
+            raise ValueError(f"out holds {out.flags.shape[0]} geometries: rows [{row}, {row + g}) do not fit")
+        need = int(self.lib.okx_ensemble_screen_scratch_bytes(g, s, k))
+        scratch = getattr(self, "_scr_scratch", None)
+        if scratch is None or scratch.numel() < need:  # grow-only; a captured graph keeps the buffer it was captured with alive
+            scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+            self._scr_keep = getattr(self, "_scr_keep", []) + [scratch]
+            self._scr_scratch = scratch
+        self._select_call("okx_ensemble_screen", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.limits), _ptr(out.scale),
+                          int(geometry_offset), 1 if accumulate else 0, _ptr(out.flags[row:]), _ptr(out.margin[row:]), _ptr(out.entry[row:]),
+                          _ptr(out.tally), _ptr(out.blame), _ptr(out.pass_index), out.pass_index.shape[0], _ptr(out.pass_count),
+                          _ptr(scratch), scratch.numel())
         return out
 
     def ensemble_targets(self, geom_pos: torch.Tensor, relative) -> torch.Tensor:

@@ -272,14 +272,26 @@ class ShardedEnsemble:
     with the same bits whatever the world size and chunking.  ``quantiles()`` returns ``ensemble_stats.EnsembleQuantiles``;
     the traffic is ``select_exchange_bytes_per_rank`` (``exchange_bytes_per_rank`` stays the accumulators').  A rank
     without a geometry contributes a zero histogram.
+
+    ``screen=True`` (with ``reduce=True`` and ``limits``; ``quantiles`` not needed; ``screen_scale``: ``[S, K]`` / ``[K]`` / a
+    scalar, None: 1) adds the JOINT verdict per geometry (``okx_ensemble_screen``): right after a chunk's reduction its rows
+    of ``metric_local`` are screened into this rank's per-geometry tables, tally and blame accumulate and the survivors are
+    appended.  ``step()`` then ends with one integer ``all_reduce`` of ``tally | blame`` and one all-gather of the flag bytes
+    (1 B per geometry, padded to the largest shard).  ``screen()`` returns the ``ensemble_stats.EnsembleScreen`` of the WHOLE
+    ensemble - ``tally``, ``blame``, ``flags [G]``, ``passed`` -, the same bits on every rank whatever the world size and
+    chunking; ``screen_local()`` this rank's ``margin`` / ``entry`` / ``pass_index`` tensors, which stay where they are;
+    ``screen_exchange_bytes_per_rank`` what the rank sends.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
-                 metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, **solve_kw):
+                 metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
+                 **solve_kw):
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
-        if (quantiles is not None or limits is not None) and (not reduce or quantiles is None):
+        if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
+            raise ValueError("screen=True screens the reduced ensemble: it needs reduce=True and limits (and screen_scale needs screen=True)")
+        if (quantiles is not None or (limits is not None and not screen)) and (not reduce or quantiles is None):
             raise ValueError("quantiles / limits select over the reduced ensemble: they need reduce=True (and limits need quantiles)")
         self.reduce = bool(reduce)
         if metric_columns is not None:
@@ -395,6 +407,10 @@ class ShardedEnsemble:
         self.select_exchange_bytes_per_rank = 0
         if quantiles is not None:
             self._init_selection(quantiles, limits)
+        self.screening = bool(screen)
+        self.screen_exchange_bytes_per_rank = 0
+        if self.screening:
+            self._init_screen(limits, screen_scale)
 
     # ---- reduce=True: the accumulators of ensemble_stats.py instead of a gathered table ----
 
@@ -577,6 +593,98 @@ class ShardedEnsemble:
             self._quantiles = self._selection.finalize()
         return self._quantiles
 
+    # ---- screen=True: the joint verdict per geometry, chunk by chunk; tally | blame summed and the flag bytes gathered ----
+
+    def _init_screen(self, limits, scale) -> None:
+        from .ensemble_stats import check_screen_arguments
+
+        glo, ghi = self.geometry_range
+        k = len(self.metric_index)
+        self.screen_limits, self.screen_scale = check_screen_arguments(limits, scale, self.steps, k)
+        self._largest_shard = max(hi - lo for lo, hi in (shard_range(self.n_geom, r, self.world) for r in range(self.world)))
+        self._screening = self._screen_part = self._screen_result = None
+        self._screen_counts = self._screen_flags = None
+        self._screened_any = False
+        if self.device.type == "cuda":  # (no quiet host screening of device tables: a program without the device pass is an error)
+            self._screening = self.dp.screen_prepare(self.steps, k, self.screen_limits, self.screen_scale, ghi - glo)
+        self.screen_exchange_bytes_per_rank = 8 * (4 + 2 * self.steps * k) + self._largest_shard if self.world > 1 else 0
+
+    def _screen_rows(self, a: int, b: int, local) -> None:
+        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's screen."""
+        glo = self.geometry_range[0]
+        values = self.metric_local[local]
+        status = self.info_local[local][:, 32]
+        if self._screening is not None:
+            self.dp.screen_ensemble(values, steps_per_geometry=self.steps, status=status, geometry_offset=a, out=self._screening,
+                                    accumulate=self._screened_any, first_row=a - glo)
+        else:  # the CPU tests' stand-in: the NumPy screen, merged the same way
+            from .ensemble_stats import screen_host
+
+            part = screen_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
+                               self.screen_limits, self.screen_scale, a)
+            self._screen_part = self._screen_part.merge(part) if self._screened_any else part
+        self._screened_any = True
+
+    def _exchange_screen(self) -> None:
+        """One integer all-reduce of tally | blame and one all-gather of the flag bytes: the same bits on every rank."""
+        import numpy as np
+
+        glo, ghi = self.geometry_range
+        if self._screening is not None:
+            run = self._screening
+            counts = torch.cat([run.tally, run.blame.reshape(-1)])
+            flags = run.flags
+        else:
+            part = self._screen_part
+            counts = torch.from_numpy(np.concatenate([part.tally, part.blame.reshape(-1)]))
+            flags = torch.from_numpy(part.flags)
+        self._screen_result = None
+        if self.world == 1:
+            self._screen_counts, self._screen_flags = counts, flags
+            return
+        padded = torch.zeros(self._largest_shard, dtype=torch.uint8, device=flags.device)
+        padded[: ghi - glo] = flags
+        if counts.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
+            counts, padded = counts.cpu(), padded.cpu()
+        gathered = torch.empty(self.world * self._largest_shard, dtype=torch.uint8, device=padded.device)
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+        dist.all_gather_into_tensor(gathered, padded, group=self.group)
+        spans = [shard_range(self.n_geom, r, self.world) for r in range(self.world)]
+        self._screen_flags = torch.cat([gathered[r * self._largest_shard : r * self._largest_shard + hi - lo] for r, (lo, hi) in enumerate(spans)])
+        self._screen_counts = counts
+
+    def screen(self):
+        """``ensemble_stats.EnsembleScreen`` of the WHOLE ensemble after the last ``step()`` (``screen=True``): ``tally``, ``blame``,
+        ``flags [G]`` and ``passed``; ``margin`` / ``entry`` stay with their ranks (``screen_local``).  The same bits on every rank."""
+        if not self.screening:
+            raise ValueError("screen() needs screen=True")
+        if self._screen_counts is None:
+            raise RuntimeError("no step() yet")
+        if self._screen_result is None:
+            import numpy as np
+
+            from .ensemble_stats import EnsembleScreen
+
+            counts = self._screen_counts.cpu().numpy()
+            flags = self._screen_flags.cpu().numpy()
+            blame = counts[4:].reshape(self.steps, len(self.metric_index), 2).copy()
+            self._screen_result = EnsembleScreen(flags, None, None, counts[:4].copy(), blame, np.flatnonzero(flags == 0).astype(np.int64))
+        return self._screen_result
+
+    def screen_local(self) -> dict:
+        """This rank's tables of the last ``step()``: ``flags`` / ``margin`` / ``entry [n_local]``, ``pass_index`` (ascending global
+        indices of its geometries that pass, ``pass_count`` of them) - tensors where the table lives, nothing is copied."""
+        if not self.screening:
+            raise ValueError("screen_local() needs screen=True")
+        if self._screening is not None:
+            run = self._screening
+            return {"flags": run.flags, "margin": run.margin, "entry": run.entry, "pass_index": run.pass_index, "pass_count": run.pass_count}
+        if self._screen_part is None:
+            raise RuntimeError("no step() yet")
+        part = self._screen_part
+        return {"flags": torch.from_numpy(part.flags), "margin": torch.from_numpy(part.margin), "entry": torch.from_numpy(part.entry),
+                "pass_index": torch.from_numpy(part.passed), "pass_count": torch.tensor([part.passed.size], dtype=torch.int64)}
+
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
         if not self.reduce:
@@ -645,6 +753,8 @@ class ShardedEnsemble:
         if self.reduce:
             torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_local[local])
             self._reduce_rows(a, b, local)
+            if self.screening:
+                self._screen_rows(a, b, local)
             return
         torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_full[rows])
         if self.status_only:
@@ -788,6 +898,8 @@ class ShardedEnsemble:
         pending = []
         if self.reduce:
             self._reduced_any = False
+        if self.screening:
+            self._screened_any = False
         for k in range(self.chunks):
             self._solve_chunk(k)
             works = self._exchange_chunk(k)
@@ -806,6 +918,11 @@ class ShardedEnsemble:
             merged = self._exchange_accumulators()
             if self.select_probs is not None:
                 self._run_selection()
+            if self.screening:
+                if not self._screened_any:  # a rank without a geometry: zero counts, no verdicts
+                    glo = self.geometry_range[0]
+                    self._screen_rows(glo, glo, slice(0, 0))
+                self._exchange_screen()
             return merged
         if self.metric_index is not None:
             return self.metric_full

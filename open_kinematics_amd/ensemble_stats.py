@@ -10,6 +10,9 @@ Three layers, the same accumulator in each (``include/okx.h``, ``okx_ensemble_re
 * ``dist.ShardedEnsemble(reduce=True)``: every rank reduces its own shard chunk by chunk and the ranks exchange the
   accumulators alone.
 
+Beside the moments: exact quantiles and per-entry spec-limit yield (``select_host``, ``okx_ensemble_select``) and the JOINT
+spec-limit verdict per geometry (``screen_host`` / ``EnsembleScreen``, ``okx_ensemble_screen``), each in the same three layers.
+
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
 """
@@ -476,9 +479,124 @@ def select_rounds_host(values, status=None, probs=(0.5,), limits=None, chunks: i
         select_descend_round(rnd, state, hist, p)
     return select_finish(state, p, lim is not None)
 
+# ---- joint spec-limit screening: the verdict of every GEOMETRY against all its limits at once (okx_ensemble_screen) ----
+
+SCREEN_OUTSIDE = 1     # OKX_SCREEN_OUTSIDE: a looked-at entry that counts lies strictly below lo or above hi
+SCREEN_UNRESOLVED = 2  # OKX_SCREEN_UNRESOLVED: a looked-at entry does not count
+TALLY_SEEN, TALLY_PASSED, TALLY_OUTSIDE, TALLY_UNRESOLVED = range(4)
+
+
+@dataclass
+class EnsembleScreen:
+    """
+    The joint verdict of an ensemble against ``limits [S, K, 2]`` (NumPy, host).  An entry is LOOKED AT when at least one of
+    its limits is finite and COUNTS by the rule of the reduction (``status & 7 == 1`` and a finite value).  Per geometry:
+    ``flags [G]`` uint8 (``SCREEN_OUTSIDE`` | ``SCREEN_UNRESOLVED``; 0: the geometry passes), ``margin [G]`` - the minimum
+    over the looked-at entries that count of ``min((v - lo) / scale, (hi - v) / scale)``, +inf when nothing qualifies,
+    negative when ``SCREEN_OUTSIDE`` is set (short of an underflow of the division) - and ``entry [G]`` int32, ``s K + k`` of
+    that minimum (the lowest on ties, -1 when nothing qualifies).  Per ensemble, int64: ``tally [4]`` = geometries seen,
+    passed, outside, unresolved (the last two may overlap), ``blame [S, K, 2]`` - per ``SCREEN_OUTSIDE`` geometry one count
+    at its ``entry``, side 0 when the value there is below ``lo``, side 1 otherwise - and ``passed``, the ascending global
+    indices of the passing geometries.  ``margin`` / ``entry`` are None where only the verdicts were gathered
+    (``ShardedEnsemble.screen``).
+    """
+
+    flags: np.ndarray
+    margin: np.ndarray | None
+    entry: np.ndarray | None
+    tally: np.ndarray
+    blame: np.ndarray
+    passed: np.ndarray
+
+    @property
+    def joint_yield(self) -> float:
+        """``passed / seen``; NaN for an ensemble of no geometry."""
+        seen = int(self.tally[TALLY_SEEN])
+        return float(self.tally[TALLY_PASSED]) / seen if seen else float("nan")
+
+    def merge(self, other: "EnsembleScreen") -> "EnsembleScreen":
+        """``self`` then ``other``, consecutive runs of geometries, as one screen: per-geometry tables concatenate, integers add."""
+        if self.blame.shape != other.blame.shape:
+            raise ValueError("screens of different shapes")
+        both = lambda a, b: None if a is None or b is None else np.concatenate([a, b])  # noqa: E731
+        return EnsembleScreen(both(self.flags, other.flags), both(self.margin, other.margin), both(self.entry, other.entry),
+                              self.tally + other.tally, self.blame + other.blame, both(self.passed, other.passed))
+
+
+def check_screen_arguments(limits, scale=None, steps: int | None = None, n_columns: int | None = None):
+    """``(limits [S, K, 2], scale [S, K] or None)`` as float64 arrays, or ValueError in the words of ``okx_ensemble_screen_check``."""
+    if limits is None:
+        raise ValueError("okx_ensemble_screen: null limits")
+    lim = np.asarray(limits, dtype=np.float64)
+    sc = None if scale is None else np.asarray(scale, dtype=np.float64)
+    if steps is not None:
+        if lim.shape[-1:] != (2,) or lim.size not in (2, n_columns * 2, steps * n_columns * 2):
+            raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
+        lim = np.ascontiguousarray(np.broadcast_to(lim.reshape((-1, 2)) if lim.size != steps * n_columns * 2 else lim.reshape(steps, n_columns, 2),
+                                                   (steps, n_columns, 2)))
+        if sc is not None:
+            if sc.size not in (1, n_columns, steps * n_columns):
+                raise ValueError("scale must be [S, K], [K] or a scalar")
+            sc = np.ascontiguousarray(np.broadcast_to(sc.reshape(steps, n_columns) if sc.size == steps * n_columns else sc.reshape(-1),
+                                                      (steps, n_columns)))
+    flat = lim.reshape(-1, 2)
+    nan = np.flatnonzero(np.isnan(flat).any(axis=1))
+    if nan.size:
+        raise ValueError(f"okx_ensemble_screen: limit {int(nan[0])} is NaN (an open side is -inf / +inf)")
+    bad = np.flatnonzero(flat[:, 0] > flat[:, 1])
+    if bad.size:
+        raise ValueError(f"okx_ensemble_screen: limit {int(bad[0])} has lo > hi ({flat[bad[0], 0]:g} > {flat[bad[0], 1]:g})")
+    if sc is not None:
+        bad = np.flatnonzero(~(np.isfinite(sc.reshape(-1)) & (sc.reshape(-1) > 0.0)))
+        if bad.size:
+            raise ValueError(f"okx_ensemble_screen: scale {int(bad[0])} is {sc.reshape(-1)[bad[0]]:g}, not finite and > 0")
+    return lim, sc
+
+
+def screen_host(values, status=None, limits=None, scale=None, geometry_offset: int = 0) -> EnsembleScreen:
+    """
+    The joint screen in NumPy: ``values [G, S, K]``, ``status [G, S]`` or None, ``limits`` ``[S, K, 2]`` / ``[K, 2]`` / ``[2]``
+    (lo, hi; -inf / +inf leaves a side open), ``scale`` ``[S, K]`` / ``[K]`` / a scalar (None: 1).  Every operation is
+    rounded on its own, in the device's order: ``x = (v - lo) / scale``, ``y = (hi - v) / scale``, ``m = y if y < x else x``.
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    lim, sc = check_screen_arguments(limits, scale, s, k)
+    n = s * k
+    lo, hi = lim[..., 0].reshape(-1), lim[..., 1].reshape(-1)
+    looked = np.isfinite(lo) | np.isfinite(hi)
+    v, ok = v.reshape(g, n), ok.reshape(g, n)
+    counts = ok & looked[None]
+    below, above = counts & (v < lo[None]), counts & (v > hi[None])
+    flags = np.where((below | above).any(axis=1), SCREEN_OUTSIDE, 0) | np.where((looked[None] & ~ok).any(axis=1), SCREEN_UNRESOLVED, 0)
+    flags = flags.astype(np.uint8)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        x, y = v - lo[None], hi[None] - v
+        if sc is not None:
+            x, y = x / sc.reshape(-1)[None], y / sc.reshape(-1)[None]
+        m = np.where(counts, np.where(y < x, y, x), np.inf)
+    if n:
+        holds = counts & (m == m.min(axis=1)[:, None])
+        some = holds.any(axis=1)
+        first = holds.argmax(axis=1)  # the first True: the lowest entry among the ties
+    else:
+        some, first = np.zeros(g, dtype=bool), np.zeros(g, dtype=np.int64)
+    rows = np.arange(g)
+    entry = np.where(some, first, -1).astype(np.int32)
+    margin = np.where(some, m[rows, first], np.inf) if n else np.full(g, np.inf)
+    blame = np.zeros((n, 2), dtype=np.int64)
+    out = np.flatnonzero((flags & SCREEN_OUTSIDE) != 0)
+    if out.size:
+        at = first[out]
+        np.add.at(blame, (at, np.where(v[out, at] < lo[at], 0, 1)), 1)
+    tally = np.array([g, int((flags == 0).sum()), out.size, int(((flags & SCREEN_UNRESOLVED) != 0).sum())], dtype=np.int64)
+    passed = (int(geometry_offset) + np.flatnonzero(flags == 0)).astype(np.int64)
+    return EnsembleScreen(flags, margin, entry, tally, blame.reshape(s, k, 2), passed)
+
 
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
            "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "SELECT_BITS", "SELECT_BINS",
-           "SELECT_ROUNDS", "SELECT_MAX_PROBS"]
+           "SELECT_ROUNDS", "SELECT_MAX_PROBS", "EnsembleScreen", "screen_host", "check_screen_arguments", "SCREEN_OUTSIDE",
+           "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED"]
