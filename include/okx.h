@@ -907,6 +907,50 @@ int32_t okx_ensemble_screen(int64_t n_geometries, int64_t steps, int32_t n_colum
 size_t okx_ensemble_screen_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns);
 int32_t okx_ensemble_screen_check(const double* limits, const double* scale /* or NULL */, int64_t n_entries);
 
+/*
+ * Ensemble covariance on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): how the entries of the
+ * same table move TOGETHER over the geometries - what the per-entry moments, the quantiles and the per-geometry verdict do
+ * not say.  d_entries: n_entries DISTINCT indices s * n_columns + k, in the order the caller wants rows and columns; NULL:
+ * all steps * n_columns entries in natural order (n_entries must then be that number).  1 <= n_entries <=
+ * OKX_ENS_COV_MAX_ENTRIES.  An entry COUNTS by the rule of okx_ensemble_reduce (status & 7 == 1 and a finite value).
+ * COMPLETE CASES: a geometry is USED when every SELECTED entry of it counts; otherwise it is DROPPED and contributes nothing
+ * (an entry that is not selected never drops a geometry).  One count therefore serves the whole matrix, the matrix is a true
+ * Gram matrix (positive semidefinite up to rounding), and the used set is exactly okx_ensemble_screen's "not UNRESOLVED" for
+ * the same looked-at entries.  Pairwise-complete moments are not offered.  With d = value - d_shift[entry] (d_shift
+ * [steps][n_columns], indexed by the entry, finite) over the used geometries, N = n_entries:
+ *   d_gram   [N][N] double  sum d_n d_m, the full square; gram[n][m] and gram[m][n] are the same bits
+ *   d_sum    [N]    double  sum d_n
+ *   d_counts [2]    int64   geometries used, dropped
+ *   d_used   [n_geometries] uint8 or NULL: 1 where geometry g of THIS call is used
+ * accumulate = 0 overwrites gram, sum and counts; accumulate = 1 adds this call after what they hold - additions only, so it
+ * needs the same shift and the same entries as the calls before.  The host finishes: n = used, mean = shift + sum / n,
+ * covariance = (gram - sum sum^T / n) / (n - 1) (NaN for n < 2), correlation NaN where a variance is 0.
+ * Launch-only, stream-ordered, no host read-back, no allocation, legal inside a stream capture; n_geometries = 0 is legal.
+ * No floating-point atomics (no atomics on device memory at all): the geometries are cut into slabs by a plan that is a
+ * function of (n_geometries, steps, n_columns, n_entries) alone and never looks at the device, a slab is summed in ascending
+ * geometry order, four at a time in v_mfma_f64_16x16x4_f64, and the slabs are added in ascending order per output element -
+ * two runs, or two devices, give the same bits.  DIFFERENT CHUNKINGS of the same geometries agree to rounding only, as for
+ * okx_ensemble_reduce: |result - exact| <= (G + 2) u sum |d_n d_m| each (exactly where every product and sum is
+ * representable).  d_scratch: okx_ensemble_covariance_scratch_bytes.  The launch cannot read d_entries on the host:
+ * okx_ensemble_covariance_check validates a HOST copy (an index outside [0, n_table_entries), a duplicate, a count outside
+ * 1 .. OKX_ENS_COV_MAX_ENTRIES: OKX_ERR_INVALID with okx_last_error text) before it is uploaded; on the device an index out
+ * of range is never dereferenced - its entry never counts, every geometry is dropped.
+ */
+enum { OKX_ENS_COV_MAX_ENTRIES = 2048 };
+
+int32_t okx_ensemble_covariance(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                                const double* d_values, int64_t ld,
+                                const uint8_t* d_status, int64_t status_stride, /* or NULL                              */
+                                const int32_t* d_entries, int32_t n_entries,    /* or NULL: all, n_entries = steps * n_columns */
+                                const double* d_shift,
+                                int32_t accumulate,
+                                double* d_gram, double* d_sum, int64_t* d_counts,
+                                uint8_t* d_used,                                /* or NULL                              */
+                                void* d_scratch, size_t scratch_bytes, void* stream);
+/* host only */
+size_t okx_ensemble_covariance_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_entries);
+int32_t okx_ensemble_covariance_check(const int32_t* entries /* or NULL */, int32_t n_entries, int64_t n_table_entries);
+
 #ifdef __cplusplus
 }
 #endif

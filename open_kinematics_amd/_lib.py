@@ -73,6 +73,9 @@ EXPORTS = (
     "okx_ensemble_screen",
     "okx_ensemble_screen_scratch_bytes",
     "okx_ensemble_screen_check",
+    "okx_ensemble_covariance",
+    "okx_ensemble_covariance_scratch_bytes",
+    "okx_ensemble_covariance_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -254,6 +257,12 @@ def load() -> C.CDLL:
     lib.okx_ensemble_screen_scratch_bytes.restype = C.c_size_t
     lib.okx_ensemble_screen_check.argtypes = [vp, vp, i64]
     lib.okx_ensemble_screen_check.restype = i32
+    lib.okx_ensemble_covariance.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_covariance.restype = i32
+    lib.okx_ensemble_covariance_scratch_bytes.argtypes = [i64, i64, i32, i32]
+    lib.okx_ensemble_covariance_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_covariance_check.argtypes = [vp, i32, i64]
+    lib.okx_ensemble_covariance_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -1066,6 +1066,60 @@ class DeviceProgram:
                           _ptr(scratch), scratch.numel())
         return out
 
+    # ---- okx_ensemble_covariance: Gram matrix and sums of selected entries over the complete cases (ensemble_stats) ----
+
+    def covariance_ensemble(self, values, *, steps_per_geometry: int, status=None, entries=None, shift=None, out=None, accumulate: bool = False):
+        """
+        ``okx_ensemble_covariance``: the covariance accumulator (``ensemble_stats.CovarianceAccumulator``, device tensors:
+        ``gram [N, N]``, ``sum [N]``, ``counts [2]`` = used, dropped, ``used [G]`` uint8) of ``entries`` - N distinct indices
+        ``s K + k`` in the order wanted for rows and columns, None: all ``S K`` - of a column table in HBM over its COMPLETE
+        geometries, those whose every selected entry counts.  ``values`` and ``status`` as ``reduce_ensemble`` takes them (unit
+        column stride; strided rows and a strided status byte are passed on, nothing is copied); ``shift [S, K]`` the common
+        shift (None: the table's own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift, pass it
+        or pass ``out=``).  ``out``: the accumulator of an earlier call - it carries its own shift and entries - to write
+        (``accumulate=False``) or add into (``True``); with it and a table shape seen before, the call uploads and allocates
+        nothing and is legal inside a stream capture (``out.used`` is written when it holds a byte per geometry of the call).
+        ``.finalize()`` copies to the host: mean, covariance, std, correlation.  Bit-identical from run to run; different
+        chunkings agree to rounding.
+        """
+        from .ensemble_stats import CovarianceAccumulator, check_covariance_arguments
+
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        dev = self.device
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+            host = None if entries is None else np.ascontiguousarray(check_covariance_arguments(
+                entries.detach().cpu().numpy() if isinstance(entries, torch.Tensor) else entries, s * k))
+            n = s * k if host is None else host.size
+            rc = self.lib.okx_ensemble_covariance_check(None if host is None else host.ctypes.data_as(C.c_void_p), min(n, 1 << 30), s * k)
+            _lib.check(rc, "okx_ensemble_covariance")
+            if shift is None:
+                shift = torch.nan_to_num(values[:s], nan=0.0, posinf=0.0, neginf=0.0) if g else torch.zeros((s, k), dtype=torch.float64, device=dev)
+            shift = _as_f64(shift, dev).reshape(s, k).contiguous()
+            index = torch.arange(n, dtype=torch.int32, device=dev) if host is None else torch.as_tensor(host, device=dev)
+            out = CovarianceAccumulator(torch.empty((n, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                                        torch.empty(2, dtype=torch.int64, device=dev), shift, index, torch.empty(g, dtype=torch.uint8, device=dev))
+            out.natural = host is None  # (all entries in natural order: the call passes no entry list)
+        elif shift is not None or entries is not None:
+            raise ValueError("out= carries its own shift and entries")
+        n = int(out.entries.shape[0])
+        tables = (out.gram, out.sum, out.counts, out.shift, out.entries)
+        if tuple(out.shift.shape) != (s, k) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in tables) \
+                or out.entries.dtype != torch.int32 or out.gram.dtype != torch.float64 or out.sum.dtype != torch.float64 or out.counts.dtype != torch.int64:
+            raise ValueError(f"out must hold contiguous device tables gram [N, N], sum [N], counts [2], entries [N] and shift [S, K] = [{s}, {k}]")
+        used = out.used if out.used is not None and out.used.shape[0] >= g and out.used.is_contiguous() and out.used.device == dev else None
+        need = int(self.lib.okx_ensemble_covariance_scratch_bytes(g, s, k, n))
+        scratch = getattr(self, "_cov_scratch", None)
+        if scratch is None or scratch.numel() < need:  # grow-only; a captured graph keeps the buffer it was captured with alive
+            scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+            self._cov_keep = getattr(self, "_cov_keep", []) + [scratch]
+            self._cov_scratch = scratch
+        index = None if getattr(out, "natural", False) and n == s * k else _ptr(out.entries)
+        self._select_call("okx_ensemble_covariance", g, s, k, _ptr(values), ld, _ptr(status), stride, index, n, _ptr(out.shift),
+                          1 if accumulate else 0, _ptr(out.gram), _ptr(out.sum), _ptr(out.counts), _ptr(used), _ptr(scratch), scratch.numel())
+        return out
+
     def ensemble_targets(self, geom_pos: torch.Tensor, relative) -> torch.Tensor:
         """
         Absolute targets ``[G * S, T]`` of an ensemble from per-step RELATIVE displacements ``[S, T]``: every

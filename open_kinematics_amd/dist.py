@@ -281,18 +281,33 @@ class ShardedEnsemble:
     ensemble - ``tally``, ``blame``, ``flags [G]``, ``passed`` -, the same bits on every rank whatever the world size and
     chunking; ``screen_local()`` this rank's ``margin`` / ``entry`` / ``pass_index`` tensors, which stay where they are;
     ``screen_exchange_bytes_per_rank`` what the rank sends.
+
+    ``covariance=True`` or ``covariance=entries`` (with ``reduce=True``; ``entries``: N distinct indices ``s K + k`` of the
+    chosen columns' table, ``True``: all ``S K``, at most 2048) adds how the entries move TOGETHER
+    (``okx_ensemble_covariance``): right after a chunk's reduction, with the reduction's shift, its rows of ``metric_local``
+    are accumulated into this rank's Gram matrix, sums and counts over the COMPLETE geometries (every selected entry
+    counts).  ``step()`` then ends with one all-gather of ``gram | sum | counts``, merged on every rank in rank order - the
+    same bits on every rank; different world sizes and chunkings agree to rounding, as the accumulators of the reduction
+    do.  ``covariance()`` returns the ``ensemble_stats.EnsembleCovariance`` (mean, covariance, std, correlation),
+    ``covariance_accumulator`` holds the merged tables and ``covariance_local_used`` this rank's per-geometry used bytes.
+    ``covariance_exchange_bytes_per_rank`` is ``8 (N^2 + N + 2)`` - 8 MB at N = 1024 however few geometries there are, which
+    is why a SUBSET of entries (a few steps of a few columns) is the intended use at scale; no rank ever holds the table.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
-                 **solve_kw):
+                 covariance=None, **solve_kw):
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
         if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
             raise ValueError("screen=True screens the reduced ensemble: it needs reduce=True and limits (and screen_scale needs screen=True)")
         if (quantiles is not None or (limits is not None and not screen)) and (not reduce or quantiles is None):
             raise ValueError("quantiles / limits select over the reduced ensemble: they need reduce=True (and limits need quantiles)")
+        if covariance is False:
+            covariance = None
+        if covariance is not None and not reduce:
+            raise ValueError("covariance= accumulates the reduced ensemble: it needs reduce=True")
         self.reduce = bool(reduce)
         if metric_columns is not None:
             records, info = False, "status"   # nothing of the positions travels or is written
@@ -411,6 +426,10 @@ class ShardedEnsemble:
         self.screen_exchange_bytes_per_rank = 0
         if self.screening:
             self._init_screen(limits, screen_scale)
+        self.covarying = covariance is not None
+        self.covariance_exchange_bytes_per_rank = 0
+        if self.covarying:
+            self._init_covariance(covariance)
 
     # ---- reduce=True: the accumulators of ensemble_stats.py instead of a gathered table ----
 
@@ -685,6 +704,97 @@ class ShardedEnsemble:
         return {"flags": torch.from_numpy(part.flags), "margin": torch.from_numpy(part.margin), "entry": torch.from_numpy(part.entry),
                 "pass_index": torch.from_numpy(part.passed), "pass_count": torch.tensor([part.passed.size], dtype=torch.int64)}
 
+    # ---- covariance=...: Gram matrix, sums and counts of the selected entries, chunk by chunk; one all-gather, merged in rank order ----
+
+    def _init_covariance(self, covariance) -> None:
+        from .ensemble_stats import CovarianceAccumulator, check_covariance_arguments
+
+        glo, ghi = self.geometry_range
+        k, device = len(self.metric_index), self.device
+        entries = check_covariance_arguments(None if covariance is True else
+                                             (covariance.detach().cpu().numpy() if isinstance(covariance, torch.Tensor) else covariance), self.steps * k)
+        n = int(entries.size)
+        self.covariance_entries = entries
+        shift = self.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's
+        self._cov_local = CovarianceAccumulator(torch.zeros((n, n), dtype=torch.float64, device=device), torch.zeros(n, dtype=torch.float64, device=device),
+                                                torch.zeros(2, dtype=torch.int64, device=device), shift, torch.as_tensor(entries, device=device),
+                                                torch.zeros(ghi - glo, dtype=torch.uint8, device=device))
+        self._cov_local.natural = covariance is True
+        self.covariance_accumulator = None
+        self._cov_result = None
+        self._cov_any = False
+        words = n * n + n + 2
+        self._cov_send = torch.empty(words, dtype=torch.float64, device=device) if self.world > 1 else None
+        self._cov_recv = torch.empty((self.world, words), dtype=torch.float64, device=device) if self.world > 1 else None
+        self.covariance_exchange_bytes_per_rank = 8 * words if self.world > 1 else 0
+
+    def _covariance_rows(self, a: int, b: int, local) -> None:
+        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's covariance accumulator."""
+        from .ensemble_stats import CovarianceAccumulator, covariance_host
+
+        glo = self.geometry_range[0]
+        mine = self._cov_local
+        values = self.metric_local[local]
+        status = self.info_local[local][:, 32]
+        if values.is_cuda:  # (no quiet host pass over device tables: a program without the device pass is an error)
+            view = CovarianceAccumulator(mine.gram, mine.sum, mine.counts, mine.shift, mine.entries, mine.used[a - glo :])
+            view.natural = mine.natural
+            self.dp.covariance_ensemble(values, steps_per_geometry=self.steps, status=status, out=view, accumulate=self._cov_any)
+        else:  # the CPU tests' stand-in: the NumPy accumulator, merged the same way
+            part = covariance_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
+                                   self.covariance_entries, mine.shift.cpu().numpy())
+            if not self._cov_any:
+                mine.gram.zero_(), mine.sum.zero_(), mine.counts.zero_()
+            mine.gram += torch.from_numpy(part.gram)
+            mine.sum += torch.from_numpy(part.sum)
+            mine.counts += torch.from_numpy(part.counts)
+            mine.used[a - glo : b - glo] = torch.from_numpy(part.used)
+        self._cov_any = True
+
+    def _exchange_covariance(self) -> None:
+        """ONE all-gather of gram | sum | counts (the counts as their int64 bits) and the merge in rank order: the same bits on every rank."""
+        from .ensemble_stats import CovarianceAccumulator
+
+        mine = self._cov_local
+        self._cov_result = None
+        if self.world == 1:
+            self.covariance_accumulator = mine
+            return
+        n = int(mine.entries.shape[0])
+        self._cov_send[: n * n] = mine.gram.reshape(-1)
+        self._cov_send[n * n : n * n + n] = mine.sum
+        self._cov_send[n * n + n :] = mine.counts.view(torch.float64)
+        if self._cov_send.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
+            host = torch.empty(self._cov_recv.numel(), dtype=torch.float64)
+            dist.all_gather_into_tensor(host, self._cov_send.cpu(), group=self.group)
+            self._cov_recv.view(-1).copy_(host)
+        else:
+            dist.all_gather_into_tensor(self._cov_recv.view(-1), self._cov_send, group=self.group)
+        merged = None
+        for r in range(self.world):
+            row = self._cov_recv[r]
+            part = CovarianceAccumulator(row[: n * n].reshape(n, n), row[n * n : n * n + n], row[n * n + n :].view(torch.int64), mine.shift, mine.entries)
+            merged = part if merged is None else merged.merge(part)
+        self.covariance_accumulator = merged
+
+    @property
+    def covariance_local_used(self) -> torch.Tensor:
+        """This rank's used byte per geometry of the last ``step()`` (``covariance=``), where the table lives."""
+        if not self.covarying:
+            raise ValueError("covariance_local_used needs covariance=")
+        return self._cov_local.used
+
+    def covariance(self):
+        """``ensemble_stats.EnsembleCovariance`` of the WHOLE ensemble after the last ``step()`` (``covariance=``): count, mean,
+        covariance, std and correlation of the selected entries over the complete geometries.  The same bits on every rank."""
+        if not self.covarying:
+            raise ValueError("covariance() needs covariance=True or covariance=entries")
+        if self.covariance_accumulator is None:
+            raise RuntimeError("no step() yet")
+        if self._cov_result is None:
+            self._cov_result = self.covariance_accumulator.finalize()
+        return self._cov_result
+
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
         if not self.reduce:
@@ -755,6 +865,8 @@ class ShardedEnsemble:
             self._reduce_rows(a, b, local)
             if self.screening:
                 self._screen_rows(a, b, local)
+            if self.covarying:
+                self._covariance_rows(a, b, local)
             return
         torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_full[rows])
         if self.status_only:
@@ -900,6 +1012,8 @@ class ShardedEnsemble:
             self._reduced_any = False
         if self.screening:
             self._screened_any = False
+        if self.covarying:
+            self._cov_any = False
         for k in range(self.chunks):
             self._solve_chunk(k)
             works = self._exchange_chunk(k)
@@ -923,6 +1037,11 @@ class ShardedEnsemble:
                     glo = self.geometry_range[0]
                     self._screen_rows(glo, glo, slice(0, 0))
                 self._exchange_screen()
+            if self.covarying:
+                if not self._cov_any:  # a rank without a geometry: zero tables
+                    glo = self.geometry_range[0]
+                    self._covariance_rows(glo, glo, slice(0, 0))
+                self._exchange_covariance()
             return merged
         if self.metric_index is not None:
             return self.metric_full

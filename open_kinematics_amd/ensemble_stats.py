@@ -11,7 +11,9 @@ Three layers, the same accumulator in each (``include/okx.h``, ``okx_ensemble_re
   accumulators alone.
 
 Beside the moments: exact quantiles and per-entry spec-limit yield (``select_host``, ``okx_ensemble_select``) and the JOINT
-spec-limit verdict per geometry (``screen_host`` / ``EnsembleScreen``, ``okx_ensemble_screen``), each in the same three layers.
+spec-limit verdict per geometry (``screen_host`` / ``EnsembleScreen``, ``okx_ensemble_screen``), each in the same three layers;
+and how the entries move TOGETHER over the geometries: covariance and correlation of selected entries over the complete cases
+(``covariance_host`` / ``CovarianceAccumulator`` / ``EnsembleCovariance``, ``okx_ensemble_covariance``), in the same three.
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -594,9 +596,143 @@ def screen_host(values, status=None, limits=None, scale=None, geometry_offset: i
     return EnsembleScreen(flags, margin, entry, tally, blame.reshape(s, k, 2), passed)
 
 
+# ---- covariance and correlation of the selected entries over the complete cases (okx_ensemble_covariance) ----
+
+COV_MAX_ENTRIES = 2048  # OKX_ENS_COV_MAX_ENTRIES
+
+
+@dataclass
+class EnsembleCovariance:
+    """
+    What ``CovarianceAccumulator.finalize`` returns (NumPy, host), for the ``N`` selected entries in the caller's order:
+    ``entries [N]`` (``s K + k``), ``count`` the geometries used - those whose EVERY selected entry counts -, ``dropped`` the
+    others, ``mean [N]``, ``covariance [N, N]`` (unbiased; NaN for ``count < 2``), ``std [N]`` the square root of its diagonal
+    and ``correlation [N, N]`` (NaN where a variance is 0).  Symmetric bit for bit.
+    """
+
+    entries: np.ndarray
+    count: int
+    dropped: int
+    mean: np.ndarray
+    covariance: np.ndarray
+    std: np.ndarray
+    correlation: np.ndarray
+
+
+def check_covariance_arguments(entries, n_table_entries: int) -> np.ndarray:
+    """``entries [N]`` as int32 (None: all ``n_table_entries`` in natural order), or ValueError in the words of
+    ``okx_ensemble_covariance_check``."""
+    n_table = int(n_table_entries)
+    if entries is None:
+        e = np.arange(min(n_table, COV_MAX_ENTRIES + 1), dtype=np.int64)
+        if not 1 <= n_table <= COV_MAX_ENTRIES:
+            raise ValueError(f"okx_ensemble_covariance: {n_table} entries selected, 1 to {COV_MAX_ENTRIES} allowed")
+        return e.astype(np.int32)
+    e = np.atleast_1d(np.asarray(entries)).reshape(-1)
+    if e.size and not np.issubdtype(e.dtype, np.integer):
+        raise ValueError("entries must be integers s * n_columns + k")
+    e = e.astype(np.int64)
+    if not 1 <= e.size <= COV_MAX_ENTRIES:
+        raise ValueError(f"okx_ensemble_covariance: {e.size} entries selected, 1 to {COV_MAX_ENTRIES} allowed")
+    bad = np.flatnonzero((e < 0) | (e >= n_table))
+    if bad.size:
+        raise ValueError(f"okx_ensemble_covariance: entry {int(bad[0])} is {int(e[bad[0]])}, outside [0, {n_table})")
+    _, first = np.unique(e, return_index=True)
+    again = np.setdiff1d(np.arange(e.size), first)  # the positions that repeat an earlier one, ascending
+    if again.size:
+        at = int(again[0])
+        raise ValueError(f"okx_ensemble_covariance: entry {at} repeats entry {int(np.flatnonzero(e == e[at])[0])} (index {int(e[at])})")
+    return e.astype(np.int32)
+
+
+class CovarianceAccumulator:
+    """
+    The raw tables of ``okx_ensemble_covariance``: ``gram [N, N]`` and ``sum [N]`` float64, ``counts [2]`` int64 (used,
+    dropped), ``shift [S, K]`` and ``entries [N]`` int32 - NumPy arrays or torch tensors (host or device), whatever produced
+    them.  ``used [G]`` uint8 (or None) is the per-geometry byte of the LAST call that filled it.
+    """
+
+    def __init__(self, gram, sum, counts, shift, entries, used=None):  # noqa: A002
+        self.gram, self.sum, self.counts, self.shift, self.entries, self.used = gram, sum, counts, shift, entries, used
+        self.natural = False  # (set by DeviceProgram.covariance_ensemble: all entries in natural order, no entry list is passed)
+        n = int(entries.shape[0])
+        if tuple(gram.shape) != (n, n) or tuple(sum.shape) != (n,) or tuple(counts.shape) != (2,) or shift.ndim != 2:
+            raise ValueError("gram must be [N, N], sum [N], counts [2], shift [S, K] and entries [N]")
+
+    @classmethod
+    def empty(cls, shift, entries=None) -> "CovarianceAccumulator":
+        """The accumulator of no geometry at all (the neutral element of ``merge``), NumPy."""
+        shift = np.asarray(shift, dtype=np.float64)
+        e = check_covariance_arguments(entries, shift.size)
+        return cls(np.zeros((e.size, e.size)), np.zeros(e.size), np.zeros(2, dtype=np.int64), shift, e)
+
+    def numpy(self) -> "CovarianceAccumulator":
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(self.gram):
+            return self
+        host = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
+        return CovarianceAccumulator(host(self.gram), host(self.sum), host(self.counts), host(self.shift), host(self.entries), host(self.used))
+
+    def merge(self, other: "CovarianceAccumulator") -> "CovarianceAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been
+        taken with the same shift and the same entries.  Works on NumPy arrays and on torch tensors alike."""
+        xp = __import__("torch") if _is_tensor(self.gram) else np
+        equal = (lambda a, b: a is b or bool(xp.equal(a, b))) if xp is not np else (lambda a, b: a is b or np.array_equal(a, b))
+        if tuple(self.entries.shape) != tuple(other.entries.shape) or not equal(self.entries, other.entries):
+            raise ValueError("accumulators of different entries cannot be merged")
+        if tuple(self.shift.shape) != tuple(other.shift.shape) or not equal(self.shift, other.shift):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        return CovarianceAccumulator(self.gram + other.gram, self.sum + other.sum, self.counts + other.counts, self.shift, self.entries)
+
+    def finalize(self) -> EnsembleCovariance:
+        """Mean, covariance, std and correlation on the host in fp64."""
+        h = self.numpy()
+        gram, s1 = np.asarray(h.gram, dtype=np.float64), np.asarray(h.sum, dtype=np.float64)
+        entries = np.asarray(h.entries, dtype=np.int64)
+        shift = np.asarray(h.shift, dtype=np.float64).reshape(-1)[entries]
+        n, dropped = int(h.counts[0]), int(h.counts[1])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = shift + s1 / n if n > 0 else np.full(s1.shape, np.nan)
+            # sum (d_n - mean_n)(d_m - mean_m) = gram - s1 s1^T / n, about a shift that lies inside the data
+            cov = (gram - np.outer(s1, s1) / n) / (n - 1) if n > 1 else np.full(gram.shape, np.nan)
+            var = np.maximum(np.diag(cov), 0.0) if n > 1 else np.diag(cov)
+            std = np.sqrt(var)
+            scale = np.outer(std, std)
+            corr = np.where(scale > 0.0, cov / scale, np.nan)
+        return EnsembleCovariance(entries, n, dropped, mean, cov, std, corr)
+
+
+def covariance_host(values, status=None, entries=None, shift=None) -> CovarianceAccumulator:
+    """
+    The accumulator of ``okx_ensemble_covariance`` in NumPy.  ``values [G, S, K]``; ``status [G, S]`` uint8 or None (every
+    state accepted); ``entries [N]`` distinct ``s K + k`` (None: all, natural order); ``shift [S, K]`` (None: the values of
+    geometry 0, undefined entries 0).  A geometry is USED when every selected entry of it counts (``status & 7 == 1`` and a
+    finite value); the sums run over the used geometries in ascending order, one after the other.
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    e = check_covariance_arguments(entries, s * k)
+    if shift is None:
+        shift = clean_shift(v[0]) if g else np.zeros((s, k))
+    shift = np.asarray(shift, dtype=np.float64).reshape(s, k)
+    if not np.all(np.isfinite(shift)):
+        raise ValueError("the shift must be finite (clean_shift replaces undefined entries)")
+    at = e.astype(np.int64)
+    used = ok.reshape(g, s * k)[:, at].all(axis=1)
+    with np.errstate(invalid="ignore"):
+        d = np.where(used[:, None], v.reshape(g, s * k)[:, at] - shift.reshape(-1)[at][None], 0.0)
+    gram, s1 = np.zeros((e.size, e.size)), np.zeros(e.size)
+    for i in np.flatnonzero(used):  # ascending geometry order, as the device walks a slab
+        gram += np.outer(d[i], d[i])
+        s1 += d[i]
+    counts = np.array([int(used.sum()), g - int(used.sum())], dtype=np.int64)
+    return CovarianceAccumulator(gram, s1, counts, shift, e, used.astype(np.uint8))
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
            "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "SELECT_BITS", "SELECT_BINS",
            "SELECT_ROUNDS", "SELECT_MAX_PROBS", "EnsembleScreen", "screen_host", "check_screen_arguments", "SCREEN_OUTSIDE",
-           "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED"]
+           "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED", "EnsembleCovariance", "CovarianceAccumulator",
+           "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES"]
