@@ -53,6 +53,44 @@ def all_gather_rows(local: torch.Tensor, n_total: int, group=None, spans=None) -
     return torch.cat([gathered[r * biggest : r * biggest + (b - a)] for r, (a, b) in enumerate(spans)], dim=0)
 
 
+def _takes_host_tensors(tensor: torch.Tensor, group) -> bool:
+    """A device tensor over gloo (ranks rehearsing on one GPU): the collective is given a host copy."""
+    return tensor.is_cuda and dist.get_backend(group) == "gloo"
+
+
+def broadcast_from_rank_zero(tensor: torch.Tensor, group=None) -> torch.Tensor:
+    """Rank 0's ``tensor`` on every rank, on the device it was given on."""
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    sent = tensor.cpu() if _takes_host_tensors(tensor, group) else tensor
+    dist.broadcast(sent, src, group=group)
+    return sent.to(tensor.device)
+
+
+def all_reduce_sum(tensor: torch.Tensor, group=None) -> None:
+    """``tensor`` summed over the ranks, in place; a world of one does nothing."""
+    if _world(group)[0] == 1:
+        return
+    if _takes_host_tensors(tensor, group):
+        host = tensor.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        tensor.copy_(host)
+    else:
+        dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=group)
+
+
+def all_gather_flat(local: torch.Tensor, group=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Every rank's flat ``local [words]`` as the rows of one ``[world, words]`` table (``out``, or a new one) on ``local``'s device."""
+    if out is None:
+        out = torch.empty((dist.get_world_size(group), local.numel()), dtype=local.dtype, device=local.device)
+    if _takes_host_tensors(local, group):
+        host = torch.empty(out.numel(), dtype=out.dtype)
+        dist.all_gather_into_tensor(host, local.cpu(), group=group)
+        out.view(-1).copy_(host)
+    else:
+        dist.all_gather_into_tensor(out.view(-1), local, group=group)
+    return out
+
+
 class GatherPipeline:
     """
     Overlaps the exchange step with the next solve: the all-gather of step ``k`` runs on the
@@ -416,384 +454,67 @@ class ShardedEnsemble:
         self._expand_graphs = {}
         self.use_graphs = device.type == "cuda"
         self.p2p_groups = self.p2p_ops = 0  # grouped point-to-point calls / operations issued so far
-        if self.reduce:
-            self._init_reduction(hardpoints, targets, relative_targets, factors, shift)
+        # the stages of a reduced ensemble that are switched on, by name and in the order they run in (ensemble_stages.py)
+        self.stages = {}
         self.select_probs = None
-        self.select_exchange_bytes_per_rank = 0
-        if quantiles is not None:
-            self._init_selection(quantiles, limits)
-        self.screening = bool(screen)
-        self.screen_exchange_bytes_per_rank = 0
-        if self.screening:
-            self._init_screen(limits, screen_scale)
-        self.covarying = covariance is not None
-        self.covariance_exchange_bytes_per_rank = 0
-        if self.covarying:
-            self._init_covariance(covariance)
+        self.screening, self.covarying = bool(screen), covariance is not None
+        if self.reduce:
+            from . import ensemble_stages as stages
 
-    # ---- reduce=True: the accumulators of ensemble_stats.py instead of a gathered table ----
+            first = self.stages["reduce"] = stages.Reduction(self, hardpoints, targets, relative_targets, factors, shift)
+            self.local_accumulator, self.exchange_bytes_per_rank = first.local, first.bytes_per_rank
+            self.factor_names, self.n_factors, self.my_factors = first.factor_names, first.n_factors, first.my_factors
+            if quantiles is not None:
+                stage = self.stages["select"] = stages.Selection(self, quantiles, limits)
+                self.select_probs, self.select_limits = stage.probs, stage.limits
+            if self.screening:
+                stage = self.stages["screen"] = stages.Screening(self, limits, screen_scale)
+                self.screen_limits, self.screen_scale = stage.limits, stage.scale
+            if self.covarying:
+                stage = self.stages["covariance"] = stages.Covariance(self, covariance)
+                self.covariance_entries = stage.entries
+        sent = {name: stage.bytes_per_rank for name, stage in self.stages.items()}
+        self.select_exchange_bytes_per_rank, self.screen_exchange_bytes_per_rank = sent.get("select", 0), sent.get("screen", 0)
+        self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
 
-    def _init_reduction(self, hardpoints, targets, relative_targets, factors, shift) -> None:
-        import numpy as np
+    # ---- reduce=True: the stages of ensemble_stages.py; what they hold and answer, by the names it has always had ----
 
-        from .ensemble_stats import ENS_FIELDS, EnsembleAccumulator, clean_shift, factor_moment_count, hardpoint_factors
-
-        glo, ghi = self.geometry_range
-        device, k = self.device, len(self.metric_index)
-        self.factor_names = None
-        if isinstance(factors, str):
-            if factors != "hardpoints":
-                raise ValueError("factors must be None, 'hardpoints' or a [G, P] table")
-            program = self.dp.program
-            table = torch.as_tensor(hardpoints).detach().cpu().numpy()
-            # (derived points are recomputed from the authored ones by rebind: their coordinates are no factors)
-            from .program import key_name
-
-            authored = np.setdiff1d(np.arange(table.shape[1]), np.asarray(program.dop_out, dtype=np.int64))
-            names = [key_name(program.point_keys[i]).lower() for i in authored]
-            factors, self.factor_names = hardpoint_factors(table[:, authored], names)
-        if factors is not None:
-            factors = np.ascontiguousarray(torch.as_tensor(factors).detach().cpu().numpy(), dtype=np.float64).reshape(self.n_geom, -1)
-        p = 0 if factors is None else factors.shape[1]
-        self.n_factors = p
-        self.my_factors = torch.as_tensor(factors[glo:ghi], device=device).contiguous() if p else None
-        # the shift: ONE table for every partial that is ever merged
-        if shift is None:
-            shift = torch.zeros((self.steps, k), dtype=torch.float64, device=device)
-            if self.rank == 0 and self.n_geom > 0:
-                gpos, gparam = self.dp.rebind(torch.as_tensor(hardpoints)[:1])
-                first = self.dp.ensemble_targets(gpos, targets) if relative_targets else targets[: self.steps]
-                res = self.dp.solve_evaluated(first, geom_pos=gpos, geom_row_param=gparam, steps_per_geometry=self.steps,
-                                              output="none", **self.solve_kw)
-                rows = res.eval.reshape(self.steps, -1).to(device)
-                shift = torch.nan_to_num(torch.index_select(rows, 1, self.metric_index), nan=0.0, posinf=0.0, neginf=0.0)
-            if self.world > 1:
-                shift = self._broadcast_from_rank_zero(shift.contiguous())
-        else:
-            shift = torch.as_tensor(clean_shift(torch.as_tensor(shift).detach().cpu().numpy()), device=device)
-        shift = shift.reshape(self.steps, k).contiguous()
-        # the unmasked factor moments of this rank's geometries, once: the factors never change (ascending order, as the device sums)
-        factor_acc = None
-        if p:
-            mine = factors[glo:ghi]
-            rows, cols = np.tril_indices(p)
-            moments = np.zeros(factor_moment_count(p))
-            if ghi > glo:
-                moments[:p] = np.cumsum(mine, axis=0)[-1]
-                moments[p:-1] = np.cumsum(mine[:, rows] * mine[:, cols], axis=0)[-1]
-            moments[-1] = ghi - glo
-            factor_acc = torch.as_tensor(moments, device=device)
-        self.local_accumulator = EnsembleAccumulator(torch.empty((self.steps, k, ENS_FIELDS + p), dtype=torch.float64, device=device),
-                                                     shift, factor_acc, self.factor_names)
-        self.accumulator = self.local_accumulator
-        words = self.local_accumulator.acc.numel() + (factor_acc.numel() if p else 0)
-        self._acc_send = torch.empty(words, dtype=torch.float64, device=device) if self.world > 1 else None
-        self._acc_recv = torch.empty((self.world, words), dtype=torch.float64, device=device) if self.world > 1 else None
-        self.exchange_bytes_per_rank = 8 * words if self.world > 1 else 0
-        self._reduced_any = False
-
-    def _broadcast_from_rank_zero(self, tensor: torch.Tensor) -> torch.Tensor:
-        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
-        if tensor.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
-            host = tensor.cpu()
-            dist.broadcast(host, src, group=self.group)
-            return host.to(tensor.device)
-        dist.broadcast(tensor, src, group=self.group)
-        return tensor
-
-    def _reduce_rows(self, a: int, b: int, local) -> None:
-        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's accumulator."""
-        glo = self.geometry_range[0]
-        acc = self.local_accumulator
-        values = self.metric_local[local]
-        status = self.info_local[local][:, 32]
-        factors = self.my_factors[a - glo : b - glo] if self.n_factors else None
-        if values.is_cuda:  # (no quiet host reduction of device tables: a program without the device pass is an error)
-            self.dp.reduce_ensemble(values, steps_per_geometry=self.steps, status=status, factors=factors, geometry_offset=a, out=acc,
-                                    accumulate=self._reduced_any, factor_moments=False)
-        else:  # the CPU tests' stand-in: the NumPy accumulator, merged the same way
-            from .ensemble_stats import EnsembleAccumulator, reduce_host
-
-            part = reduce_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
-                               None if factors is None else factors.cpu().numpy(), acc.shift.cpu().numpy(), a)
-            part = EnsembleAccumulator(torch.as_tensor(part.acc, device=self.device), acc.shift, None)
-            if self._reduced_any:
-                part = EnsembleAccumulator(acc.acc, acc.shift, None).merge(part)
-            acc.acc.copy_(part.acc)
-        self._reduced_any = True
-
-    def _exchange_accumulators(self):
-        """ONE all-gather of the ranks' accumulators and their merge in rank order: the same bits on every rank."""
-        from .ensemble_stats import EnsembleAccumulator
-
-        mine = self.local_accumulator
-        if self.world == 1:
-            self.accumulator = mine
-            return mine
-        n_acc = mine.acc.numel()
-        self._acc_send[:n_acc] = mine.acc.reshape(-1)
-        if self.n_factors:
-            self._acc_send[n_acc:] = mine.factor_acc
-        if self._acc_send.is_cuda and dist.get_backend(self.group) == "gloo":
-            host = torch.empty(self._acc_recv.numel(), dtype=torch.float64)
-            dist.all_gather_into_tensor(host, self._acc_send.cpu(), group=self.group)
-            self._acc_recv.view(-1).copy_(host)
-        else:
-            dist.all_gather_into_tensor(self._acc_recv.view(-1), self._acc_send, group=self.group)
-        merged = None
-        for r in range(self.world):
-            part = EnsembleAccumulator(self._acc_recv[r, :n_acc].reshape(mine.acc.shape), mine.shift,
-                                       self._acc_recv[r, n_acc:] if self.n_factors else None, self.factor_names)
-            merged = part if merged is None else merged.merge(part)
-        self.accumulator = merged
-        return merged
-
-    # ---- quantiles=...: the select rounds of ensemble_stats.py over the rank's shard, histograms summed over the ranks ----
-
-    def _init_selection(self, quantiles, limits) -> None:
-        from .ensemble_stats import SELECT_BINS, SELECT_ROUNDS, check_select_arguments
-
-        k = len(self.metric_index)
-        self.select_probs, self.select_limits = check_select_arguments(quantiles, limits, self.steps, k)
-        self._selection = self._quantiles = None
-        self._selected = False
-        if self.device.type == "cuda":  # (no quiet host selection of device tables: a program without the device pass is an error)
-            self._selection = self.dp.select_prepare(self.steps, k, self.select_probs, self.select_limits, rounds=True)
-            rounds, words = self.dp.select_rounds, self._selection.hist.numel()
-        else:
-            rounds, words = SELECT_ROUNDS, self.steps * k * 2 * len(self.select_probs) * SELECT_BINS
-        self.select_exchange_bytes_per_rank = rounds * 8 * words if self.world > 1 else 0
-
-    def _sum_histograms(self, hist: torch.Tensor) -> None:
-        if self.world == 1:
-            return
-        if hist.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
-            host = hist.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=self.group)
-            hist.copy_(host)
-        else:
-            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=self.group)
-
-    def _run_selection(self) -> None:
-        """Every round: count this rank's shard, sum the histograms over the ranks, descend."""
-        glo, ghi = self.geometry_range
-        values, status = self.metric_local, self.info_local[:, 32]
-        if self._selection is not None:
-            run, dp = self._selection, self.dp
-            dp.select_begin(run)
-            for rnd in range(dp.select_rounds):
-                if ghi > glo:
-                    dp.select_count(run, rnd, values, steps_per_geometry=self.steps, status=status)
-                self._sum_histograms(run.hist)
-                dp.select_descend(run, rnd)
-            dp.select_finish(run)
-            self._quantiles, self._selected = None, True
-            return
-        # the CPU tests' stand-in: the same protocol by the NumPy rounds
-        from .ensemble_stats import SELECT_ROUNDS, select_begin, select_count_round, select_descend_round, select_finish
-
-        k = values.shape[1]
-        v = values.numpy().reshape(ghi - glo, self.steps, k)
-        st = status.numpy().reshape(ghi - glo, self.steps)
-        state, hist = select_begin(self.steps, k, len(self.select_probs))
-        for rnd in range(SELECT_ROUNDS):
-            select_count_round(rnd, v, st, state, hist, self.select_limits)
-            self._sum_histograms(torch.from_numpy(hist))
-            select_descend_round(rnd, state, hist, self.select_probs)
-        self._quantiles = select_finish(state, self.select_probs, self.select_limits is not None)
+    accumulator = property(lambda self: self.stages["reduce"].merged, doc="The merged accumulator of the last ``step()`` (``reduce=True``).")
+    covariance_accumulator = property(lambda self: self.stages["covariance"].merged, doc="The merged covariance tables of the last ``step()``; None before.")
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""
         if self.select_probs is None:
             raise ValueError("quantiles() needs quantiles=(p, ...)")
-        if self._quantiles is None:
-            if not self._selected:
-                raise RuntimeError("no step() yet")
-            self._quantiles = self._selection.finalize()
-        return self._quantiles
-
-    # ---- screen=True: the joint verdict per geometry, chunk by chunk; tally | blame summed and the flag bytes gathered ----
-
-    def _init_screen(self, limits, scale) -> None:
-        from .ensemble_stats import check_screen_arguments
-
-        glo, ghi = self.geometry_range
-        k = len(self.metric_index)
-        self.screen_limits, self.screen_scale = check_screen_arguments(limits, scale, self.steps, k)
-        self._largest_shard = max(hi - lo for lo, hi in (shard_range(self.n_geom, r, self.world) for r in range(self.world)))
-        self._screening = self._screen_part = self._screen_result = None
-        self._screen_counts = self._screen_flags = None
-        self._screened_any = False
-        if self.device.type == "cuda":  # (no quiet host screening of device tables: a program without the device pass is an error)
-            self._screening = self.dp.screen_prepare(self.steps, k, self.screen_limits, self.screen_scale, ghi - glo)
-        self.screen_exchange_bytes_per_rank = 8 * (4 + 2 * self.steps * k) + self._largest_shard if self.world > 1 else 0
-
-    def _screen_rows(self, a: int, b: int, local) -> None:
-        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's screen."""
-        glo = self.geometry_range[0]
-        values = self.metric_local[local]
-        status = self.info_local[local][:, 32]
-        if self._screening is not None:
-            self.dp.screen_ensemble(values, steps_per_geometry=self.steps, status=status, geometry_offset=a, out=self._screening,
-                                    accumulate=self._screened_any, first_row=a - glo)
-        else:  # the CPU tests' stand-in: the NumPy screen, merged the same way
-            from .ensemble_stats import screen_host
-
-            part = screen_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
-                               self.screen_limits, self.screen_scale, a)
-            self._screen_part = self._screen_part.merge(part) if self._screened_any else part
-        self._screened_any = True
-
-    def _exchange_screen(self) -> None:
-        """One integer all-reduce of tally | blame and one all-gather of the flag bytes: the same bits on every rank."""
-        import numpy as np
-
-        glo, ghi = self.geometry_range
-        if self._screening is not None:
-            run = self._screening
-            counts = torch.cat([run.tally, run.blame.reshape(-1)])
-            flags = run.flags
-        else:
-            part = self._screen_part
-            counts = torch.from_numpy(np.concatenate([part.tally, part.blame.reshape(-1)]))
-            flags = torch.from_numpy(part.flags)
-        self._screen_result = None
-        if self.world == 1:
-            self._screen_counts, self._screen_flags = counts, flags
-            return
-        padded = torch.zeros(self._largest_shard, dtype=torch.uint8, device=flags.device)
-        padded[: ghi - glo] = flags
-        if counts.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
-            counts, padded = counts.cpu(), padded.cpu()
-        gathered = torch.empty(self.world * self._largest_shard, dtype=torch.uint8, device=padded.device)
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
-        dist.all_gather_into_tensor(gathered, padded, group=self.group)
-        spans = [shard_range(self.n_geom, r, self.world) for r in range(self.world)]
-        self._screen_flags = torch.cat([gathered[r * self._largest_shard : r * self._largest_shard + hi - lo] for r, (lo, hi) in enumerate(spans)])
-        self._screen_counts = counts
+        return self.stages["select"].quantiles()
 
     def screen(self):
         """``ensemble_stats.EnsembleScreen`` of the WHOLE ensemble after the last ``step()`` (``screen=True``): ``tally``, ``blame``,
         ``flags [G]`` and ``passed``; ``margin`` / ``entry`` stay with their ranks (``screen_local``).  The same bits on every rank."""
         if not self.screening:
             raise ValueError("screen() needs screen=True")
-        if self._screen_counts is None:
-            raise RuntimeError("no step() yet")
-        if self._screen_result is None:
-            import numpy as np
-
-            from .ensemble_stats import EnsembleScreen
-
-            counts = self._screen_counts.cpu().numpy()
-            flags = self._screen_flags.cpu().numpy()
-            blame = counts[4:].reshape(self.steps, len(self.metric_index), 2).copy()
-            self._screen_result = EnsembleScreen(flags, None, None, counts[:4].copy(), blame, np.flatnonzero(flags == 0).astype(np.int64))
-        return self._screen_result
+        return self.stages["screen"].screen()
 
     def screen_local(self) -> dict:
         """This rank's tables of the last ``step()``: ``flags`` / ``margin`` / ``entry [n_local]``, ``pass_index`` (ascending global
         indices of its geometries that pass, ``pass_count`` of them) - tensors where the table lives, nothing is copied."""
         if not self.screening:
             raise ValueError("screen_local() needs screen=True")
-        if self._screening is not None:
-            run = self._screening
-            return {"flags": run.flags, "margin": run.margin, "entry": run.entry, "pass_index": run.pass_index, "pass_count": run.pass_count}
-        if self._screen_part is None:
-            raise RuntimeError("no step() yet")
-        part = self._screen_part
-        return {"flags": torch.from_numpy(part.flags), "margin": torch.from_numpy(part.margin), "entry": torch.from_numpy(part.entry),
-                "pass_index": torch.from_numpy(part.passed), "pass_count": torch.tensor([part.passed.size], dtype=torch.int64)}
-
-    # ---- covariance=...: Gram matrix, sums and counts of the selected entries, chunk by chunk; one all-gather, merged in rank order ----
-
-    def _init_covariance(self, covariance) -> None:
-        from .ensemble_stats import CovarianceAccumulator, check_covariance_arguments
-
-        glo, ghi = self.geometry_range
-        k, device = len(self.metric_index), self.device
-        entries = check_covariance_arguments(None if covariance is True else
-                                             (covariance.detach().cpu().numpy() if isinstance(covariance, torch.Tensor) else covariance), self.steps * k)
-        n = int(entries.size)
-        self.covariance_entries = entries
-        shift = self.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's
-        self._cov_local = CovarianceAccumulator(torch.zeros((n, n), dtype=torch.float64, device=device), torch.zeros(n, dtype=torch.float64, device=device),
-                                                torch.zeros(2, dtype=torch.int64, device=device), shift, torch.as_tensor(entries, device=device),
-                                                torch.zeros(ghi - glo, dtype=torch.uint8, device=device))
-        self._cov_local.natural = covariance is True
-        self.covariance_accumulator = None
-        self._cov_result = None
-        self._cov_any = False
-        words = n * n + n + 2
-        self._cov_send = torch.empty(words, dtype=torch.float64, device=device) if self.world > 1 else None
-        self._cov_recv = torch.empty((self.world, words), dtype=torch.float64, device=device) if self.world > 1 else None
-        self.covariance_exchange_bytes_per_rank = 8 * words if self.world > 1 else 0
-
-    def _covariance_rows(self, a: int, b: int, local) -> None:
-        """Geometries [a, b) of this rank (rows ``local`` of its tables) into the rank's covariance accumulator."""
-        from .ensemble_stats import CovarianceAccumulator, covariance_host
-
-        glo = self.geometry_range[0]
-        mine = self._cov_local
-        values = self.metric_local[local]
-        status = self.info_local[local][:, 32]
-        if values.is_cuda:  # (no quiet host pass over device tables: a program without the device pass is an error)
-            view = CovarianceAccumulator(mine.gram, mine.sum, mine.counts, mine.shift, mine.entries, mine.used[a - glo :])
-            view.natural = mine.natural
-            self.dp.covariance_ensemble(values, steps_per_geometry=self.steps, status=status, out=view, accumulate=self._cov_any)
-        else:  # the CPU tests' stand-in: the NumPy accumulator, merged the same way
-            part = covariance_host(values.reshape(b - a, self.steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, self.steps).cpu().numpy(),
-                                   self.covariance_entries, mine.shift.cpu().numpy())
-            if not self._cov_any:
-                mine.gram.zero_(), mine.sum.zero_(), mine.counts.zero_()
-            mine.gram += torch.from_numpy(part.gram)
-            mine.sum += torch.from_numpy(part.sum)
-            mine.counts += torch.from_numpy(part.counts)
-            mine.used[a - glo : b - glo] = torch.from_numpy(part.used)
-        self._cov_any = True
-
-    def _exchange_covariance(self) -> None:
-        """ONE all-gather of gram | sum | counts (the counts as their int64 bits) and the merge in rank order: the same bits on every rank."""
-        from .ensemble_stats import CovarianceAccumulator
-
-        mine = self._cov_local
-        self._cov_result = None
-        if self.world == 1:
-            self.covariance_accumulator = mine
-            return
-        n = int(mine.entries.shape[0])
-        self._cov_send[: n * n] = mine.gram.reshape(-1)
-        self._cov_send[n * n : n * n + n] = mine.sum
-        self._cov_send[n * n + n :] = mine.counts.view(torch.float64)
-        if self._cov_send.is_cuda and dist.get_backend(self.group) == "gloo":  # (ranks rehearsing on one GPU: gloo takes host tensors)
-            host = torch.empty(self._cov_recv.numel(), dtype=torch.float64)
-            dist.all_gather_into_tensor(host, self._cov_send.cpu(), group=self.group)
-            self._cov_recv.view(-1).copy_(host)
-        else:
-            dist.all_gather_into_tensor(self._cov_recv.view(-1), self._cov_send, group=self.group)
-        merged = None
-        for r in range(self.world):
-            row = self._cov_recv[r]
-            part = CovarianceAccumulator(row[: n * n].reshape(n, n), row[n * n : n * n + n], row[n * n + n :].view(torch.int64), mine.shift, mine.entries)
-            merged = part if merged is None else merged.merge(part)
-        self.covariance_accumulator = merged
+        return self.stages["screen"].screen_local()
 
     @property
     def covariance_local_used(self) -> torch.Tensor:
         """This rank's used byte per geometry of the last ``step()`` (``covariance=``), where the table lives."""
         if not self.covarying:
             raise ValueError("covariance_local_used needs covariance=")
-        return self._cov_local.used
+        return self.stages["covariance"].local.used
 
     def covariance(self):
         """``ensemble_stats.EnsembleCovariance`` of the WHOLE ensemble after the last ``step()`` (``covariance=``): count, mean,
         covariance, std and correlation of the selected entries over the complete geometries.  The same bits on every rank."""
         if not self.covarying:
             raise ValueError("covariance() needs covariance=True or covariance=entries")
-        if self.covariance_accumulator is None:
-            raise RuntimeError("no step() yet")
-        if self._cov_result is None:
-            self._cov_result = self.covariance_accumulator.finalize()
-        return self._cov_result
+        return self.stages["covariance"].covariance()
 
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
@@ -862,11 +583,8 @@ class ShardedEnsemble:
                 info.copy_(res.info_raw)
         if self.reduce:
             torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_local[local])
-            self._reduce_rows(a, b, local)
-            if self.screening:
-                self._screen_rows(a, b, local)
-            if self.covarying:
-                self._covariance_rows(a, b, local)
+            for stage in self.stages.values():
+                stage.rows(a, b, local)
             return
         torch.index_select(ev.view(ev.shape[0], -1), 1, self.metric_index, out=self.metric_full[rows])
         if self.status_only:
@@ -1008,12 +726,8 @@ class ShardedEnsemble:
     def step(self):
         """One pass over the whole ensemble: returns ``positions`` (``records=True``) or the gathered free coordinates."""
         pending = []
-        if self.reduce:
-            self._reduced_any = False
-        if self.screening:
-            self._screened_any = False
-        if self.covarying:
-            self._cov_any = False
+        for stage in self.stages.values():
+            stage.begin_step()
         for k in range(self.chunks):
             self._solve_chunk(k)
             works = self._exchange_chunk(k)
@@ -1026,23 +740,11 @@ class ShardedEnsemble:
         if self.expand_stream is not None:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
         if self.reduce:
-            if not self._reduced_any:  # a rank without a geometry contributes the neutral accumulator
-                glo = self.geometry_range[0]
-                self._reduce_rows(glo, glo, slice(0, 0))
-            merged = self._exchange_accumulators()
-            if self.select_probs is not None:
-                self._run_selection()
-            if self.screening:
-                if not self._screened_any:  # a rank without a geometry: zero counts, no verdicts
-                    glo = self.geometry_range[0]
-                    self._screen_rows(glo, glo, slice(0, 0))
-                self._exchange_screen()
-            if self.covarying:
-                if not self._cov_any:  # a rank without a geometry: zero tables
-                    glo = self.geometry_range[0]
-                    self._covariance_rows(glo, glo, slice(0, 0))
-                self._exchange_covariance()
-            return merged
+            # every rank, with or without a geometry, in this order: the accumulators' all-gather, the select rounds' all-reduces,
+            # the screen's all-reduce and all-gather, the covariance's all-gather
+            for stage in self.stages.values():
+                stage.end_step()
+            return self.accumulator
         if self.metric_index is not None:
             return self.metric_full
         return self.positions if self.records else self.free_full

@@ -1,0 +1,376 @@
+"""
+The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce`` (moments, extremes, sensitivities),
+``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry) and
+``okx_ensemble_covariance``.  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ensemble_stats import _host_f64
+
+
+@dataclass
+class EnsembleSelection:
+    """
+    What ``DeviceProgram.select_ensemble`` returns and its round-level calls work on, device tensors: ``probs [Q]`` and
+    ``limits [S, K, 2]`` (or None) as uploaded, ``order [S, K, Q, 2]`` the order statistics below / above every quantile,
+    ``count [S, K]`` and ``outside [S, K, 2]`` (or None) int64; ``state`` / ``hist`` (``select_prepare(rounds=True)``) the
+    opaque state and the int64 histogram ``[S, K, 2 Q, bins]`` of ``okx_ensemble_select_count``.
+    """
+
+    probs_host: np.ndarray
+    probs: torch.Tensor
+    limits: torch.Tensor | None
+    order: torch.Tensor
+    count: torch.Tensor
+    outside: torch.Tensor | None
+    state: torch.Tensor | None = None
+    hist: torch.Tensor | None = None
+
+    @property
+    def shape(self) -> tuple:
+        """``(S, K, Q)``."""
+        return tuple(self.order.shape[:3])
+
+    def finalize(self):
+        """Host copy, interpolated: ``ensemble_stats.EnsembleQuantiles``."""
+        from .ensemble_stats import quantiles_from_order
+
+        return quantiles_from_order(self.probs_host, self.order.cpu().numpy(), self.count.cpu().numpy(),
+                                    None if self.outside is None else self.outside.cpu().numpy())
+
+
+@dataclass
+class EnsembleScreening:
+    """
+    What ``DeviceProgram.screen_ensemble`` returns, device tensors: ``limits [S, K, 2]`` and ``scale [S, K]`` (or None) as
+    uploaded; per geometry ``flags [G]`` uint8, ``margin [G]`` float64 and ``entry [G]`` int32; per ensemble ``tally [4]`` and
+    ``blame [S, K, 2]`` int64, ``pass_index [capacity]`` int64 (the ascending global indices of the geometries that pass;
+    slots beyond ``min(pass_count, capacity)`` are never written) and ``pass_count [1]`` int64, the survivors found.
+    """
+
+    limits: torch.Tensor
+    scale: torch.Tensor | None
+    flags: torch.Tensor
+    margin: torch.Tensor
+    entry: torch.Tensor
+    tally: torch.Tensor
+    blame: torch.Tensor
+    pass_index: torch.Tensor
+    pass_count: torch.Tensor
+
+    @property
+    def shape(self) -> tuple:
+        """``(S, K)``."""
+        return tuple(self.blame.shape[:2])
+
+    def finalize(self):
+        """Host copy: ``ensemble_stats.EnsembleScreen`` (``passed`` holds the survivors that fit the capacity)."""
+        from .ensemble_stats import EnsembleScreen
+
+        tally = self.tally.cpu().numpy()
+        n = min(int(self.pass_count.item()), self.pass_index.shape[0])
+        seen = min(int(tally[0]), self.flags.shape[0])  # (accumulated chunks fill the tables from the front)
+        return EnsembleScreen(self.flags[:seen].cpu().numpy(), self.margin[:seen].cpu().numpy(), self.entry[:seen].cpu().numpy(), tally,
+                              self.blame.cpu().numpy(), self.pass_index[:n].cpu().numpy())
+
+
+def _ptr(t: torch.Tensor | None) -> C.c_void_p:
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _as_f64(t, device) -> torch.Tensor:
+    """A contiguous float64 tensor ON the device: always a snapshot of host data (synchronous copy), whatever its kind."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t, dtype=np.float64))
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+class EnsembleReductions:
+    """
+    The ensemble passes of a ``DeviceProgram`` (a mixin).  They read column tables, not the constraint program: all they
+    need of the object is ``self.lib`` (the loaded library) and ``self.device``.
+    """
+
+    def _ensemble_table(self, values, status, steps_per_geometry: int):
+        """``(G, S, K, ld, status stride)`` of a column table view of an ensemble pass: ``values [G * S, K]`` float64 with
+        unit column stride (rows may be strided), ``status [G * S]`` uint8 (may be strided) or None."""
+        s = int(steps_per_geometry)
+        if values.dim() != 2 or values.dtype != torch.float64 or values.device != self.device or (values.shape[1] > 1 and values.stride(1) != 1):
+            raise ValueError("values must be a float64 [G * S, K] device tensor with unit column stride")
+        b, k = values.shape
+        if s < 1 or b % s:
+            raise ValueError("bad steps_per_geometry")
+        ld = values.stride(0) if b > 1 else max(k, values.stride(0))
+        if ld < k:
+            raise ValueError("rows of values overlap")
+        stride = 0
+        if status is not None:
+            if status.dtype != torch.uint8 or status.dim() != 1 or status.shape[0] != b or status.device != self.device:
+                raise ValueError("status must be a uint8 [G * S] device tensor")
+            stride = status.stride(0) if b > 1 else 1
+        return b // s, s, k, ld, stride
+
+    def _ensemble_shift(self, shift, values, g: int, s: int, k: int) -> torch.Tensor:
+        """The common shift ``[S, K]`` on the device; None: geometry 0 of the table, undefined entries 0 (no geometry: zeros)."""
+        if shift is None:
+            shift = torch.nan_to_num(values[:s], nan=0.0, posinf=0.0, neginf=0.0) if g else torch.zeros((s, k), dtype=torch.float64, device=self.device)
+        return _as_f64(shift, self.device).reshape(s, k).contiguous()
+
+    def _ensemble_scratch(self, which: str, need: int) -> torch.Tensor:
+        """The scratch buffer of pass ``which`` (one per pass), at least ``need`` bytes."""
+        if not hasattr(self, "_ensemble_buffers"):
+            self._ensemble_buffers = {}
+        held = self._ensemble_buffers.setdefault(which, [])
+        if not held or held[-1].numel() < need:  # grow-only; a captured graph keeps the buffer it was captured with alive
+            held.append(torch.empty(max(need, 8), dtype=torch.uint8, device=self.device))
+        return held[-1]
+
+    def _ensemble_call(self, name: str, *args) -> None:
+        """``name(*args, stream)`` of the library on torch's current stream of the device, its status checked."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(*args, C.c_void_p(stream))
+        _lib.check(rc, name)
+
+    def reduce_ensemble(self, values, *, steps_per_geometry: int, status=None, factors=None, shift=None, geometry_offset: int = 0,
+                        out=None, accumulate: bool = False, factor_moments: bool = True):
+        """
+        ``okx_ensemble_reduce``: the statistics accumulator (``ensemble_stats.EnsembleAccumulator``, device tensors) of a
+        column table in HBM over its geometries.  ``values [G * S, K]`` float64 with unit column stride - the gathered
+        ``metric_full`` of an evaluated ensemble, or a strided view of its evaluation rows (``eval[:, 0, :]``: nothing is
+        copied, the row stride is passed on); ``status [G * S]`` uint8, the low byte of ``okx_info.flags`` (``info_raw[:, 32]``
+        is fine), or None: every state accepted; ``factors [G, P]`` per-geometry factors or None; ``shift [S, K]`` the common
+        shift of the sums (None: the table's own geometry 0, undefined entries 0 - partial accumulators that are merged
+        later need ONE shift, pass it); ``geometry_offset`` the global index of the table's geometry 0.  ``out``: an
+        accumulator to write (``accumulate=False``) or merge into (``True``); with it and a table shape seen before, the call
+        allocates nothing and is legal inside a stream capture.  ``factor_moments=False`` skips the factor moments (a caller
+        that merges chunks of fixed factors takes them once).
+        """
+        from .ensemble_stats import ENS_FIELDS, EnsembleAccumulator, factor_moment_count
+
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        p = 0
+        if factors is not None:
+            factors = _as_f64(factors, self.device)
+            if factors.dim() != 2 or factors.shape[0] != g:
+                raise ValueError("factors must be [G, P]")
+            factors = factors.contiguous()
+            p = factors.shape[1]
+        if out is None:
+            shift = self._ensemble_shift(shift, values, g, s, k)
+            out = EnsembleAccumulator(torch.empty((s, k, ENS_FIELDS + p), dtype=torch.float64, device=self.device), shift,
+                                      torch.empty(factor_moment_count(p), dtype=torch.float64, device=self.device) if p and factor_moments else None)
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+        elif shift is not None:
+            raise ValueError("out= carries its own shift")
+        if tuple(out.acc.shape) != (s, k, ENS_FIELDS + p) or not out.acc.is_contiguous() or not out.shift.is_contiguous() \
+                or out.acc.device != self.device or out.shift.device != self.device:
+            raise ValueError(f"out must hold contiguous device tables [S, K, {ENS_FIELDS + p}] and [S, K]")
+        factor_acc = out.factor_acc if factor_moments and p else None
+        scratch = self._ensemble_scratch("reduce", int(self.lib.okx_ensemble_scratch_bytes(g, s, k, p)))
+        self._ensemble_call("okx_ensemble_reduce", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(factors), p, _ptr(out.shift),
+                            int(geometry_offset), 1 if accumulate else 0, _ptr(out.acc), _ptr(factor_acc), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_select: exact order statistics and spec-limit counts (ensemble_stats.EnsembleQuantiles) ----
+
+    def select_prepare(self, steps: int, n_columns: int, probs, limits=None, *, rounds: bool = False) -> "EnsembleSelection":
+        """
+        The tables of a select over ``[steps, n_columns]`` entries: ``probs`` (``[Q]`` in [0, 1]) and ``limits`` (``[S, K, 2]``,
+        ``[K, 2]`` or ``[2]`` = (lo, hi), -inf / +inf leaves a side open; None: no limit counts) are validated by
+        ``okx_ensemble_select_check`` on the host and uploaded ONCE; outputs are allocated.  ``rounds=True`` adds the state and
+        the histogram the round-level calls (``select_begin`` / ``select_count`` / ``select_descend`` / ``select_finish``) work on.
+        """
+        from .ensemble_stats import SELECT_MAX_PROBS, broadcast_limits
+
+        s, k = int(steps), int(n_columns)
+        p = np.ascontiguousarray(np.atleast_1d(_host_f64(probs)).reshape(-1))
+        lim = None if limits is None else broadcast_limits(limits, s, k)
+        rc = self.lib.okx_ensemble_select_check(p.ctypes.data_as(C.c_void_p), min(p.size, SELECT_MAX_PROBS + 1),
+                                                None if lim is None else lim.ctypes.data_as(C.c_void_p), 0 if lim is None else s * k)
+        _lib.check(rc, "okx_ensemble_select")
+        q, dev = p.size, self.device
+        run = EnsembleSelection(p, torch.as_tensor(p, device=dev), None if lim is None else torch.as_tensor(lim, device=dev),
+                                torch.empty((s, k, q, 2), dtype=torch.float64, device=dev), torch.empty((s, k), dtype=torch.int64, device=dev),
+                                None if lim is None else torch.empty((s, k, 2), dtype=torch.int64, device=dev))
+        if rounds:
+            run.state = torch.empty(max(1, int(self.lib.okx_ensemble_select_state_bytes(s, k, q))), dtype=torch.uint8, device=dev)
+            run.hist = torch.empty((s, k, 2 * q, int(self.lib.okx_ensemble_select_hist_len(s, k, q)) // max(1, s * k * 2 * q)),
+                                   dtype=torch.int64, device=dev)
+        return run
+
+    @property
+    def select_rounds(self) -> int:
+        return int(self.lib.okx_ensemble_select_rounds())
+
+    def select_begin(self, run: "EnsembleSelection") -> None:
+        """State and histogram of ``run`` zeroed on the stream (``okx_ensemble_select_begin``)."""
+        s, k, q = run.shape
+        self._ensemble_call("okx_ensemble_select_begin", s, k, q, _ptr(run.state), _ptr(run.hist))
+
+    def select_count(self, run: "EnsembleSelection", rnd: int, values, *, steps_per_geometry: int, status=None) -> None:
+        """Round ``rnd`` over one chunk of geometries ``values [G' * S, K]``, added into ``run.hist`` (``okx_ensemble_select_count``)."""
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if (s, k) != run.shape[:2]:
+            raise ValueError(f"the select was prepared for [S, K] = {list(run.shape[:2])}")
+        self._ensemble_call("okx_ensemble_select_count", int(rnd), g, s, k, _ptr(values), ld, _ptr(status), stride, run.shape[2],
+                            _ptr(run.limits), _ptr(run.state), _ptr(run.hist))
+
+    def select_descend(self, run: "EnsembleSelection", rnd: int) -> None:
+        """``run.hist`` consumed and re-zeroed, the state advanced by one round (``okx_ensemble_select_descend``)."""
+        s, k, q = run.shape
+        self._ensemble_call("okx_ensemble_select_descend", int(rnd), s, k, _ptr(run.probs), q, _ptr(run.state), _ptr(run.hist))
+
+    def select_finish(self, run: "EnsembleSelection") -> "EnsembleSelection":
+        """``run.order`` / ``count`` / ``outside`` written from the state (``okx_ensemble_select_finish``)."""
+        s, k, q = run.shape
+        self._ensemble_call("okx_ensemble_select_finish", s, k, q, _ptr(run.state), _ptr(run.order), _ptr(run.count), _ptr(run.outside))
+        return run
+
+    def select_ensemble(self, values, *, steps_per_geometry: int, probs=None, status=None, limits=None, out=None):
+        """
+        ``okx_ensemble_select``: per (step, column) entry of a column table in HBM, over the geometries whose state counts
+        (the rule of ``reduce_ensemble``), the two order statistics around every probability of ``probs`` - exact bits of
+        table values - the count, and with ``limits`` the counts of values strictly below ``lo`` / above ``hi``.  ``values``
+        and ``status`` as ``reduce_ensemble`` takes them (unit column stride; strided rows and a strided status byte are
+        passed on, nothing is copied).  Returns an ``EnsembleSelection`` of device tensors (``order [S, K, Q, 2]``, ``count
+        [S, K]``, ``outside [S, K, 2]`` or None); ``.finalize()`` copies it to the host and interpolates
+        (``ensemble_stats.EnsembleQuantiles``).  ``out``: the selection of an earlier call or of ``select_prepare`` - it carries
+        its own probabilities and limits; with it and a table shape seen before, the call uploads and allocates nothing and
+        is legal inside a stream capture.  Bit-identical from run to run: integer counting only.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if out is None:
+            if probs is None:
+                raise ValueError("probs is needed (or out=, which carries its own)")
+            out = self.select_prepare(s, k, probs, limits)
+        elif probs is not None or limits is not None:
+            raise ValueError("out= carries its own probabilities and limits")
+        if out.shape[:2] != (s, k) or out.order.device != self.device:
+            raise ValueError(f"out was prepared for [S, K] = {list(out.shape[:2])} on {out.order.device}")
+        q = out.shape[2]
+        scratch = self._ensemble_scratch("select", int(self.lib.okx_ensemble_select_scratch_bytes(s, k, q)))
+        self._ensemble_call("okx_ensemble_select", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.probs), q, _ptr(out.limits),
+                            _ptr(out.order), _ptr(out.count), _ptr(out.outside), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_screen: the joint spec-limit verdict of every geometry (ensemble_stats.EnsembleScreen) ----
+
+    def screen_prepare(self, steps: int, n_columns: int, limits, scale=None, n_geometries: int = 0, capacity: int | None = None) -> "EnsembleScreening":
+        """
+        The tables of a screen over ``[steps, n_columns]`` entries and ``n_geometries`` geometries: ``limits`` (``[S, K, 2]``,
+        ``[K, 2]`` or ``[2]`` = (lo, hi), -inf / +inf leaves a side open) and ``scale`` (``[S, K]``, ``[K]`` or a scalar, finite
+        and > 0; None: 1) are validated by ``okx_ensemble_screen_check`` on the host and uploaded ONCE; the outputs are
+        allocated, the survivor list with ``capacity`` slots (None: one per geometry).
+        """
+        from .ensemble_stats import broadcast_limits, broadcast_scale
+
+        s, k, g = int(steps), int(n_columns), int(n_geometries)
+        if limits is None:
+            raise ValueError("limits are needed: [S, K, 2], [K, 2] or [2] (lo, hi)")
+        lim = broadcast_limits(limits, s, k)
+        sc = None if scale is None else broadcast_scale(scale, s, k)
+        rc = self.lib.okx_ensemble_screen_check(lim.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p), s * k)
+        _lib.check(rc, "okx_ensemble_screen")
+        if g < 0 or (capacity is not None and int(capacity) < 0):
+            raise ValueError("negative geometry count or capacity")
+        dev = self.device
+        cap = g if capacity is None else int(capacity)
+        return EnsembleScreening(torch.as_tensor(lim, device=dev), None if sc is None else torch.as_tensor(sc, device=dev),
+                                 torch.empty(g, dtype=torch.uint8, device=dev), torch.empty(g, dtype=torch.float64, device=dev),
+                                 torch.empty(g, dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int64, device=dev),
+                                 torch.zeros((s, k, 2), dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev),
+                                 torch.zeros(1, dtype=torch.int64, device=dev))
+
+    def screen_ensemble(self, values, *, steps_per_geometry: int, limits=None, status=None, scale=None, geometry_offset: int = 0,
+                        capacity: int | None = None, out=None, accumulate: bool = False, first_row: int | None = None):
+        """
+        ``okx_ensemble_screen``: per GEOMETRY of a column table in HBM, whether it meets every limit at every step
+        (``flags``), its worst margin in units of ``scale`` and the entry that holds it; per ensemble the tally, the blame
+        counts and the ascending list of the geometries that pass.  ``values`` and ``status`` as ``select_ensemble`` takes them
+        (unit column stride; strided rows and a strided status byte are passed on, nothing is copied).  Returns an
+        ``EnsembleScreening`` of device tensors - ``margin`` and ``pass_index`` stay in HBM for whatever follows -;
+        ``.finalize()`` copies it to the host (``ensemble_stats.EnsembleScreen``).  ``out``: the screening of an earlier call or
+        of ``screen_prepare`` - it carries its own limits and scale; with it and a table shape seen before, the call uploads
+        and allocates nothing and is legal inside a stream capture.  ``accumulate=True`` (with ``out``) adds this chunk to
+        what ``out`` holds: tally and blame add and the survivors are appended.  The call's per-geometry verdicts are written
+        from row ``first_row`` of ``out``'s tables on (None: ``geometry_offset`` with ``out=``, else 0).  Bit-identical from
+        run to run.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        row = int(first_row) if first_row is not None else (0 if out is None else int(geometry_offset))
+        if out is None:
+            if limits is None:
+                raise ValueError("limits are needed (or out=, which carries its own)")
+            if accumulate:
+                raise ValueError("accumulate=True adds to out=")
+            out = self.screen_prepare(s, k, limits, scale, row + g, capacity)
+        elif limits is not None or scale is not None or capacity is not None:
+            raise ValueError("out= carries its own limits, scale and capacity")
+        if out.shape != (s, k) or out.blame.device != self.device:
+            raise ValueError(f"out was prepared for [S, K] = {list(out.shape)} on {out.blame.device}")
+        if row < 0 or row + g > out.flags.shape[0]:
+            raise ValueError(f"out holds {out.flags.shape[0]} geometries: rows [{row}, {row + g}) do not fit")
+        scratch = self._ensemble_scratch("screen", int(self.lib.okx_ensemble_screen_scratch_bytes(g, s, k)))
+        self._ensemble_call("okx_ensemble_screen", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.limits), _ptr(out.scale),
+                            int(geometry_offset), 1 if accumulate else 0, _ptr(out.flags[row:]), _ptr(out.margin[row:]), _ptr(out.entry[row:]),
+                            _ptr(out.tally), _ptr(out.blame), _ptr(out.pass_index), out.pass_index.shape[0], _ptr(out.pass_count),
+                            _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_covariance: Gram matrix and sums of selected entries over the complete cases (ensemble_stats) ----
+
+    def covariance_ensemble(self, values, *, steps_per_geometry: int, status=None, entries=None, shift=None, out=None, accumulate: bool = False):
+        """
+        ``okx_ensemble_covariance``: the covariance accumulator (``ensemble_stats.CovarianceAccumulator``, device tensors:
+        ``gram [N, N]``, ``sum [N]``, ``counts [2]`` = used, dropped, ``used [G]`` uint8) of ``entries`` - N distinct indices
+        ``s K + k`` in the order wanted for rows and columns, None: all ``S K`` - of a column table in HBM over its COMPLETE
+        geometries, those whose every selected entry counts.  ``values`` and ``status`` as ``reduce_ensemble`` takes them (unit
+        column stride; strided rows and a strided status byte are passed on, nothing is copied); ``shift [S, K]`` the common
+        shift (None: the table's own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift, pass it
+        or pass ``out=``).  ``out``: the accumulator of an earlier call - it carries its own shift and entries - to write
+        (``accumulate=False``) or add into (``True``); with it and a table shape seen before, the call uploads and allocates
+        nothing and is legal inside a stream capture (``out.used`` is written when it holds a byte per geometry of the call).
+        ``.finalize()`` copies to the host: mean, covariance, std, correlation.  Bit-identical from run to run; different
+        chunkings agree to rounding.
+        """
+        from .ensemble_stats import CovarianceAccumulator, check_covariance_arguments
+
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        dev = self.device
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+            host = None if entries is None else np.ascontiguousarray(check_covariance_arguments(
+                entries.detach().cpu().numpy() if isinstance(entries, torch.Tensor) else entries, s * k))
+            n = s * k if host is None else host.size
+            rc = self.lib.okx_ensemble_covariance_check(None if host is None else host.ctypes.data_as(C.c_void_p), min(n, 1 << 30), s * k)
+            _lib.check(rc, "okx_ensemble_covariance")
+            shift = self._ensemble_shift(shift, values, g, s, k)
+            index = torch.arange(n, dtype=torch.int32, device=dev) if host is None else torch.as_tensor(host, device=dev)
+            out = CovarianceAccumulator(torch.empty((n, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                                        torch.empty(2, dtype=torch.int64, device=dev), shift, index, torch.empty(g, dtype=torch.uint8, device=dev),
+                                        natural=host is None)  # (all entries in natural order: the call passes no entry list)
+        elif shift is not None or entries is not None:
+            raise ValueError("out= carries its own shift and entries")
+        n = int(out.entries.shape[0])
+        tables = (out.gram, out.sum, out.counts, out.shift, out.entries)
+        if tuple(out.shift.shape) != (s, k) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in tables) \
+                or out.entries.dtype != torch.int32 or out.gram.dtype != torch.float64 or out.sum.dtype != torch.float64 or out.counts.dtype != torch.int64:
+            raise ValueError(f"out must hold contiguous device tables gram [N, N], sum [N], counts [2], entries [N] and shift [S, K] = [{s}, {k}]")
+        used = out.used if out.used is not None and out.used.shape[0] >= g and out.used.is_contiguous() and out.used.device == dev else None
+        scratch = self._ensemble_scratch("covariance", int(self.lib.okx_ensemble_covariance_scratch_bytes(g, s, k, n)))
+        index = None if out.natural and n == s * k else _ptr(out.entries)
+        self._ensemble_call("okx_ensemble_covariance", g, s, k, _ptr(values), ld, _ptr(status), stride, index, n, _ptr(out.shift),
+                            1 if accumulate else 0, _ptr(out.gram), _ptr(out.sum), _ptr(out.counts), _ptr(used), _ptr(scratch), scratch.numel())
+        return out

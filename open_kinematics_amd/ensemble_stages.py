@@ -1,0 +1,325 @@
+"""
+The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
+(moments, extremes, sensitivities), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``) and ``Covariance``
+(``covariance=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+
+* the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
+* ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
+  first chunk of a step writes, later chunks accumulate;
+* ``end_step()``: a rank that took in nothing contributes the neutral element (the pass over no geometry), then the stage's
+  collectives run - on every rank, whether or not it holds a geometry; then the result accessors answer.
+
+A stage runs the device pass (``ensemble_device.py``) when the ensemble lives on a GPU and the NumPy stand-in of
+``ensemble_stats.py`` otherwise (the CPU tests): decided once, and never a quiet host pass over device tables.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ensemble_stats as es
+from .dist import all_gather_flat, all_reduce_sum, broadcast_from_rank_zero, shard_range
+
+
+class _Stage:
+    bytes_per_rank = 0
+
+    def __init__(self, owner):
+        self.owner = owner
+        self.on_device = owner.device.type == "cuda"
+        self.taken = False  # something was taken in since begin_step()
+
+    def begin_step(self) -> None:
+        self.taken = False
+
+    def rows(self, a: int, b: int, local) -> None:
+        o = self.owner
+        self.take(a, b, o.metric_local[local], o.info_local[local][:, 32])
+        self.taken = True
+
+    def end_step(self) -> None:
+        if not self.taken:  # a rank without a geometry: the pass over no geometry, the neutral element
+            glo = self.owner.geometry_range[0]
+            self.rows(glo, glo, slice(0, 0))
+        self.exchange()
+
+    def host_tables(self, a: int, b: int, values, status) -> tuple:
+        """``values [G', S, K]`` and ``status [G', S]`` of a chunk as the NumPy stand-ins take them."""
+        steps = self.owner.steps
+        return values.reshape(b - a, steps, values.shape[1]).cpu().numpy(), status.reshape(b - a, steps).cpu().numpy()
+
+
+class _AccumulatorStage(_Stage):
+    """A stage whose partial result is float64 tables that merge: packed, all-gathered, merged in rank order."""
+
+    def allocate_exchange(self, words: int) -> None:
+        o = self.owner
+        self.send = torch.empty(words, dtype=torch.float64, device=o.device) if o.world > 1 else None
+        self.recv = torch.empty((o.world, words), dtype=torch.float64, device=o.device) if o.world > 1 else None
+        self.bytes_per_rank = 8 * words if o.world > 1 else 0
+
+    def merged_over_ranks(self, mine, parts, unpack):
+        """ONE all-gather of ``parts`` (this rank's tables, flat, in order) and the merge of ``unpack(row)`` of every rank's
+        row in rank order: the same bits on every rank.  A world of one keeps ``mine``."""
+        o = self.owner
+        if o.world == 1:
+            return mine
+        at = 0
+        for part in parts:
+            self.send[at : at + part.numel()] = part.reshape(-1)
+            at += part.numel()
+        all_gather_flat(self.send, o.group, out=self.recv)
+        merged = None
+        for r in range(o.world):
+            part = unpack(self.recv[r])
+            merged = part if merged is None else merged.merge(part)
+        return merged
+
+
+class Reduction(_AccumulatorStage):
+    """``reduce=True``: the accumulators of ``ensemble_stats.py`` instead of a gathered table."""
+
+    def __init__(self, owner, hardpoints, targets, relative_targets, factors, shift):
+        super().__init__(owner)
+        o = owner
+        glo, ghi = o.geometry_range
+        device, k = o.device, len(o.metric_index)
+        self.factor_names = None
+        if isinstance(factors, str):
+            if factors != "hardpoints":
+                raise ValueError("factors must be None, 'hardpoints' or a [G, P] table")
+            program = o.dp.program
+            table = torch.as_tensor(hardpoints).detach().cpu().numpy()
+            # (derived points are recomputed from the authored ones by rebind: their coordinates are no factors)
+            from .program import key_name
+
+            authored = np.setdiff1d(np.arange(table.shape[1]), np.asarray(program.dop_out, dtype=np.int64))
+            names = [key_name(program.point_keys[i]).lower() for i in authored]
+            factors, self.factor_names = es.hardpoint_factors(table[:, authored], names)
+        if factors is not None:
+            factors = np.ascontiguousarray(torch.as_tensor(factors).detach().cpu().numpy(), dtype=np.float64).reshape(o.n_geom, -1)
+        p = 0 if factors is None else factors.shape[1]
+        self.n_factors = p
+        self.my_factors = torch.as_tensor(factors[glo:ghi], device=device).contiguous() if p else None
+        # the shift: ONE table for every partial that is ever merged
+        if shift is None:
+            shift = torch.zeros((o.steps, k), dtype=torch.float64, device=device)
+            if o.rank == 0 and o.n_geom > 0:
+                gpos, gparam = o.dp.rebind(torch.as_tensor(hardpoints)[:1])
+                first = o.dp.ensemble_targets(gpos, targets) if relative_targets else targets[: o.steps]
+                res = o.dp.solve_evaluated(first, geom_pos=gpos, geom_row_param=gparam, steps_per_geometry=o.steps,
+                                           output="none", **o.solve_kw)
+                rows = res.eval.reshape(o.steps, -1).to(device)
+                shift = torch.nan_to_num(torch.index_select(rows, 1, o.metric_index), nan=0.0, posinf=0.0, neginf=0.0)
+            if o.world > 1:
+                shift = broadcast_from_rank_zero(shift.contiguous(), o.group)
+        else:
+            shift = torch.as_tensor(es.clean_shift(torch.as_tensor(shift).detach().cpu().numpy()), device=device)
+        shift = shift.reshape(o.steps, k).contiguous()
+        # the unmasked factor moments of this rank's geometries, once: the factors never change (ascending order, as the device sums)
+        factor_acc = None
+        if p:
+            mine = factors[glo:ghi]
+            rows, cols = np.tril_indices(p)
+            moments = np.zeros(es.factor_moment_count(p))
+            if ghi > glo:
+                moments[:p] = np.cumsum(mine, axis=0)[-1]
+                moments[p:-1] = np.cumsum(mine[:, rows] * mine[:, cols], axis=0)[-1]
+            moments[-1] = ghi - glo
+            factor_acc = torch.as_tensor(moments, device=device)
+        self.local = es.EnsembleAccumulator(torch.empty((o.steps, k, es.ENS_FIELDS + p), dtype=torch.float64, device=device),
+                                            shift, factor_acc, self.factor_names)
+        self.merged = self.local
+        self.allocate_exchange(self.local.acc.numel() + (factor_acc.numel() if p else 0))
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, acc = self.owner, self.local
+        glo = o.geometry_range[0]
+        factors = self.my_factors[a - glo : b - glo] if self.n_factors else None
+        if self.on_device:
+            o.dp.reduce_ensemble(values, steps_per_geometry=o.steps, status=status, factors=factors, geometry_offset=a, out=acc,
+                                 accumulate=self.taken, factor_moments=False)
+            return
+        part = es.reduce_host(*self.host_tables(a, b, values, status), None if factors is None else factors.cpu().numpy(), acc.shift.cpu().numpy(), a)
+        part = es.EnsembleAccumulator(torch.as_tensor(part.acc, device=o.device), acc.shift, None)
+        if self.taken:
+            part = es.EnsembleAccumulator(acc.acc, acc.shift, None).merge(part)
+        acc.acc.copy_(part.acc)
+
+    def exchange(self) -> None:
+        mine = self.local
+        n_acc = mine.acc.numel()
+
+        def unpack(row):
+            return es.EnsembleAccumulator(row[:n_acc].reshape(mine.acc.shape), mine.shift, row[n_acc:] if self.n_factors else None, self.factor_names)
+
+        self.merged = self.merged_over_ranks(mine, (mine.acc, mine.factor_acc) if self.n_factors else (mine.acc,), unpack)
+
+
+class Selection(_Stage):
+    """``quantiles=...``: the select rounds over the rank's whole shard at the end of a step, the histograms summed over the ranks."""
+
+    def __init__(self, owner, quantiles, limits):
+        super().__init__(owner)
+        o = owner
+        k = len(o.metric_index)
+        self.probs, self.limits = es.check_select_arguments(quantiles, limits, o.steps, k)
+        self.run = self.result = None
+        self.stepped = False
+        if self.on_device:
+            self.run = o.dp.select_prepare(o.steps, k, self.probs, self.limits, rounds=True)
+            rounds, words = o.dp.select_rounds, self.run.hist.numel()
+        else:
+            rounds, words = es.SELECT_ROUNDS, o.steps * k * 2 * len(self.probs) * es.SELECT_BINS
+        self.bytes_per_rank = rounds * 8 * words if o.world > 1 else 0
+
+    def rows(self, a: int, b: int, local) -> None:
+        pass
+
+    def end_step(self) -> None:
+        """Every round: count this rank's shard, sum the histograms over the ranks (one all-reduce), descend."""
+        o = self.owner
+        glo, ghi = o.geometry_range
+        values, status = o.metric_local, o.info_local[:, 32]
+        if self.on_device:
+            run, dp = self.run, o.dp
+            dp.select_begin(run)
+            for rnd in range(dp.select_rounds):
+                if ghi > glo:  # (a rank without a geometry contributes a zero histogram)
+                    dp.select_count(run, rnd, values, steps_per_geometry=o.steps, status=status)
+                all_reduce_sum(run.hist, o.group)
+                dp.select_descend(run, rnd)
+            dp.select_finish(run)
+            self.result, self.stepped = None, True
+            return
+        v, st = self.host_tables(glo, ghi, values, status)
+        state, hist = es.select_begin(o.steps, values.shape[1], len(self.probs))
+        for rnd in range(es.SELECT_ROUNDS):
+            es.select_count_round(rnd, v, st, state, hist, self.limits)
+            all_reduce_sum(torch.from_numpy(hist), o.group)
+            es.select_descend_round(rnd, state, hist, self.probs)
+        self.result = es.select_finish(state, self.probs, self.limits is not None)
+
+    def quantiles(self):
+        if self.result is None:
+            if not self.stepped:
+                raise RuntimeError("no step() yet")
+            self.result = self.run.finalize()
+        return self.result
+
+
+class Screening(_Stage):
+    """``screen=True``: the joint verdict per geometry, chunk by chunk; ``tally | blame`` summed and the flag bytes gathered."""
+
+    def __init__(self, owner, limits, scale):
+        super().__init__(owner)
+        o = owner
+        glo, ghi = o.geometry_range
+        k = len(o.metric_index)
+        self.limits, self.scale = es.check_screen_arguments(limits, scale, o.steps, k)
+        self.largest_shard = max(hi - lo for lo, hi in (shard_range(o.n_geom, r, o.world) for r in range(o.world)))
+        self.run = self.part = self.result = self.counts = self.flags = None
+        if self.on_device:
+            self.run = o.dp.screen_prepare(o.steps, k, self.limits, self.scale, ghi - glo)
+        self.bytes_per_rank = 8 * (4 + 2 * o.steps * k) + self.largest_shard if o.world > 1 else 0
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o = self.owner
+        if self.on_device:
+            o.dp.screen_ensemble(values, steps_per_geometry=o.steps, status=status, geometry_offset=a, out=self.run,
+                                 accumulate=self.taken, first_row=a - o.geometry_range[0])
+            return
+        part = es.screen_host(*self.host_tables(a, b, values, status), self.limits, self.scale, a)
+        self.part = self.part.merge(part) if self.taken else part
+
+    def exchange(self) -> None:
+        """One integer all-reduce of tally | blame and one all-gather of the flag bytes (padded to the largest shard): the same
+        bits on every rank."""
+        o = self.owner
+        if self.on_device:
+            counts, flags = torch.cat([self.run.tally, self.run.blame.reshape(-1)]), self.run.flags
+        else:
+            counts, flags = torch.from_numpy(np.concatenate([self.part.tally, self.part.blame.reshape(-1)])), torch.from_numpy(self.part.flags)
+        self.result = None
+        if o.world > 1:
+            padded = torch.zeros(self.largest_shard, dtype=torch.uint8, device=flags.device)
+            padded[: flags.shape[0]] = flags
+            all_reduce_sum(counts, o.group)
+            table = all_gather_flat(padded, o.group)
+            spans = [shard_range(o.n_geom, r, o.world) for r in range(o.world)]
+            flags = torch.cat([table[r, : hi - lo] for r, (lo, hi) in enumerate(spans)])
+        self.counts, self.flags = counts, flags
+
+    def screen(self):
+        if self.counts is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            o = self.owner
+            counts, flags = self.counts.cpu().numpy(), self.flags.cpu().numpy()
+            blame = counts[4:].reshape(o.steps, len(o.metric_index), 2).copy()
+            self.result = es.EnsembleScreen(flags, None, None, counts[:4].copy(), blame, np.flatnonzero(flags == 0).astype(np.int64))
+        return self.result
+
+    def screen_local(self) -> dict:
+        if self.on_device:
+            run = self.run
+            return {"flags": run.flags, "margin": run.margin, "entry": run.entry, "pass_index": run.pass_index, "pass_count": run.pass_count}
+        if self.part is None:
+            raise RuntimeError("no step() yet")
+        part = self.part
+        return {"flags": torch.from_numpy(part.flags), "margin": torch.from_numpy(part.margin), "entry": torch.from_numpy(part.entry),
+                "pass_index": torch.from_numpy(part.passed), "pass_count": torch.tensor([part.passed.size], dtype=torch.int64)}
+
+
+class Covariance(_AccumulatorStage):
+    """``covariance=...``: Gram matrix, sums and counts of the selected entries, chunk by chunk, with the reduction's shift."""
+
+    def __init__(self, owner, covariance):
+        super().__init__(owner)
+        o = owner
+        glo, ghi = o.geometry_range
+        k, device = len(o.metric_index), o.device
+        entries = es.check_covariance_arguments(None if covariance is True else
+                                                (covariance.detach().cpu().numpy() if isinstance(covariance, torch.Tensor) else covariance), o.steps * k)
+        n = int(entries.size)
+        self.entries = entries
+        shift = o.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's (itself, no copy)
+        self.local = es.CovarianceAccumulator(torch.zeros((n, n), dtype=torch.float64, device=device), torch.zeros(n, dtype=torch.float64, device=device),
+                                              torch.zeros(2, dtype=torch.int64, device=device), shift, torch.as_tensor(entries, device=device),
+                                              torch.zeros(ghi - glo, dtype=torch.uint8, device=device), natural=covariance is True)
+        self.merged = self.result = None
+        self.allocate_exchange(n * n + n + 2)
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        if self.on_device:
+            view = es.CovarianceAccumulator(mine.gram, mine.sum, mine.counts, mine.shift, mine.entries, mine.used[a - glo :], natural=mine.natural)
+            o.dp.covariance_ensemble(values, steps_per_geometry=o.steps, status=status, out=view, accumulate=self.taken)
+            return
+        part = es.covariance_host(*self.host_tables(a, b, values, status), self.entries, mine.shift.cpu().numpy())
+        if not self.taken:
+            mine.gram.zero_(), mine.sum.zero_(), mine.counts.zero_()
+        mine.gram += torch.from_numpy(part.gram)
+        mine.sum += torch.from_numpy(part.sum)
+        mine.counts += torch.from_numpy(part.counts)
+        mine.used[a - glo : b - glo] = torch.from_numpy(part.used)
+
+    def exchange(self) -> None:
+        """(the counts travel as their int64 bits)"""
+        mine = self.local
+        n = int(mine.entries.shape[0])
+        self.result = None
+
+        def unpack(row):
+            return es.CovarianceAccumulator(row[: n * n].reshape(n, n), row[n * n : n * n + n], row[n * n + n :].view(torch.int64), mine.shift, mine.entries)
+
+        self.merged = self.merged_over_ranks(mine, (mine.gram, mine.sum, mine.counts.view(torch.float64)), unpack)
+
+    def covariance(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result

@@ -6,7 +6,7 @@ factors (hardpoint perturbations).
 Three layers, the same accumulator in each (``include/okx.h``, ``okx_ensemble_reduce``):
 
 * ``reduce_host``: NumPy over ``values [G, S, K]``; the fallback without a GPU and the cross-check of the device pass;
-* ``DeviceProgram.reduce_ensemble`` (``batch.py``): the device pass over a column table in HBM;
+* ``DeviceProgram.reduce_ensemble`` (``ensemble_device.py``): the device pass over a column table in HBM;
 * ``dist.ShardedEnsemble(reduce=True)``: every rank reduces its own shard chunk by chunk and the ranks exchange the
   accumulators alone.
 
@@ -298,6 +298,29 @@ class EnsembleQuantiles:
     yield_: np.ndarray | None = None
 
 
+def _host_f64(table) -> np.ndarray:
+    """A float64 NumPy COPY of an array, a sequence or a torch tensor (host or device)."""
+    return np.array(table.detach().cpu().numpy() if _is_tensor(table) else table, dtype=np.float64)
+
+
+def broadcast_limits(limits, steps: int, n_columns: int) -> np.ndarray:
+    """``limits`` given as ``[S, K, 2]``, ``[K, 2]`` or ``[2]`` = (lo, hi) as a contiguous float64 ``[S, K, 2]`` table of its own."""
+    s, k = int(steps), int(n_columns)
+    lim = _host_f64(limits)
+    if lim.shape[-1:] != (2,) or lim.size not in (2, 2 * k, 2 * s * k):
+        raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
+    return np.array(np.broadcast_to(lim.reshape(s, k, 2) if lim.size == 2 * s * k else lim.reshape(-1, 2), (s, k, 2)), order="C")
+
+
+def broadcast_scale(scale, steps: int, n_columns: int) -> np.ndarray:
+    """``scale`` given as ``[S, K]``, ``[K]`` or a scalar as a contiguous float64 ``[S, K]`` table of its own."""
+    s, k = int(steps), int(n_columns)
+    sc = _host_f64(scale)
+    if sc.size not in (1, k, s * k):
+        raise ValueError("scale must be [S, K], [K] or a scalar")
+    return np.array(np.broadcast_to(sc.reshape(s, k) if sc.size == s * k else sc.reshape(-1), (s, k)), order="C")
+
+
 def check_select_arguments(probs, limits=None, steps: int | None = None, n_columns: int | None = None):
     """``(probs [Q], limits [S, K, 2] or None)`` as float64 arrays, or ValueError in the words of ``okx_ensemble_select_check``."""
     p = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
@@ -308,12 +331,7 @@ def check_select_arguments(probs, limits=None, steps: int | None = None, n_colum
         raise ValueError(f"okx_ensemble_select: probability {int(bad[0])} is {p[bad[0]]:g}, outside [0, 1]")
     if limits is None:
         return p, None
-    lim = np.asarray(limits, dtype=np.float64)
-    if steps is not None:
-        if lim.shape[-1:] != (2,) or lim.size not in (2, n_columns * 2, steps * n_columns * 2):
-            raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
-        lim = np.ascontiguousarray(np.broadcast_to(lim.reshape((-1, 2)) if lim.size != steps * n_columns * 2 else lim.reshape(steps, n_columns, 2),
-                                                   (steps, n_columns, 2)))
+    lim = np.asarray(limits, dtype=np.float64) if steps is None else broadcast_limits(limits, steps, n_columns)
     flat = lim.reshape(-1, 2)
     nan = np.flatnonzero(np.isnan(flat).any(axis=1))
     if nan.size:
@@ -529,18 +547,10 @@ def check_screen_arguments(limits, scale=None, steps: int | None = None, n_colum
     """``(limits [S, K, 2], scale [S, K] or None)`` as float64 arrays, or ValueError in the words of ``okx_ensemble_screen_check``."""
     if limits is None:
         raise ValueError("okx_ensemble_screen: null limits")
-    lim = np.asarray(limits, dtype=np.float64)
-    sc = None if scale is None else np.asarray(scale, dtype=np.float64)
-    if steps is not None:
-        if lim.shape[-1:] != (2,) or lim.size not in (2, n_columns * 2, steps * n_columns * 2):
-            raise ValueError("limits must be [S, K, 2], [K, 2] or [2] (lo, hi)")
-        lim = np.ascontiguousarray(np.broadcast_to(lim.reshape((-1, 2)) if lim.size != steps * n_columns * 2 else lim.reshape(steps, n_columns, 2),
-                                                   (steps, n_columns, 2)))
-        if sc is not None:
-            if sc.size not in (1, n_columns, steps * n_columns):
-                raise ValueError("scale must be [S, K], [K] or a scalar")
-            sc = np.ascontiguousarray(np.broadcast_to(sc.reshape(steps, n_columns) if sc.size == steps * n_columns else sc.reshape(-1),
-                                                      (steps, n_columns)))
+    lim = np.asarray(limits, dtype=np.float64) if steps is None else broadcast_limits(limits, steps, n_columns)
+    sc = None
+    if scale is not None:
+        sc = np.asarray(scale, dtype=np.float64) if steps is None else broadcast_scale(scale, steps, n_columns)
     flat = lim.reshape(-1, 2)
     nan = np.flatnonzero(np.isnan(flat).any(axis=1))
     if nan.size:
@@ -652,9 +662,9 @@ class CovarianceAccumulator:
     them.  ``used [G]`` uint8 (or None) is the per-geometry byte of the LAST call that filled it.
     """
 
-    def __init__(self, gram, sum, counts, shift, entries, used=None):  # noqa: A002
+    def __init__(self, gram, sum, counts, shift, entries, used=None, *, natural: bool = False):  # noqa: A002
         self.gram, self.sum, self.counts, self.shift, self.entries, self.used = gram, sum, counts, shift, entries, used
-        self.natural = False  # (set by DeviceProgram.covariance_ensemble: all entries in natural order, no entry list is passed)
+        self.natural = bool(natural)  # (all entries in natural order: the device pass is given no entry list)
         n = int(entries.shape[0])
         if tuple(gram.shape) != (n, n) or tuple(sum.shape) != (n,) or tuple(counts.shape) != (2,) or shift.ndim != 2:
             raise ValueError("gram must be [N, N], sum [N], counts [2], shift [S, K] and entries [N]")
@@ -732,7 +742,7 @@ def covariance_host(values, status=None, entries=None, shift=None) -> Covariance
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
-           "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "SELECT_BITS", "SELECT_BINS",
+           "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "broadcast_limits", "broadcast_scale", "SELECT_BITS", "SELECT_BINS",
            "SELECT_ROUNDS", "SELECT_MAX_PROBS", "EnsembleScreen", "screen_host", "check_screen_arguments", "SCREEN_OUTSIDE",
            "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED", "EnsembleCovariance", "CovarianceAccumulator",
            "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES"]

@@ -2,7 +2,7 @@
 GPU: okx_ensemble_reduce (DeviceProgram.reduce_ensemble) and ShardedEnsemble(reduce=True) - against the statistics the
 fixture generator took from the REFERENCE's metrics (tests/golden/ensemble_stats_dw.npz), against the NumPy accumulator
 on the copied tables, at full size (BASELINE config 5), in chunks, over two ranks rehearsed on one GPU, inside a captured
-graph and on strided views of evaluation rows.  The bounds are those derived in tests/test_ensemble_stats.py.
+graph, on strided views of evaluation rows, and with all four stages of the sharded ensemble switched on together.  The bounds are those derived in tests/test_ensemble_stats.py.
 """
 
 import json
@@ -147,6 +147,63 @@ def test_reference_states_to_statistics():
     assert np.allclose(got.numpy().factor_acc, want.factor_acc, rtol=0, atol=2 * (g + 1) * U * np.abs(want.factor_acc).max())
     full = pipe.stats()
     assert np.all(full.count == g) and np.all(full.r2 > 0.999) and full.sensitivity.shape == (s, k, 30)
+
+
+def test_all_four_stages_in_one_ensemble():
+    """Reduction with hardpoint factors, quantiles with limits, the joint screen and the covariance of a subset switched on in ONE
+    ensemble (a world of one, five geometries in chunks of 3 + 2: the second chunk accumulates onto the first): every answer equals,
+    bit for bit, that of an ensemble with that stage alone, and a second step() repeats the first - the passes' scratch buffers are
+    reused and every stage starts from nothing.  One authored point is perturbed (the fixture's own perturbations of it): five
+    geometries carry three slopes and an intercept, no more."""
+    import open_kinematics_amd.dist as okd
+    from test_ensemble_stages import _tables, same_bits
+
+    fx = load_fixture()
+    dp, program = _fixture_program(fx)
+    g, (s, k) = 5, fx["table"].shape[1:]
+    cols = _fixture_columns(program, fx)
+    point = int(np.setdiff1d(np.arange(program.n_points), np.asarray(program.dop_out, dtype=np.int64))[0])
+    table = np.repeat(fx["hardpoints"][:1], g, axis=0)
+    table[:, point] = fx["hardpoints"][:g, point]
+    hard = torch.as_tensor(table, device="cuda:0")
+    rel = np.stack([np.zeros(s), fx["bump"]], axis=1)
+    kw = dict(chunks=2, metric_columns=cols, reduce=True, factors="hardpoints")
+    plain = okd.ShardedEnsemble(dp, hard, rel, s, **kw)
+    plain.step()
+    torch.cuda.synchronize()
+    assert plain.pieces == [[(0, 3)], [(3, 5)]] and plain.n_factors == 3
+    # limits inside the spread of what the five geometries give, entry by entry: values on both sides of them
+    values = plain.metric_local.cpu().numpy().reshape(g, s, k)
+    values = np.where(np.isfinite(values), values, np.nan)
+    with np.errstate(all="ignore"):
+        limits = np.stack([np.nanquantile(values, 0.1, axis=0), np.nanquantile(values, 0.9, axis=0)], axis=2)
+        scale = np.nan_to_num(np.nanstd(values, axis=0)) + 1.0
+    limits = np.where(np.isnan(limits), np.array([-np.inf, np.inf]), limits)
+    entries = [13, 2, 7, 8, 0, k + 3, (s - 1) * k + 14]
+    probs = (0.1, 0.5, 0.9)
+    arguments = {"stats": {}, "quantiles": dict(quantiles=probs, limits=limits), "screen": dict(limits=limits, screen=True, screen_scale=scale),
+                 "covariance": dict(covariance=entries)}
+    together = okd.ShardedEnsemble(dp, hard, rel, s, **kw, quantiles=probs, limits=limits, screen=True, screen_scale=scale, covariance=entries)
+    alone = {name: plain if name == "stats" else okd.ShardedEnsemble(dp, hard, rel, s, **kw, **arguments[name]) for name in arguments}
+    for pipe in alone.values():
+        pipe.step()
+    answers = []
+    for _ in range(2):
+        merged = together.step()
+        torch.cuda.synchronize()
+        assert merged is together.accumulator
+        answers.append({name: _tables(getattr(together, name)()) for name in arguments})
+    for name, pipe in alone.items():
+        assert same_bits(answers[0][name], _tables(getattr(pipe, name)())), name
+        assert same_bits(answers[1][name], answers[0][name]), name  # the second step: the same bits
+    for sent in ("exchange_bytes_per_rank", "select_exchange_bytes_per_rank", "screen_exchange_bytes_per_rank", "covariance_exchange_bytes_per_rank"):
+        assert getattr(together, sent) == 0 and all(getattr(pipe, sent) == 0 for pipe in alone.values())
+    # the inputs are worth the test: every state counts, verdicts on both sides, complete geometries
+    stats, screen, cov = answers[0]["stats"], answers[0]["screen"], answers[0]["covariance"]
+    print("tally:", screen["tally"], "covariance count:", cov["count"])
+    assert np.all(stats["count"][np.isfinite(limits[..., 0])] == g) and np.all(np.isfinite(stats["sensitivity"][stats["count"] == g]))
+    assert screen["tally"][0] == g and screen["tally"][2] > 0 and screen["blame"].sum() == screen["tally"][2]
+    assert answers[0]["quantiles"]["below"].sum() > 0 and answers[0]["quantiles"]["above"].sum() > 0 and cov["count"] + cov["dropped"] == g
 
 
 def _c5(n_geom=4096, steps=256):
