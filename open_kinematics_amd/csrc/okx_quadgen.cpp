@@ -24,6 +24,7 @@
 //
 // Same objective, same residual/Jacobian definitions and same LM policy as okx_solve_kernel
 // (DESIGN.md §4); only the parallel decomposition differs.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -465,6 +466,66 @@ class Gen : public GenBase {
   }
   std::map<int, std::string> pin_cross_;  // leader row -> (p - line point) x line dir
 
+  // ---- batched norm chains ----
+  // A distance row's sum of squares, `+ EPS_SQ`, fast_sqrt_rsqrt and `- EPS` are quad-uniform: serially, all four lanes
+  // of a quad run the same 16-instruction chain for one row.  Batched, up to four such rows share ONE chain, lane k
+  // working on row k: a transposed quad sum (qsum_t*: the association of qsum, so the same bits) leaves row k's sum in
+  // lane k, the chain runs once, and each row fetches its reciprocal root and `root - EPS` with a broadcast where the
+  // row is.  Every IEEE operation per row is the serial text's, on the same inputs.  OKX_DEV=quad_serial_chains: the
+  // serial text.
+  bool batch_chains = !dev_switch("quad_serial_chains");
+  bool batched_any = false;  // the text uses qsum_t* / QB3 (the module then defines them)
+  struct ChainPre { std::string d, v1, v2, x, rt, iv, re; int lane; };  // (d: what is squared; v1, v2, x, rt: angle rows)
+  static bool chain_row(int type) {
+    return type == OKX_ROW_DISTANCE || type == OKX_ROW_SPHERICAL || type == OKX_ROW_ANGLE || type == OKX_ROW_THREE_POINT_ANGLE;
+  }
+  std::map<int, ChainPre> chain_pre_;  // row -> its difference vector and the batch's chain results, lane of the row
+  // The batches in emission order: first row of a batch -> its rows.  A last batch of one row stays serial.
+  std::map<int, std::vector<int>> chain_batches() const {
+    std::map<int, std::vector<int>> res;
+    if (!batch_chains) return res;
+    std::vector<int> rows;
+    for (int i = 0; i < P.m; ++i)
+      if (chain_row(P.row_type[i])) rows.push_back(i);
+    for (size_t k = 0; k + 1 < rows.size(); k += 4)
+      res[rows[k]] = std::vector<int>(rows.begin() + k, rows.begin() + std::min(k + 4, rows.size()));
+    return res;
+  }
+  void emit_chain_batch(const std::vector<int>& rows) {
+    const int n = (int)rows.size();
+    std::string sq;
+    for (int k = 0; k < n; ++k) {
+      const int* pts = P.row_pts[rows[k]];
+      ChainPre& cp = chain_pre_[rows[k]];
+      cp.lane = k;
+      const int type = P.row_type[rows[k]];
+      if (type == OKX_ROW_DISTANCE || type == OKX_ROW_SPHERICAL) {
+        cp.d = vsub(pn(pts[1]), pn(pts[0]));
+      } else {  // the angle rows: |v1 x v2|^2
+        if (type == OKX_ROW_ANGLE) {
+          cp.v1 = vsub(pn(pts[1]), pn(pts[0]));
+          cp.v2 = vsub(pn(pts[3]), pn(pts[2]));
+        } else {
+          cp.v1 = vsub(pn(pts[0]), pn(pts[1]));
+          cp.v2 = vsub(pn(pts[2]), pn(pts[1]));
+        }
+        cp.d = cross(cp.v1, cp.v2);
+      }
+      sq += cp.d + " * " + cp.d + ", ";
+    }
+    std::string s = tmp("cs"), x = tmp("cx"), root = tmp("rt"), inv = tmp("iv"), re = tmp("re");
+    f("    // norm chains of rows %d..%d, row k in lane k", rows.front(), rows.back());
+    f("    const double %s = qsum_t%d(%sc);", s.c_str(), n, sq.c_str());
+    f("    const double %s = %s + EPS_SQ;", x.c_str(), s.c_str());
+    f("    double %s, %s; fast_sqrt_rsqrt(%s, &%s, &%s);", root.c_str(), inv.c_str(), x.c_str(), root.c_str(), inv.c_str());
+    f("    const double %s = %s - EPS;", re.c_str(), root.c_str());
+    for (int k = 0; k < n; ++k) {
+      ChainPre& cp = chain_pre_[rows[k]];
+      cp.x = x, cp.rt = root, cp.iv = inv, cp.re = re;
+    }
+    batched_any = true;
+  }
+
   bool row(int i, RowOut* ro) {
     const int type = P.row_type[i];
     const int* pts = P.row_pts[i];
@@ -475,6 +536,20 @@ class Gen : public GenBase {
     switch (type) {
       case OKX_ROW_DISTANCE:
       case OKX_ROW_SPHERICAL: {  // constraints.py:125-134,162-170; jacobians.py:35-51
+        auto cp = chain_pre_.find(i);
+        if (cp != chain_pre_.end()) {  // the chain ran with its batch: fetch this row's results from its lane
+          const ChainPre& c = cp->second;
+          std::string inv = tmp("iv"), re = tmp("re"), g = tmp("g");
+          f("    const double %s = QB%d(%s), %s = QB%d(%s);", inv.c_str(), c.lane, c.iv.c_str(), re.c_str(), c.lane, c.re.c_str());
+          f("    const double %s = %s * %s;", g.c_str(), c.d.c_str(), inv.c_str());
+          if (type == OKX_ROW_DISTANCE)
+            f("    const double %s = %s - %s;", r.c_str(), re.c_str(), rp(i, 0).c_str());
+          else
+            f("    const double %s = %s;", r.c_str(), re.c_str());
+          ro->partial.push_back({pts[0], {g, -1}});
+          ro->partial.push_back({pts[1], {g, 1}});
+          return true;
+        }
         std::string d = vsub(pn(pts[1]), pn(pts[0]));
         std::string s = dot(d, d);
         std::string root = tmp("rt"), inv = tmp("iv"), g = tmp("g");
@@ -491,7 +566,17 @@ class Gen : public GenBase {
       }
       case OKX_ROW_ANGLE:
       case OKX_ROW_THREE_POINT_ANGLE: {  // constraints.py:223-243,287-308; jacobians.py:55-188
-        std::string v1, v2;
+        std::string v1, v2, cv, dt;
+        std::string s, is, t15;
+        auto cp = chain_pre_.find(i);
+        if (cp != chain_pre_.end()) {  // EPS_SQ + |v1 x v2|^2 and its roots came with the batch: fetch them from the row's lane
+          const ChainPre& c = cp->second;
+          v1 = c.v1, v2 = c.v2, cv = c.d;
+          dt = dot(v1, v2);
+          s = tmp("s"), is = tmp("is"), t15 = tmp("t");
+          f("    const double %s = QB%d(%s), %s = QB%d(%s), %s = QB%d(%s);", t15.c_str(), c.lane, c.x.c_str(), s.c_str(), c.lane,
+            c.rt.c_str(), is.c_str(), c.lane, c.iv.c_str());
+        } else {
         if (type == OKX_ROW_ANGLE) {
           v1 = vsub(pn(pts[1]), pn(pts[0]));
           v2 = vsub(pn(pts[3]), pn(pts[2]));
@@ -499,13 +584,14 @@ class Gen : public GenBase {
           v1 = vsub(pn(pts[0]), pn(pts[1]));
           v2 = vsub(pn(pts[2]), pn(pts[1]));
         }
-        std::string cv = cross(v1, v2);
+        cv = cross(v1, v2);
         std::string c2 = dot(cv, cv);
-        std::string dt = dot(v1, v2);
-        std::string s = tmp("s"), is = tmp("is"), t15 = tmp("t");
+        dt = dot(v1, v2);
+        s = tmp("s"), is = tmp("is"), t15 = tmp("t");
         f("    const double %s = EPS_SQ + %s;", t15.c_str(), c2.c_str());
         f("    double %s, %s; fast_sqrt_rsqrt(%s, &%s, &%s);", s.c_str(), is.c_str(), t15.c_str(), s.c_str(),
           is.c_str());
+        }
         std::string inv = tmp("iv"), ka = tmp("ka"), kb = tmp("kb");
         f("    const double %s = fast_rcp(%s + %s * %s);", inv.c_str(), t15.c_str(), dt.c_str(), dt.c_str());
         f("    const double %s = %s * %s * %s, %s = %s * %s;", ka.c_str(), dt.c_str(), inv.c_str(), is.c_str(),
@@ -701,8 +787,10 @@ class Gen : public GenBase {
   // land within tolerance.  Row code is shared with emit_rows; the unused partials fold away.
   bool emit_rows_residual_only() {
     f("    double ss = 0.0, mres_new = 0.0;");
+    const std::map<int, std::vector<int>> batches = chain_batches();
     for (int i = 0; i < P.m; ++i) {
       RowOut ro;
+      if (batches.count(i)) emit_chain_batch(batches.at(i));
       if (!row(i, &ro)) return false;
       f("    ss = fma(%s, %s, ss);", ro.r.c_str(), ro.r.c_str());
       if (!ro.absres.empty()) f("    mres_new = fmax(mres_new, %s);", ro.absres.c_str());
@@ -738,9 +826,11 @@ class Gen : public GenBase {
     }
     if (!jtv) f("    double ss = 0.0, mres_new = 0.0;");
     std::set<std::string> declared;
+    const std::map<int, std::vector<int>> batches = chain_batches();
     for (int i = 0; i < P.m; ++i) {
       RowOut ro;
       mark(1);
+      if (batches.count(i)) emit_chain_batch(batches.at(i));
       if (!row(i, &ro)) return false;
       if (!jtv) {
       f("    ss = fma(%s, %s, ss);", ro.r.c_str(), ro.r.c_str());
@@ -1555,6 +1645,32 @@ class QuadModule {
       g.f("#define PSUM(v) qsum(v)");
       g.f("#define PMAX(v) qmax(v)");
       g.f("#define PJOIN_SUM(v) (v)");
+    }
+    if (ev.batched_any) {
+      g.f("// Transposed quad sums (batched norm chains): lane k of the quad gets the quad sum of s<k>, in qsum's association");
+      g.f("// (s[k] + s[k^1]) + (s[k^2] + s[k^3]) - bit for bit what qsum(s<k>) gives.  Round one exchanges with lane ^ 1 (even");
+      g.f("// lanes keep s0 / s2, odd lanes s1 / s3), round two with lane ^ 2.  For sums of squares only (no signed zeros).");
+      g.f("#define QB3(v) qperm<0xFF>(v)");
+      g.f("DEV double qsum_t2(double s0, double s1, int c) {");
+      g.f("#pragma clang fp contract(off)");
+      g.f("  const bool odd = (c & 1) != 0;");
+      g.f("  const double a = (odd ? s1 : s0) + qperm<0xB1>(odd ? s0 : s1);");
+      g.f("  return a + qperm<0x4E>(a);");
+      g.f("}");
+      g.f("DEV double qsum_t3(double s0, double s1, double s2, int c) {");
+      g.f("#pragma clang fp contract(off)");
+      g.f("  const bool odd = (c & 1) != 0, hi = (c & 2) != 0;");
+      g.f("  const double a = (odd ? s1 : s0) + qperm<0xB1>(odd ? s0 : s1);");
+      g.f("  const double b = s2 + qperm<0xB1>(s2);");
+      g.f("  return (hi ? b : a) + qperm<0x4E>(hi ? a : b);");
+      g.f("}");
+      g.f("DEV double qsum_t4(double s0, double s1, double s2, double s3, int c) {");
+      g.f("#pragma clang fp contract(off)");
+      g.f("  const bool odd = (c & 1) != 0, hi = (c & 2) != 0;");
+      g.f("  const double a = (odd ? s1 : s0) + qperm<0xB1>(odd ? s0 : s1);");
+      g.f("  const double b = (odd ? s3 : s2) + qperm<0xB1>(odd ? s2 : s3);");
+      g.f("  return (hi ? b : a) + qperm<0x4E>(hi ? a : b);");
+      g.f("}");
     }
     g.f("");
   }

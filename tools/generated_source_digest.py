@@ -4,8 +4,10 @@ program fixture of tests/golden, both line-row forms, with OKX_DEV unset and wit
 tests/test_dev_switches.py::GENERATOR_SWITCHES on the fixture named there, ``{case: sha256(text) | "refused: <message>"}``
 as sorted JSON.  A change that only restructures the generators leaves this file identical to the parent commit's; the
 generated text is the kernel cache key (okx_jit.cpp), so identical text means identical code objects.  Every OKX_DEV
-setting runs in a fresh child process.
-  python tools/generated_source_digest.py [out.json]      (default: standard output)"""
+setting runs in a fresh child process.  ``--with a,b`` adds the switches a and b to every run without naming them in the case
+keys: the record of a build whose new text sits behind switches (``--with quad_serial_chains``) is then the
+same file as the parent commit's record when those switches restore the parent's text.
+  python tools/generated_source_digest.py [--with switch,...] [out.json]      (default: standard output)"""
 import ctypes as C
 import glob
 import hashlib
@@ -59,25 +61,28 @@ def digest(fixture, mode, entry):
     return hashlib.sha256(buf.value).hexdigest()
 
 
-def child(cases):
-    """The digests of `cases` under this process's OKX_DEV."""
-    tag = os.environ.get("OKX_DEV", "")
+def child(cases, tag):
+    """The digests of `cases` under this process's OKX_DEV, recorded under the switch `tag`."""
     return {f"{fixture}|{mode}|{entry}|{tag}": digest(fixture, mode, entry) for fixture, mode, entry in cases}
 
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        json.dump(child(json.loads(sys.argv[2])), sys.stdout)
+        json.dump(child(json.loads(sys.argv[2]), sys.argv[3]), sys.stdout)
         return
+    always = ""
+    if len(sys.argv) > 2 and sys.argv[1] == "--with":
+        always = sys.argv[2]
+        del sys.argv[1:3]
     fixtures = program_fixtures()
     runs = [("", [(f, m, e) for f in fixtures for m in MODES for e in ENTRIES])]
     runs += [(switch, [(fixture, m, entry) for m in MODES]) for switch, fixture, entry in generator_switches()]
     record = {}
     for switch, cases in runs:
         env = {k: v for k, v in os.environ.items() if k != "OKX_DEV"}
-        if switch:
-            env["OKX_DEV"] = switch
-        proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(cases)], env=env,
+        if switch or always:
+            env["OKX_DEV"] = ",".join(item for item in (switch, always) if item)
+        proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(cases), switch], env=env,
                               capture_output=True, text=True)
         if proc.returncode != 0:
             raise SystemExit(f"OKX_DEV={switch!r}: {proc.stderr[-2000:]}")
