@@ -76,6 +76,11 @@ void GenBase::f(const char* fmt, ...) {
   out += '\n';
 }
 
+void GenBase::fill_info(const char* indent) {
+  f("%sokx_info inf; inf.max_residual = mres; inf.cost = Fc; inf.last_step = last_step;", indent);
+  f("%sinf.iterations = iters; inf.nfev = nfev; inf.flags = flags; inf.reserved = 0;", indent);
+}
+
 HeadLayout::HeadLayout(const DevProgram& P, const PairView* pv) {
   const int nf = P.n_free, T = P.n_targets, prog_targets = pv ? pv->n_prog_targets : T;
   cols.push_back({-1, -1, -1});

@@ -43,6 +43,7 @@ class GenBase {
 
   void f(const char* fmt, ...) __attribute__((format(printf, 2, 3)));  // one line of text (printf-style) + '\n'
   std::string tmp(const char* base) { return "_" + std::string(base) + std::to_string(uid++); }
+  void fill_info(const char* indent);  // `okx_info inf` filled from a solve's final scalars: the same text in both modules
 };
 
 // Layout of one geometry's first-step table (okx_quad_head_u/_g write it, the solve bodies and the lane kernels read
@@ -75,8 +76,9 @@ struct HeadLayout {
 };
 
 // Device functions both generated modules define with the same text; each generator splices them into its own prelude
-// where that prelude has always had them.  Everything else of the two preludes differs at least in its comments (the
-// `QArgs` mirror of QuadArgs among it) and stays with its generator: generated text is the kernel cache key.
+// where that prelude has always had them (the argument structs' declarations: okx_quad.hpp, beside their host mirrors).
+// Everything else of the two preludes differs at least in its comments and stays with its generator: generated text is
+// the kernel cache key.
 constexpr const char* kDevFastRcp = R"SRC(DEV double fast_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = fma(-x, r, 1.0);

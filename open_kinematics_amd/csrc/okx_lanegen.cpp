@@ -1050,30 +1050,16 @@ class LGen : public GenBase {
   }
 };
 
-// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the `QArgs` mirror and the
-// comments around them differ between the two modules and are left as they are - the text is the kernel cache key)
-const std::string kLanePreamble = std::string(R"SRC(
-// Generated by okx_lanegen.cpp for one constraint program — do not edit.
-typedef struct { double max_residual, cost, last_step; int iterations, nfev, flags, reserved; } okx_info;
-// One wavefront per workgroup: its LDS instructions execute in program order, so what separates a lane's LDS writes from
+// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the argument structs'
+// declarations: okx_quad.hpp, beside their host mirrors - the comments around them differ between the two modules and are
+// left as they are: the text is the kernel cache key)
+const std::string kLanePreamble = std::string("\n// Generated by okx_lanegen.cpp for one constraint program — do not edit.\n") + kOkxInfoDecl + R"SRC(// One wavefront per workgroup: its LDS instructions execute in program order, so what separates a lane's LDS writes from
 // another lane's reads is an ordering for the COMPILER.  __syncthreads() is more than that: a workgroup-scope release
 // fence, i.e. a wait for every global store the wavefront has in flight - the record stores of a wave unit (4 us of HBM
 // time for 64 records) would be waited for before the next unit may start instead of draining behind it.
 typedef const __attribute__((address_space(4))) double* okx_cptr;  // loads through it are scalar-cache loads (s_load)
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-struct QArgs {
-  const double* targets; const double* geom_pos; const double* geom_row_param;
-  double* out_pos; okx_info* info;
-  long long n_problems, steps_per_geometry, chain_len;
-  int max_iter, confirm;
-  double step_tol, grad_tol, ftol, lambda0, residual_tolerance;
-  const double* design_pos; const double* row_param; const double* dop_param;
-  double* trace; long long trace_problem;
-  const double* predictor; long long predictor_mode; long long predictor_len;
-  const double* head;
-  long long out_mode;   // okx_solve_opts.output: 0 records of every output point, 1 the free points only, 2 nothing
-};
-#define EPS_SQ 1e-12
+)SRC" + kLaneQArgsDecl + R"SRC(#define EPS_SQ 1e-12
 #define EPS 1e-6
 #define DEV __device__ __forceinline__
 #define INFO_CONVERGED 1
@@ -1092,7 +1078,7 @@ DEV long long uni64(long long v) {
   const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
   return ((long long)hi << 32) | (unsigned int)lo;
 }
-)SRC") + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X, profiles/r02/README.md): one Newton step for a pivot.
+)SRC" + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X, profiles/r02/README.md): one Newton step for a pivot.
 )SRC" + kDevPivotRcp + R"SRC(// a product / a sum that is rounded where it stands (never fused into a neighbour): the final state's squared norms are
 // summed in the quad kernels' order with them
 DEV double okx_mul_rn(double a, double b) {
@@ -1474,7 +1460,7 @@ class LaneModule {
     g.f("");
     if (EV) {
       g.out += eval_metrics_source(*es);
-      g.f("struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; };");
+      g.out += kQEvArgsDecl;
     }
     {
       // every table entry a constant's name can stand for (unused macros cost nothing)
@@ -2192,8 +2178,7 @@ class LaneModule {
     }
     stamp(b, 13);
     g.f("    if (valid && !GIVEN) {");
-    g.f("      okx_info inf; inf.max_residual = mres; inf.cost = Fc; inf.last_step = last_step;");
-    g.f("      inf.iterations = iters; inf.nfev = nfev; inf.flags = flags; inf.reserved = 0;");
+    g.fill_info("      ");
     g.f("      a.info[bb] = inf;");
     g.f("    }");
     stamp(b, 14);
@@ -2451,8 +2436,7 @@ class LaneModule {
 
   // ---- parity / debug kernel: r, J^T J, J^T r at given x, and the damped step for a given lambda ----
   void emit_eval_kernel() {
-    g.f("struct QEvalArgs { const double* x; const double* targets; double* r; double* ata; double* atr; double* dx;");
-    g.f("  double lambda; long long n_problems; const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQEvalArgsDecl;
     g.f("#undef GL\n#define GL(o) gl[(o) + kz]");
     g.f("extern \"C\" __global__ void __launch_bounds__(64, 1) okx_lane_eval(QEvalArgs a) {");
     g.f("  const double* gp = a.design_pos; const double* gq = a.row_param; (void)gq;");

@@ -15,8 +15,9 @@ namespace okx {
 // tests/test_dev_switches.py (generated source still compiles and is deterministic); the switches that change generated
 // source are part of its text and therefore of the kernel cache key.
 //   generators   quad_mark, quad_timeline, quad_no_light, quad_no_head, quad_no_fast, quad_two_waves, pair_no_head, pair_first_order_head,
-//                pair_lds_homes, pair_cold_lds, quad_serial_chains, lane_mark, lane_timeline, lane_lds_tables, lane_nested, lane_refine
-//   library      no_quad, no_lane, no_cold, tangent_generic, evaluate_quad, evaluate_lane, keep_source
+//                pair_lds_homes, pair_cold_lds, quad_serial_chains, lane_mark, lane_timeline, lane_lds_tables, lane_nested, lane_refine,
+//                lane_g_scalar
+//   library      no_quad, no_lane, no_cold, tangent_generic, evaluate_quad, evaluate_lane, keep_source, cov_valu
 bool dev_switch(const char* name);
 
 // default / largest degree of the chain-head predictor's Chebyshev series
@@ -29,7 +30,42 @@ constexpr int kQuadMaxJoins = 4;          // pair mode: rows joining the two hal
 constexpr int kQuadMaxFreePerSide = 11;  // pair mode (two identical halves, one quad each): free points per half (rocker corner + droplink + heave pickup)
 constexpr int kLaneMaxFree = 6;          // lane kernel (one lane per problem): n <= 18 unknowns, lower triangle of J^T J <= 171 doubles
 
-// Kernel arguments of the generated kernels (mirrors `struct QArgs` in the generated source).
+// The generated modules declare their argument structs themselves: each declaration's text stands directly beside the host
+// struct that mirrors it (a field is added in both, here), and both generators splice it in.  Generated text is the kernel
+// cache key: a change of one of these constants recompiles every module that declares the struct.
+constexpr const char* kOkxInfoDecl =  // okx_info of okx.h
+    "typedef struct { double max_residual, cost, last_step; int iterations, nfev, flags, reserved; } okx_info;\n";
+
+// Kernel arguments of the generated kernels (mirrors `struct QArgs` in the generated source; the two generators' texts
+// differ in their comments).
+constexpr const char* kQArgsDecl = R"SRC(struct QArgs {
+  const double* targets; const double* geom_pos; const double* geom_row_param;
+  double* out_pos; okx_info* info;
+  long long n_problems, steps_per_geometry, chain_len;
+  int max_iter, confirm;   // confirm != 0: never end on the predicted-convergence test (always a full pass)
+  double step_tol, grad_tol, ftol, lambda0, residual_tolerance;
+  const double* design_pos; const double* row_param; const double* dop_param;
+  double* trace; long long trace_problem;   // diagnostic: 8 doubles per LM pass of one problem (null: off)
+  const double* predictor;  // polynomial model of the solution over the fitted target range for chain heads (null: off)
+  long long predictor_mode; // 2: every chain step starts from the model, not only the heads
+  long long predictor_len;  // doubles in the table
+  const double* head;       // per-geometry first-step table of okx_quad_head_u/_g (null: every chain head takes its own first pass)
+  long long out_mode;       // okx_solve_opts.output: 0 records of every output point, 1 the free points only, 2 nothing
+};
+)SRC";
+constexpr const char* kLaneQArgsDecl = R"SRC(struct QArgs {
+  const double* targets; const double* geom_pos; const double* geom_row_param;
+  double* out_pos; okx_info* info;
+  long long n_problems, steps_per_geometry, chain_len;
+  int max_iter, confirm;
+  double step_tol, grad_tol, ftol, lambda0, residual_tolerance;
+  const double* design_pos; const double* row_param; const double* dop_param;
+  double* trace; long long trace_problem;
+  const double* predictor; long long predictor_mode; long long predictor_len;
+  const double* head;
+  long long out_mode;   // okx_solve_opts.output: 0 records of every output point, 1 the free points only, 2 nothing
+};
+)SRC";
 struct QuadArgs {
   const double* targets;
   const double* geom_pos;
@@ -53,6 +89,9 @@ struct QuadArgs {
 
 // Arguments of the generated `okx_quad_head_u/_g` (mirrors `struct QHeadArgs`): one quad per geometry evaluates the
 // design state once and tabulates the first Levenberg-Marquardt step of every chain head of that geometry.
+constexpr const char* kQHeadArgsDecl =
+    "struct QHeadArgs { const double* geom_pos; const double* geom_row_param; double* head; long long n_geometries; double lambda0;\n"
+    "  const double* design_pos; const double* row_param; const double* dop_param; };\n";
 struct QuadHeadArgs {
   const double* geom_pos;
   const double* geom_row_param;
@@ -69,6 +108,9 @@ struct QuadHeadArgs {
 int quad_head_stride(const DevProgram& program);
 
 // Arguments of the generated parity kernel `okx_quad_eval` (mirrors `struct QEvalArgs`).
+constexpr const char* kQEvalArgsDecl =
+    "struct QEvalArgs { const double* x; const double* targets; double* r; double* ata; double* atr; double* dx;\n"
+    "  double lambda; long long n_problems; const double* design_pos; const double* row_param; const double* dop_param; };\n";
 struct QuadEvalArgs {
   const double* x;
   const double* targets;
@@ -84,6 +126,9 @@ struct QuadEvalArgs {
 };
 
 // Arguments of the generated `okx_quad_expand` (mirrors `struct QExpandArgs`).
+constexpr const char* kQExpandArgsDecl =
+    "struct QExpandArgs { const double* free; const double* geom_pos; double* out_pos; long long n_problems, steps_per_geometry;\n"
+    "  const double* design_pos; const double* row_param; const double* dop_param; };\n";
 struct QuadExpandArgs {
   const double* free;
   const double* geom_pos;
@@ -95,6 +140,11 @@ struct QuadExpandArgs {
 };
 
 // Arguments of the generated tangent kernels `okx_quad_tangent_u/_g` (mirrors `struct QTanArgs`).
+constexpr const char* kQTanArgsDecl =  // (with okx_tangent_info of okx.h)
+    "typedef struct { double min_pivot, max_pivot; int flags, reserved; } okx_tangent_info;\n"
+    "struct QTanArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan;\n"
+    "  okx_tangent_info* tinfo; long long n_problems, steps_per_geometry;\n"
+    "  const double* design_pos; const double* row_param; const double* dop_param; };\n";
 struct QuadTanArgs {
   const double* pos;
   const double* geom_pos;
@@ -141,6 +191,8 @@ std::string eval_roles_source();  // the role kinds of okx_rotation_role on dual
 // Arguments of the evaluated solve kernels okx_quad_evsolve_u/_g, okx_quad_evcold_u, okx_lane_evsolve_u/_g (mirrors
 // `struct QEvArgs`): the solve's own arguments, then what the epilogue writes and the roles' numeric part.  The generated
 // corner modules declare the struct up to `cfg`; pair-mode modules read the right corner's numbers and the roles' as well.
+constexpr const char* kQEvArgsDecl = "struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; };\n";  // corner modules
+constexpr const char* kQEvArgsAxleDecl = "struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; EvCfg cfg_r; EvRoleNum roles[8]; };\n";
 struct QuadEvArgs {
   QuadArgs q;
   double* tan;    // [B][T][n_out][3] or null
@@ -150,6 +202,12 @@ struct QuadEvArgs {
   EvalRoleNum roles[8];
 };
 // Arguments of okx_quad_evaluate_u/_g (mirrors `struct QEvPosArgs`): the same epilogue on given solved states.
+constexpr const char* kQEvPosArgsDecl =  // corner modules
+    "struct QEvPosArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan; double* ev;\n"
+    "  long long n_problems, steps_per_geometry; const double* design_pos; const double* row_param; const double* dop_param; EvCfg cfg; };\n";
+constexpr const char* kQEvPosArgsAxleDecl =
+    "struct QEvPosArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan; double* ev;\n"
+    "  long long n_problems, steps_per_geometry; const double* design_pos; const double* row_param; const double* dop_param; EvCfg cfg; EvCfg cfg_r; EvRoleNum roles[8]; };\n";
 struct QuadEvPosArgs {
   const double* pos;
   const double* geom_pos;
@@ -211,7 +269,7 @@ bool lane_generate(const DevProgram& P, std::string* src, std::string* why, int 
 // Otherwise (double wishbone: 72 + 8) the chain body IS the independent-solve body in one flat loop over
 // (wave unit, chain step), and everything a chain carries from step to step - the last three solutions, whether they
 // converged, the damping - lives in a per-launch global scratch of lane_flat_chain_doubles() per wavefront, passed in
-// QuadArgs.predictor (the lane kernel has no fitted model).  OKX_LANE_FLAT_CHAIN=0/1 forces either.
+// QuadArgs.predictor (the lane kernel has no fitted model).
 bool lane_chain_is_flat(int n_vars);
 inline long long lane_flat_chain_doubles(int n_vars) { return 3LL * (n_vars + 2) * 64; }
 // The NESTED start mode of the lane kernel (okx_lane_nest_*; okx_lanegen.cpp): a lane owns four consecutive steps, solved in

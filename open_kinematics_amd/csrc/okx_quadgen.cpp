@@ -173,6 +173,15 @@ class Gen : public GenBase {
     f("    const double %s = qsum(%s * %s);", t.c_str(), a.c_str(), b.c_str());
     return t;
   }
+  // A wavefront's contiguous rows out of LDS: `n_doubles` of them leave `stage` for `base` in 16-byte-per-lane stores, an
+  // odd last double through lane 0 to `last` (C expressions; `last` as the site spells that address).
+  void copy_rows_out(const char* ind, const std::string& n_doubles, const std::string& base, const char* stage, const std::string& last) {
+    f("%sconst int n_doubles = %s;", ind, n_doubles.c_str());
+    f("%sdouble2* dst = reinterpret_cast<double2*>(%s);", ind, base.c_str());
+    f("%sconst double2* src = reinterpret_cast<const double2*>(%s);", ind, stage);
+    f("%sfor (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];", ind);
+    f("%sif ((n_doubles & 1) && lane == 0) %s = %s[n_doubles - 1];", ind, last.c_str(), stage);
+  }
 
   // ---- derived points ----
   std::map<int, Blk> blocks_of_point(int p) {
@@ -806,7 +815,7 @@ class Gen : public GenBase {
   // OKX_QUAD_MARK=1: `s_nop 11..17` between the sections of a pass (tools/quad_sections.py counts the instructions
   // in between; scheduling barriers keep the sections apart, so the marked kernel is for counting, not for timing)
   bool marks = false;
-  bool tl_marks = false;  // OKX_QUAD_TIMELINE=1: section stamps inside a pass (OKX_TL is defined per kernel body)
+  bool tl_marks = false;  // quad_timeline: section stamps inside a pass (OKX_TL is defined per kernel body)
   void mark(int n) {
     if (marks) f("    __builtin_amdgcn_sched_barrier(0); asm volatile(\"s_nop %d\"); __builtin_amdgcn_sched_barrier(0);", 10 + n);
     if (tl_marks && n >= 5) f("    OKX_TL(%d)", n);
@@ -1108,26 +1117,15 @@ template <class Fn> std::string capture(Gen& gen, Fn&& emit) {
   return kept;
 }
 
-// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the `QArgs` mirror and the
-// comments around them differ between the two modules and are left as they are - the text is the kernel cache key)
-const std::string kPreamble = std::string(R"SRC(
-// Generated by okx_quadgen.cpp for one constraint program — do not edit.
-typedef struct { double max_residual, cost, last_step; int iterations, nfev, flags, reserved; } okx_info;
-struct QArgs {
-  const double* targets; const double* geom_pos; const double* geom_row_param;
-  double* out_pos; okx_info* info;
-  long long n_problems, steps_per_geometry, chain_len;
-  int max_iter, confirm;   // confirm != 0: never end on the predicted-convergence test (always a full pass)
-  double step_tol, grad_tol, ftol, lambda0, residual_tolerance;
-  const double* design_pos; const double* row_param; const double* dop_param;
-  double* trace; long long trace_problem;   // diagnostic: 8 doubles per LM pass of one problem (null: off)
-  const double* predictor;  // polynomial model of the solution over the fitted target range for chain heads (null: off)
-  long long predictor_mode; // 2: every chain step starts from the model, not only the heads
-  long long predictor_len;  // doubles in the table
-  const double* head;       // per-geometry first-step table of okx_quad_head_u/_g (null: every chain head takes its own first pass)
-  long long out_mode;       // okx_solve_opts.output: 0 records of every output point, 1 the free points only, 2 nothing
-};
-#define EPS_SQ 1e-12
+// (fast_rcp, pivot_rcp, fast_sqrt_rsqrt: the text shared with the other generator, okx_gen.hpp; the argument structs'
+// declarations: okx_quad.hpp, beside their host mirrors - the comments around them differ between the two modules and are
+// left as they are: the text is the kernel cache key)
+// The wavefront-scope release / barrier / acquire statement between a wavefront's LDS writes and other lanes' reads of them,
+// and its form without the acquire (after the last read: what follows may not move ahead of it).
+constexpr const char* kWaveSync = "__builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");";
+constexpr const char* kWaveRelease = "__builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier();";
+
+const std::string kPreamble = std::string("\n// Generated by okx_quadgen.cpp for one constraint program — do not edit.\n") + kOkxInfoDecl + kQArgsDecl + R"SRC(#define EPS_SQ 1e-12
 #define EPS 1e-6
 #define DEV __device__ __forceinline__
 // lane component load: lanes 0..2 read their component, lane 3 (address clamped to component 2 by the caller)
@@ -1167,7 +1165,7 @@ DEV double qsum(double v) {
 }
 DEV double qmax(double v) { v = fmax(v, qperm<0xB1>(v)); v = fmax(v, qperm<0x4E>(v)); return v; }
 
-)SRC") + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X over 2^20 arguments, profiles/r02/README.md).
+)SRC" + kDevFastRcp + R"SRC(// v_rcp_f64 / v_rsq_f64 deliver 2^-24.3 (measured on MI355X over 2^20 arguments, profiles/r02/README.md).
 // Reciprocal of a pivot: ONE Newton step (2^-48.6).  The factor only steers the Levenberg-Marquardt step (and the
 // tangents to 1e-9): a 2e-15 relative error in L is far inside what the damping already does to it.
 )SRC" + kDevPivotRcp + R"SRC(// sqrt(x) to the last bit or so and 1 / sqrt(x) to 4e-15: one Goldschmidt step (both to ~1.5 * 2^-48.4), then the
@@ -1272,7 +1270,7 @@ class QuadModule {
   const int REC, EVC, TP, RECP, EVA;                           // evaluated modules: doubles per record / per result row
   Gen g;   // the module's text
   Gen ev;  // the passes: its tables (sparsity, hoisted loads, target gradients) serve every kernel
-  // (OKX_PAIR_NO_HEAD=1 leaves the table out of a pair-mode module)
+  // (pair_no_head leaves the table out of a pair-mode module)
   const bool head_ok;
   const HeadLayout head;
   const int HK, NPAIR;
@@ -1608,13 +1606,106 @@ class QuadModule {
     return l.side * MV + 3 * mov_index[l.point];
   }
 
+  // ---- the fragments the kernels have in common: one emitter each ----
+  // How a lane finds its problem, its half (pair mode: `side`, the name of the side bit here) and its component.
+  void open_lanes(const char* side = nullptr) {
+    if (pv)
+      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, %s = (lane >> 2) & 1, cc = c < 3 ? c : 2;", side);
+    else
+      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+  }
+  void unit_vectors() { g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;"); }
+  // The grid-stride loop over wave units of the kernels that take one problem (geometry) per quad: `index` of the quad's
+  // own, clamped to the last of `count` (`valid`: it really has one).
+  void open_unit_loop(const char* index, const char* count) {
+    g.f("  for (long long wu = blockIdx.x; wu * %d < %s; wu += gridDim.x) {", PPW, count);
+    g.f("    long long %s = wu * %d + quad; const bool valid = %s < %s; if (!valid) %s = %s - 1;", index, PPW, index, count, index, count);
+  }
+  // Registers of the points some row, derived op or output reads, from the geometry table `gp`.  kInHomes: the solve
+  // bodies, whose fixed points live in LDS where the module's layout says so; kFixedAgain: another geometry's fixed points
+  // into registers declared before.
+  enum PointLoads { kDeclare, kInHomes, kFixedAgain };
+  void load_used_points(const char* ind, PointLoads how = kDeclare) {
+    int slot = 0;
+    for (int p = 0; p < NP; ++p) {
+      if (!used[p]) continue;
+      const bool fixed = ev.blk_of_point[p] < 0 && ev.dop_of_point[p] < 0;
+      if (how == kFixedAgain) {
+        if (fixed) g.f("%sp%d = ld3(gp + %s + cc, c);", ind, p, ev.point3(p).c_str());
+      } else if (how == kInHomes && ev.lds_constants && fixed && !fixed_in_regs) {
+        g.f("%sdouble& p%d = psl[%d + lane]; p%d = ld3(gp + %s + cc, c);", ind, p, 64 * slot++, p, ev.point3(p).c_str());
+      } else {
+        g.f("%sdouble p%d = ld3(gp + %s + cc, c);", ind, p, ev.point3(p).c_str());
+      }
+    }
+  }
+  // The lane's components of its problem's record into `stage` [problem][record].  Pair mode: each half stores its own
+  // points, the left half (`side` clear) also what only it writes and the fixed points neither half moves.
+  void stage_record(const char* ind, const char* side = nullptr) {
+    g.f("%sdouble* st = stage + quad * %d + c;", ind, RECP);
+    for (int k = 0; k < P.n_out; ++k) {
+      if (!pv) {
+        g.f("%sst[%d] = p%d;", ind, 3 * k, P.out_point[k]);
+        continue;
+      }
+      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
+      if (k1 >= 0) g.f("%sst[%s ? %d : %d] = p%d;", ind, side, 3 * k1, 3 * k0, P.out_point[k]);
+      else g.f("%sif (!%s) st[%d] = p%d;", ind, side, 3 * k0, P.out_point[k]);
+    }
+    if (pv)
+      for (size_t k = 0; k < pv->shared_out.size(); ++k)
+        g.f("%sif (!%s) st[%d] = gp[%d + c];", ind, side, 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+  }
+  // The wavefront's consecutive problems' rows of `per` doubles, staged in `stage`, to a.out_pos as one block.
+  void copy_block_out(const char* ind, const char* stage, int per) {
+    g.f("%sconst long long rem = a.n_problems - wu * %d;", ind, PPW);
+    g.copy_rows_out(ind, sfmt("(int)(rem < %d ? rem : %d) * %d", PPW, PPW, per), sfmt("a.out_pos + wu * %d * %d", PPW, per), stage,
+                    sfmt("a.out_pos[wu * %d * %d + n_doubles - 1]", PPW, per));
+  }
+  // Chains: a quad's problems are far apart in memory, each lane stores its own 8-byte components of problem `index`'s
+  // record.
+  void store_record_by_lane(const char* ind, const char* index) {
+    if (!pv) {
+      g.f("%sdouble* o = a.out_pos + %s * %d + c;", ind, index, RECP);
+      for (int k = 0; k < P.n_out; ++k) g.f("%so[%d] = p%d;", ind, 3 * k, P.out_point[k]);
+      return;
+    }
+    // The two halves' records usually sit a constant distance apart in the output list (left block, right block):
+    // one select on the side bit then serves every store.  Otherwise each store selects its own index, on a fresh
+    // opaque copy of the side bit so that the selects are made here instead of being kept (and spilled) as invariants.
+    long long delta = 0;
+    bool uniform_delta = true, first = true;
+    for (int k = 0; k < P.n_out; ++k) {
+      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
+      if (k1 < 0) continue;
+      if (first) delta = 3LL * (k1 - k0), first = false;
+      else uniform_delta = uniform_delta && delta == 3LL * (k1 - k0);
+    }
+    g.f("%sint q1s = q1; asm volatile(\"\" : \"+v\"(q1s));", ind);
+    if (uniform_delta)
+      g.f("%sdouble* o = a.out_pos + %s * %d + c + (q1s ? %lld : 0);", ind, index, RECP, delta);
+    else
+      g.f("%sdouble* o = a.out_pos + %s * %d + c;", ind, index, RECP);
+    for (int k = 0; k < P.n_out; ++k) {
+      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
+      if (k1 >= 0 && uniform_delta)
+        g.f("%so[%d] = p%d;", ind, 3 * k0, P.out_point[k]);
+      else if (k1 >= 0)
+        g.f("%so[q1s ? %d : %d] = p%d;", ind, 3 * k1, 3 * k0, P.out_point[k]);
+      else
+        g.f("%sif (!q1s) o[%d] = p%d;", ind, 3 * k0, P.out_point[k]);
+    }
+    for (size_t k = 0; k < pv->shared_out.size(); ++k)
+      g.f("%sif (!q1s) o[%d] = gp[%d + c];", ind, 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+  }
+
   void emit_preamble_and_helpers() {
     g.out += kPreamble;
     if (EV) {
       g.out += eval_metrics_source(*es);
       if (EVP) {
         g.out += eval_roles_source();
-        g.f("struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; EvCfg cfg_r; EvRoleNum roles[8]; };");
+        g.out += kQEvArgsAxleDecl;
         std::string table = "__constant__ short kVelMap[" + std::to_string(3 * prog_out) + "] = {";
         for (int k = 0; k < prog_out; ++k)
           for (int cc2 = 0; cc2 < 3; ++cc2) {
@@ -1623,8 +1714,8 @@ class QuadModule {
           }
         g.out += table + "};  // record element -> offset in a problem-target block of the staged velocities\n";
       } else
-        g.f("struct QEvArgs { QArgs q; double* tan; double* ev; EvCfg cfg; };");
-      g.f("#define EV_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\"); } while (0)");
+        g.out += kQEvArgsDecl;
+      g.f("#define EV_WAVE_SYNC() do { %s } while (0)", kWaveSync);
     }
     if (ev.tl_marks) g.f("#define OKX_TL(k)");
     g.f("");
@@ -1726,11 +1817,8 @@ class QuadModule {
     ev.f("    const int ev_rows = (int)(ev_rem < 16 ? ev_rem : 16);  // problems of a contiguous wavefront block");
     auto copy_out = [&](const char* dst, const char* stage_name, int per_problem) {
       ev.f("      if (%s) {", contig.c_str());
-      ev.f("        const int n_doubles = ev_rows * %d;", per_problem);
-      ev.f("        double2* dst = reinterpret_cast<double2*>(%s + wu * 16 * %d);", dst, per_problem);
-      ev.f("        const double2* src = reinterpret_cast<const double2*>(%s);", stage_name);
-      ev.f("        for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-      ev.f("        if ((n_doubles & 1) && lane == 0) (%s + wu * 16 * %d)[n_doubles - 1] = %s[n_doubles - 1];", dst, per_problem, stage_name);
+      ev.copy_rows_out("        ", sfmt("ev_rows * %d", per_problem), sfmt("%s + wu * 16 * %d", dst, per_problem), stage_name,
+                       sfmt("(%s + wu * 16 * %d)[n_doubles - 1]", dst, per_problem));
       ev.f("      } else if (valid) {  // chains: a quad's problems are far apart in memory");
       ev.f("        double* dst = %s + bb * %d;", dst, per_problem);
       ev.f("        const double* src = %s + quad * %d;", stage_name, per_problem);
@@ -2107,7 +2195,7 @@ class QuadModule {
     // the evaluated cold body 2 %: their register files are full).  pair_cold_lds: the old layout everywhere.
     b.pair_state_lds = pv != nullptr && !(CD && NK == 1 && nf <= 10 && !EV && !dev_switch("pair_cold_lds"));
     b.tl_body = CD && ev.tl_marks;
-    // (developer build, OKX_QUAD_TIMELINE=1: wavefront w stamps the shader clock into a.trace[16 w + k] - 0 entry, 1 loads
+    // (developer switch quad_timeline: wavefront w stamps the shader clock into a.trace[16 w + k] - 0 entry, 1 loads
     //  consumed / first step in hand, 2 ... 11 top of each LM pass, 13 passes done, 14 records stored; tools/quad_timeline.py)
     b.timeline = CD && dev_switch("quad_timeline");
     b.fast_loop = CD && !dev_switch("quad_no_fast");  // (developer switch: the cold body with the general loop only)
@@ -2140,12 +2228,9 @@ class QuadModule {
     stamp(b, "0");
     // (the device's 100 MHz real-time counter, the same on every XCD, at entry and at the end: slots 0 / 1 of the second half)
     if (b.timeline) g.f("    if (a.trace && (threadIdx.x & 63) == 0) a.trace[(gridDim.x + blockIdx.x) * 16 + 0] = (double)__builtin_amdgcn_s_memrealtime();");
-    if (pv)
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, q1_lane = (lane >> 2) & 1, cc = c < 3 ? c : 2;");
-    else
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+    open_lanes("q1_lane");
     g.out += atan_decl;
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    unit_vectors();
     if (!pv && !b.CD) g.f("  __shared__ double pls[%d];  // LDS copy of the chain-head predictor's table", kPredictorLdsDoubles);
   }
   // Cold body: every table the prologue reads - first-step table, design positions, row and derived-op parameters - is
@@ -2194,7 +2279,7 @@ class QuadModule {
     for (int q = 0; q < 3; ++q)
       for (int k = 0; 64 * k < pieces[q].n; ++k) g.f("    if (lane + %d < %d) cst[%d + lane] = sp%d_%d;", 64 * k, pieces[q].n, pieces[q].off + 64 * k, q, k);
     // (one wavefront per workgroup: its LDS instructions execute in order, only the compiler must keep them in order)
-    g.f("    __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");");
+    g.f("    %s", kWaveSync);
     g.f("  }");
     g.f("  const double* const c_rp = cst + %d; const double* const c_dp = cst + %d; (void)c_dp; (void)c_rp;", b.cs_rp, b.cs_dp);
   }
@@ -2326,17 +2411,7 @@ class QuadModule {
     g.out += couple_hoist;
     // point registers; in the register-bound pair kernel the fixed points (read once or twice per pass, never
     // written) live in LDS instead: the compiler would otherwise park them in scratch
-    {
-      int slot = 0;
-      for (int p = 0; p < NP; ++p) {
-        if (!used[p]) continue;
-        const bool fixed = ev.blk_of_point[p] < 0 && ev.dop_of_point[p] < 0;
-        if (ev.lds_constants && fixed && !fixed_in_regs)
-          g.f("    double& p%d = psl[%d + lane]; p%d = ld3(gp + %s + cc, c);", p, 64 * slot++, p, ev.point3(p).c_str());
-        else
-          g.f("    double p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
-      }
-    }
+    load_used_points("    ", kInHomes);
     for (int F = 0; F < nf; ++F) {
       if (ev.lds_constants && b.CD) {  // cold pair body: the accepted point and the step in hand, no chain history
         g.f("    double& x%d = xsl[%d + lane]; double& dx%d = xsl[%d + lane]; x%d = p%d; dx%d = 0.0;", F, 64 * F, F, 64 * (nf + F), F, ev.fp(F), F);
@@ -2985,14 +3060,9 @@ class QuadModule {
         else g.f("        st[%d] = x%d;", 3 * ordinal[pt], F);
       }
       g.f("      }");
-      g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");");
-      g.f("      const long long rem = a.n_problems - wu * %d;", PPW);
-      g.f("      const int n_doubles = (int)(rem < %d ? rem : %d) * %d;", PPW, PPW, 3 * program.n_free);
-      g.f("      double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * %d * %d);", PPW, 3 * program.n_free);
-      g.f("      const double2* src = reinterpret_cast<const double2*>(fstage);");
-      g.f("      for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-      g.f("      if ((n_doubles & 1) && lane == 0) a.out_pos[wu * %d * %d + n_doubles - 1] = fstage[n_doubles - 1];", PPW, 3 * program.n_free);
-      g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier();");
+      g.f("      %s", kWaveSync);
+      copy_block_out("      ", "fstage", 3 * program.n_free);
+      g.f("      %s", kWaveRelease);
       g.f("    }");
       g.f("    if (false) { long long bf = 0;");
     } else {
@@ -3024,24 +3094,12 @@ class QuadModule {
       // written as the output mode says - whole rows where the wavefront's eight records are contiguous
       g.f("    if (c < 3) {");
       g.f("      int q1s = q1; asm volatile(\"\" : \"+v\"(q1s));");
-      g.f("      double* st = stage + quad * %d + c;", RECP);
-      for (int k = 0; k < P.n_out; ++k) {
-        const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-        if (k1 >= 0) g.f("      st[q1s ? %d : %d] = p%d;", 3 * k1, 3 * k0, P.out_point[k]);
-        else g.f("      if (!q1s) st[%d] = p%d;", 3 * k0, P.out_point[k]);
-      }
-      for (size_t k = 0; k < pv->shared_out.size(); ++k)
-        g.f("      if (!q1s) st[%d] = gp[%d + c];", 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+      stage_record("      ", "q1s");
       g.f("    }");
       g.f("    EV_WAVE_SYNC();");
       g.f("    if (a.out_mode == 0) {");
       g.f("      if (unit_len == 1) {");
-      g.f("        const long long rem = a.n_problems - wu * %d;", PPW);
-      g.f("        const int n_doubles = (int)(rem < %d ? rem : %d) * %d;", PPW, PPW, RECP);
-      g.f("        double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * %d * %d);", PPW, RECP);
-      g.f("        const double2* src = reinterpret_cast<const double2*>(stage);");
-      g.f("        for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-      g.f("        if ((n_doubles & 1) && lane == 0) a.out_pos[wu * %d * %d + n_doubles - 1] = stage[n_doubles - 1];", PPW, RECP);
+      copy_block_out("        ", "stage", RECP);
       g.f("      } else if (valid) {  // chains: a problem's record by its own eight lanes");
       g.f("        double* o = a.out_pos + bb * %d;", RECP);
       g.f("        for (int i = lane & 7; i < %d; i += 8) o[i] = stage[quad * %d + i];", RECP, RECP);
@@ -3053,21 +3111,14 @@ class QuadModule {
       // the output mode says - whole rows where the wavefront's records are contiguous
       g.f("    __shared__ __attribute__((aligned(16))) double stage[16 * %d];", 3 * P.n_out);
       g.f("    if (c < 3) {");
-      g.f("      double* st = stage + quad * %d + c;", 3 * P.n_out);
-      for (int k = 0; k < P.n_out; ++k) g.f("      st[%d] = p%d;", 3 * k, P.out_point[k]);
+      stage_record("      ");
       g.f("    }");
       g.f("    EV_WAVE_SYNC();");
       g.f("    if (a.out_mode == 0) {");
       g.f("      if (unit_len == 1) {");
-      g.f("        const long long rem = a.n_problems - wu * 16;");
-      g.f("        const int n_doubles = (int)(rem < 16 ? rem : 16) * %d;", 3 * P.n_out);
-      g.f("        double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * 16 * %d);", 3 * P.n_out);
-      g.f("        const double2* src = reinterpret_cast<const double2*>(stage);");
-      g.f("        for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-      g.f("        if ((n_doubles & 1) && lane == 0) a.out_pos[wu * 16 * %d + n_doubles - 1] = stage[n_doubles - 1];", 3 * P.n_out);
+      copy_block_out("        ", "stage", REC);
       g.f("      } else if (valid && c < 3) {");
-      g.f("        double* o = a.out_pos + bb * %d + c;", 3 * P.n_out);
-      for (int k = 0; k < P.n_out; ++k) g.f("        o[%d] = p%d;", 3 * k, P.out_point[k]);
+      store_record_by_lane("        ", "bb");
       g.f("      }");
       g.f("    }");
       g.f("    if (false) {");
@@ -3080,23 +3131,11 @@ class QuadModule {
     g.f("      __shared__ __attribute__((aligned(16))) double stage[%d * %d];", PPW, 3 * prog_out);
     g.f("      if (c < 3) {");
     g.f("        int q1s = q1; asm volatile(\"\" : \"+v\"(q1s));");
-    g.f("        double* st = stage + quad * %d + c;", 3 * prog_out);
-    for (int k = 0; k < P.n_out; ++k) {
-      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-      if (k1 >= 0) g.f("        st[q1s ? %d : %d] = p%d;", 3 * k1, 3 * k0, P.out_point[k]);
-      else g.f("        if (!q1s) st[%d] = p%d;", 3 * k0, P.out_point[k]);
-    }
-    for (size_t k = 0; k < pv->shared_out.size(); ++k)
-      g.f("        if (!q1s) st[%d] = gp[%d + c];", 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+    stage_record("        ", "q1s");
     g.f("      }");
-    g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");");
-    g.f("      const long long rem = a.n_problems - wu * %d;", PPW);
-    g.f("      const int n_doubles = (int)(rem < %d ? rem : %d) * %d;", PPW, PPW, 3 * prog_out);
-    g.f("      double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * %d * %d);", PPW, 3 * prog_out);
-    g.f("      const double2* src = reinterpret_cast<const double2*>(stage);");
-    g.f("      for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-    g.f("      if ((n_doubles & 1) && lane == 0) a.out_pos[wu * %d * %d + n_doubles - 1] = stage[n_doubles - 1];", PPW, 3 * prog_out);
-    g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier();");
+    g.f("      %s", kWaveSync);
+    copy_block_out("      ", "stage", RECP);
+    g.f("      %s", kWaveRelease);
     g.f("    }");
     g.f("    if (false) {");
   }
@@ -3105,33 +3144,7 @@ class QuadModule {
     // (the record's address is rebuilt from an opaque copy of the problem index: as an induction variable the compiler
     //  keeps one strength-reduced 64-bit address per output point alive across the chain loop and spills all of them)
     g.f("      long long bo = bb; asm volatile(\"\" : \"+v\"(bo));");
-    // The two halves' records usually sit a constant distance apart in the output list (left block, right block):
-    // one select on the side bit then serves every store.  Otherwise each store selects its own index, on a fresh
-    // opaque copy of the side bit so that the selects are made here instead of being kept (and spilled) as invariants.
-    long long delta = 0;
-    bool uniform_delta = true, first = true;
-    for (int k = 0; k < P.n_out; ++k) {
-      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-      if (k1 < 0) continue;
-      if (first) delta = 3LL * (k1 - k0), first = false;
-      else uniform_delta = uniform_delta && delta == 3LL * (k1 - k0);
-    }
-    g.f("      int q1s = q1; asm volatile(\"\" : \"+v\"(q1s));");
-    if (uniform_delta)
-      g.f("      double* o = a.out_pos + bo * %d + c + (q1s ? %lld : 0);", 3 * prog_out, delta);
-    else
-      g.f("      double* o = a.out_pos + bo * %d + c;", 3 * prog_out);
-    for (int k = 0; k < P.n_out; ++k) {
-      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-      if (k1 >= 0 && uniform_delta)
-        g.f("      o[%d] = p%d;", 3 * k0, P.out_point[k]);
-      else if (k1 >= 0)
-        g.f("      o[q1s ? %d : %d] = p%d;", 3 * k1, 3 * k0, P.out_point[k]);
-      else
-        g.f("      if (!q1s) o[%d] = p%d;", 3 * k0, P.out_point[k]);
-    }
-    for (size_t k = 0; k < pv->shared_out.size(); ++k)
-      g.f("      if (!q1s) o[%d] = gp[%d + c];", 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+    store_record_by_lane("      ", "bo");
     g.f("    }");
     g.f("    if (false) {");
   }
@@ -3140,37 +3153,29 @@ class QuadModule {
     g.f("    } else if (unit_len == 1) {");
     g.f("      __shared__ double stage[16 * %d];", 3 * P.n_out);
     g.f("      if (c < 3) {");
-    g.f("        double* st = stage + quad * %d + c;", 3 * P.n_out);
-    for (int k = 0; k < P.n_out; ++k) g.f("        st[%d] = p%d;", 3 * k, P.out_point[k]);
+    stage_record("        ");
     g.f("      }");
-    if (b.CD) g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");");
+    if (b.CD) g.f("      %s", kWaveSync);
     else
     g.f("      __syncthreads();");
-    g.f("      const long long rem = a.n_problems - wu * 16;");
-    g.f("      const int n_doubles = (int)(rem < 16 ? rem : 16) * %d;", 3 * P.n_out);
-    g.f("      double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * 16 * %d);", 3 * P.n_out);
-    g.f("      const double2* src = reinterpret_cast<const double2*>(stage);");
-    g.f("      for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-    g.f("      if ((n_doubles & 1) && lane == 0) a.out_pos[wu * 16 * %d + n_doubles - 1] = stage[n_doubles - 1];", 3 * P.n_out);
+    copy_block_out("      ", "stage", REC);
     // (cold body: no workgroup barrier here - it is a release fence, i.e. a wait for every record store of this unit to
     //  complete, ~1500 cycles at the end of the ONLY unit most wavefronts have; one wavefront's LDS accesses are ordered anyway)
-    if (b.CD) g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier();");
+    if (b.CD) g.f("      %s", kWaveRelease);
     else
     g.f("      __syncthreads();  // stage is reused by the next unit of this wavefront");
     g.f("    } else if (valid && c < 3) {");
-    g.f("      double* o = a.out_pos + bb * %d + c;", 3 * P.n_out);
-    for (int k = 0; k < P.n_out; ++k) g.f("      o[%d] = p%d;", 3 * k, P.out_point[k]);
+    store_record_by_lane("      ", "bb");
   }
   void body_info(const QuadBody& b) {
     if (b.CD) {
       // the sixteen 40-byte records of the wavefront are contiguous too: one staged block, 8 bytes per lane
       g.f("    __shared__ __attribute__((aligned(16))) okx_info istage[%d];", PPW);
       g.f("    if (c == 0%s) {", pv ? " && !q1" : "");
-      g.f("      okx_info inf; inf.max_residual = mres; inf.cost = Fc; inf.last_step = last_step;");
-      g.f("      inf.iterations = iters; inf.nfev = nfev; inf.flags = flags; inf.reserved = 0;");
+      g.fill_info("      ");
       g.f("      istage[quad] = inf;");
       g.f("    }");
-      g.f("    __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");");
+      g.f("    %s", kWaveSync);
       g.f("    {");
       g.f("      const long long rem = a.n_problems - wu * %d;", PPW);
       g.f("      const int n_words = (int)(rem < %d ? rem : %d) * 5;  // doubles of info records", PPW, PPW);
@@ -3178,12 +3183,11 @@ class QuadModule {
       g.f("      const double* src = reinterpret_cast<const double*>(istage);");
       g.f("      if (lane < n_words) dst[lane] = src[lane];");
       g.f("      if (lane + 64 < n_words) dst[lane + 64] = src[lane + 64];");
-      g.f("      __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); __builtin_amdgcn_wave_barrier();");
+      g.f("      %s", kWaveRelease);
       g.f("    }");
     } else {
     g.f("    if (valid && c == 0%s) {", pv ? " && !q1" : "");
-    g.f("      okx_info inf; inf.max_residual = mres; inf.cost = Fc; inf.last_step = last_step;");
-    g.f("      inf.iterations = iters; inf.nfev = nfev; inf.flags = flags; inf.reserved = 0;");
+    g.fill_info("      ");
     g.f("      a.info[bb] = inf;");
     g.f("    }");
     }
@@ -3281,8 +3285,7 @@ class QuadModule {
         return false;
       }
     }
-    g.f("struct QEvPosArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan; double* ev;");
-    g.f("  long long n_problems, steps_per_geometry; const double* design_pos; const double* row_param; const double* dop_param; EvCfg cfg; EvCfg cfg_r; EvRoleNum roles[8]; };");
+    g.out += kQEvPosArgsAxleDecl;
     // two bodies: on the program's own geometry the chain constants and the fixed points are the same for every state - read
     // once per wavefront, ahead of a persistent loop over its wave units (okx_evaluate_batch caps that grid at one wavefront
     // per SIMD); with geometry tables they belong to the wave unit
@@ -3290,26 +3293,24 @@ class QuadModule {
       g.f("DEV void okx_quad_evaluate_body_%s(const QEvPosArgs& a) {", pg ? "g" : "u");
       g.f("  constexpr bool PG = %s;", pg ? "true" : "false");
       g.f("  const QEvPosArgs& ea = a;");
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, q1 = (lane >> 2) & 1, cc = c < 3 ? c : 2;");
+      open_lanes("q1");
       g.out += atan_decl;
       g.out += lds_decl;
-      g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+      unit_vectors();
       g.f("  __shared__ __attribute__((aligned(16))) double stage[%d];", PPW * RECP);
       g.f("  __shared__ __attribute__((aligned(16))) double vst[%d];  // velocities [problem][target][half][moving point][3]", PPW * TP * 2 * MV);
       g.f("  __shared__ double vok[%d];", PPW);
       auto constants = [&]() {
         g.out += ev.hoisted;
         g.out += couple_hoist;
-        for (int p = 0; p < NP; ++p)
-          if (used[p]) g.f("    double p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
+        load_used_points("    ");
       };
       if (!pg) {
         g.f("  const double* gp = a.design_pos;");
         g.f("  const double* gq = a.row_param;");
         constants();
       }
-      g.f("  for (long long wu = blockIdx.x; wu * %d < a.n_problems; wu += gridDim.x) {", PPW);
-      g.f("    long long bb = wu * %d + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;", PPW);
+      open_unit_loop("bb", "a.n_problems");
       if (pg) {
         g.f("    const long long geom = bb / a.steps_per_geometry;");
         g.f("    const double* gp = a.geom_pos + geom * %d;", 3 * prog_points);
@@ -3325,14 +3326,7 @@ class QuadModule {
       g.out += final_src;
       g.f("    }");
       g.f("    if (c < 3) {");
-      g.f("      double* st = stage + quad * %d + c;", RECP);
-      for (int k = 0; k < P.n_out; ++k) {
-        const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-        if (k1 >= 0) g.f("      st[q1 ? %d : %d] = p%d;", 3 * k1, 3 * k0, P.out_point[k]);
-        else g.f("      if (!q1) st[%d] = p%d;", 3 * k0, P.out_point[k]);
-      }
-      for (size_t k = 0; k < pv->shared_out.size(); ++k)
-        g.f("      if (!q1) st[%d] = gp[%d + c];", 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+      stage_record("      ", "q1");
       g.f("    }");
       g.f("    EV_WAVE_SYNC();");
       {
@@ -3354,22 +3348,19 @@ class QuadModule {
   //      evaluate_solved_sweep): free points from the records, fixed points from the geometry, every derived point
   //      re-evaluated - one launch instead of tangents -> metrics, no tangent tensor in between unless asked for ----
   bool emit_evaluate_kernel() {
-    g.f("struct QEvPosArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan; double* ev;");
-    g.f("  long long n_problems, steps_per_geometry; const double* design_pos; const double* row_param; const double* dop_param; EvCfg cfg; };");
+    g.out += kQEvPosArgsDecl;
     g.f("template <bool PG> DEV void okx_quad_evaluate_body(const QEvPosArgs& a) {");
     g.f("  const QEvPosArgs& ea = a;");
-    g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+    open_lanes();
     g.out += atan_decl;
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    unit_vectors();
     g.f("  __shared__ __attribute__((aligned(16))) double stage[16 * %d];", 3 * P.n_out);
-    g.f("  for (long long wu = blockIdx.x; wu * 16 < a.n_problems; wu += gridDim.x) {");
-    g.f("    long long bb = wu * 16 + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;");
+    open_unit_loop("bb", "a.n_problems");
     g.f("    const long long geom = PG ? bb / a.steps_per_geometry : 0;");
     g.f("    const double* gp = PG ? a.geom_pos + geom * %d : a.design_pos;", 3 * NP);
     g.f("    const double* gq = PG ? a.geom_row_param + geom * %d : a.row_param;", 8 * P.n_crows);
     g.out += ev.hoisted;
-    for (int p = 0; p < NP; ++p)
-      if (used[p]) g.f("    double p%d = ld3(gp + %d + cc, c);", p, 3 * p);
+    load_used_points("    ");
     {
       std::vector<int> oi(NP, -1);
       for (int k = 0; k < P.n_out; ++k) oi[P.out_point[k]] = k;
@@ -3380,8 +3371,7 @@ class QuadModule {
     g.out += final_src;
     g.f("    }");
     g.f("    if (c < 3) {");
-    g.f("      double* st = stage + quad * %d + c;", 3 * P.n_out);
-    for (int k = 0; k < P.n_out; ++k) g.f("      st[%d] = p%d;", 3 * k, P.out_point[k]);
+    stage_record("      ");
     g.f("    }");
     g.f("    EV_WAVE_SYNC();");
     {
@@ -3405,11 +3395,10 @@ class QuadModule {
   void emit_expand_pair() {
     std::vector<int> ordinal(program.n_points, 0);
     for (int k = 0; k < program.n_free; ++k) ordinal[program.free_point[k]] = k;
-    g.f("struct QExpandArgs { const double* free; const double* geom_pos; double* out_pos; long long n_problems, steps_per_geometry;");
-    g.f("  const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQExpandArgsDecl;
     g.f("extern \"C\" __global__ void __launch_bounds__(64) okx_quad_expand(QExpandArgs a) {");
-    g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, q1 = (lane >> 2) & 1, cc = c < 3 ? c : 2;");
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    open_lanes("q1");
+    unit_vectors();
     g.f("  (void)e0; (void)e1; (void)e2;");
     g.out += lds_decl;
     g.f("  __shared__ __attribute__((aligned(16))) double stage[%d * %d];", PPW, 3 * prog_out);
@@ -3420,10 +3409,8 @@ class QuadModule {
     g.f("  const double* gp = a.design_pos;");
     g.f("  const double* gq = a.row_param; (void)gq;");
     g.out += ev.hoisted;
-    for (int p = 0; p < NP; ++p)
-      if (used[p]) g.f("  double p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
-    g.f("  for (long long wu = blockIdx.x; wu * %d < a.n_problems; wu += gridDim.x) {", PPW);
-    g.f("    long long bb = wu * %d + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;", PPW);
+    load_used_points("  ");
+    open_unit_loop("bb", "a.n_problems");
     g.f("    {  // input rows: one contiguous block, 16 bytes per lane, then each lane its components from LDS");
     g.f("      const long long rem_in = a.n_problems - wu * %d;", PPW);
     g.f("      const int n_in = (int)(rem_in < %d ? rem_in : %d) * %d;", PPW, PPW, 3 * program.n_free);
@@ -3438,8 +3425,7 @@ class QuadModule {
     g.f("    if (!own) {");
     g.f("      const long long geom = bb / a.steps_per_geometry;");
     g.f("      gp = a.geom_pos + geom * %d;", 3 * prog_points);
-    for (int p = 0; p < NP; ++p)
-      if (used[p] && ev.blk_of_point[p] < 0 && ev.dop_of_point[p] < 0) g.f("      p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
+    load_used_points("      ", kFixedAgain);
     g.f("    }");
     g.f("    __syncthreads();");
     for (int F = 0; F < nf; ++F) {
@@ -3449,22 +3435,10 @@ class QuadModule {
     }
     g.out += final_src;
     g.f("    if (c < 3) {");
-    g.f("      double* st = stage + quad * %d + c;", 3 * prog_out);
-    for (int k = 0; k < P.n_out; ++k) {
-      const int k0 = pv->out[0][k], k1 = pv->out[1][k];
-      if (k1 >= 0) g.f("      st[q1 ? %d : %d] = p%d;", 3 * k1, 3 * k0, P.out_point[k]);
-      else g.f("      if (!q1) st[%d] = p%d;", 3 * k0, P.out_point[k]);
-    }
-    for (size_t k = 0; k < pv->shared_out.size(); ++k)
-      g.f("      if (!q1) st[%d] = gp[%d + c];", 3 * pv->shared_out[k], 3 * pv->shared_pt[k]);
+    stage_record("      ", "q1");
     g.f("    }");
     g.f("    __syncthreads();");
-    g.f("    const long long rem = a.n_problems - wu * %d;", PPW);
-    g.f("    const int n_doubles = (int)(rem < %d ? rem : %d) * %d;", PPW, PPW, 3 * prog_out);
-    g.f("    double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * %d * %d);", PPW, 3 * prog_out);
-    g.f("    const double2* src = reinterpret_cast<const double2*>(stage);");
-    g.f("    for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-    g.f("    if ((n_doubles & 1) && lane == 0) a.out_pos[wu * %d * %d + n_doubles - 1] = stage[n_doubles - 1];", PPW, 3 * prog_out);
+    copy_block_out("    ", "stage", RECP);
     g.f("    __syncthreads();");
     g.f("  }");
     g.f("}");
@@ -3473,35 +3447,26 @@ class QuadModule {
   // ---- output positions from free coordinates (okx_expand_positions_batch): fixed points from the design table,
   //      every derived point re-evaluated, records written like the solve kernel's ----
   void emit_expand() {
-    g.f("struct QExpandArgs { const double* free; const double* geom_pos; double* out_pos; long long n_problems, steps_per_geometry;");
-    g.f("  const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQExpandArgsDecl;
     g.f("extern \"C\" __global__ void __launch_bounds__(64) okx_quad_expand(QExpandArgs a) {");
-    g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    open_lanes();
+    unit_vectors();
     g.f("  (void)e0; (void)e1; (void)e2;");
     if (ev.lds_constants) g.out += lds_decl;
     g.f("  __shared__ double stage[16 * %d];", 3 * P.n_out);
-    g.f("  for (long long wu = blockIdx.x; wu * 16 < a.n_problems; wu += gridDim.x) {");
-    g.f("    long long bb = wu * 16 + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;");
+    open_unit_loop("bb", "a.n_problems");
     g.f("    const long long geom = a.geom_pos != nullptr ? bb / a.steps_per_geometry : 0;");
     g.f("    const double* gp = a.geom_pos != nullptr ? a.geom_pos + geom * %d : a.design_pos;", 3 * NP);
     g.f("    const double* gq = a.row_param; (void)gq;");
     g.out += ev.hoisted;
-    for (int p = 0; p < NP; ++p)
-      if (used[p]) g.f("    double p%d = ld3(gp + %d + cc, c);", p, 3 * p);
+    load_used_points("    ");
     for (int F = 0; F < nf; ++F) g.f("    p%d = ld3(a.free + bb * %d + %d + cc, c);", ev.fp(F), 3 * nf, 3 * ev.perm[F]);
     g.out += final_src;
     g.f("    if (c < 3) {");
-    g.f("      double* st = stage + quad * %d + c;", 3 * P.n_out);
-    for (int k = 0; k < P.n_out; ++k) g.f("      st[%d] = p%d;", 3 * k, P.out_point[k]);
+    stage_record("      ");
     g.f("    }");
     g.f("    __syncthreads();");
-    g.f("    const long long rem = a.n_problems - wu * 16;");
-    g.f("    const int n_doubles = (int)(rem < 16 ? rem : 16) * %d;", 3 * P.n_out);
-    g.f("    double2* dst = reinterpret_cast<double2*>(a.out_pos + wu * 16 * %d);", 3 * P.n_out);
-    g.f("    const double2* src = reinterpret_cast<const double2*>(stage);");
-    g.f("    for (int i = lane; i < n_doubles / 2; i += 64) dst[i] = src[i];");
-    g.f("    if ((n_doubles & 1) && lane == 0) a.out_pos[wu * 16 * %d + n_doubles - 1] = stage[n_doubles - 1];", 3 * P.n_out);
+    copy_block_out("    ", "stage", REC);
     g.f("    __syncthreads();");
     g.f("  }");
     g.f("}");
@@ -3509,17 +3474,15 @@ class QuadModule {
   }
   // ---- parity / debug kernel: r, J^T J, J^T r at given x, and the damped step for a given lambda ----
   void emit_eval_debug() {
-    g.f("struct QEvalArgs { const double* x; const double* targets; double* r; double* ata; double* atr; double* dx;");
-    g.f("  double lambda; long long n_problems; const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQEvalArgsDecl;
     g.f("extern \"C\" __global__ void __launch_bounds__(64, %d) okx_quad_eval(QEvalArgs a) {", waves_per_simd);
-    g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+    open_lanes();
     g.out += atan_decl;
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    unit_vectors();
     if (ev.lds_constants) g.out += lds_decl;
     g.f("  const double* gp = a.design_pos; const double* gq = a.row_param;");
     g.out += ev.hoisted;
-    g.f("  for (long long wu = blockIdx.x; wu * 16 < a.n_problems; wu += gridDim.x) {");
-    g.f("    long long bb = wu * 16 + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;");
+    open_unit_loop("bb", "a.n_problems");
     for (int p = 0; p < NP; ++p)
       if (used[p]) g.f("    double p%d = c < 3 ? gp[%d + cc] : 0.0;", p, 3 * p);
     for (int F = 0; F < nf; ++F) g.f("    p%d = c < 3 ? a.x[bb * %d + %d + cc] : 0.0;", ev.fp(F), 3 * nf, 3 * ev.perm[F]);
@@ -3573,27 +3536,19 @@ class QuadModule {
       return false;
     }
     const std::string factor_src = capture(ev, [&] { ev.emit_factor(); });
-    g.f("typedef struct { double min_pivot, max_pivot; int flags, reserved; } okx_tangent_info;");
-    g.f("struct QTanArgs { const double* pos; const double* geom_pos; const double* geom_row_param; double* tan;");
-    g.f("  okx_tangent_info* tinfo; long long n_problems, steps_per_geometry;");
-    g.f("  const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQTanArgsDecl;
     g.f("template <bool PG> DEV void okx_quad_tangent_body(const QTanArgs& a) {");
-    if (pv)
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, q1 = (lane >> 2) & 1, cc = c < 3 ? c : 2;");
-    else
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+    open_lanes("q1");
     g.out += atan_decl;
     if (ev.lds_constants) g.out += lds_decl;
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
-    g.f("  for (long long wu = blockIdx.x; wu * %d < a.n_problems; wu += gridDim.x) {", PPW);
-    g.f("    long long bb = wu * %d + quad; const bool valid = bb < a.n_problems; if (!valid) bb = a.n_problems - 1;", PPW);
+    unit_vectors();
+    open_unit_loop("bb", "a.n_problems");
     g.f("    const long long geom = a.steps_per_geometry > 0 ? bb / a.steps_per_geometry : 0;");
     g.f("    const double* gp = PG ? a.geom_pos + geom * %d : a.design_pos;", 3 * prog_points);
     g.f("    const double* gq = PG ? a.geom_row_param + geom * %d : a.row_param;", 8 * prog_crows);
     g.out += ev.hoisted;
     g.out += couple_hoist;
-    for (int p = 0; p < NP; ++p)
-      if (used[p]) g.f("    double p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
+    load_used_points("    ");
     for (int F = 0; F < nf; ++F) {
       const int k = out_index[ev.fp(F)];
       const std::string off = pv ? Gen::sel(3 * pv->out[0][k], 3 * pv->out[1][k]) : std::to_string(3 * k);
@@ -3732,24 +3687,18 @@ class QuadModule {
   }
   void head_design_state(const HeadKernel& h) {
     const int n_fd_dirs = h.n_fd_dirs, fd_rows = h.fd_rows;
-    g.f("struct QHeadArgs { const double* geom_pos; const double* geom_row_param; double* head; long long n_geometries; double lambda0;");
-    g.f("  const double* design_pos; const double* row_param; const double* dop_param; };");
+    g.out += kQHeadArgsDecl;
     g.f("template <bool PG> DEV void okx_quad_head_body(const QHeadArgs& a) {");
-    if (pv)
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 3, q1 = (lane >> 2) & 1, cc = c < 3 ? c : 2;");
-    else
-      g.f("  const int lane = threadIdx.x, c = lane & 3, quad = lane >> 2, cc = c < 3 ? c : 2;");
+    open_lanes("q1");
     g.out += atan_decl;
-    g.f("  const double e0 = c == 0 ? 1.0 : 0.0, e1 = c == 1 ? 1.0 : 0.0, e2 = c == 2 ? 1.0 : 0.0;");
+    unit_vectors();
     if (ev.lds_constants) g.out += lds_decl;
-    g.f("  for (long long wu = blockIdx.x; wu * %d < a.n_geometries; wu += gridDim.x) {", PPW);
-    g.f("    long long geom = wu * %d + quad; const bool valid = geom < a.n_geometries; if (!valid) geom = a.n_geometries - 1;", PPW);
+    open_unit_loop("geom", "a.n_geometries");
     g.f("    const double* gp = PG ? a.geom_pos + geom * %d : a.design_pos;", 3 * prog_points);
     g.f("    const double* gq = PG ? a.geom_row_param + geom * %d : a.row_param;", 8 * prog_crows);
     g.out += ev.hoisted;
     g.out += couple_hoist;
-    for (int p = 0; p < NP; ++p)
-      if (used[p]) g.f("    double p%d = ld3(gp + %s + cc, c);", p, ev.point3(p).c_str());
+    load_used_points("    ");
     // targets at their design values: the target rows vanish, ss / mres_new are the constraint rows' alone
     ev.reset_caches();
     g.out += capture(ev, [&] {
