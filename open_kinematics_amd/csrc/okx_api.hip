@@ -1,7 +1,8 @@
-// okx_api.hip — the C-ABI of include/okx.h on top of the gfx950 kernels: everything that has to see the kernels
-// (kernel selection, launches) and the extern "C" entry points.  The program object and the shared helpers are in
-// okx_program.hpp, the generated kernels' life cycle (compile job, module loads, first-step tables) in okx_attach.cpp,
-// the choice of kernel family, start mode, chain length and grid for a launch in okx_launch.cpp.
+// okx_api.hip — the C-ABI of include/okx.h on top of the interpreter kernels: everything that has to see them (kernel
+// selection, their launches), the solve path and the program's life cycle.  The program object and the shared helpers are in
+// okx_program.hpp (which says what the other units hold), the generated kernels' life cycle (compile job, module loads,
+// first-step tables) in okx_attach.cpp, the choice of kernel family, start mode, chain length and grid for a launch in
+// okx_launch.cpp.  Every other pass keeps its entry points beside its kernels, in a unit of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -9,7 +10,6 @@
 #include <cstring>
 #include <new>
 
-#include <cmath>
 #include <functional>
 #include <memory>
 #include <string>
@@ -17,10 +17,6 @@
 
 #include "okx_kernels.hip"
 #include "okx_packed.hip"
-#include "okx_metrics.hip"
-#include "okx_shim.hip"
-#include "okx_diagnose.hip"
-#include "okx_ensemble.hip"
 #include "okx_program.hpp"
 #include "okx_launch.hpp"
 
@@ -34,10 +30,13 @@ using okx::kMaxLdsBytes;
 using okx::attach_when_ready;
 using okx::quad_waves_per_simd;
 using okx::stream_is_capturing;
+using okx::fill_launch_caps;
+using okx::geometry_tables_paired;
+using okx::steps_per_geometry_fits;
+using okx::with_dev_program;
 
 typedef void (*solve_kernel_t)(const okx::DevProgram*, okx::SolveArgs);
 typedef void (*packed_kernel_t)(const okx::DevProgram*, okx::SolveArgs, int);
-
 
 // Every program gets the one-problem-per-wavefront kernel (register LDL^T, template on the
 // padded row length) and, when a problem fits 32 lanes, the lane-group packed kernel too.
@@ -116,6 +115,66 @@ int grid_for(const okx_program* p, long long units) {
 }
 
 }  // namespace
+
+// What the other units of the C-ABI use of this one (declared in okx_program.hpp).
+namespace okx {
+
+// What okx_quad_source / okx_lane_source / the precompile entry points share: the DevProgram of `desc`, handed to `use`
+// (which returns an okx_status and reports its own failures through fail()).
+int with_dev_program(const okx_program_desc* desc, const std::function<int(const DevProgram&)>& use) {
+  DevProgram* tmp = new (std::nothrow) DevProgram;
+  if (!tmp) return fail(OKX_ERR_ALLOC, "out of host memory");
+  int rc = build_dev_program(desc, tmp, g_err, (int)sizeof(g_err));
+  if (rc == OKX_OK) rc = use(*tmp);
+  delete tmp;
+  return rc;
+}
+
+// The shape of a batch with optional per-geometry tables (every entry point that takes one; each has its own message texts)
+bool geometry_tables_paired(const double* d_geom_pos, const double* d_geom_row_param) {
+  return (d_geom_pos == nullptr) == (d_geom_row_param == nullptr);
+}
+bool steps_per_geometry_fits(long long n_problems, long long spg, bool geometry_tables) {
+  return !(spg < 0 || (geometry_tables && spg == 0) || (spg > 0 && n_problems % spg != 0));
+}
+
+// What the planner reads of a program (under the program's shared lock); the developer switches as the environment has them.
+void fill_launch_caps(const okx_program* p, okx_launch_caps* c) {
+  c->lane_min_problems = p->lane_min_problems;
+  c->n_cu = p->n_cu;
+  c->n = p->host.n;
+  c->nreg = p->nreg;
+  c->n_targets = p->host.n_targets;
+  c->blocks_per_cu = p->blocks_per_cu;
+  c->packed_blocks_per_cu = p->packed_blocks_per_cu;
+  c->groups = p->groups;
+  c->has_packed = p->packed_fn != nullptr;
+  c->has_quad = p->quad_fn_u != nullptr;
+  c->quad_ppw = p->quad_ppw;
+  c->quad_waves_per_cu = p->quad_waves_per_cu;
+  c->has_head = p->quad_fn_head_u != nullptr;
+  c->has_cold = p->quad_fn_cold_u != nullptr;
+  c->has_lane = p->lane_fn_u != nullptr;
+  c->lane_cold_ok = p->lane_cold_ok;
+  c->lane_chain_ok = p->lane_chain_ok;
+  c->has_nest = p->lane_nest[0] != nullptr;
+  c->has_refine = p->lane_refine[0] != nullptr;
+  c->ev_enabled = p->ev_solve_u != nullptr;
+  c->ev_lane = p->ev_lane_u != nullptr;
+  c->ev_cold = p->ev_cold_u != nullptr;
+  c->ev_lane_pos = p->ev_lane_pos_u != nullptr;
+  c->line_row = p->line_row;
+  c->trace = p->quad_trace != nullptr;
+  c->predictor = p->predictor_dev != nullptr;
+  const bool dev = std::getenv("OKX_DEV") != nullptr;  // (one look at the environment per launch)
+  c->lane_timeline = dev && okx::dev_switch("lane_timeline");
+  c->quad_timeline = dev && okx::dev_switch("quad_timeline");
+  c->no_cold = dev && okx::dev_switch("no_cold");
+  c->evaluate_quad = dev && okx::dev_switch("evaluate_quad");
+  c->evaluate_lane = dev && okx::dev_switch("evaluate_lane");
+}
+
+}  // namespace okx
 
 extern "C" {
 
@@ -226,16 +285,6 @@ int32_t okx_program_lane_bodies(const okx_program* p) {
   return p && p->lane_fn_u ? (p->lane_cold_ok ? 1 : 0) | (p->lane_chain_ok ? 2 : 0) : 0;
 }
 
-/* What okx_quad_source / okx_lane_source / okx_precompile share: the DevProgram of `desc`, handed to `use` (which returns
-   an okx_status and reports its own failures through fail()). */
-static int with_dev_program(const okx_program_desc* desc, const std::function<int(const okx::DevProgram&)>& use) {
-  okx::DevProgram* tmp = new (std::nothrow) okx::DevProgram;
-  if (!tmp) return fail(OKX_ERR_ALLOC, "out of host memory");
-  int rc = okx::build_dev_program(desc, tmp, g_err, (int)sizeof(g_err));
-  if (rc == OKX_OK) rc = use(*tmp);
-  delete tmp;
-  return rc;
-}
 /* Generated source of a program's kernel of one family into the caller's buffer: the number of bytes the full text needs
    (including the terminator) or a negative okx_status. */
 static int64_t generated_source(const okx_program_desc* desc, char* buf, int64_t buflen, const char* family,
@@ -317,19 +366,9 @@ int32_t okx_debug_lane_scratch(const okx_program_desc* desc, int32_t* out3) {
   });
 }
 
-static int32_t check_corner_roles(const okx_corner_roles* roles, int32_t n_out, const char* who);
-
 }  // extern "C"
 
 namespace {
-
-// The shape of a batch with optional per-geometry tables (every entry point that takes one; each has its own message texts)
-bool geometry_tables_paired(const double* d_geom_pos, const double* d_geom_row_param) {
-  return (d_geom_pos == nullptr) == (d_geom_row_param == nullptr);
-}
-bool steps_per_geometry_fits(long long n_problems, long long spg, bool geometry_tables) {
-  return !(spg < 0 || (geometry_tables && spg == 0) || (spg > 0 && n_problems % spg != 0));
-}
 
 // One launch of okx_solve_batch / okx_solve_evaluated_batch (`evaluated`: the launch runs the program's evaluated kernels,
 // whose epilogue writes d_tangents / d_eval).
@@ -381,42 +420,6 @@ int32_t validate_launch(const okx_program* p, const okx_solve_opts* opts, int64_
   if (opts->max_iter < 1) return fail(OKX_ERR_INVALID, "max_iter must be >= 1");
   if (!(opts->lambda0 >= 0.0) || !(opts->lambda0 < 1e300)) return fail(OKX_ERR_INVALID, "lambda0 must be finite and >= 0");
   return OKX_OK;
-}
-
-// What the planner reads of a program (under the program's shared lock); the developer switches as the environment has them.
-void fill_launch_caps(const okx_program* p, okx_launch_caps* c) {
-  c->lane_min_problems = p->lane_min_problems;
-  c->n_cu = p->n_cu;
-  c->n = p->host.n;
-  c->nreg = p->nreg;
-  c->n_targets = p->host.n_targets;
-  c->blocks_per_cu = p->blocks_per_cu;
-  c->packed_blocks_per_cu = p->packed_blocks_per_cu;
-  c->groups = p->groups;
-  c->has_packed = p->packed_fn != nullptr;
-  c->has_quad = p->quad_fn_u != nullptr;
-  c->quad_ppw = p->quad_ppw;
-  c->quad_waves_per_cu = p->quad_waves_per_cu;
-  c->has_head = p->quad_fn_head_u != nullptr;
-  c->has_cold = p->quad_fn_cold_u != nullptr;
-  c->has_lane = p->lane_fn_u != nullptr;
-  c->lane_cold_ok = p->lane_cold_ok;
-  c->lane_chain_ok = p->lane_chain_ok;
-  c->has_nest = p->lane_nest[0] != nullptr;
-  c->has_refine = p->lane_refine[0] != nullptr;
-  c->ev_enabled = p->ev_solve_u != nullptr;
-  c->ev_lane = p->ev_lane_u != nullptr;
-  c->ev_cold = p->ev_cold_u != nullptr;
-  c->ev_lane_pos = p->ev_lane_pos_u != nullptr;
-  c->line_row = p->line_row;
-  c->trace = p->quad_trace != nullptr;
-  c->predictor = p->predictor_dev != nullptr;
-  const bool dev = std::getenv("OKX_DEV") != nullptr;  // (one look at the environment per launch)
-  c->lane_timeline = dev && okx::dev_switch("lane_timeline");
-  c->quad_timeline = dev && okx::dev_switch("quad_timeline");
-  c->no_cold = dev && okx::dev_switch("no_cold");
-  c->evaluate_quad = dev && okx::dev_switch("evaluate_quad");
-  c->evaluate_lane = dev && okx::dev_switch("evaluate_lane");
 }
 
 // The first-step table of a launch into q->head: the own geometry's (found or filled, okx::own_head_table) or the per-geometry
@@ -562,6 +565,25 @@ int32_t launch_quad(const SolveCall& c, const okx::LaunchPlan& plan) {
   return OKX_OK;
 }
 
+// Arguments of the interpreter kernels for independent confirmed solves on the program's own geometry: a launch sets what
+// differs (okx_debug_phase_profile: nothing but its counters).
+okx::SolveArgs interpreter_args(const okx_solve_opts* opts, int64_t n_problems, const double* d_targets, double* d_out_pos, okx_info* d_info) {
+  okx::SolveArgs a{};  // (no geometry tables, steps_per_geometry 0, no phase counters)
+  a.targets = d_targets;
+  a.out_pos = d_out_pos;
+  a.info = d_info;
+  a.n_problems = n_problems;
+  a.max_iter = opts->max_iter;
+  a.confirm = 1;
+  a.chain_len = 1;
+  a.step_tol = opts->step_tol;
+  a.grad_tol = opts->grad_tol;
+  a.ftol = opts->ftol;
+  a.lambda0 = opts->lambda0;
+  a.residual_tolerance = opts->residual_tolerance;
+  return a;
+}
+
 // the interpreter kernels: one problem per wavefront, or the lane-group packed kernel
 int32_t launch_interpreter(const SolveCall& c, const okx::LaunchPlan& plan) {
   const okx_program* p = c.p;
@@ -569,23 +591,12 @@ int32_t launch_interpreter(const SolveCall& c, const okx::LaunchPlan& plan) {
   if (opts->output != OKX_OUTPUT_RECORDS)
     return fail(OKX_ERR_INVALID, "output mode %d needs a generated kernel (this launch runs the interpreter: %s)", opts->output,
                 p->quad_note[0] ? p->quad_note : "kernel option");
-  okx::SolveArgs a;
-  a.targets = c.d_targets;
+  okx::SolveArgs a = interpreter_args(opts, c.n_problems, c.d_targets, c.d_out_pos, c.d_info);
   a.geom_pos = c.d_geom_pos;
   a.geom_row_param = c.d_geom_row_param;
-  a.out_pos = c.d_out_pos;
-  a.info = c.d_info;
-  a.n_problems = c.n_problems;
   a.steps_per_geometry = opts->steps_per_geometry;
-  a.max_iter = opts->max_iter;
   a.confirm = plan.confirm;
   a.chain_len = plan.chain_len;
-  a.step_tol = opts->step_tol;
-  a.grad_tol = opts->grad_tol;
-  a.ftol = opts->ftol;
-  a.lambda0 = opts->lambda0;
-  a.residual_tolerance = opts->residual_tolerance;
-  a.phase_cycles = nullptr;
   const okx::DevProgram* dev = p->dev;
   if (plan.family == okx::kFamilyPacked) {
     int width = p->group_width;
@@ -707,392 +718,13 @@ int32_t okx_debug_program_caps(okx_program* p, okx_launch_caps* caps) {
   return OKX_OK;
 }
 
-int32_t okx_program_enable_evaluation(okx_program* p, const okx_corner_roles* roles) {
-  if (!p || !roles) return fail(OKX_ERR_INVALID, "null program or roles");
-  if (int32_t rc = check_corner_roles(roles, p->host.n_out, "roles")) return rc;
-  attach_when_ready(p, true);  // the evaluated kernels share the solve kernels' first-step tables: those first
-  okx::EvalSpec spec;
-  std::string why;
-  if (!okx::eval_spec_from_roles(p->host, *roles, &spec, &why)) return fail(OKX_ERR_INVALID, "%s", why.c_str());
-  bool with_lane = false;
-  {
-    std::shared_lock<std::shared_mutex> readers(p->kern_mutex);
-    if (!p->quad_fn_u || p->quad_ppw != 16) {
-      const std::string note = p->quad_note[0] ? p->quad_note : "a pair-mode program";
-      readers.unlock();
-      std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-      std::snprintf(p->ev_note, sizeof(p->ev_note), "no single-mode quad kernel (%.180s)", note.c_str());
-      return fail(OKX_ERR_INVALID, "evaluated solves need the program's single-mode quad kernel: %s", p->ev_note);
-    }
-    if (p->ev_solve_u && std::memcmp(&spec, &p->ev_spec, sizeof(spec)) == 0) {
-      // same role points as before: only the numbers change (launches read them as a kernel argument)
-      readers.unlock();
-      std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-      okx::eval_scalars_from_roles(*roles, &p->ev_cfg);
-      return OKX_OK;
-    }
-    with_lane = p->lane_fn_u != nullptr && !okx::dev_switch("no_lane");
-  }
-  // generate + compile (or fetch from the cache) outside the lock: launches of this program go on meanwhile
-  std::string code, lcode, lwhy;
-  int lane_scratch = -1;
-  if (!okx::quad_eval_build(p->host, spec, quad_waves_per_simd(), &code, &why)) {
-    std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-    std::snprintf(p->ev_note, sizeof(p->ev_note), "%.250s", why.c_str());
-    return fail(OKX_ERR_LIMIT, "no evaluated kernels for this program: %s", why.c_str());
-  }
-  const bool lane_built = with_lane && okx::lane_eval_build(p->host, spec, &lcode, &lwhy, false, &lane_scratch);
-  std::unique_lock<std::shared_mutex> kernels(p->kern_mutex);
-  hipFunction_t su = nullptr;
-  if (const int32_t rc = okx::load_evaluated_module(p, code, &su)) return rc;
-  p->ev_spec = spec;
-  p->ev_axle = false;
-  okx::eval_scalars_from_roles(*roles, &p->ev_cfg);
-  // the lane form, for programs whose solves have one (failure only means the quad form serves every batch size)
-  if (with_lane && !lane_built) {
-    std::snprintf(p->ev_note, sizeof(p->ev_note), "no lane form: %.230s", lwhy.c_str());
-  } else if (with_lane && lane_scratch > 512) {
-    std::snprintf(p->ev_note, sizeof(p->ev_note), "the lane form spills %d B of scratch: not used", lane_scratch);
-  } else if (with_lane) {
-    hipModule_t lmod = nullptr;
-    if (hipModuleLoadData(&lmod, lcode.data()) == hipSuccess &&
-        hipModuleGetFunction(&p->ev_lane_u, lmod, "okx_lane_evsolve_u") == hipSuccess &&
-        hipModuleGetFunction(&p->ev_lane_g, lmod, "okx_lane_evsolve_g") == hipSuccess) {
-      p->ev_lane_mod = lmod;
-      p->ev_lane_scratch = lane_scratch;
-      // the same epilogue on given states (optional: programs whose free points are not all output points have none)
-      if (hipModuleGetFunction(&p->ev_lane_pos_u, lmod, "okx_lane_evaluate_u") != hipSuccess ||
-          hipModuleGetFunction(&p->ev_lane_pos_g, lmod, "okx_lane_evaluate_g") != hipSuccess) {
-        (void)hipGetLastError();
-        p->ev_lane_pos_u = p->ev_lane_pos_g = nullptr;
-      }
-    } else {
-      (void)hipGetLastError();
-      if (lmod) (void)hipModuleUnload(lmod);
-      p->ev_lane_u = p->ev_lane_g = nullptr;
-      p->ev_lane_pos_u = p->ev_lane_pos_g = nullptr;
-      std::snprintf(p->ev_note, sizeof(p->ev_note), "the lane form's code object did not load");
-    }
-  }
-  p->ev_solve_u = su;  // the gate of the evaluated launch paths
-  return OKX_OK;
-}
-
-int32_t okx_program_evaluation(const okx_program* p) { return p && p->ev_solve_u ? 1 | (p->ev_lane_u ? 2 : 0) : 0; }
-const char* okx_program_evaluation_note(const okx_program* p) { return p ? p->ev_note : ""; }
-int32_t okx_program_eval_columns(const okx_program* p) {
-  return p && p->ev_solve_u ? (p->ev_axle ? OKX_EVAL_AXLE_COLUMNS : OKX_EVAL_COLUMNS) : 0;
-}
-
-static int32_t check_axle_roles(const okx_axle_roles* roles, int32_t n_out) {
-  if (int32_t rc = check_corner_roles(&roles->left, n_out, "left")) return rc;
-  if (int32_t rc = check_corner_roles(&roles->right, n_out, "right")) return rc;
-  if (roles->n_roles < 0 || roles->n_roles > OKX_MAX_ROTATIONS) return fail(OKX_ERR_INVALID, "n_roles must be 0 .. %d", OKX_MAX_ROTATIONS);
-  return OKX_OK;
-}
-
-static void axle_numbers_from_roles(okx_program* p, const okx_axle_roles* roles) {
-  okx::eval_scalars_from_roles(roles->left, &p->ev_cfg);
-  okx::eval_scalars_from_roles(roles->right, &p->ev_cfg_r);
-  std::memset(p->ev_roles, 0, sizeof(p->ev_roles));
-  for (int k = 0; k < roles->n_roles; ++k) {
-    const okx_rotation_role& r = roles->roles[k];
-    okx::EvalRoleNum& n = p->ev_roles[k];
-    for (int i = 0; i < 3; ++i) n.design[i] = r.design[i], n.axis_point[i] = r.axis_point[i], n.axis_dir[i] = r.axis_dir[i];
-    n.scale = r.scale;
-  }
-}
-
-/* okx_program_enable_evaluation for a composed axle (pair-mode program): see okx.h. */
-int32_t okx_program_enable_axle_evaluation(okx_program* p, const okx_axle_roles* roles) {
-  if (!p || !roles) return fail(OKX_ERR_INVALID, "null program or roles");
-  if (int32_t rc = check_axle_roles(roles, p->host.n_out)) return rc;
-  attach_when_ready(p, true);
-  okx::AxleEvalSpec spec;
-  std::memset(&spec, 0, sizeof(spec));
-  std::string why;
-  if (!okx::axle_eval_spec_from_roles(p->host, *roles, &spec, &why)) return fail(OKX_ERR_INVALID, "%s", why.c_str());
-  {
-    std::shared_lock<std::shared_mutex> readers(p->kern_mutex);
-    if (!p->quad_fn_u || p->quad_ppw != 8) {
-      const std::string note = p->quad_note[0] ? p->quad_note : "a single-mode program (use okx_program_enable_evaluation)";
-      readers.unlock();
-      std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-      std::snprintf(p->ev_note, sizeof(p->ev_note), "no pair-mode quad kernel (%.180s)", note.c_str());
-      return fail(OKX_ERR_INVALID, "an axle's evaluated solves need the program's pair-mode quad kernel: %s", p->ev_note);
-    }
-    if (p->ev_solve_u && p->ev_axle && std::memcmp(&spec, &p->ev_axle_spec, sizeof(spec)) == 0) {
-      readers.unlock();
-      std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-      axle_numbers_from_roles(p, roles);  // same points: only the numbers change (launches read them as kernel arguments)
-      return OKX_OK;
-    }
-  }
-  std::string code;
-  if (!okx::quad_axle_eval_build(p->host, spec, quad_waves_per_simd(), &code, &why)) {
-    std::unique_lock<std::shared_mutex> writer(p->kern_mutex);
-    std::snprintf(p->ev_note, sizeof(p->ev_note), "%.250s", why.c_str());
-    return fail(OKX_ERR_LIMIT, "no evaluated kernels for this program: %s", why.c_str());
-  }
-  std::unique_lock<std::shared_mutex> kernels(p->kern_mutex);
-  hipFunction_t su = nullptr;
-  if (const int32_t rc = okx::load_evaluated_module(p, code, &su)) return rc;
-  p->ev_axle = true;
-  p->ev_axle_spec = spec;
-  axle_numbers_from_roles(p, roles);
-  p->ev_solve_u = su;  // the gate of the evaluated launch paths
-  return OKX_OK;
-}
-
-int32_t okx_precompile_axle_evaluation(const okx_program_desc* desc, const okx_axle_roles* roles) {
-  if (!desc || !roles) return fail(OKX_ERR_INVALID, "null pointer");
-  return with_dev_program(desc, [&](const okx::DevProgram& program) {
-    if (int32_t rc = check_axle_roles(roles, program.n_out)) return (int)rc;
-    okx::AxleEvalSpec spec;
-    std::memset(&spec, 0, sizeof(spec));
-    std::string why, code;
-    if (!okx::axle_eval_spec_from_roles(program, *roles, &spec, &why)) return fail(OKX_ERR_INVALID, "%s", why.c_str());
-    if (!okx::quad_axle_eval_build(program, spec, quad_waves_per_simd(), &code, &why))
-      return fail(why.compare(0, 14, "compile failed") == 0 ? OKX_ERR_DEVICE : OKX_ERR_LIMIT, "no evaluated kernels for this program: %s", why.c_str());
-    return (int)OKX_OK;
-  });
-}
-
-int32_t okx_evaluate_batch(okx_program* p, int64_t n_problems, int64_t steps_per_geometry, const double* d_pos,
-                           const double* d_geom_pos, const double* d_geom_row_param, double* d_tangents, double* d_eval,
-                           void* stream) {
-  if (!p) return fail(OKX_ERR_INVALID, "null program");
-  std::shared_lock<std::shared_mutex> kernels(p->kern_mutex);
-  if (!p->ev_solve_u) return fail(OKX_ERR_INVALID, "okx_evaluate_batch needs okx_program_enable_evaluation first%s%s", p->ev_note[0] ? ": " : "", p->ev_note);
-  if (n_problems < 0) return fail(OKX_ERR_INVALID, "negative problem count");
-  if (n_problems == 0) return OKX_OK;
-  if (!d_pos || (!d_tangents && !d_eval)) return fail(OKX_ERR_INVALID, "null pointer");
-  if (!geometry_tables_paired(d_geom_pos, d_geom_row_param))
-    return fail(OKX_ERR_INVALID, "geometry positions and row parameters must be given together");
-  if (!steps_per_geometry_fits(n_problems, steps_per_geometry, d_geom_pos != nullptr)) return fail(OKX_ERR_INVALID, "bad steps_per_geometry");
-  {
-    okx_launch_caps caps;
-    fill_launch_caps(p, &caps);  // (evaluate_on_lane reads n_cu, ev_lane_pos and the evaluate_quad / evaluate_lane switches of it)
-    long long units = 0;
-    if (okx::evaluate_on_lane(caps, n_problems, steps_per_geometry, &units)) {
-      okx::QuadEvArgs qe{};
-      okx::QuadArgs& a = qe.q;
-      a.targets = d_pos;  // (the GIVEN bodies read the records through this pointer: okx_lanegen.cpp)
-      a.geom_pos = d_geom_pos;
-      a.geom_row_param = d_geom_row_param;
-      a.out_pos = nullptr;
-      a.info = nullptr;
-      a.n_problems = n_problems;
-      a.steps_per_geometry = steps_per_geometry;
-      a.chain_len = 1;
-      a.max_iter = 0;
-      a.confirm = 0;
-      a.step_tol = a.ftol = a.lambda0 = a.residual_tolerance = 0.0;
-      a.grad_tol = 0.0;
-      okx::set_program_tables(p, &a);
-      a.trace = nullptr;
-      a.trace_problem = 0;
-      a.predictor = nullptr;
-      a.predictor_mode = 0;
-      a.predictor_len = 0;
-      a.head = nullptr;
-      a.out_mode = OKX_OUTPUT_NONE;
-      qe.tan = d_tangents;
-      qe.ev = d_eval;
-      qe.cfg = p->ev_cfg;
-      const long long cap = (long long)p->n_cu * 4;
-      void* kargs[] = {(void*)&qe};
-      HIP_TRY(hipModuleLaunchKernel(d_geom_pos ? p->ev_lane_pos_g : p->ev_lane_pos_u, (int)(units < cap ? units : cap), 1, 1, okx::kWave, 1, 1,
-                                    0, (hipStream_t)stream, kargs, nullptr));
-      return OKX_OK;
-    }
-  }
-  okx::QuadEvPosArgs q;
-  q.pos = d_pos;
-  q.geom_pos = d_geom_pos;
-  q.geom_row_param = d_geom_row_param;
-  q.tan = d_tangents;
-  q.ev = d_eval;
-  q.n_problems = n_problems;
-  q.steps_per_geometry = steps_per_geometry > 0 ? steps_per_geometry : n_problems;
-  okx::set_program_tables(p, &q);
-  q.cfg = p->ev_cfg;
-  q.cfg_r = p->ev_cfg_r;
-  std::memcpy(q.roles, p->ev_roles, sizeof(q.roles));
-  const long long waves = (n_problems + p->quad_ppw - 1) / p->quad_ppw;
-  // (a streaming launch: several rounds' worth of workgroups - but an axle's own-geometry body keeps its chain constants and
-  //  fixed points across a persistent loop: one wavefront per SIMD)
-  const long long cap = (long long)p->n_cu * p->quad_waves_per_cu * (p->ev_axle && !d_geom_pos ? 1 : 8);
-  void* kargs[] = {(void*)&q};
-  HIP_TRY(hipModuleLaunchKernel(d_geom_pos ? p->ev_pos_g : p->ev_pos_u, (int)(waves < cap ? waves : cap), 1, 1, okx::kWave, 1, 1, 0,
-                                (hipStream_t)stream, kargs, nullptr));
-  return OKX_OK;
-}
-
-int32_t okx_precompile_evaluation(const okx_program_desc* desc, const okx_corner_roles* roles) {
-  if (!desc || !roles) return fail(OKX_ERR_INVALID, "null pointer");
-  return with_dev_program(desc, [&](const okx::DevProgram& program) {
-    okx::EvalSpec spec;
-    std::string why, code;
-    if (!okx::eval_spec_from_roles(program, *roles, &spec, &why)) return fail(OKX_ERR_INVALID, "%s", why.c_str());
-    if (!okx::quad_eval_build(program, spec, quad_waves_per_simd(), &code, &why))
-      return fail(why.compare(0, 14, "compile failed") == 0 ? OKX_ERR_DEVICE : OKX_ERR_LIMIT, "no evaluated kernels for this program: %s", why.c_str());
-    if (program.n_free <= okx::kLaneMaxFree) {
-      std::string lcode, lwhy;
-      (void)okx::lane_eval_build(program, spec, &lcode, &lwhy);  // (programs / variants it does not fit simply have no lane form)
-    }
-    return (int)OKX_OK;
-  });
-}
-
-int32_t okx_program_has_predictor(const okx_program* p) { return p && p->predictor_dev ? 1 : 0; }
-
-/* The node solve of okx_program_fit_predictor: the program at `targets` (info->size() cold starts on the quad kernel,
-   synchronous), records and info back on the host. */
-static int32_t solve_predictor_nodes(okx_program* p, const std::vector<double>& targets, std::vector<double>* out, std::vector<okx_info>* info,
-                                     void* stream) {
-  const long long S = (long long)info->size();
-  // one scratch allocation for the node solve: targets | positions | info records
-  const size_t bytes_t = targets.size() * sizeof(double), bytes_out = out->size() * sizeof(double);
-  const size_t bytes_info = (size_t)S * sizeof(okx_info);
-  char* d_scratch = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_scratch, bytes_t + bytes_out + bytes_info));
-  double* d_t = reinterpret_cast<double*>(d_scratch);
-  double* d_out = reinterpret_cast<double*>(d_scratch + bytes_t);
-  okx_info* d_info = reinterpret_cast<okx_info*>(d_scratch + bytes_t + bytes_out);
-  int32_t rc = OKX_OK;
-  okx_solve_opts o;
-  okx_default_opts(&o);
-  o.chain_len = 1;
-  o.kernel = 3;
-  o.confirm_full_pass = 1;  // end on a computed correction: the fit wants every digit
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemcpyAsync(d_t, targets.data(), bytes_t, hipMemcpyHostToDevice, st) != hipSuccess)
-    rc = fail(OKX_ERR_DEVICE, "copy failed");
-  if (rc == OKX_OK) rc = okx_solve_batch(p, &o, S, d_t, nullptr, nullptr, d_out, d_info, stream);
-  if (rc == OKX_OK &&
-      (hipMemcpyAsync(out->data(), d_out, bytes_out, hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipMemcpyAsync(info->data(), d_info, bytes_info, hipMemcpyDeviceToHost, st) != hipSuccess ||
-       hipStreamSynchronize(st) != hipSuccess))
-    rc = fail(OKX_ERR_DEVICE, "node solve failed: %s", hipGetErrorString(hipGetLastError()));
-  (void)hipFree(d_scratch);
-  return rc;
-}
-
-/* Fits the chain-head predictor of a program with a quad kernel over the target box [lo, hi] (absolute
-   target values, host arrays of n_targets; lo[t] == hi[t]: that target is held): solves the program at the
-   (degree + 1)^d Chebyshev nodes of the d varying targets (one cold-start launch, synchronous), takes the
-   tensor Chebyshev coefficients of every free coordinate by discrete orthogonality and keeps the terms up to
-   total degree `degree` (<= 0: 7).  Launches with opts.predictor != 0 on the program's own geometry start
-   every chain head at that polynomial (targets clamped to the box) instead of the design state.  Refitting
-   replaces the previous model. */
-int32_t okx_program_fit_predictor(okx_program* p, const double* lo, const double* hi, int32_t degree, void* stream) {
-  if (!p || !lo || !hi) return fail(OKX_ERR_INVALID, "null pointer");
-  attach_when_ready(p, false);
-  {
-    std::shared_lock<std::shared_mutex> kernels(p->kern_mutex);  // (released before the node solve takes it itself)
-    if (!p->quad_fn_u) return fail(OKX_ERR_INVALID, "the predictor belongs to the quad kernel: %s", p->quad_note);
-    if (p->quad_ppw != 16) return fail(OKX_ERR_INVALID, "pair-mode kernels carry no predictor (register-bound)");
-  }
-  const okx::DevProgram& H = p->host;
-  const int T = H.n_targets;
-  if (T < 1) return fail(OKX_ERR_INVALID, "program has no targets");
-  const int D = degree <= 0 ? okx::kPredictorDegree : degree;
-  if (D > okx::kPredictorMaxDegree) return fail(OKX_ERR_INVALID, "degree must be <= %d", okx::kPredictorMaxDegree);
-  std::vector<int> out_of(H.n_points, -1);
-  for (int k = 0; k < H.n_out; ++k) out_of[H.out_point[k]] = k;
-  for (int f = 0; f < H.n_free; ++f)
-    if (out_of[H.free_point[f]] < 0) return fail(OKX_ERR_INVALID, "free point %d is not an output point", H.free_point[f]);
-  std::vector<double> mid(T), half(T);
-  std::vector<int> deg(T), vary;
-  for (int t = 0; t < T; ++t) {
-    if (!(hi[t] >= lo[t])) return fail(OKX_ERR_INVALID, "target %d: hi < lo", t);
-    mid[t] = 0.5 * (lo[t] + hi[t]);
-    half[t] = 0.5 * (hi[t] - lo[t]);
-    deg[t] = half[t] > 1e-9 ? D : 0;
-    if (deg[t]) vary.push_back(t);
-  }
-  const int d = (int)vary.size(), N = D + 1;
-  long long S = 1;
-  for (int k = 0; k < d; ++k) {
-    S *= N;
-    if (S > 32768) return fail(OKX_ERR_LIMIT, "%d varying targets at degree %d need too many nodes", d, D);
-  }
-  std::vector<double> node(N);
-  for (int a = 0; a < N; ++a) node[a] = cos(3.14159265358979323846 * (a + 0.5) / N);
-  // node k <-> digits a_0 .. a_{d-1} (dimension 0 slowest)
-  auto digit = [&](long long k, int j) {
-    for (int q = d - 1; q > j; --q) k /= N;
-    return (int)(k % N);
-  };
-  std::vector<double> targets((size_t)S * T);
-  for (long long k = 0; k < S; ++k) {
-    for (int t = 0; t < T; ++t) targets[(size_t)k * T + t] = mid[t];
-    for (int j = 0; j < d; ++j) targets[(size_t)k * T + vary[j]] = mid[vary[j]] + half[vary[j]] * node[digit(k, j)];
-  }
-  std::vector<double> out((size_t)S * H.n_out * 3);
-  std::vector<okx_info> info((size_t)S);
-  if (const int32_t rc = solve_predictor_nodes(p, targets, &out, &info, stream)) return rc;
-  for (long long k = 0; k < S; ++k)
-    if (!(info[k].flags & OKX_INFO_CONVERGED) || (info[k].flags & (OKX_INFO_FAILED | OKX_INFO_RESIDUAL_EXCEEDED)))
-      return fail(OKX_ERR_INVALID, "node %lld of the target box did not converge", k);
-  // Chebyshev values at the nodes
-  std::vector<double> cheb((size_t)N * N);  // [i][a] = T_i(node_a)
-  for (int a = 0; a < N; ++a) {
-    cheb[a] = 1.0;
-    if (N > 1) cheb[(size_t)N + a] = node[a];
-    for (int i = 2; i < N; ++i) cheb[(size_t)i * N + a] = 2.0 * node[a] * cheb[(size_t)(i - 1) * N + a] - cheb[(size_t)(i - 2) * N + a];
-  }
-  // Table in the kernel's layout (okx_quadgen.cpp): per target (mid, 1 / half-range, degree), the
-  // total-degree cap, the table length, then one [free][4] block per term in the kernel's loop order:
-  // target 0 outermost, index i_t <= degree_t and <= the remaining total degree.
-  const int nv = H.n_free * 4;
-  std::vector<double> table((size_t)3 * T + 2, 0.0);
-  for (int t = 0; t < T; ++t) {
-    table[3 * t] = mid[t];
-    table[3 * t + 1] = deg[t] ? 1.0 / half[t] : 0.0;
-    table[3 * t + 2] = (double)deg[t];
-  }
-  table[3 * T] = (double)D;
-  std::vector<int> idx(T, 0), slot_of(T, -1);
-  for (int j = 0; j < d; ++j) slot_of[vary[j]] = j;
-  std::vector<double> block(nv);
-  std::function<void(int, int)> walk = [&](int t, int budget) {
-    if (t == T) {
-      std::fill(block.begin(), block.end(), 0.0);
-      double scale = 1.0;
-      for (int j = 0; j < d; ++j) scale *= (idx[vary[j]] == 0 ? 1.0 : 2.0) / N;
-      for (long long k = 0; k < S; ++k) {
-        double w = scale;
-        for (int j = 0; j < d; ++j) w *= cheb[(size_t)idx[vary[j]] * N + digit(k, j)];
-        for (int f = 0; f < H.n_free; ++f) {
-          const int o = out_of[H.free_point[f]];
-          for (int c = 0; c < 3; ++c) block[f * 4 + c] += w * out[((size_t)k * H.n_out + o) * 3 + c];
-        }
-      }
-      table.insert(table.end(), block.begin(), block.end());
-      return;
-    }
-    for (int i = 0; i <= deg[t] && i <= budget; ++i) {
-      idx[t] = i;
-      walk(t + 1, budget - i);
-    }
-    idx[t] = 0;
-  };
-  walk(0, D);
-  table[3 * T + 1] = (double)table.size();
-  double* d_table = nullptr;
-  HIP_TRY(hipMalloc(&d_table, table.size() * sizeof(double)));
-  if (hipMemcpy(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d_table);
-    return fail(OKX_ERR_DEVICE, "copy failed");
-  }
-  if (p->predictor_dev) {
-    HIP_TRY(hipDeviceSynchronize());  // launches in flight may still read the old table
-    (void)hipFree(p->predictor_dev);
-  }
-  p->predictor_dev = d_table;
-  p->predictor_len = (long long)table.size();
+/* The interpreter's evaluation kernel at d_x: residuals, and the Jacobian (okx_eval_batch) or the normal equations
+   (okx_debug_normal_equations). */
+static int32_t launch_eval(okx_program* p, okx::EvalArgs a, void* stream) {
+  const okx::DevProgram* dev = p->dev;
+  void* kargs[] = {(void*)&dev, (void*)&a};
+  HIP_TRY(hipLaunchKernel(p->eval_fn, dim3(grid_for(p, a.n_problems)), dim3(p->threads), kargs, p->lds_bytes,
+                          (hipStream_t)stream));
   return OKX_OK;
 }
 
@@ -1101,19 +733,7 @@ int32_t okx_eval_batch(okx_program* p, int64_t n_problems, const double* d_x,
   if (!p) return fail(OKX_ERR_INVALID, "null program");
   if (n_problems <= 0) return n_problems == 0 ? OKX_OK : fail(OKX_ERR_INVALID, "negative count");
   if (!d_x || !d_r) return fail(OKX_ERR_INVALID, "null pointer");
-  okx::EvalArgs a;
-  a.x = d_x;
-  a.targets = d_targets;
-  a.r = d_r;
-  a.jac = d_jac;
-  a.ata = nullptr;
-  a.atr = nullptr;
-  a.n_problems = n_problems;
-  const okx::DevProgram* dev = p->dev;
-  void* kargs[] = {(void*)&dev, (void*)&a};
-  HIP_TRY(hipLaunchKernel(p->eval_fn, dim3(grid_for(p, n_problems)), dim3(p->threads), kargs, p->lds_bytes,
-                          (hipStream_t)stream));
-  return OKX_OK;
+  return launch_eval(p, {d_x, d_targets, d_r, d_jac, nullptr, nullptr, n_problems}, stream);
 }
 
 /* Test hook (not part of the reference boundary): J^T J and J^T r as the solver forms them. */
@@ -1122,19 +742,7 @@ int32_t okx_debug_normal_equations(okx_program* p, int64_t n_problems, const dou
                                    double* d_atr, void* stream) {
   if (!p || !d_x || !d_r) return fail(OKX_ERR_INVALID, "null pointer");
   if (n_problems <= 0) return OKX_OK;
-  okx::EvalArgs a;
-  a.x = d_x;
-  a.targets = d_targets;
-  a.r = d_r;
-  a.jac = nullptr;
-  a.ata = d_ata;
-  a.atr = d_atr;
-  a.n_problems = n_problems;
-  const okx::DevProgram* dev = p->dev;
-  void* kargs[] = {(void*)&dev, (void*)&a};
-  HIP_TRY(hipLaunchKernel(p->eval_fn, dim3(grid_for(p, n_problems)), dim3(p->threads), kargs, p->lds_bytes,
-                          (hipStream_t)stream));
-  return OKX_OK;
+  return launch_eval(p, {d_x, d_targets, d_r, nullptr, d_ata, d_atr, n_problems}, stream);
 }
 
 int32_t okx_rebind_design(okx_program* p, int64_t n_geometries, const double* d_hardpoints,
@@ -1256,163 +864,6 @@ int32_t okx_tangent_batch(okx_program* p, int64_t n_problems, int64_t steps_per_
   return OKX_OK;
 }
 
-static_assert(sizeof(okx_corner_roles) == 128, "okx_corner_roles layout is part of the ABI (ctypes mirror in metrics.py)");
-
-static int32_t check_corner_roles(const okx_corner_roles* roles, int32_t n_out, const char* who) {
-  const int32_t idx[6] = {roles->wheel_center, roles->contact_patch, roles->axle_inboard,
-                          roles->axle_outboard, roles->steer_lower, roles->steer_upper};
-  for (int k = 0; k < 6; ++k)
-    if (idx[k] < 0 || idx[k] >= n_out) return fail(OKX_ERR_INVALID, "%s: role %d is not an output point", who, k);
-  if (!(roles->side_sign == 1.0 || roles->side_sign == -1.0))
-    return fail(OKX_ERR_INVALID, "%s: side_sign must be +-1", who);
-  const int n_axis = roles->instant_axis_kind == OKX_IA_TWO_PLANES ? 6
-                     : roles->instant_axis_kind == OKX_IA_PLANE_AND_STRUT ? 4
-                     : roles->instant_axis_kind == OKX_IA_NONE ? 0 : -1;
-  if (n_axis < 0) return fail(OKX_ERR_INVALID, "%s: unknown instant_axis_kind %d", who, roles->instant_axis_kind);
-  for (int k = 0; k < n_axis; ++k)
-    if (roles->instant_axis_point[k] < 0 || roles->instant_axis_point[k] >= n_out)
-      return fail(OKX_ERR_INVALID, "%s: instant-axis point %d is not an output point", who, k);
-  if ((roles->damper_top < 0) != (roles->damper_bottom < 0) || roles->damper_top >= n_out || roles->damper_bottom >= n_out)
-    return fail(OKX_ERR_INVALID, "%s: damper points must both be output points or both be -1", who);
-  if (roles->rack_attachment >= n_out) return fail(OKX_ERR_INVALID, "%s: rack attachment is not an output point", who);
-  for (int32_t v : {roles->axle_position, roles->driven_axle})
-    if (v != OKX_AXLE_UNSET && v != OKX_AXLE_FRONT && v != OKX_AXLE_REAR)
-      return fail(OKX_ERR_INVALID, "%s: axle_position / driven_axle must be OKX_AXLE_*", who);
-  return OKX_OK;
-}
-
-int32_t okx_axis_rotation_batch(const okx_rotation_role* roles, int32_t n_roles, int64_t n_states, int32_t n_out,
-                                int32_t n_targets, const double* d_pos, const double* d_tangents, double* d_angles,
-                                double* d_dangles, void* stream) {
-  if (!roles || !d_pos || !d_angles) return fail(OKX_ERR_INVALID, "null pointer");
-  if (n_roles < 1 || n_roles > OKX_MAX_ROTATIONS) return fail(OKX_ERR_INVALID, "1..%d rotations per call", OKX_MAX_ROTATIONS);
-  if (n_states < 0 || n_out <= 0 || n_targets < 0) return fail(OKX_ERR_INVALID, "bad dimension");
-  if ((d_tangents == nullptr) != (d_dangles == nullptr))
-    return fail(OKX_ERR_INVALID, "tangents and derivative output must be given together");
-  okx::RotationArgs a;
-  for (int k = 0; k < n_roles; ++k) {
-    if (roles[k].point < 0 || roles[k].point >= n_out) return fail(OKX_ERR_INVALID, "rotation %d: not an output point", k);
-    if (roles[k].kind < OKX_ROLE_AXIS_ROTATION || roles[k].kind > OKX_ROLE_MIDPOINT_COORDINATE)
-      return fail(OKX_ERR_INVALID, "rotation %d: unknown kind %d", k, roles[k].kind);
-    if (roles[k].kind != OKX_ROLE_AXIS_ROTATION && (roles[k].point_b < 0 || roles[k].point_b >= n_out))
-      return fail(OKX_ERR_INVALID, "rotation %d: second point is not an output point", k);
-    const double* d = roles[k].axis_dir;
-    const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(std::fabs(len - 1.0) <= 1e-9)) return fail(OKX_ERR_INVALID, "rotation %d: axis_dir must be a unit vector", k);
-    a.roles[k] = roles[k];
-  }
-  if (n_states == 0) return OKX_OK;
-  a.n_roles = n_roles;
-  a.pos = d_pos;
-  a.tan = d_tangents;
-  a.angles = d_angles;
-  a.dangles = d_dangles;
-  a.n_states = n_states;
-  a.n_out = n_out;
-  a.n_targets = n_targets;
-  const long long blocks = (n_states + 255) / 256;
-  hipLaunchKernelGGL(okx::okx_axis_rotation_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return OKX_OK;
-}
-
-int32_t okx_axle_metrics_batch(const okx_corner_roles* left, const okx_corner_roles* right, int64_t n_states,
-                               int32_t n_out, const double* d_pos, double* d_metrics, void* stream) {
-  if (!left || !right || !d_pos || !d_metrics) return fail(OKX_ERR_INVALID, "null pointer");
-  if (n_states < 0 || n_out <= 0) return fail(OKX_ERR_INVALID, "bad dimension");
-  if (int32_t rc = check_corner_roles(left, n_out, "left")) return rc;
-  if (int32_t rc = check_corner_roles(right, n_out, "right")) return rc;
-  if (n_states == 0) return OKX_OK;
-  okx::AxleMetricsArgs a;
-  a.left = *left;
-  a.right = *right;
-  a.pos = d_pos;
-  a.metrics = d_metrics;
-  a.n_states = n_states;
-  a.n_out = n_out;
-  const long long blocks = (n_states + 255) / 256;
-  hipLaunchKernelGGL(okx::okx_axle_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return OKX_OK;
-}
-
-int32_t okx_corner_metrics_batch(const okx_corner_roles* roles, int64_t n_states, int32_t n_out, int32_t n_targets,
-                                 const double* d_pos, const double* d_tangents, double* d_metrics,
-                                 double* d_dmetrics, void* stream) {
-  if (!roles || !d_pos || !d_metrics) return fail(OKX_ERR_INVALID, "null pointer");
-  if (n_states < 0 || n_out <= 0 || n_targets < 0) return fail(OKX_ERR_INVALID, "bad dimension");
-  if ((d_tangents == nullptr) != (d_dmetrics == nullptr))
-    return fail(OKX_ERR_INVALID, "tangents and derivative output must be given together");
-  if (int32_t rc = check_corner_roles(roles, n_out, "roles")) return rc;
-  if (n_states == 0) return OKX_OK;
-  okx::MetricsArgs a;
-  a.roles = *roles;
-  a.pos = d_pos;
-  a.tan = d_tangents;
-  a.metrics = d_metrics;
-  a.dmetrics = d_dmetrics;
-  a.n_states = n_states;
-  a.n_out = n_out;
-  a.n_targets = n_targets;
-  // Records of up to 21 points (corners): 64 states per wavefront, records, tangent rows and results staged through LDS
-  // (okx_corner_metrics_tiled); longer records (the corners of a composed axle): one thread per state.  The same
-  // formulas either way: same bits.
-  okx::TileArgs ta;
-  ta.rec = 3u * (uint32_t)n_out;
-  ta.rec_inv = (uint32_t)((1ull << 32) / ta.rec) + 1u;
-  ta.stride = ta.rec | 1u;
-  const size_t lds_bytes = sizeof(double) * okx::kTileStates * (ta.stride > OKX_METRIC_COUNT ? ta.stride : OKX_METRIC_COUNT);
-  const long long tiles = (n_states + okx::kTileStates - 1) / okx::kTileStates;
-  if (ta.rec <= 63 && tiles < 0x7fffffffll) {
-    if (d_tangents)
-      hipLaunchKernelGGL(okx::okx_corner_metrics_tiled<true>, dim3((unsigned)tiles), dim3(okx::kTileStates), lds_bytes, (hipStream_t)stream, a, ta);
-    else
-      hipLaunchKernelGGL(okx::okx_corner_metrics_tiled<false>, dim3((unsigned)tiles), dim3(okx::kTileStates), lds_bytes, (hipStream_t)stream, a, ta);
-    HIP_TRY(hipGetLastError());
-    return OKX_OK;
-  }
-  const long long blocks = (n_states + 255) / 256;
-  hipLaunchKernelGGL(okx::okx_corner_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return OKX_OK;
-}
-
-int32_t okx_camber_shim_batch(const okx_shim_roles* roles, int64_t n_geometries, int32_t n_points, double* d_points,
-                              const double* d_shim, okx_shim_info* d_info, void* stream) {
-  if (!roles || !d_points || !d_shim) return fail(OKX_ERR_INVALID, "null pointer");
-  if (n_geometries < 0 || n_points <= 0) return fail(OKX_ERR_INVALID, "bad dimension");
-  auto bad = [&](int32_t k) { return k < 0 || k >= n_points; };
-  if (bad(roles->upper_outboard) || bad(roles->lower_outboard) || bad(roles->upper_inboard_front) ||
-      bad(roles->upper_inboard_rear) || bad(roles->heading_inboard) || bad(roles->heading_outboard))
-    return fail(OKX_ERR_INVALID, "shim role is not a point of the table");
-  if (roles->n_upright_points < 0 || roles->n_upright_points > OKX_SHIM_MAX_POINTS || roles->n_rocker_points < 0 ||
-      roles->n_rocker_points > OKX_SHIM_MAX_POINTS)
-    return fail(OKX_ERR_INVALID, "at most %d upright / rocker points", OKX_SHIM_MAX_POINTS);
-  for (int k = 0; k < roles->n_upright_points; ++k)
-    if (bad(roles->upright_point[k]) || roles->upright_point[k] == roles->lower_outboard)
-      return fail(OKX_ERR_INVALID, "upright point %d is not a movable point of the table", k);
-  if (roles->rocker != 0 && roles->rocker != 1) return fail(OKX_ERR_INVALID, "rocker must be 0 or 1");
-  if (roles->rocker) {
-    if (bad(roles->rocker_axis_a) || bad(roles->rocker_axis_b) || bad(roles->pushrod_inboard) ||
-        bad(roles->pushrod_outboard))
-      return fail(OKX_ERR_INVALID, "rocker coupling role is not a point of the table");
-    for (int k = 0; k < roles->n_rocker_points; ++k)
-      if (bad(roles->rocker_point[k])) return fail(OKX_ERR_INVALID, "rocker point %d is not a point of the table", k);
-  }
-  if (n_geometries == 0) return OKX_OK;
-  okx::shim::ShimArgs a;
-  a.roles = *roles;
-  a.points = d_points;
-  a.shim = d_shim;
-  a.info = d_info;
-  a.n_geometries = n_geometries;
-  a.n_points = n_points;
-  const long long blocks = (n_geometries + 63) / 64;
-  hipLaunchKernelGGL(okx::shim::okx_camber_shim_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return OKX_OK;
-}
-
 /* Diagnostic (okx_debug.h): record the LM passes of ONE problem of this program's subsequent quad-kernel
    solves into d_trace [256][8] = (mode, trial cost, accepted cost, lambda, step, gain ratio, accepted, done);
    pass a null pointer to switch it off. */
@@ -1420,6 +871,26 @@ int32_t okx_debug_quad_trace(okx_program* p, double* d_trace, int64_t problem) {
   if (!p) return fail(OKX_ERR_INVALID, "null program");
   p->quad_trace = d_trace;
   p->quad_trace_problem = d_trace ? problem : -1;
+  return OKX_OK;
+}
+
+/* okx_debug_quad_eval / okx_debug_lane_eval: the parity kernel of the quad or the lane family, 16 or 64 problems per
+   wavefront, at most 4096 or 1024 workgroups. */
+static int32_t debug_generated_eval(okx_program* p, bool lane, int64_t n_problems, const double* d_x, const double* d_targets, double lambda,
+                                    double* d_r, double* d_ata, double* d_atr, double* d_dx, void* stream) {
+  if (!p || !d_x || !d_r || !d_ata || !d_atr || !d_dx) return fail(OKX_ERR_INVALID, "null pointer");
+  attach_when_ready(p, false);
+  std::shared_lock<std::shared_mutex> kernels(p->kern_mutex);
+  const hipFunction_t fn = lane ? p->lane_fn_eval : p->quad_fn_eval;
+  if (!fn) return fail(OKX_ERR_INVALID, "no %s kernel: %s", lane ? "lane" : "quad", lane ? p->lane_note : p->quad_note);
+  if (n_problems <= 0) return OKX_OK;
+  const int per_wave = lane ? 64 : 16, max_grid = lane ? 1024 : 4096;
+  okx::QuadEvalArgs q = {d_x, d_targets, d_r, d_ata, d_atr, d_dx, lambda, n_problems};
+  okx::set_program_tables(p, &q);
+  const long long waves = (n_problems + per_wave - 1) / per_wave;
+  void* kargs[] = {(void*)&q};
+  HIP_TRY(hipModuleLaunchKernel(fn, (int)(waves < max_grid ? waves : max_grid), 1, 1, okx::kWave, 1, 1, 0,
+                                (hipStream_t)stream, kargs, nullptr));
   return OKX_OK;
 }
 
@@ -1431,52 +902,14 @@ int32_t okx_debug_quad_trace(okx_program* p, double* d_trace, int64_t problem) {
 int32_t okx_debug_quad_eval(okx_program* p, int64_t n_problems, const double* d_x, const double* d_targets,
                             double lambda, double* d_r, double* d_ata, double* d_atr, double* d_dx,
                             void* stream) {
-  if (!p || !d_x || !d_r || !d_ata || !d_atr || !d_dx) return fail(OKX_ERR_INVALID, "null pointer");
-  attach_when_ready(p, false);
-  std::shared_lock<std::shared_mutex> kernels(p->kern_mutex);
-  if (!p->quad_fn_eval) return fail(OKX_ERR_INVALID, "no quad kernel: %s", p->quad_note);
-  if (n_problems <= 0) return OKX_OK;
-  okx::QuadEvalArgs q;
-  q.x = d_x;
-  q.targets = d_targets;
-  q.r = d_r;
-  q.ata = d_ata;
-  q.atr = d_atr;
-  q.dx = d_dx;
-  q.lambda = lambda;
-  q.n_problems = n_problems;
-  okx::set_program_tables(p, &q);
-  const long long waves = (n_problems + 15) / 16;
-  void* kargs[] = {(void*)&q};
-  HIP_TRY(hipModuleLaunchKernel(p->quad_fn_eval, (int)(waves < 4096 ? waves : 4096), 1, 1, okx::kWave, 1, 1, 0,
-                                (hipStream_t)stream, kargs, nullptr));
-  return OKX_OK;
+  return debug_generated_eval(p, false, n_problems, d_x, d_targets, lambda, d_r, d_ata, d_atr, d_dx, stream);
 }
 
 /* Test hook: okx_debug_quad_eval's quantities as the LANE kernel's straight-line code computes them. */
 int32_t okx_debug_lane_eval(okx_program* p, int64_t n_problems, const double* d_x, const double* d_targets,
                             double lambda, double* d_r, double* d_ata, double* d_atr, double* d_dx,
                             void* stream) {
-  if (!p || !d_x || !d_r || !d_ata || !d_atr || !d_dx) return fail(OKX_ERR_INVALID, "null pointer");
-  attach_when_ready(p, false);
-  std::shared_lock<std::shared_mutex> kernels(p->kern_mutex);
-  if (!p->lane_fn_eval) return fail(OKX_ERR_INVALID, "no lane kernel: %s", p->lane_note);
-  if (n_problems <= 0) return OKX_OK;
-  okx::QuadEvalArgs q;
-  q.x = d_x;
-  q.targets = d_targets;
-  q.r = d_r;
-  q.ata = d_ata;
-  q.atr = d_atr;
-  q.dx = d_dx;
-  q.lambda = lambda;
-  q.n_problems = n_problems;
-  okx::set_program_tables(p, &q);
-  const long long waves = (n_problems + 63) / 64;
-  void* kargs[] = {(void*)&q};
-  HIP_TRY(hipModuleLaunchKernel(p->lane_fn_eval, (int)(waves < 1024 ? waves : 1024), 1, 1, okx::kWave, 1, 1, 0,
-                                (hipStream_t)stream, kargs, nullptr));
-  return OKX_OK;
+  return debug_generated_eval(p, true, n_problems, d_x, d_targets, lambda, d_r, d_ata, d_atr, d_dx, stream);
 }
 
 /* Diagnostic (not part of the reference boundary): same as okx_solve_batch for an n = 18
@@ -1488,22 +921,7 @@ int32_t okx_debug_phase_profile(okx_program* p, const okx_solve_opts* opts, int6
                                 const double* d_targets, double* d_out_pos, okx_info* d_info,
                                 unsigned long long* d_phase_cycles, void* stream) {
   if (!p || !opts || p->nreg != 18) return fail(OKX_ERR_INVALID, "phase profile needs an n = 18 program");
-  okx::SolveArgs a;
-  a.targets = d_targets;
-  a.geom_pos = nullptr;
-  a.geom_row_param = nullptr;
-  a.out_pos = d_out_pos;
-  a.info = d_info;
-  a.n_problems = n_problems;
-  a.steps_per_geometry = 0;
-  a.max_iter = opts->max_iter;
-  a.confirm = 1;
-  a.chain_len = 1;
-  a.step_tol = opts->step_tol;
-  a.grad_tol = opts->grad_tol;
-  a.ftol = opts->ftol;
-  a.lambda0 = opts->lambda0;
-  a.residual_tolerance = opts->residual_tolerance;
+  okx::SolveArgs a = interpreter_args(opts, n_problems, d_targets, d_out_pos, d_info);
   a.phase_cycles = d_phase_cycles;
   const okx::DevProgram* dev = p->dev;
   if (p->groups == 3 && opts->kernel == 2) {
@@ -1520,211 +938,6 @@ int32_t okx_debug_phase_profile(okx_program* p, const okx_solve_opts* opts, int6
   HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes));
   HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(p, n_problems)), dim3(okx::kWave), kargs,
                           p->lds_bytes, (hipStream_t)stream));
-  return OKX_OK;
-}
-
-static_assert(sizeof(okx_diag_roles) == 232 && sizeof(okx_diag_summary) == 80 && sizeof(okx_diag_issue) == 40,
-              "the okx_diag_* layouts are part of the ABI (ctypes / NumPy mirrors in diagnostics.py)");
-
-/* The program's grow-only displacement scratch of okx_diagnose_sweeps_batch (long sweeps), at least `need` doubles. */
-static int32_t diag_scratch(okx_program* p, long long need, long long steps_per_sweep, hipStream_t st, double** disp) {
-  std::lock_guard<std::mutex> lock(p->head_mutex);
-  if (need > p->diag_scratch_len) {
-    if (stream_is_capturing(st))
-      return fail(OKX_ERR_INVALID, "okx_diagnose_sweeps_batch: sweeps of %lld steps need a scratch buffer; run this shape once outside the stream capture first", steps_per_sweep);
-    if (p->diag_scratch) {  // replaced in stream order, like the geometry-table scratch of the solve
-      double* old = p->diag_scratch;
-      p->diag_scratch = nullptr;
-      p->diag_scratch_len = 0;
-      HIP_TRY(hipFreeAsync(old, st));
-    }
-    double* fresh = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&fresh, sizeof(double) * (size_t)need, st));
-    p->diag_scratch = fresh;
-    p->diag_scratch_len = need;
-  }
-  *disp = p->diag_scratch;
-  return OKX_OK;
-}
-
-int32_t okx_diagnose_sweeps_batch(okx_program* p, const okx_diag_roles* roles, int64_t n_sweeps, int64_t steps_per_sweep,
-                                  int32_t layout, const double* d_pos, const okx_info* d_info, const double* d_geom_pos,
-                                  double residual_tolerance, okx_diag_summary* d_summary, okx_diag_issue* d_issues,
-                                  int64_t capacity, int64_t* d_issue_count, void* stream) {
-  namespace dg = okx::diag;
-  if (!p || !roles) return fail(OKX_ERR_INVALID, "null program or roles");
-  if (n_sweeps < 0 || steps_per_sweep < 1) return fail(OKX_ERR_INVALID, "bad sweep count or steps_per_sweep");
-  if (layout != OKX_OUTPUT_RECORDS && layout != OKX_OUTPUT_FREE) return fail(OKX_ERR_INVALID, "layout must be OKX_OUTPUT_RECORDS or OKX_OUTPUT_FREE");
-  if (!d_issue_count || capacity < 0 || (capacity > 0 && !d_issues)) return fail(OKX_ERR_INVALID, "null issue count / issue buffer");
-  if (n_sweeps > 0 && (!d_pos || !d_summary)) return fail(OKX_ERR_INVALID, "null pointer");
-  if (steps_per_sweep > 0x7fffffffll || n_sweeps > 0x7fffffffll) return fail(OKX_ERR_LIMIT, "too many sweeps or steps for one launch");
-  const okx::DevProgram& h = p->host;
-  if (roles->n_points < 0 || roles->n_points > dg::kTracked) return fail(OKX_ERR_LIMIT, "at most %d tracked points", dg::kTracked);
-  if (roles->n_sides != 0 && roles->n_sides != 2) return fail(OKX_ERR_INVALID, "n_sides must be 0 or 2");
-  const int n_rows = layout == OKX_OUTPUT_RECORDS ? h.n_out : h.n_free;
-  const int32_t* rows = layout == OKX_OUTPUT_RECORDS ? h.out_point : h.free_point;
-  if (n_rows < 1) return fail(OKX_ERR_INVALID, "the layout carries no point");
-  auto row_of = [&](int point) { for (int k = 0; k < n_rows; ++k) if (rows[k] == point) return k; return -1; };
-  auto moving = [&](int point) {
-    for (int k = 0; k < h.n_free; ++k) if (h.free_point[k] == point) return true;
-    for (int k = 0; k < h.n_derived; ++k) if (h.dop_out[k] == point) return true;
-    return false;
-  };
-  int bad = 0;
-  // a role point's reference: its first double in a record, or -(point + 1) for a fixed point the layout leaves out
-  auto ref_of = [&](int point, const char* what) {
-    if (point < 0 || point >= h.n_points) { if (!bad) { bad = 1; fail(OKX_ERR_INVALID, "%s: point index %d out of range", what, point); } return 0; }
-    const int row = row_of(point);
-    if (row >= 0) return 3 * row;
-    if (moving(point)) { if (!bad) { bad = 1; fail(OKX_ERR_INVALID, "%s: moving point %d is not part of the %s layout", what, point, layout == OKX_OUTPUT_RECORDS ? "records" : "free-point"); } return 0; }
-    return -(point + 1);
-  };
-  dg::DiagArgs a{};
-  a.pos = d_pos;
-  a.info = d_info;
-  a.summary = d_summary;
-  a.issues = capacity > 0 ? d_issues : nullptr;
-  a.capacity = capacity;
-  a.count = reinterpret_cast<unsigned long long*>(d_issue_count);
-  a.n_sweeps = n_sweeps;
-  a.steps = steps_per_sweep;
-  a.residual_tolerance = residual_tolerance;
-  a.rowd = 3 * n_rows;
-  a.batch = 512 / a.rowd < 1 ? 1 : (512 / a.rowd > 8 ? 8 : 512 / a.rowd);
-  a.n_points = roles->n_points;
-  a.n_sides = roles->n_sides;
-  if (d_geom_pos) {
-    a.design = d_geom_pos;
-    a.design_stride = 3ll * h.n_points;
-  } else {
-    a.design = reinterpret_cast<const double*>(reinterpret_cast<const char*>(p->dev) + offsetof(okx::DevProgram, design_pos));
-    a.design_stride = 0;
-  }
-  for (int k = 0; k < roles->n_points; ++k) {
-    const int ref = ref_of(roles->point[k], "tracked point");
-    if (!bad && ref < 0) { bad = 1; fail(OKX_ERR_INVALID, "tracked point %d is a fixed point", roles->point[k]); }
-    a.pt_off[k] = ref;
-  }
-  for (int s = 0; s < roles->n_sides && !bad; ++s) {
-    const okx_diag_side& r = roles->side[s];
-    dg::SideRefs& o = a.side[s];
-    o.rocker = ref_of(r.droplink_rocker, "droplink_rocker");
-    o.arm = ref_of(r.droplink_u_bar, "droplink_u_bar");
-    o.rocker_pt = r.droplink_rocker;
-    o.arm_pt = r.droplink_u_bar;
-    o.has_rocker = r.rocker_axis_a >= 0 && r.rocker_axis_b >= 0 && r.pushrod_inboard >= 0 && r.pushrod_outboard >= 0;
-    if (o.has_rocker) {
-      o.axis_a = ref_of(r.rocker_axis_a, "rocker_axis_a");
-      o.axis_b = ref_of(r.rocker_axis_b, "rocker_axis_b");
-      o.push_in = ref_of(r.pushrod_inboard, "pushrod_inboard");
-      o.push_out = ref_of(r.pushrod_outboard, "pushrod_outboard");
-    }
-  }
-  if (roles->n_sides && !bad) {
-    if (roles->bar_axis_a < 0 || roles->bar_axis_a >= h.n_points || roles->bar_axis_b < 0 || roles->bar_axis_b >= h.n_points)
-      return fail(OKX_ERR_INVALID, "bar axis point out of range");
-    a.bar_a = roles->bar_axis_a;
-    a.bar_b = roles->bar_axis_b;
-  }
-  if (bad) return OKX_ERR_INVALID;
-  const hipStream_t st = (hipStream_t)stream;
-  {
-    const long long init_blocks = (n_sweeps > 0 ? n_sweeps + 255 : 256) / 256;
-    hipLaunchKernelGGL(dg::okx_diagnose_init, dim3((unsigned)init_blocks), dim3(256), 0, st, d_summary, (long long)n_sweeps, a.count);
-    HIP_TRY(hipGetLastError());
-  }
-  if (n_sweeps == 0) return OKX_OK;
-  const size_t slot_bytes = sizeof(double) * (size_t)(a.batch + 1) * (size_t)a.rowd * dg::kWaves;
-  const size_t short_bytes = slot_bytes + sizeof(double) * (size_t)a.n_points * (size_t)(steps_per_sweep - 1);
-  if (short_bytes <= 64 * 1024) {
-    // a whole sweep per workgroup (ensembles of short sweeps): displacements in LDS
-    const long long grid = n_sweeps < (long long)p->n_cu * 64 ? n_sweeps : (long long)p->n_cu * 64;
-    hipLaunchKernelGGL(dg::okx_diagnose_short, dim3((unsigned)grid), dim3(dg::kThreads), short_bytes, st, a);
-    HIP_TRY(hipGetLastError());
-    return OKX_OK;
-  }
-  // long sweeps: displacements staged in the program's scratch buffer, then one wavefront per sweep and tracked point
-  const long long need = n_sweeps * (long long)a.n_points * (steps_per_sweep - 1);
-  if (const int32_t rc = diag_scratch(p, need, steps_per_sweep, st, &a.disp)) return rc;
-  const long long per_tile = (long long)dg::kWaves * dg::kLongChunk;
-  const long long tiles_per_sweep = (steps_per_sweep + per_tile - 1) / per_tile;
-  const long long n_tiles = tiles_per_sweep * n_sweeps;
-  const long long cap = (long long)p->n_cu * 64;
-  hipLaunchKernelGGL(dg::okx_diagnose_states, dim3((unsigned)(n_tiles < cap ? n_tiles : cap)), dim3(dg::kThreads), slot_bytes, st, a,
-                     tiles_per_sweep);
-  HIP_TRY(hipGetLastError());
-  if (a.n_points > 0) {
-    const long long jobs = n_sweeps * a.n_points;
-    hipLaunchKernelGGL(dg::okx_diagnose_select, dim3((unsigned)(jobs < cap ? jobs : cap)), dim3(64), 0, st, a);
-    HIP_TRY(hipGetLastError());
-  }
-  return OKX_OK;
-}
-
-size_t okx_ensemble_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_factors) {
-  namespace en = okx::ens;
-  if (n_geometries <= 0 || steps < 0 || n_columns < 0 || n_factors < 0) return 0;
-  const long long n_entries = (long long)steps * n_columns;
-  long long n_slabs, slab_len;
-  en::slab_plan(n_geometries, n_entries, &n_slabs, &slab_len);
-  return sizeof(double) * (size_t)n_slabs * ((size_t)(en::kFields + n_factors) * (size_t)n_entries + (size_t)en::factor_moments(n_factors));
-}
-
-int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_columns, const double* d_values, int64_t ld,
-                            const uint8_t* d_status, int64_t status_stride, const double* d_factors, int32_t n_factors,
-                            const double* d_shift, int64_t geometry_offset, int32_t accumulate, double* d_acc, double* d_factor_acc,
-                            void* d_scratch, size_t scratch_bytes, void* stream) {
-  namespace en = okx::ens;
-  if (n_geometries < 0 || steps < 0 || n_columns < 0) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: negative geometry, step or column count");
-  if (n_factors < 0 || n_factors > OKX_ENS_MAX_FACTORS) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: at most %d factors", OKX_ENS_MAX_FACTORS);
-  if (geometry_offset < 0 || geometry_offset + n_geometries > (1ll << 53)) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: geometry indices beyond 2^53");
-  const long long n_entries = (long long)steps * n_columns;
-  if (steps > 0x7fffffffll || n_entries * (long long)(okx::ens::kFields + n_factors) > (1ll << 38))
-    return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: too many entries for one call");
-  if (n_entries > 0 && (!d_acc || !d_shift)) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: null accumulator or shift table");
-  if (n_entries > 0 && n_geometries > 0 && (!d_values || ld < n_columns)) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: null table or ld < n_columns");
-  if (d_status && status_stride < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: status_stride must be positive");
-  if (n_factors > 0 && n_geometries > 0 && !d_factors) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: n_factors > 0 without a factor table");
-  if (d_factor_acc && n_factors < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: factor moments need factors");
-  const size_t need = okx_ensemble_scratch_bytes(n_geometries, steps, n_columns, n_factors);
-  if (need > 0 && (!d_scratch || scratch_bytes < need))
-    return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: %zu bytes of scratch needed (okx_ensemble_scratch_bytes), %zu given", need, scratch_bytes);
-  long long n_slabs, slab_len;
-  en::slab_plan(n_geometries, n_entries, &n_slabs, &slab_len);
-  if (n_slabs > 65535) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: too many geometries for one call");
-  const hipStream_t st = (hipStream_t)stream;
-  const int rows = en::kFields + n_factors;
-  double* partial = static_cast<double*>(d_scratch);
-  if (n_entries > 0) {
-    if (n_slabs > 0) {
-      en::EnsArgs a{};
-      a.values = d_values; a.status = d_status; a.factors = d_factors; a.shift = d_shift; a.partial = partial;
-      a.ld = ld; a.status_stride = d_status ? status_stride : 0;
-      a.n_geom = n_geometries; a.steps = steps; a.n_entries = n_entries; a.slab_len = slab_len; a.geometry_offset = geometry_offset;
-      a.n_columns = n_columns; a.n_factors = n_factors;
-      // the cross sums of a lane stay in registers: blocks of 8, 16 or 32 factors, more than 32 as further workgroups
-      if (n_factors == 0) HIP_TRY(en::launch_partial<0>(a, n_slabs, st));
-      else if (n_factors <= 8) HIP_TRY(en::launch_partial<8>(a, n_slabs, st));
-      else if (n_factors <= 16) HIP_TRY(en::launch_partial<16>(a, n_slabs, st));
-      else HIP_TRY(en::launch_partial<en::kFactorBlock>(a, n_slabs, st));
-    }
-    const long long threads = n_entries * rows;
-    hipLaunchKernelGGL(en::okx_ensemble_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, partial, n_slabs, n_entries, rows,
-                       accumulate ? 1 : 0, d_acc);
-    HIP_TRY(hipGetLastError());
-  }
-  if (d_factor_acc) {
-    const long long n_moments = en::factor_moments(n_factors);
-    double* fpart = partial + (size_t)n_slabs * (size_t)rows * (size_t)n_entries;
-    if (n_slabs > 0) {
-      hipLaunchKernelGGL(en::okx_ensemble_factor_partial, dim3((unsigned)n_slabs), dim3(256), 0, st, d_factors, n_factors,
-                         (long long)n_geometries, slab_len, n_moments, fpart);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(en::okx_ensemble_factor_merge, dim3((unsigned)((n_moments + 255) / 256)), dim3(256), 0, st, fpart, n_slabs, n_moments,
-                       accumulate ? 1 : 0, d_factor_acc);
-    HIP_TRY(hipGetLastError());
-  }
   return OKX_OK;
 }
 

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/okx.h"
+#include "okx_enstable.hpp"
 #include "okx_program.hpp"
 #include "okx_quad.hpp"
 
@@ -329,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void okx_cov_merge(MergeArgs a) {
 }
 
 inline int check_sizes(const char* who, long long n_geom, long long steps, int n_columns, long long n) {
-  if (n_geom < 0 || steps < 0 || n_columns < 0) return fail(OKX_ERR_INVALID, "%s: negative geometry, step or column count", who);
+  if (int rc = enstable::check_counts(who, n_geom, steps, n_columns)) return rc;
   if (steps > 0x7fffffffll || (long long)steps * n_columns > kMaxTable) return fail(OKX_ERR_LIMIT, "%s: too many entries in the table for one call", who);
   if (n < 1 || n > OKX_ENS_COV_MAX_ENTRIES)
     return fail(OKX_ERR_INVALID, "%s: %lld entries selected, 1 to %d allowed", who, n, (int)OKX_ENS_COV_MAX_ENTRIES);
@@ -340,6 +341,7 @@ inline int check_sizes(const char* who, long long n_geom, long long steps, int n
 }  // namespace okx
 
 using okx::fail;
+namespace et = okx::enstable;
 
 extern "C" {
 
@@ -391,13 +393,11 @@ int32_t okx_ensemble_covariance(int64_t n_geometries, int64_t steps, int32_t n_c
     return fail(OKX_ERR_INVALID, "%s: without an entry list all %lld entries are selected, not %lld", who, n_table, (long long)n_entries);
   if (n_entries > n_table) return fail(OKX_ERR_INVALID, "%s: %lld distinct entries of a table of %lld", who, (long long)n_entries, n_table);
   if (!d_gram || !d_sum || !d_counts || !d_shift) return fail(OKX_ERR_INVALID, "%s: null gram, sum, counts or shift", who);
-  if (n_geometries > 0 && (!d_values || ld < n_columns)) return fail(OKX_ERR_INVALID, "%s: null table or ld < n_columns", who);
-  if (d_status && status_stride < 1) return fail(OKX_ERR_INVALID, "%s: status_stride must be positive", who);
+  if (int rc = et::check_table(who, n_geometries > 0, d_values, ld, n_columns, d_status, status_stride)) return rc;
   const cv::Plan plan = cv::plan_for(n_geometries, n_entries);
   const cv::Layout lay = cv::layout_for(plan, n_geometries);
   const size_t need = okx_ensemble_covariance_scratch_bytes(n_geometries, steps, n_columns, n_entries);
-  if (!d_scratch || scratch_bytes < need)
-    return fail(OKX_ERR_INVALID, "%s: %zu bytes of scratch needed (okx_ensemble_covariance_scratch_bytes), %zu given", who, need, scratch_bytes);
+  if (int rc = et::check_scratch(who, "okx_ensemble_covariance_scratch_bytes", need, d_scratch, scratch_bytes)) return rc;
   if (plan.ugroups > 0x7fffffffll) return fail(OKX_ERR_LIMIT, "%s: too many geometries for one call", who);
   unsigned char* base = static_cast<unsigned char*>(d_scratch);
   unsigned char* used = base + lay.used;

@@ -12,12 +12,13 @@
 // The median of the positive displacements is exact: positive doubles order like their bit patterns, so a bisection over
 // the 63 value bits with wavefront ballots finds the lower middle order statistic, one more pass the upper one; only
 // (a + b) / 2 is arithmetic.  Both paths run the same two device functions, so their records are bit-identical.
-#pragma once
-
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstddef>
+
 #include "../../include/okx.h"
+#include "okx_program.hpp"
 
 namespace okx {
 namespace diag {
@@ -356,3 +357,147 @@ __global__ __launch_bounds__(64) void okx_diagnose_select(DiagArgs a) {
 
 }  // namespace diag
 }  // namespace okx
+
+using okx::fail;
+
+extern "C" {
+
+static_assert(sizeof(okx_diag_roles) == 232 && sizeof(okx_diag_summary) == 80 && sizeof(okx_diag_issue) == 40,
+              "the okx_diag_* layouts are part of the ABI (ctypes / NumPy mirrors in diagnostics.py)");
+
+/* The program's grow-only displacement scratch of okx_diagnose_sweeps_batch (long sweeps), at least `need` doubles. */
+static int32_t diag_scratch(okx_program* p, long long need, long long steps_per_sweep, hipStream_t st, double** disp) {
+  std::lock_guard<std::mutex> lock(p->head_mutex);
+  if (need > p->diag_scratch_len) {
+    if (okx::stream_is_capturing(st))
+      return fail(OKX_ERR_INVALID, "okx_diagnose_sweeps_batch: sweeps of %lld steps need a scratch buffer; run this shape once outside the stream capture first", steps_per_sweep);
+    if (p->diag_scratch) {  // replaced in stream order, like the geometry-table scratch of the solve
+      double* old = p->diag_scratch;
+      p->diag_scratch = nullptr;
+      p->diag_scratch_len = 0;
+      HIP_TRY(hipFreeAsync(old, st));
+    }
+    double* fresh = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&fresh, sizeof(double) * (size_t)need, st));
+    p->diag_scratch = fresh;
+    p->diag_scratch_len = need;
+  }
+  *disp = p->diag_scratch;
+  return OKX_OK;
+}
+
+int32_t okx_diagnose_sweeps_batch(okx_program* p, const okx_diag_roles* roles, int64_t n_sweeps, int64_t steps_per_sweep,
+                                  int32_t layout, const double* d_pos, const okx_info* d_info, const double* d_geom_pos,
+                                  double residual_tolerance, okx_diag_summary* d_summary, okx_diag_issue* d_issues,
+                                  int64_t capacity, int64_t* d_issue_count, void* stream) {
+  namespace dg = okx::diag;
+  if (!p || !roles) return fail(OKX_ERR_INVALID, "null program or roles");
+  if (n_sweeps < 0 || steps_per_sweep < 1) return fail(OKX_ERR_INVALID, "bad sweep count or steps_per_sweep");
+  if (layout != OKX_OUTPUT_RECORDS && layout != OKX_OUTPUT_FREE) return fail(OKX_ERR_INVALID, "layout must be OKX_OUTPUT_RECORDS or OKX_OUTPUT_FREE");
+  if (!d_issue_count || capacity < 0 || (capacity > 0 && !d_issues)) return fail(OKX_ERR_INVALID, "null issue count / issue buffer");
+  if (n_sweeps > 0 && (!d_pos || !d_summary)) return fail(OKX_ERR_INVALID, "null pointer");
+  if (steps_per_sweep > 0x7fffffffll || n_sweeps > 0x7fffffffll) return fail(OKX_ERR_LIMIT, "too many sweeps or steps for one launch");
+  const okx::DevProgram& h = p->host;
+  if (roles->n_points < 0 || roles->n_points > dg::kTracked) return fail(OKX_ERR_LIMIT, "at most %d tracked points", dg::kTracked);
+  if (roles->n_sides != 0 && roles->n_sides != 2) return fail(OKX_ERR_INVALID, "n_sides must be 0 or 2");
+  const int n_rows = layout == OKX_OUTPUT_RECORDS ? h.n_out : h.n_free;
+  const int32_t* rows = layout == OKX_OUTPUT_RECORDS ? h.out_point : h.free_point;
+  if (n_rows < 1) return fail(OKX_ERR_INVALID, "the layout carries no point");
+  auto row_of = [&](int point) { for (int k = 0; k < n_rows; ++k) if (rows[k] == point) return k; return -1; };
+  auto moving = [&](int point) {
+    for (int k = 0; k < h.n_free; ++k) if (h.free_point[k] == point) return true;
+    for (int k = 0; k < h.n_derived; ++k) if (h.dop_out[k] == point) return true;
+    return false;
+  };
+  int bad = 0;
+  // a role point's reference: its first double in a record, or -(point + 1) for a fixed point the layout leaves out
+  auto ref_of = [&](int point, const char* what) {
+    if (point < 0 || point >= h.n_points) { if (!bad) { bad = 1; fail(OKX_ERR_INVALID, "%s: point index %d out of range", what, point); } return 0; }
+    const int row = row_of(point);
+    if (row >= 0) return 3 * row;
+    if (moving(point)) { if (!bad) { bad = 1; fail(OKX_ERR_INVALID, "%s: moving point %d is not part of the %s layout", what, point, layout == OKX_OUTPUT_RECORDS ? "records" : "free-point"); } return 0; }
+    return -(point + 1);
+  };
+  dg::DiagArgs a{};
+  a.pos = d_pos;
+  a.info = d_info;
+  a.summary = d_summary;
+  a.issues = capacity > 0 ? d_issues : nullptr;
+  a.capacity = capacity;
+  a.count = reinterpret_cast<unsigned long long*>(d_issue_count);
+  a.n_sweeps = n_sweeps;
+  a.steps = steps_per_sweep;
+  a.residual_tolerance = residual_tolerance;
+  a.rowd = 3 * n_rows;
+  a.batch = 512 / a.rowd < 1 ? 1 : (512 / a.rowd > 8 ? 8 : 512 / a.rowd);
+  a.n_points = roles->n_points;
+  a.n_sides = roles->n_sides;
+  if (d_geom_pos) {
+    a.design = d_geom_pos;
+    a.design_stride = 3ll * h.n_points;
+  } else {
+    a.design = reinterpret_cast<const double*>(reinterpret_cast<const char*>(p->dev) + offsetof(okx::DevProgram, design_pos));
+    a.design_stride = 0;
+  }
+  for (int k = 0; k < roles->n_points; ++k) {
+    const int ref = ref_of(roles->point[k], "tracked point");
+    if (!bad && ref < 0) { bad = 1; fail(OKX_ERR_INVALID, "tracked point %d is a fixed point", roles->point[k]); }
+    a.pt_off[k] = ref;
+  }
+  for (int s = 0; s < roles->n_sides && !bad; ++s) {
+    const okx_diag_side& r = roles->side[s];
+    dg::SideRefs& o = a.side[s];
+    o.rocker = ref_of(r.droplink_rocker, "droplink_rocker");
+    o.arm = ref_of(r.droplink_u_bar, "droplink_u_bar");
+    o.rocker_pt = r.droplink_rocker;
+    o.arm_pt = r.droplink_u_bar;
+    o.has_rocker = r.rocker_axis_a >= 0 && r.rocker_axis_b >= 0 && r.pushrod_inboard >= 0 && r.pushrod_outboard >= 0;
+    if (o.has_rocker) {
+      o.axis_a = ref_of(r.rocker_axis_a, "rocker_axis_a");
+      o.axis_b = ref_of(r.rocker_axis_b, "rocker_axis_b");
+      o.push_in = ref_of(r.pushrod_inboard, "pushrod_inboard");
+      o.push_out = ref_of(r.pushrod_outboard, "pushrod_outboard");
+    }
+  }
+  if (roles->n_sides && !bad) {
+    if (roles->bar_axis_a < 0 || roles->bar_axis_a >= h.n_points || roles->bar_axis_b < 0 || roles->bar_axis_b >= h.n_points)
+      return fail(OKX_ERR_INVALID, "bar axis point out of range");
+    a.bar_a = roles->bar_axis_a;
+    a.bar_b = roles->bar_axis_b;
+  }
+  if (bad) return OKX_ERR_INVALID;
+  const hipStream_t st = (hipStream_t)stream;
+  {
+    const long long init_blocks = (n_sweeps > 0 ? n_sweeps + 255 : 256) / 256;
+    hipLaunchKernelGGL(dg::okx_diagnose_init, dim3((unsigned)init_blocks), dim3(256), 0, st, d_summary, (long long)n_sweeps, a.count);
+    HIP_TRY(hipGetLastError());
+  }
+  if (n_sweeps == 0) return OKX_OK;
+  const size_t slot_bytes = sizeof(double) * (size_t)(a.batch + 1) * (size_t)a.rowd * dg::kWaves;
+  const size_t short_bytes = slot_bytes + sizeof(double) * (size_t)a.n_points * (size_t)(steps_per_sweep - 1);
+  if (short_bytes <= 64 * 1024) {
+    // a whole sweep per workgroup (ensembles of short sweeps): displacements in LDS
+    const long long grid = n_sweeps < (long long)p->n_cu * 64 ? n_sweeps : (long long)p->n_cu * 64;
+    hipLaunchKernelGGL(dg::okx_diagnose_short, dim3((unsigned)grid), dim3(dg::kThreads), short_bytes, st, a);
+    HIP_TRY(hipGetLastError());
+    return OKX_OK;
+  }
+  // long sweeps: displacements staged in the program's scratch buffer, then one wavefront per sweep and tracked point
+  const long long need = n_sweeps * (long long)a.n_points * (steps_per_sweep - 1);
+  if (const int32_t rc = diag_scratch(p, need, steps_per_sweep, st, &a.disp)) return rc;
+  const long long per_tile = (long long)dg::kWaves * dg::kLongChunk;
+  const long long tiles_per_sweep = (steps_per_sweep + per_tile - 1) / per_tile;
+  const long long n_tiles = tiles_per_sweep * n_sweeps;
+  const long long cap = (long long)p->n_cu * 64;
+  hipLaunchKernelGGL(dg::okx_diagnose_states, dim3((unsigned)(n_tiles < cap ? n_tiles : cap)), dim3(dg::kThreads), slot_bytes, st, a,
+                     tiles_per_sweep);
+  HIP_TRY(hipGetLastError());
+  if (a.n_points > 0) {
+    const long long jobs = n_sweeps * a.n_points;
+    hipLaunchKernelGGL(dg::okx_diagnose_select, dim3((unsigned)(jobs < cap ? jobs : cap)), dim3(64), 0, st, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return OKX_OK;
+}
+
+}  // extern "C"

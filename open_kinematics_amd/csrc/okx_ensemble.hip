@@ -10,14 +10,14 @@
 // (entry, field) merges the slabs in ascending order, after what d_acc already holds when the call accumulates.
 // The order of every addition is a function of (G, S, K) alone - the slab count never looks at the device - so the bits
 // are the same from run to run and from machine to machine.
-#pragma once
-
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "../../include/okx.h"
+#include "okx_enstable.hpp"
+#include "okx_program.hpp"
 
 namespace okx {
 namespace ens {
@@ -227,3 +227,76 @@ __global__ __launch_bounds__(256) void okx_ensemble_factor_merge(const double* p
 
 }  // namespace ens
 }  // namespace okx
+
+using okx::fail;
+namespace et = okx::enstable;
+
+extern "C" {
+
+size_t okx_ensemble_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_factors) {
+  namespace en = okx::ens;
+  if (n_geometries <= 0 || steps < 0 || n_columns < 0 || n_factors < 0) return 0;
+  const long long n_entries = (long long)steps * n_columns;
+  long long n_slabs, slab_len;
+  en::slab_plan(n_geometries, n_entries, &n_slabs, &slab_len);
+  return sizeof(double) * (size_t)n_slabs * ((size_t)(en::kFields + n_factors) * (size_t)n_entries + (size_t)en::factor_moments(n_factors));
+}
+
+int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_columns, const double* d_values, int64_t ld,
+                            const uint8_t* d_status, int64_t status_stride, const double* d_factors, int32_t n_factors,
+                            const double* d_shift, int64_t geometry_offset, int32_t accumulate, double* d_acc, double* d_factor_acc,
+                            void* d_scratch, size_t scratch_bytes, void* stream) {
+  namespace en = okx::ens;
+  if (int rc = et::check_counts("okx_ensemble_reduce", n_geometries, steps, n_columns)) return rc;
+  if (n_factors < 0 || n_factors > OKX_ENS_MAX_FACTORS) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: at most %d factors", OKX_ENS_MAX_FACTORS);
+  if (geometry_offset < 0 || geometry_offset + n_geometries > (1ll << 53)) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: geometry indices beyond 2^53");
+  const long long n_entries = (long long)steps * n_columns;
+  if (steps > 0x7fffffffll || n_entries * (long long)(okx::ens::kFields + n_factors) > (1ll << 38))
+    return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: too many entries for one call");
+  if (n_entries > 0 && (!d_acc || !d_shift)) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: null accumulator or shift table");
+  if (int rc = et::check_table("okx_ensemble_reduce", n_entries > 0 && n_geometries > 0, d_values, ld, n_columns, d_status, status_stride)) return rc;
+  if (n_factors > 0 && n_geometries > 0 && !d_factors) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: n_factors > 0 without a factor table");
+  if (d_factor_acc && n_factors < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: factor moments need factors");
+  const size_t need = okx_ensemble_scratch_bytes(n_geometries, steps, n_columns, n_factors);
+  if (need > 0)
+    if (int rc = et::check_scratch("okx_ensemble_reduce", "okx_ensemble_scratch_bytes", need, d_scratch, scratch_bytes)) return rc;
+  long long n_slabs, slab_len;
+  en::slab_plan(n_geometries, n_entries, &n_slabs, &slab_len);
+  if (n_slabs > 65535) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: too many geometries for one call");
+  const hipStream_t st = (hipStream_t)stream;
+  const int rows = en::kFields + n_factors;
+  double* partial = static_cast<double*>(d_scratch);
+  if (n_entries > 0) {
+    if (n_slabs > 0) {
+      en::EnsArgs a{};
+      a.values = d_values; a.status = d_status; a.factors = d_factors; a.shift = d_shift; a.partial = partial;
+      a.ld = ld; a.status_stride = d_status ? status_stride : 0;
+      a.n_geom = n_geometries; a.steps = steps; a.n_entries = n_entries; a.slab_len = slab_len; a.geometry_offset = geometry_offset;
+      a.n_columns = n_columns; a.n_factors = n_factors;
+      // the cross sums of a lane stay in registers: blocks of 8, 16 or 32 factors, more than 32 as further workgroups
+      if (n_factors == 0) HIP_TRY(en::launch_partial<0>(a, n_slabs, st));
+      else if (n_factors <= 8) HIP_TRY(en::launch_partial<8>(a, n_slabs, st));
+      else if (n_factors <= 16) HIP_TRY(en::launch_partial<16>(a, n_slabs, st));
+      else HIP_TRY(en::launch_partial<en::kFactorBlock>(a, n_slabs, st));
+    }
+    const long long threads = n_entries * rows;
+    hipLaunchKernelGGL(en::okx_ensemble_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, partial, n_slabs, n_entries, rows,
+                       accumulate ? 1 : 0, d_acc);
+    HIP_TRY(hipGetLastError());
+  }
+  if (d_factor_acc) {
+    const long long n_moments = en::factor_moments(n_factors);
+    double* fpart = partial + (size_t)n_slabs * (size_t)rows * (size_t)n_entries;
+    if (n_slabs > 0) {
+      hipLaunchKernelGGL(en::okx_ensemble_factor_partial, dim3((unsigned)n_slabs), dim3(256), 0, st, d_factors, n_factors,
+                         (long long)n_geometries, slab_len, n_moments, fpart);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(en::okx_ensemble_factor_merge, dim3((unsigned)((n_moments + 255) / 256)), dim3(256), 0, st, fpart, n_slabs, n_moments,
+                       accumulate ? 1 : 0, d_factor_acc);
+    HIP_TRY(hipGetLastError());
+  }
+  return OKX_OK;
+}
+
+}  // extern "C"

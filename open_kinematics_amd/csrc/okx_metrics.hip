@@ -12,10 +12,12 @@
 // Instant centres, swing arms and the anti-geometry follow swing_arms.py / anti_geometry.py over
 // the corner's instant axis; axle-scope metrics follow axle_metrics.py.
 #include <hip/hip_runtime.h>
-#pragma once
 #include <stdint.h>
 
+#include <cmath>
+
 #include "../../include/okx.h"
+#include "okx_program.hpp"
 
 namespace okx {
 
@@ -509,3 +511,131 @@ __global__ void __launch_bounds__(256) okx_axis_rotation_kernel(RotationArgs a) 
 }
 
 }  // namespace okx
+
+using okx::check_corner_roles;
+using okx::fail;
+
+static_assert(sizeof(okx_corner_roles) == 128, "okx_corner_roles layout is part of the ABI (ctypes mirror in metrics.py)");
+
+int okx::check_corner_roles(const okx_corner_roles* roles, int32_t n_out, const char* who) {
+  const int32_t idx[6] = {roles->wheel_center, roles->contact_patch, roles->axle_inboard,
+                          roles->axle_outboard, roles->steer_lower, roles->steer_upper};
+  for (int k = 0; k < 6; ++k)
+    if (idx[k] < 0 || idx[k] >= n_out) return fail(OKX_ERR_INVALID, "%s: role %d is not an output point", who, k);
+  if (!(roles->side_sign == 1.0 || roles->side_sign == -1.0))
+    return fail(OKX_ERR_INVALID, "%s: side_sign must be +-1", who);
+  const int n_axis = roles->instant_axis_kind == OKX_IA_TWO_PLANES ? 6
+                     : roles->instant_axis_kind == OKX_IA_PLANE_AND_STRUT ? 4
+                     : roles->instant_axis_kind == OKX_IA_NONE ? 0 : -1;
+  if (n_axis < 0) return fail(OKX_ERR_INVALID, "%s: unknown instant_axis_kind %d", who, roles->instant_axis_kind);
+  for (int k = 0; k < n_axis; ++k)
+    if (roles->instant_axis_point[k] < 0 || roles->instant_axis_point[k] >= n_out)
+      return fail(OKX_ERR_INVALID, "%s: instant-axis point %d is not an output point", who, k);
+  if ((roles->damper_top < 0) != (roles->damper_bottom < 0) || roles->damper_top >= n_out || roles->damper_bottom >= n_out)
+    return fail(OKX_ERR_INVALID, "%s: damper points must both be output points or both be -1", who);
+  if (roles->rack_attachment >= n_out) return fail(OKX_ERR_INVALID, "%s: rack attachment is not an output point", who);
+  for (int32_t v : {roles->axle_position, roles->driven_axle})
+    if (v != OKX_AXLE_UNSET && v != OKX_AXLE_FRONT && v != OKX_AXLE_REAR)
+      return fail(OKX_ERR_INVALID, "%s: axle_position / driven_axle must be OKX_AXLE_*", who);
+  return OKX_OK;
+}
+
+extern "C" {
+
+int32_t okx_axis_rotation_batch(const okx_rotation_role* roles, int32_t n_roles, int64_t n_states, int32_t n_out,
+                                int32_t n_targets, const double* d_pos, const double* d_tangents, double* d_angles,
+                                double* d_dangles, void* stream) {
+  if (!roles || !d_pos || !d_angles) return fail(OKX_ERR_INVALID, "null pointer");
+  if (n_roles < 1 || n_roles > OKX_MAX_ROTATIONS) return fail(OKX_ERR_INVALID, "1..%d rotations per call", OKX_MAX_ROTATIONS);
+  if (n_states < 0 || n_out <= 0 || n_targets < 0) return fail(OKX_ERR_INVALID, "bad dimension");
+  if ((d_tangents == nullptr) != (d_dangles == nullptr))
+    return fail(OKX_ERR_INVALID, "tangents and derivative output must be given together");
+  okx::RotationArgs a;
+  for (int k = 0; k < n_roles; ++k) {
+    if (roles[k].point < 0 || roles[k].point >= n_out) return fail(OKX_ERR_INVALID, "rotation %d: not an output point", k);
+    if (roles[k].kind < OKX_ROLE_AXIS_ROTATION || roles[k].kind > OKX_ROLE_MIDPOINT_COORDINATE)
+      return fail(OKX_ERR_INVALID, "rotation %d: unknown kind %d", k, roles[k].kind);
+    if (roles[k].kind != OKX_ROLE_AXIS_ROTATION && (roles[k].point_b < 0 || roles[k].point_b >= n_out))
+      return fail(OKX_ERR_INVALID, "rotation %d: second point is not an output point", k);
+    const double* d = roles[k].axis_dir;
+    const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(std::fabs(len - 1.0) <= 1e-9)) return fail(OKX_ERR_INVALID, "rotation %d: axis_dir must be a unit vector", k);
+    a.roles[k] = roles[k];
+  }
+  if (n_states == 0) return OKX_OK;
+  a.n_roles = n_roles;
+  a.pos = d_pos;
+  a.tan = d_tangents;
+  a.angles = d_angles;
+  a.dangles = d_dangles;
+  a.n_states = n_states;
+  a.n_out = n_out;
+  a.n_targets = n_targets;
+  const long long blocks = (n_states + 255) / 256;
+  hipLaunchKernelGGL(okx::okx_axis_rotation_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return OKX_OK;
+}
+
+int32_t okx_axle_metrics_batch(const okx_corner_roles* left, const okx_corner_roles* right, int64_t n_states,
+                               int32_t n_out, const double* d_pos, double* d_metrics, void* stream) {
+  if (!left || !right || !d_pos || !d_metrics) return fail(OKX_ERR_INVALID, "null pointer");
+  if (n_states < 0 || n_out <= 0) return fail(OKX_ERR_INVALID, "bad dimension");
+  if (int32_t rc = check_corner_roles(left, n_out, "left")) return rc;
+  if (int32_t rc = check_corner_roles(right, n_out, "right")) return rc;
+  if (n_states == 0) return OKX_OK;
+  okx::AxleMetricsArgs a;
+  a.left = *left;
+  a.right = *right;
+  a.pos = d_pos;
+  a.metrics = d_metrics;
+  a.n_states = n_states;
+  a.n_out = n_out;
+  const long long blocks = (n_states + 255) / 256;
+  hipLaunchKernelGGL(okx::okx_axle_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return OKX_OK;
+}
+
+int32_t okx_corner_metrics_batch(const okx_corner_roles* roles, int64_t n_states, int32_t n_out, int32_t n_targets,
+                                 const double* d_pos, const double* d_tangents, double* d_metrics,
+                                 double* d_dmetrics, void* stream) {
+  if (!roles || !d_pos || !d_metrics) return fail(OKX_ERR_INVALID, "null pointer");
+  if (n_states < 0 || n_out <= 0 || n_targets < 0) return fail(OKX_ERR_INVALID, "bad dimension");
+  if ((d_tangents == nullptr) != (d_dmetrics == nullptr))
+    return fail(OKX_ERR_INVALID, "tangents and derivative output must be given together");
+  if (int32_t rc = check_corner_roles(roles, n_out, "roles")) return rc;
+  if (n_states == 0) return OKX_OK;
+  okx::MetricsArgs a;
+  a.roles = *roles;
+  a.pos = d_pos;
+  a.tan = d_tangents;
+  a.metrics = d_metrics;
+  a.dmetrics = d_dmetrics;
+  a.n_states = n_states;
+  a.n_out = n_out;
+  a.n_targets = n_targets;
+  // Records of up to 21 points (corners): 64 states per wavefront, records, tangent rows and results staged through LDS
+  // (okx_corner_metrics_tiled); longer records (the corners of a composed axle): one thread per state.  The same
+  // formulas either way: same bits.
+  okx::TileArgs ta;
+  ta.rec = 3u * (uint32_t)n_out;
+  ta.rec_inv = (uint32_t)((1ull << 32) / ta.rec) + 1u;
+  ta.stride = ta.rec | 1u;
+  const size_t lds_bytes = sizeof(double) * okx::kTileStates * (ta.stride > OKX_METRIC_COUNT ? ta.stride : OKX_METRIC_COUNT);
+  const long long tiles = (n_states + okx::kTileStates - 1) / okx::kTileStates;
+  if (ta.rec <= 63 && tiles < 0x7fffffffll) {
+    if (d_tangents)
+      hipLaunchKernelGGL(okx::okx_corner_metrics_tiled<true>, dim3((unsigned)tiles), dim3(okx::kTileStates), lds_bytes, (hipStream_t)stream, a, ta);
+    else
+      hipLaunchKernelGGL(okx::okx_corner_metrics_tiled<false>, dim3((unsigned)tiles), dim3(okx::kTileStates), lds_bytes, (hipStream_t)stream, a, ta);
+    HIP_TRY(hipGetLastError());
+    return OKX_OK;
+  }
+  const long long blocks = (n_states + 255) / 256;
+  hipLaunchKernelGGL(okx::okx_corner_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return OKX_OK;
+}
+
+}  // extern "C"

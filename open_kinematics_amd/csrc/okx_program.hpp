@@ -1,12 +1,20 @@
-// okx_program.hpp — the program object behind include/okx.h and what the pieces of the C-ABI share:
-// okx_attach.cpp (generated kernels: compile job, module loads, first-step tables; HIP runtime API only) and
-// okx_api.hip (everything that must see the kernels, and the extern "C" entry points).
+// okx_program.hpp — the program object behind include/okx.h and what the units of the C-ABI share.  Which unit holds what:
+//   okx_api.hip         the interpreter kernels (okx_kernels.hip, okx_packed.hip) and everything that must see them: program
+//                       life cycle and kernel selection, source and precompile entry points, the solve path and the plan
+//                       entry points, okx_eval_batch, okx_rebind_design, okx_expand_positions_batch, okx_tangent_batch, the
+//                       okx_debug_* hooks
+//   okx_attach.cpp      generated kernels: compile job, module loads, first-step tables (HIP runtime API only)
+//   okx_evaluation.cpp  the evaluated modules: enabling, precompiling, okx_evaluate_batch (HIP runtime API only)
+//   okx_predictor.cpp   okx_program_fit_predictor (on top of the public okx_solve_batch)
+//   okx_metrics.hip, okx_shim_api.hip (kernel: okx_shim.hip), okx_diagnose.hip, okx_ensemble.hip, okx_select.hip,
+//   okx_screen.hip, okx_covariance.hip: one pass each - kernels, launch plan, argument checks and entry points together
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
 #include <cstddef>
+#include <functional>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -14,6 +22,8 @@
 #include <vector>
 
 #include "okx_quad.hpp"
+
+struct okx_launch_caps;  // include/okx_debug.h
 
 struct okx_program {
   okx::DevProgram host{};      // host copy (dimensions, launch sizing)
@@ -158,5 +168,13 @@ void release_evaluation(okx_program* p);
 // Loads an evaluated quad module into the program's ev_* slots (ev_mod, ev_solve_g, ev_pos_u/_g, the optional ev_cold_u);
 // *solve_u is the gate the caller publishes last, after its role numbers.
 int load_evaluated_module(okx_program* p, const std::string& code, hipFunction_t* solve_u);
+
+// okx_api.hip, for the units beside it
+int with_dev_program(const okx_program_desc* desc, const std::function<int(const DevProgram&)>& use);  // a description's DevProgram, handed to `use`
+bool geometry_tables_paired(const double* d_geom_pos, const double* d_geom_row_param);
+bool steps_per_geometry_fits(long long n_problems, long long spg, bool geometry_tables);
+void fill_launch_caps(const okx_program* p, okx_launch_caps* c);  // under the program's shared lock
+// okx_metrics.hip: a corner's metric roles against the record's n_out points (`who` opens the message)
+int check_corner_roles(const okx_corner_roles* roles, int32_t n_out, const char* who);
 
 }  // namespace okx

@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "../../include/okx.h"
+#include "okx_enstable.hpp"
 #include "okx_program.hpp"
 
 #pragma clang fp contract(off)
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void okx_screen_compact(CompactArgs a) {
 }
 
 inline int check_sizes(const char* who, long long n_geom, long long steps, int n_columns) {
-  if (n_geom < 0 || steps < 0 || n_columns < 0) return fail(OKX_ERR_INVALID, "%s: negative geometry, step or column count", who);
+  if (int rc = enstable::check_counts(who, n_geom, steps, n_columns)) return rc;
   if (steps > 0x7fffffffll || (long long)steps * n_columns > kMaxEntries) return fail(OKX_ERR_LIMIT, "%s: too many entries for one call", who);
   return OKX_OK;
 }
@@ -259,6 +260,7 @@ inline int check_sizes(const char* who, long long n_geom, long long steps, int n
 }  // namespace okx
 
 using okx::fail;
+namespace et = okx::enstable;
 
 extern "C" {
 
@@ -270,11 +272,7 @@ size_t okx_ensemble_screen_scratch_bytes(int64_t n_geometries, int64_t steps, in
 
 int32_t okx_ensemble_screen_check(const double* limits, const double* scale, int64_t n_entries) {
   if (n_entries < 0 || (n_entries > 0 && !limits)) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: null limits");
-  for (int64_t i = 0; i < n_entries; ++i) {
-    const double lo = limits[2 * i], hi = limits[2 * i + 1];
-    if (std::isnan(lo) || std::isnan(hi)) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: limit %lld is NaN (an open side is -inf / +inf)", (long long)i);
-    if (lo > hi) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: limit %lld has lo > hi (%g > %g)", (long long)i, lo, hi);
-  }
+  if (int rc = et::check_limits("okx_ensemble_screen", limits, n_entries)) return rc;
   if (scale)
     for (int64_t i = 0; i < n_entries; ++i)
       if (!(std::isfinite(scale[i]) && scale[i] > 0.0))
@@ -292,12 +290,10 @@ int32_t okx_ensemble_screen(int64_t n_geometries, int64_t steps, int32_t n_colum
   if (!d_tally || !d_pass_count || (n_entries > 0 && !d_blame)) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: null tally, blame or survivor count");
   if (n_geometries > 0 && (!d_flags || !d_margin || !d_entry)) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: null flags, margin or entry table");
   if (n_entries > 0 && !d_limits) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: null limits");
-  if (n_geometries > 0 && n_entries > 0 && (!d_values || ld < n_columns)) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: null table or ld < n_columns");
-  if (d_status && status_stride < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: status_stride must be positive");
+  if (int rc = et::check_table("okx_ensemble_screen", n_geometries > 0 && n_entries > 0, d_values, ld, n_columns, d_status, status_stride)) return rc;
   if (capacity < 0) return fail(OKX_ERR_INVALID, "okx_ensemble_screen: negative capacity");
   const size_t need = okx_ensemble_screen_scratch_bytes(n_geometries, steps, n_columns);
-  if (!d_scratch || scratch_bytes < need)
-    return fail(OKX_ERR_INVALID, "okx_ensemble_screen: %zu bytes of scratch needed (okx_ensemble_screen_scratch_bytes), %zu given", need, scratch_bytes);
+  if (int rc = et::check_scratch("okx_ensemble_screen", "okx_ensemble_screen_scratch_bytes", need, d_scratch, scratch_bytes)) return rc;
   const sc::Plan plan = sc::plan_for(n_geometries, n_entries);
   if (plan.groups > 0x7fffffffll) return fail(OKX_ERR_LIMIT, "okx_ensemble_screen: too many geometries for one call");
   long long* base = static_cast<long long*>(d_scratch);

@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "../../include/okx.h"
+#include "okx_enstable.hpp"
 #include "okx_program.hpp"
 
 namespace okx {
@@ -254,6 +255,7 @@ inline int check_sizes(const char* who, long long steps, int n_columns, int n_pr
 }  // namespace okx
 
 using okx::fail;
+namespace et = okx::enstable;
 
 extern "C" {
 
@@ -281,12 +283,7 @@ int32_t okx_ensemble_select_check(const double* probs, int32_t n_probs, const do
   for (int32_t q = 0; q < n_probs; ++q)
     if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
       return fail(OKX_ERR_INVALID, "okx_ensemble_select: probability %d is %g, outside [0, 1]", (int)q, probs[q]);
-  for (int64_t i = 0; i < n_limits; ++i) {
-    const double lo = limits[2 * i], hi = limits[2 * i + 1];
-    if (std::isnan(lo) || std::isnan(hi)) return fail(OKX_ERR_INVALID, "okx_ensemble_select: limit %lld is NaN (an open side is -inf / +inf)", (long long)i);
-    if (lo > hi) return fail(OKX_ERR_INVALID, "okx_ensemble_select: limit %lld has lo > hi (%g > %g)", (long long)i, lo, hi);
-  }
-  return OKX_OK;
+  return et::check_limits("okx_ensemble_select", limits, n_limits);
 }
 
 int32_t okx_ensemble_select_begin(int64_t steps, int32_t n_columns, int32_t n_probs, void* d_state, int64_t* d_hist, void* stream) {
@@ -313,8 +310,7 @@ int32_t okx_ensemble_select_count(int32_t round, int64_t n_geometries, int64_t s
   const long long n_entries = (long long)steps * n_columns;
   if (n_entries == 0 || n_geometries == 0) return OKX_OK;
   if (!d_state || !d_hist) return fail(OKX_ERR_INVALID, "okx_ensemble_select_count: null state or histogram");
-  if (!d_values || ld < n_columns) return fail(OKX_ERR_INVALID, "okx_ensemble_select_count: null table or ld < n_columns");
-  if (d_status && status_stride < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_select_count: status_stride must be positive");
+  if (int rc = et::check_table("okx_ensemble_select_count", true, d_values, ld, n_columns, d_status, status_stride)) return rc;
   const int n_sel = 2 * n_probs, tile = sl::tile_for(n_sel);
   long long n_slabs, slab_len;
   sl::slab_plan(n_geometries, n_entries, tile, &n_slabs, &slab_len);
@@ -374,11 +370,9 @@ int32_t okx_ensemble_select(int64_t n_geometries, int64_t steps, int32_t n_colum
   if (!d_order || !d_count) return fail(OKX_ERR_INVALID, "okx_ensemble_select: null order-statistic or count table");
   if (!d_probs) return fail(OKX_ERR_INVALID, "okx_ensemble_select: null probabilities");
   if (d_outside && !d_limits) return fail(OKX_ERR_INVALID, "okx_ensemble_select: limit counts asked for without limits");
-  if (n_geometries > 0 && (!d_values || ld < n_columns)) return fail(OKX_ERR_INVALID, "okx_ensemble_select: null table or ld < n_columns");
-  if (d_status && status_stride < 1) return fail(OKX_ERR_INVALID, "okx_ensemble_select: status_stride must be positive");
+  if (int rc = et::check_table("okx_ensemble_select", n_geometries > 0, d_values, ld, n_columns, d_status, status_stride)) return rc;
   const size_t need = okx_ensemble_select_scratch_bytes(steps, n_columns, n_probs);
-  if (!d_scratch || scratch_bytes < need)
-    return fail(OKX_ERR_INVALID, "okx_ensemble_select: %zu bytes of scratch needed (okx_ensemble_select_scratch_bytes), %zu given", need, scratch_bytes);
+  if (int rc = et::check_scratch("okx_ensemble_select", "okx_ensemble_select_scratch_bytes", need, d_scratch, scratch_bytes)) return rc;
   void* state = d_scratch;
   int64_t* hist = reinterpret_cast<int64_t*>(static_cast<char*>(d_scratch) + okx_ensemble_select_state_bytes(steps, n_columns, n_probs));
   if (int rc = okx_ensemble_select_begin(steps, n_columns, n_probs, state, hist, stream)) return rc;
