@@ -951,6 +951,51 @@ int32_t okx_ensemble_covariance(int64_t n_geometries, int64_t steps, int32_t n_c
 size_t okx_ensemble_covariance_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_entries);
 int32_t okx_ensemble_covariance_check(const int32_t* entries /* or NULL */, int32_t n_entries, int64_t n_table_entries);
 
+/*
+ * Ensemble curves on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): what the four passes above
+ * do not look at - the shape of a column ALONG the sweep inside one geometry.  Per geometry g and column k of the same table
+ * the pass writes OKX_CURVE_FIELDS doubles, d_features [n_geometries][n_columns][12], and d_count [n_geometries][n_columns]
+ * int32; the features stay in HBM and are again a column table [G][K * 12] with ONE step per geometry, so
+ * okx_ensemble_reduce / _select / _screen / _covariance apply to gradients and curvatures as they do to per-step values.
+ * Abscissa: d_abscissa [steps], shared by every geometry, or NULL: column x_column of the table itself (every geometry is
+ * fitted against its own wheel travel, say).  u = (x - origin) / scale, scale finite and > 0; the window [window_lo,
+ * window_hi] is in x units and closed (-inf / +inf: open).  A step is USED for column k of geometry g when its state counts
+ * by the rule of okx_ensemble_reduce (status & 7 == 1), x is finite and inside the window, and the value is finite.
+ * The fit is the least-squares polynomial of degree 0 <= degree <= 3 in u over the used steps:
+ *   0 .. 3   c0 .. c3 in x units about origin, c_i = a_i / scale^i: the value at the origin, the gradient there, half the
+ *            curvature; degrees above `degree` are 0.0
+ *   4        rms of the residuals, sqrt(sum r^2 / n)
+ *   5        largest |r|: the departure from the fitted shape (linearity for degree 1)
+ *   6, 7     smallest and largest used value                         (exact table bits)
+ *   8, 9     the abscissa at which 6 and 7 are taken, the lowest step on ties    (exact bits)
+ *   10, 11   smallest and largest used abscissa, the lowest step on ties         (exact bits)
+ * With no used step all 12 fields are NaN.  With fewer than degree + 1 used steps, or a REFUSED fit, fields 0 .. 5 are NaN and
+ * 6 .. 11 stand.  A fit is refused when a pivot of the Cholesky factor of the normal matrix in u (N_ij = sum u^(i + j)),
+ * N_jj - sum_k L_jk^2, is not greater than 2^-40 times its diagonal entry N_jj - used abscissae that are all equal end there.
+ * NaN features need no flag: every pass above treats a non-finite value as one that does not count.
+ * The normal equations are solved by Cholesky in registers: |c_i scale^i - exact| is of the order cond(N) u max |y|, which
+ * is why u should be of order one over the window (scale = the half width).  No atomics and no scratch; the lane plan is a
+ * function of (steps, n_columns) alone and a geometry's outputs depend on its own rows only, so they are bit-identical from
+ * run to run and across chunkings, devices and ranks.  Launch-only, stream-ordered, no host read-back, no allocation, legal
+ * inside a stream capture; n_geometries = 0 is legal and does nothing, steps = 1 fits degree 0.  okx_ensemble_curves_check
+ * validates the arguments on the host (abscissa_len: the length of the shared abscissa, < 0: a column is used) with
+ * okx_last_error text; the launch runs it too.
+ */
+#define OKX_CURVE_FIELDS 12
+
+int32_t okx_ensemble_curves(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                            const double* d_values, int64_t ld,
+                            const uint8_t* d_status, int64_t status_stride, /* or NULL                                  */
+                            const double* d_abscissa,                       /* [steps] or NULL                          */
+                            int32_t x_column,                               /* used when d_abscissa is NULL             */
+                            double origin, double scale, double window_lo, double window_hi, int32_t degree,
+                            double* d_features,                             /* [n_geometries][n_columns][12]            */
+                            int32_t* d_count,                               /* [n_geometries][n_columns]                */
+                            void* stream);
+/* host only */
+int32_t okx_ensemble_curves_check(int64_t steps, int32_t n_columns, int64_t abscissa_len, int32_t x_column,
+                                  double origin, double scale, double window_lo, double window_hi, int32_t degree);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,8 @@ EXPORTS = (
     "okx_ensemble_covariance",
     "okx_ensemble_covariance_scratch_bytes",
     "okx_ensemble_covariance_check",
+    "okx_ensemble_curves",
+    "okx_ensemble_curves_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -263,6 +265,11 @@ def load() -> C.CDLL:
     lib.okx_ensemble_covariance_scratch_bytes.restype = C.c_size_t
     lib.okx_ensemble_covariance_check.argtypes = [vp, i32, i64]
     lib.okx_ensemble_covariance_check.restype = i32
+    f64 = C.c_double
+    lib.okx_ensemble_curves.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, f64, f64, f64, f64, i32, vp, vp, vp]
+    lib.okx_ensemble_curves.restype = i32
+    lib.okx_ensemble_curves_check.argtypes = [i64, i32, i64, i32, f64, f64, f64, f64, i32]
+    lib.okx_ensemble_curves_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -330,12 +330,26 @@ class ShardedEnsemble:
     ``covariance_accumulator`` holds the merged tables and ``covariance_local_used`` this rank's per-geometry used bytes.
     ``covariance_exchange_bytes_per_rank`` is ``8 (N^2 + N + 2)`` - 8 MB at N = 1024 however few geometries there are, which
     is why a SUBSET of entries (a few steps of a few columns) is the intended use at scale; no rank ever holds the table.
+
+    ``curves=dict(abscissa=..., scale=..., origin=0.0, degree=2, window=None)`` (with ``reduce=True``) adds what lies ALONG the
+    sweep (``okx_ensemble_curves``): right after a chunk's reduction, every geometry's rows of ``metric_local`` become a row of
+    12 curve characteristics per chosen column - fitted value, gradient and curvature at ``origin``, departure from the fitted
+    shape, extremes and where they occur - in this rank's feature table.  ``abscissa`` is an index into ``metric_columns`` (every
+    geometry against its own ``wheel_travel``) or a shared ``[S]`` table.  ``step()`` then ends with ONE more all-gather, of the
+    feature rows themselves (96 bytes per geometry and column, padded to the largest shard - ``S / 12`` times less than the
+    columns they came from), and every rank reduces the same table ``[G, K * 12]`` (one step per geometry,
+    ``okx_ensemble_reduce`` with the factors of all geometries): the answer carries the same bits on every rank and for every
+    world size and chunking.  The common shift is the feature row of the reduction's own shift table, so nobody solves again.
+    ``curve_stats()`` returns the ``ensemble_stats.EnsembleStats`` of the features over ALL geometries, every table
+    ``[1, K * 12]`` - moments, extremes with their geometry index and, with ``factors``, the sensitivities of gradients and
+    curvatures to the hardpoints; ``curves_local()`` this rank's ``EnsembleCurves``, which stay
+    where they are; ``curves_exchange_bytes_per_rank`` what the rank sends.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
-                 covariance=None, **solve_kw):
+                 covariance=None, curves=None, **solve_kw):
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
         if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
@@ -346,6 +360,8 @@ class ShardedEnsemble:
             covariance = None
         if covariance is not None and not reduce:
             raise ValueError("covariance= accumulates the reduced ensemble: it needs reduce=True")
+        if curves is not None and not reduce:
+            raise ValueError("curves= fits the reduced ensemble's columns: it needs reduce=True")
         self.reduce = bool(reduce)
         if metric_columns is not None:
             records, info = False, "status"   # nothing of the positions travels or is written
@@ -473,9 +489,12 @@ class ShardedEnsemble:
             if self.covarying:
                 stage = self.stages["covariance"] = stages.Covariance(self, covariance)
                 self.covariance_entries = stage.entries
+            if curves is not None:
+                self.stages["curves"] = stages.Curves(self, dict(curves))
         sent = {name: stage.bytes_per_rank for name, stage in self.stages.items()}
         self.select_exchange_bytes_per_rank, self.screen_exchange_bytes_per_rank = sent.get("select", 0), sent.get("screen", 0)
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
+        self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
 
     # ---- reduce=True: the stages of ensemble_stages.py; what they hold and answer, by the names it has always had ----
 
@@ -515,6 +534,20 @@ class ShardedEnsemble:
         if not self.covarying:
             raise ValueError("covariance() needs covariance=True or covariance=entries")
         return self.stages["covariance"].covariance()
+
+    def curves_local(self):
+        """This rank's ``ensemble_stats.EnsembleCurves`` of the last ``step()`` (``curves=``): ``features [n_local, K, 12]`` and ``count
+        [n_local, K]``, tensors where the table lives; ``.table()`` feeds the other ensemble passes with ``steps_per_geometry=1``."""
+        if "curves" not in self.stages:
+            raise ValueError("curves_local() needs curves=")
+        return self.stages["curves"].local
+
+    def curve_stats(self):
+        """``ensemble_stats.EnsembleStats`` of the curve features over the WHOLE ensemble after the last ``step()`` (``curves=``), every
+        table ``[1, K * 12]``: entry ``k * 12 + f`` is field f of column k.  The same bits on every rank."""
+        if "curves" not in self.stages:
+            raise ValueError("curve_stats() needs curves=")
+        return self.stages["curves"].curve_stats()
 
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
@@ -741,7 +774,7 @@ class ShardedEnsemble:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
         if self.reduce:
             # every rank, with or without a geometry, in this order: the accumulators' all-gather, the select rounds' all-reduces,
-            # the screen's all-reduce and all-gather, the covariance's all-gather
+            # the screen's all-reduce and all-gather, the covariance's all-gather, the curve features' all-gather
             for stage in self.stages.values():
                 stage.end_step()
             return self.accumulator

@@ -1,7 +1,7 @@
 """
 The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce`` (moments, extremes, sensitivities),
-``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry) and
-``okx_ensemble_covariance``.  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry),
+``okx_ensemble_covariance`` and ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
 is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
 """
 
@@ -373,4 +373,71 @@ class EnsembleReductions:
         index = None if out.natural and n == s * k else _ptr(out.entries)
         self._ensemble_call("okx_ensemble_covariance", g, s, k, _ptr(values), ld, _ptr(status), stride, index, n, _ptr(out.shift),
                             1 if accumulate else 0, _ptr(out.gram), _ptr(out.sum), _ptr(out.counts), _ptr(used), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_curves: the characteristics of every geometry's curves along the sweep (ensemble_stats.EnsembleCurves) ----
+
+    def curves_prepare(self, steps: int, n_columns: int, n_geometries: int, *, abscissa, scale, origin=0.0, degree: int = 2, window=None):
+        """
+        The tables of a curves pass over ``[steps, n_columns]`` entries and ``n_geometries`` geometries: the arguments are
+        validated (``okx_ensemble_curves_check``), a shared abscissa ``[S]`` is uploaded ONCE (an integer ``abscissa`` names a
+        column of the table) and ``features [G, K, 12]`` / ``count [G, K]`` are allocated.
+        """
+        from .ensemble_stats import CURVE_FIELDS, EnsembleCurves
+
+        s, k, g = int(steps), int(n_columns), int(n_geometries)
+        if g < 0:
+            raise ValueError("negative geometry count")
+        shared = None
+        if abscissa is None:
+            raise ValueError("abscissa is needed: a column of the table or a shared [S] table (or out=, which carries its own)")
+        if isinstance(abscissa, (int, np.integer)) and not isinstance(abscissa, bool):
+            kx, n_x = int(abscissa), -1
+        else:
+            shared = np.ascontiguousarray(_host_f64(abscissa).reshape(-1))
+            kx, n_x = 0, shared.size
+        degree = int(degree) if not isinstance(degree, bool) and int(degree) == degree else -1
+        lo, hi = (-np.inf, np.inf) if window is None else (float(window[0]), float(window[1]))
+        rc = self.lib.okx_ensemble_curves_check(s, k, n_x, kx, float(origin), float(scale), lo, hi, degree)
+        _lib.check(rc, "okx_ensemble_curves")
+        dev = self.device
+        return EnsembleCurves(torch.empty((g, k, CURVE_FIELDS), dtype=torch.float64, device=dev), torch.empty((g, k), dtype=torch.int32, device=dev),
+                              None if shared is None else torch.as_tensor(shared, device=dev),
+                              (kx if shared is None else -1, float(origin), float(scale), lo, hi, degree))
+
+    def curves_ensemble(self, values, *, steps_per_geometry: int, abscissa=None, scale=None, status=None, origin=None, degree=None,
+                        window=None, out=None, first_row: int = 0):
+        """
+        ``okx_ensemble_curves``: per GEOMETRY and column of a column table in HBM, the characteristics of the curve along the
+        sweep - the least-squares polynomial of ``degree`` (0 .. 3, default 2) in ``u = (x - origin) / scale`` over the used
+        steps, its residuals, the extremes and where they occur (``ensemble_stats.EnsembleCurves`` of device tensors:
+        ``features [G, K, 12]``, ``count [G, K]`` int32).  ``abscissa``: a shared ``x [S]`` or an integer column of the table
+        (every geometry against its own ``wheel_travel``); ``window = (lo, hi)`` in x units, closed.  ``values`` and ``status``
+        as ``screen_ensemble`` takes them (unit column stride; strided rows and a strided status byte are passed on, nothing
+        is copied).  ``.table()`` is the ``[G, K * 12]`` column table the other passes take with ``steps_per_geometry=1``;
+        ``.finalize()`` copies to the host.  ``out``: the curves of an earlier call or of ``curves_prepare`` - it carries its
+        own arguments; with it and a table shape seen before, the call uploads and allocates nothing and is legal inside a
+        stream capture.  The call's geometries are written from row ``first_row`` of ``out``'s tables on.  A geometry's
+        features depend on its own rows alone: bit-identical from run to run and however the geometries are chunked.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        row = int(first_row)
+        if out is None:
+            if scale is None:
+                raise ValueError("abscissa and scale are needed (or out=, which carries its own)")
+            out = self.curves_prepare(s, k, row + g, abscissa=abscissa, scale=scale, origin=0.0 if origin is None else origin,
+                                      degree=2 if degree is None else degree, window=window)
+        elif any(x is not None for x in (abscissa, scale, origin, degree, window)):
+            raise ValueError("out= carries its own abscissa, origin, scale, degree and window")
+        f, n = out.features, out.count
+        if f.dim() != 3 or tuple(f.shape[1:]) != (k, 12) or tuple(n.shape) != (f.shape[0], k) or f.device != self.device or n.device != self.device \
+                or f.dtype != torch.float64 or n.dtype != torch.int32 or not f.is_contiguous() or not n.is_contiguous():
+            raise ValueError(f"out must hold contiguous device tables features [G, {k}, 12] and count [G, {k}]")
+        if out.abscissa is not None and out.abscissa.shape[0] != s:
+            raise ValueError(f"out was prepared for {out.abscissa.shape[0]} steps")
+        if row < 0 or row + g > f.shape[0]:
+            raise ValueError(f"out holds {f.shape[0]} geometries: rows [{row}, {row + g}) do not fit")
+        kx, origin, scale, lo, hi, degree = out.arguments
+        self._ensemble_call("okx_ensemble_curves", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.abscissa), max(kx, 0), origin, scale,
+                            lo, hi, degree, _ptr(f[row:]), _ptr(n[row:]))
         return out

@@ -1,7 +1,7 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
-(moments, extremes, sensitivities), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``) and ``Covariance``
-(``covariance=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+(moments, extremes, sensitivities), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
+(``covariance=``) and ``Curves`` (``curves=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
 * ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
@@ -101,6 +101,7 @@ class Reduction(_AccumulatorStage):
             factors = np.ascontiguousarray(torch.as_tensor(factors).detach().cpu().numpy(), dtype=np.float64).reshape(o.n_geom, -1)
         p = 0 if factors is None else factors.shape[1]
         self.n_factors = p
+        self.all_factors = factors  # [G, P] on the host (or None): a stage that reduces rows of every rank takes them from here
         self.my_factors = torch.as_tensor(factors[glo:ghi], device=device).contiguous() if p else None
         # the shift: ONE table for every partial that is ever merged
         if shift is None:
@@ -318,6 +319,86 @@ class Covariance(_AccumulatorStage):
         self.merged = self.merged_over_ranks(mine, (mine.gram, mine.sum, mine.counts.view(torch.float64)), unpack)
 
     def covariance(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result
+
+
+class Curves(_Stage):
+    """``curves=dict(abscissa=, origin=, scale=, degree=, window=)``: every geometry's curve characteristics along the sweep, chunk
+    by chunk into this rank's feature table.  At the end of a step the ranks all-gather their feature rows (96 bytes per
+    geometry and column - a table ``S / 12`` times smaller than the one it came from) and every rank reduces the SAME table
+    ``[G, K * 12]``, one step per geometry, with the same factors and the same shift: the answer does not depend on how the
+    geometries were sharded or chunked."""
+
+    def __init__(self, owner, curves):
+        super().__init__(owner)
+        o = owner
+        glo, ghi = o.geometry_range
+        k, device = len(o.metric_index), o.device
+        unknown = set(curves) - {"abscissa", "origin", "scale", "degree", "window"}
+        if unknown or "abscissa" not in curves or "scale" not in curves:
+            raise ValueError(f"curves= takes abscissa, scale and optionally origin, degree, window (got {sorted(curves)})")
+        kw = dict(abscissa=curves["abscissa"], origin=curves.get("origin", 0.0), scale=curves["scale"], degree=curves.get("degree", 2),
+                  window=curves.get("window"))
+        self.arguments = es.check_curve_arguments(kw["abscissa"], kw["origin"], kw["scale"], kw["degree"], kw["window"], o.steps, k)
+        self.host_kw = dict(kw, abscissa=kw["abscissa"] if self.arguments[0] is None else self.arguments[0])
+        reduction = o.stages["reduce"]
+        n = k * es.CURVE_FIELDS
+        # the common shift: the features of the reduction's own shift table - the nominal geometry's rows, the same on every
+        # rank, so nobody solves again
+        if self.on_device:
+            self.local = o.dp.curves_prepare(o.steps, k, ghi - glo, **self.host_kw)
+            nominal = o.dp.curves_ensemble(reduction.local.shift, steps_per_geometry=o.steps, **self.host_kw)
+            shift = torch.nan_to_num(nominal.table(), nan=0.0, posinf=0.0, neginf=0.0)
+        else:
+            self.local = es.EnsembleCurves(torch.full((ghi - glo, k, es.CURVE_FIELDS), float("nan"), dtype=torch.float64),
+                                           torch.zeros((ghi - glo, k), dtype=torch.int32), None, self.arguments[1:])
+            nominal = es.curves_host(reduction.local.shift.cpu().numpy()[None], None, **self.host_kw)
+            shift = torch.as_tensor(es.clean_shift(nominal.table()))
+        p = reduction.n_factors
+        self.n_factors, self.factor_names = p, reduction.factor_names
+        self.factors = torch.as_tensor(reduction.all_factors, device=device).contiguous() if p else None  # [G, P]: every rank reduces every row
+        self.acc = es.EnsembleAccumulator(torch.empty((1, n, es.ENS_FIELDS + p), dtype=torch.float64, device=device), shift.reshape(1, n).contiguous(),
+                                          torch.empty(es.factor_moment_count(p), dtype=torch.float64, device=device) if p else None, self.factor_names)
+        self.spans = [shard_range(o.n_geom, r, o.world) for r in range(o.world)]
+        self.largest_shard = max(hi - lo for lo, hi in self.spans)
+        self.send = torch.empty((self.largest_shard, n), dtype=torch.float64, device=device) if o.world > 1 else None
+        self.recv = torch.empty((o.world, self.largest_shard * n), dtype=torch.float64, device=device) if o.world > 1 else None
+        self.merged = self.result = None
+        self.bytes_per_rank = 8 * self.largest_shard * n if o.world > 1 else 0
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o = self.owner
+        glo = o.geometry_range[0]
+        if self.on_device:
+            o.dp.curves_ensemble(values, steps_per_geometry=o.steps, status=status, out=self.local, first_row=a - glo)
+            return
+        part = es.curves_host(*self.host_tables(a, b, values, status), **self.host_kw)
+        self.local.features[a - glo : b - glo] = torch.from_numpy(part.features)
+        self.local.count[a - glo : b - glo] = torch.from_numpy(part.count)
+
+    def exchange(self) -> None:
+        """ONE all-gather of the feature rows (padded to the largest shard), then the reduction of the whole table on every rank."""
+        o, acc = self.owner, self.acc
+        table = self.local.table()
+        if o.world > 1:
+            self.send.fill_(float("nan"))
+            self.send[: table.shape[0]] = table
+            all_gather_flat(self.send.view(-1), o.group, out=self.recv)
+            n = table.shape[1]
+            table = torch.cat([self.recv[r, : (hi - lo) * n].reshape(hi - lo, n) for r, (lo, hi) in enumerate(self.spans)])
+        self.result = None
+        if self.on_device:
+            o.dp.reduce_ensemble(table, steps_per_geometry=1, factors=self.factors, out=acc)
+            self.merged = acc
+            return
+        self.merged = es.reduce_host(table.numpy()[:, None, :], None, None if self.factors is None else self.factors.numpy(), acc.shift.numpy(), 0,
+                                     self.factor_names)
+
+    def curve_stats(self):
         if self.merged is None:
             raise RuntimeError("no step() yet")
         if self.result is None:

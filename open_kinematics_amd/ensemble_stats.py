@@ -14,6 +14,9 @@ Beside the moments: exact quantiles and per-entry spec-limit yield (``select_hos
 spec-limit verdict per geometry (``screen_host`` / ``EnsembleScreen``, ``okx_ensemble_screen``), each in the same three layers;
 and how the entries move TOGETHER over the geometries: covariance and correlation of selected entries over the complete cases
 (``covariance_host`` / ``CovarianceAccumulator`` / ``EnsembleCovariance``, ``okx_ensemble_covariance``), in the same three.
+ALONG the sweep inside one geometry: the curve characteristics of every (geometry, column) - fitted value, gradient and
+curvature at an origin, departure from the fitted shape, extremes and where they occur (``curves_host`` / ``EnsembleCurves``,
+``okx_ensemble_curves``); their table ``[G, K * 12]`` is again a column table for every pass above.
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -739,10 +742,148 @@ def covariance_host(values, status=None, entries=None, shift=None) -> Covariance
     return CovarianceAccumulator(gram, s1, counts, shift, e, used.astype(np.uint8))
 
 
+
+# ---- per-geometry sweep-curve characteristics: a low-degree fit ALONG the sweep inside every geometry (okx_ensemble_curves) ----
+
+CURVE_FIELDS = 12  # OKX_CURVE_FIELDS
+CURVE_C0, CURVE_C1, CURVE_C2, CURVE_C3, CURVE_RMS, CURVE_DEPARTURE, CURVE_MIN, CURVE_MAX, CURVE_X_AT_MIN, CURVE_X_AT_MAX, CURVE_X_LO, CURVE_X_HI = range(12)
+CURVE_MAX_DEGREE = 3
+CURVE_PIVOT = 2.0 ** -40  # a fit is refused when a Cholesky pivot of the normal matrix in u is not greater than this times its diagonal entry
+
+
+@dataclass
+class EnsembleCurves:
+    """
+    What ``curves_host`` returns (NumPy) and ``DeviceProgram.curves_ensemble`` leaves in HBM (torch tensors): ``features
+    [G, K, 12]`` float64 and ``count [G, K]`` int32, the used steps of column k of geometry g.  A step is USED when its state
+    counts (``status & 7 == 1``), its abscissa x is finite and inside the closed window, and the value is finite.  Fields:
+    0 .. 3 ``c0 .. c3`` of the least-squares polynomial of degree D in ``u = (x - origin) / scale`` over the used steps, in x
+    units about ``origin`` (``c_i = a_i / scale^i``; degrees above D are 0.0); 4 the rms of the residuals ``sqrt(sum r^2 / n)``;
+    5 the largest ``abs(r)``; 6, 7 the smallest and largest used value and 8, 9 the abscissa where they are taken (the lowest
+    step on ties); 10, 11 the smallest and largest used abscissa (the lowest step on ties) - 6 .. 11 exact table bits.  With no
+    used step all 12 are NaN; with fewer than D + 1 used steps or a refused fit (``CURVE_PIVOT``) fields 0 .. 5 are NaN.
+    ``table()`` is the ``[G, K * 12]`` column table the other ensemble passes take with ``steps_per_geometry=1``.
+    """
+
+    features: object
+    count: object
+    abscissa: object = None  # device: the shared abscissa [S] as uploaded, or None (a column of the table)
+    arguments: tuple = ()    # (x_column, origin, scale, lo, hi, degree) the tables were made with
+
+    def table(self):
+        return self.features.reshape(self.features.shape[0], self.features.shape[1] * self.features.shape[2])
+
+    def _field(self, f):
+        return self.features[..., f]
+
+    value_at_origin = property(lambda self: self._field(CURVE_C0), doc="``c0 [G, K]``: the fitted value at the origin.")
+    gradient = property(lambda self: self._field(CURVE_C1), doc="``c1 [G, K]``: the fitted gradient at the origin.")
+    curvature = property(lambda self: 2.0 * self._field(CURVE_C2), doc="``2 c2 [G, K]``: the fitted second derivative at the origin.")
+    cubic = property(lambda self: self._field(CURVE_C3), doc="``c3 [G, K]``.")
+    rms = property(lambda self: self._field(CURVE_RMS), doc="rms of the fit residuals.")
+    departure = property(lambda self: self._field(CURVE_DEPARTURE), doc="Largest ``abs`` residual: linearity when D = 1.")
+    min = property(lambda self: self._field(CURVE_MIN))
+    max = property(lambda self: self._field(CURVE_MAX))
+    x_at_min = property(lambda self: self._field(CURVE_X_AT_MIN))
+    x_at_max = property(lambda self: self._field(CURVE_X_AT_MAX))
+    x_lo = property(lambda self: self._field(CURVE_X_LO))
+    x_hi = property(lambda self: self._field(CURVE_X_HI))
+
+    def finalize(self) -> "EnsembleCurves":
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(self.features):
+            return self
+        return EnsembleCurves(self.features.detach().cpu().numpy(), self.count.detach().cpu().numpy(), None, self.arguments)
+
+
+def check_curve_arguments(abscissa, origin, scale, degree, window, steps: int, n_columns: int):
+    """``(x [S] float64 or None, x_column, origin, scale, lo, hi, degree)``, or ValueError in the words of
+    ``okx_ensemble_curves_check``.  ``abscissa``: an integer (a column of the table) or a shared ``[S]`` table."""
+    s, k = int(steps), int(n_columns)
+    if isinstance(degree, bool) or int(degree) != degree or not 0 <= int(degree) <= CURVE_MAX_DEGREE:
+        raise ValueError(f"okx_ensemble_curves: degree {degree}, 0 to {CURVE_MAX_DEGREE} allowed")
+    scale, origin = float(scale), float(origin)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"okx_ensemble_curves: scale is {scale:g}, not finite and > 0")
+    if np.isnan(origin):
+        raise ValueError("okx_ensemble_curves: origin is NaN")
+    lo, hi = (-np.inf, np.inf) if window is None else (float(window[0]), float(window[1]))
+    if np.isnan(lo) or np.isnan(hi):
+        raise ValueError("okx_ensemble_curves: window is NaN (an open side is -inf / +inf)")
+    if lo > hi:
+        raise ValueError(f"okx_ensemble_curves: window has lo > hi ({lo:g} > {hi:g})")
+    if abscissa is None:
+        raise ValueError("okx_ensemble_curves: abscissa is needed: a column of the table or a shared [S] table")
+    if isinstance(abscissa, (int, np.integer)) and not isinstance(abscissa, bool):
+        if not 0 <= int(abscissa) < k:
+            raise ValueError(f"okx_ensemble_curves: abscissa column {int(abscissa)}, outside [0, {k})")
+        return None, int(abscissa), origin, scale, lo, hi, int(degree)
+    x = np.ascontiguousarray(_host_f64(abscissa).reshape(-1))
+    if x.size != s:
+        raise ValueError(f"okx_ensemble_curves: shared abscissa of {x.size} values, {s} steps")
+    return x, -1, origin, scale, lo, hi, int(degree)
+
+
+def curve_normal_refused(u, degree: int) -> bool:
+    """The refusal rule on the used ``u [n]``: a pivot of the Cholesky factor of ``V^T V`` (V the Vandermonde matrix of degree
+    ``degree``) is not greater than ``CURVE_PIVOT`` times its diagonal entry."""
+    v = np.vander(np.asarray(u, dtype=np.float64), degree + 1, increasing=True)
+    a = v.T @ v
+    low = np.zeros_like(a)
+    for j in range(degree + 1):
+        d = a[j, j] - np.dot(low[j, :j], low[j, :j])
+        if not d > CURVE_PIVOT * a[j, j]:
+            return True
+        low[j, j] = np.sqrt(d)
+        for i in range(j + 1, degree + 1):
+            low[i, j] = (a[i, j] - np.dot(low[i, :j], low[j, :j])) / low[j, j]
+    return False
+
+
+def curves_host(values, status=None, abscissa=None, origin: float = 0.0, scale: float = 1.0, degree: int = 2, window=None) -> EnsembleCurves:
+    """
+    The definition of ``okx_ensemble_curves`` in NumPy: ``values [G, S, K]``, ``status [G, S]`` or None, ``abscissa`` a shared
+    ``x [S]`` or an integer column ``kx`` (``x[g, s] = values[g, s, kx]``).  The fit is ``numpy.linalg.lstsq`` on the Vandermonde
+    matrix in ``u = (x - origin) / scale`` over the used steps of every (geometry, column); see ``EnsembleCurves``.
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    x, kx, origin, scale, lo, hi, degree = check_curve_arguments(abscissa, origin, scale, degree, window, s, k)
+    xs = np.broadcast_to(x[None], (g, s)) if x is not None else v[:, :, kx]
+    with np.errstate(invalid="ignore"):
+        inside = np.isfinite(xs) & (xs >= lo) & (xs <= hi)
+    used = ok & inside[:, :, None]
+    features = np.full((g, k, CURVE_FIELDS), np.nan)
+    count = used.sum(axis=1).astype(np.int32)
+    for gi in range(g):
+        for ki in range(k):
+            at = np.flatnonzero(used[gi, :, ki])
+            if at.size == 0:
+                continue
+            y, xu = v[gi, at, ki], xs[gi, at]
+            f = features[gi, ki]
+            # (argmin / argmax return the FIRST extreme: the lowest step)
+            f[CURVE_MIN], f[CURVE_X_AT_MIN] = y[np.argmin(y)], xu[np.argmin(y)]
+            f[CURVE_MAX], f[CURVE_X_AT_MAX] = y[np.argmax(y)], xu[np.argmax(y)]
+            f[CURVE_X_LO], f[CURVE_X_HI] = xu[np.argmin(xu)], xu[np.argmax(xu)]
+            u = (xu - origin) / scale
+            if at.size < degree + 1 or curve_normal_refused(u, degree):
+                continue
+            vander = np.vander(u, degree + 1, increasing=True)
+            a = np.linalg.lstsq(vander, y, rcond=None)[0]
+            r = y - vander @ a
+            f[:4] = 0.0
+            f[: degree + 1] = a / scale ** np.arange(degree + 1)
+            f[CURVE_RMS] = np.sqrt(np.sum(r * r) / at.size)
+            f[CURVE_DEPARTURE] = np.max(np.abs(r))
+    return EnsembleCurves(features, count, None, (kx, origin, scale, lo, hi, degree))
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
            "select_finish", "select_keys", "select_values", "quantiles_from_order", "check_select_arguments", "broadcast_limits", "broadcast_scale", "SELECT_BITS", "SELECT_BINS",
            "SELECT_ROUNDS", "SELECT_MAX_PROBS", "EnsembleScreen", "screen_host", "check_screen_arguments", "SCREEN_OUTSIDE",
            "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED", "EnsembleCovariance", "CovarianceAccumulator",
-           "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES"]
+           "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES", "EnsembleCurves", "curves_host", "check_curve_arguments",
+           "curve_normal_refused", "CURVE_FIELDS", "CURVE_MAX_DEGREE", "CURVE_PIVOT"]
