@@ -996,6 +996,57 @@ int32_t okx_ensemble_curves(int64_t n_geometries, int64_t steps, int32_t n_colum
 int32_t okx_ensemble_curves_check(int64_t steps, int32_t n_columns, int64_t abscissa_len, int32_t x_column,
                                   double origin, double scale, double window_lo, double window_hi, int32_t degree);
 
+/*
+ * Ensemble Pareto front on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): which geometries of
+ * the same table are worth keeping - those that no other geometry beats on every objective at once.  The table, the status
+ * bytes and the rule by which an entry COUNTS are those of okx_ensemble_reduce (status & 7 == 1 and a finite value).
+ * `entries`, `sense` and `target` are HOST arrays of n_objectives items, 1 <= n_objectives <= OKX_ENS_FRONT_MAX_OBJECTIVES;
+ * they are read at launch and travel as kernel arguments.  entries[m] = s * n_columns + k as in okx_ensemble_covariance,
+ * distinct and in range; sense[m] is OKX_FRONT_MIN, _MAX or _TARGET (then target[m] must be finite; target may be NULL
+ * when no objective aims at one).
+ * Geometry g is a CANDIDATE when d_mask is NULL or d_mask[g * mask_stride] == 0 - exactly the flag byte
+ * okx_ensemble_screen writes, 0 meaning pass - and every selected entry of g counts (complete cases, the rule of the
+ * covariance pass).  Its objective o_m is v (MIN), -v (MAX) or |v - target_m| (TARGET, the subtraction rounded once) of the
+ * table value v.  a DOMINATES b when o_a[m] <= o_b[m] for every m and o_a[m] < o_b[m] for some m, compared as IEEE values
+ * (-0.0 == +0.0).  Candidates with equal objective vectors do not dominate each other: all of them are on the front or none.
+ *   d_dominated [n_geometries] int32   the number of candidates of THIS call that dominate g; -1: g is no candidate;
+ *                                      0: g is on the front.  With one objective: the competition rank minus one.
+ *   d_tally [3] int64                  geometries seen, candidates, front members (the last may exceed capacity)
+ *   d_front_index [capacity] int64, d_front_values [capacity][n_objectives] double   (each may be NULL)
+ *                                      the front members in ascending row order: d_index[g] when d_index is given,
+ *                                      geometry_offset + g otherwise, and the RAW table values of the selected entries,
+ *                                      exact bits.  Slots at or beyond capacity, and beyond the count, are never written.
+ * Only comparisons and integer counts: no tolerance, no floating-point atomic, bit-identical from run to run and across
+ * chunks, devices and ranks, and fronts merge: front(A u B) = front(front(A) u front(B)) - run the pass again over the
+ * front_values rows of two calls (steps = 1, n_columns = n_objectives, the same senses and targets, the ids through d_index,
+ * a mask for the unused slots).  Launch-only, stream-ordered, no host read-back, no allocation, legal inside a stream
+ * capture.  n_geometries = 0 is legal and writes a zero tally.  The pass is O(G^2 M): n_geometries above
+ * OKX_ENS_FRONT_MAX_GEOMETRIES is OKX_ERR_INVALID - the cap bounds how long one launch occupies the card; larger ensembles go
+ * in chunks and merge.  okx_ensemble_front_check validates the host arguments without a launch (an entry out of range or
+ * repeated, a sense outside 0 .. 2, a TARGET objective with a missing or non-finite target, a count outside 1 .. 8,
+ * n_geometries above the cap: OKX_ERR_INVALID with okx_last_error text); the launch runs it too.
+ */
+enum { OKX_FRONT_MIN = 0, OKX_FRONT_MAX = 1, OKX_FRONT_TARGET = 2,
+       OKX_ENS_FRONT_MAX_OBJECTIVES = 8, OKX_ENS_FRONT_MAX_GEOMETRIES = 65536 };
+
+int32_t okx_ensemble_front(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                           const double* d_values, int64_t ld,
+                           const uint8_t* d_status, int64_t status_stride,   /* or NULL                                   */
+                           const int32_t* entries, const int32_t* sense,     /* HOST [n_objectives]                       */
+                           const double* target, int32_t n_objectives,       /* HOST [n_objectives] or NULL               */
+                           const uint8_t* d_mask, int64_t mask_stride,       /* or NULL                                   */
+                           const int64_t* d_index, int64_t geometry_offset,  /* d_index [n_geometries] or NULL            */
+                           int32_t* d_dominated,                             /* [n_geometries]                            */
+                           int64_t* d_tally,                                 /* [3]                                       */
+                           int64_t* d_front_index, double* d_front_values,   /* [capacity], [capacity][n_objectives], or NULL */
+                           int64_t capacity,
+                           void* d_scratch, size_t scratch_bytes, void* stream);
+size_t okx_ensemble_front_scratch_bytes(int64_t n_geometries, int32_t n_objectives);
+/* host only */
+int32_t okx_ensemble_front_check(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                                 const int32_t* entries, const int32_t* sense,
+                                 const double* target, int32_t n_objectives);
+
 #ifdef __cplusplus
 }
 #endif

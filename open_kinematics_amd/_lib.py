@@ -78,6 +78,9 @@ EXPORTS = (
     "okx_ensemble_covariance_check",
     "okx_ensemble_curves",
     "okx_ensemble_curves_check",
+    "okx_ensemble_front",
+    "okx_ensemble_front_scratch_bytes",
+    "okx_ensemble_front_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -270,6 +273,12 @@ def load() -> C.CDLL:
     lib.okx_ensemble_curves.restype = i32
     lib.okx_ensemble_curves_check.argtypes = [i64, i32, i64, i32, f64, f64, f64, f64, i32]
     lib.okx_ensemble_curves_check.restype = i32
+    lib.okx_ensemble_front.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, C.c_size_t, vp]
+    lib.okx_ensemble_front.restype = i32
+    lib.okx_ensemble_front_scratch_bytes.argtypes = [i64, i32]
+    lib.okx_ensemble_front_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_front_check.argtypes = [i64, i64, i32, vp, vp, vp, i32]
+    lib.okx_ensemble_front_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

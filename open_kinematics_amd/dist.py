@@ -344,12 +344,23 @@ class ShardedEnsemble:
     ``[1, K * 12]`` - moments, extremes with their geometry index and, with ``factors``, the sensitivities of gradients and
     curvatures to the hardpoints; ``curves_local()`` this rank's ``EnsembleCurves``, which stay
     where they are; ``curves_exchange_bytes_per_rank`` what the rank sends.
+
+    ``front=dict(objectives=..., source="table" | "curves", screened=False)`` (with ``reduce=True``) adds WHICH geometries are worth
+    keeping (``okx_ensemble_front``): the nondominated (Pareto) front on up to 8 objectives.  ``source="table"`` takes objectives
+    ``(step, column, sense)`` / ``(step, column, "target", value)`` over ``metric_columns``; ``source="curves"`` (needs ``curves=``)
+    takes ``(column, field, sense...)`` over the curve features; ``screened=True`` (needs ``screen=True``) lets only the geometries
+    that pass the screen be candidates - its flag bytes are the mask, as they lie in HBM.  The stage runs after the screen and
+    the curves of a chunk; chunks merge into the rank's front (``front(A u B) = front(front(A) u front(B))``, the same kernel
+    again); ``step()`` ends with one all-gather of the local front rows - id, M values and a member byte, padded to the largest
+    shard - and every rank runs the pass once more over the gathered rows.  All comparisons: the same bits on every rank and
+    for every world size and chunking.  ``front()`` returns the ensemble's ``ensemble_stats.EnsembleFront``, ``front_local()`` this
+    rank's run, ``front_exchange_bytes_per_rank`` what the rank sends.  At most 65536 geometries.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
-                 covariance=None, curves=None, **solve_kw):
+                 covariance=None, curves=None, front=None, **solve_kw):
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
         if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
@@ -362,6 +373,21 @@ class ShardedEnsemble:
             raise ValueError("covariance= accumulates the reduced ensemble: it needs reduce=True")
         if curves is not None and not reduce:
             raise ValueError("curves= fits the reduced ensemble's columns: it needs reduce=True")
+        if front is not None:
+            from .ensemble_stats import FRONT_MAX_GEOMETRIES
+
+            front = dict(front)
+            unknown = set(front) - {"objectives", "source", "screened"}
+            if not reduce:
+                raise ValueError("front= ranks the reduced ensemble's geometries: it needs reduce=True")
+            if unknown or "objectives" not in front or front.get("source", "table") not in ("table", "curves"):
+                raise ValueError(f"front= takes objectives and optionally source ('table' or 'curves') and screened (got {sorted(front)})")
+            if front.get("source", "table") == "curves" and curves is None:
+                raise ValueError("front=dict(source='curves') reads the curve features: it needs curves=")
+            if front.get("screened", False) and not screen:
+                raise ValueError("front=dict(screened=True) takes the screen's flag bytes as its mask: it needs screen=True")
+            if int(hardpoints.shape[0]) > FRONT_MAX_GEOMETRIES:
+                raise ValueError(f"front= takes at most {FRONT_MAX_GEOMETRIES} geometries, the ensemble has {int(hardpoints.shape[0])}")
         self.reduce = bool(reduce)
         if metric_columns is not None:
             records, info = False, "status"   # nothing of the positions travels or is written
@@ -491,10 +517,13 @@ class ShardedEnsemble:
                 self.covariance_entries = stage.entries
             if curves is not None:
                 self.stages["curves"] = stages.Curves(self, dict(curves))
+            if front is not None:
+                self.stages["front"] = stages.Front(self, front)
         sent = {name: stage.bytes_per_rank for name, stage in self.stages.items()}
         self.select_exchange_bytes_per_rank, self.screen_exchange_bytes_per_rank = sent.get("select", 0), sent.get("screen", 0)
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
+        self.front_exchange_bytes_per_rank = sent.get("front", 0)
 
     # ---- reduce=True: the stages of ensemble_stages.py; what they hold and answer, by the names it has always had ----
 
@@ -548,6 +577,20 @@ class ShardedEnsemble:
         if "curves" not in self.stages:
             raise ValueError("curve_stats() needs curves=")
         return self.stages["curves"].curve_stats()
+
+    def front_local(self):
+        """This rank's front run of the last ``step()`` (``front=``), its chunks merged: ``ensemble_device.EnsembleFronting`` of device
+        tensors, or ``ensemble_stats.EnsembleFront`` on a CPU ensemble; nothing is copied."""
+        if "front" not in self.stages:
+            raise ValueError("front_local() needs front=")
+        return self.stages["front"].local
+
+    def front(self):
+        """``ensemble_stats.EnsembleFront`` of the WHOLE ensemble after the last ``step()`` (``front=``): the ids and raw objective
+        values of the geometries no other geometry beats, ``tally`` = seen, candidates, members.  The same bits on every rank."""
+        if "front" not in self.stages:
+            raise ValueError("front() needs front=")
+        return self.stages["front"].front()
 
     def stats(self):
         """``ensemble_stats.EnsembleStats`` of the last ``step()`` (``reduce=True``): the merged accumulator, finalized on the host."""
@@ -774,7 +817,8 @@ class ShardedEnsemble:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
         if self.reduce:
             # every rank, with or without a geometry, in this order: the accumulators' all-gather, the select rounds' all-reduces,
-            # the screen's all-reduce and all-gather, the covariance's all-gather, the curve features' all-gather
+            # the screen's all-reduce and all-gather, the covariance's all-gather, the curve features' all-gather, the front
+            # rows' all-gather
             for stage in self.stages.values():
                 stage.end_step()
             return self.accumulator

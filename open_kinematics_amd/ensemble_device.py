@@ -1,7 +1,8 @@
 """
 The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce`` (moments, extremes, sensitivities),
 ``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry),
-``okx_ensemble_covariance`` and ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+``okx_ensemble_covariance``, ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry) and
+``okx_ensemble_front`` (the nondominated front of the ensemble).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
 is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
 """
 
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensemble_stats import _host_f64
+from .ensemble_stats import FRONT_TARGET, _host_f64
 
 
 @dataclass
@@ -81,6 +82,67 @@ class EnsembleScreening:
         seen = min(int(tally[0]), self.flags.shape[0])  # (accumulated chunks fill the tables from the front)
         return EnsembleScreen(self.flags[:seen].cpu().numpy(), self.margin[:seen].cpu().numpy(), self.entry[:seen].cpu().numpy(), tally,
                               self.blame.cpu().numpy(), self.pass_index[:n].cpu().numpy())
+
+
+@dataclass
+class EnsembleFronting:
+    """
+    What ``DeviceProgram.front_ensemble`` returns, device tensors: per geometry ``dominated [G]`` int32 (None for a merged
+    run); per ensemble ``tally [3]`` int64 (seen, candidates, front members), ``front_index [capacity]`` int64 and
+    ``front_values [capacity, M]`` float64 - the ids and the raw table values of the front members in ascending row order;
+    slots beyond ``min(tally[2], capacity)`` are never written.  ``entries`` / ``sense`` / ``target`` are the HOST arrays the launch
+    reads; ``overflow [1]`` bool says that a run this one was merged from did not fit its capacity.
+    """
+
+    owner: object
+    entries: np.ndarray
+    sense: np.ndarray
+    target: np.ndarray
+    dominated: torch.Tensor | None
+    tally: torch.Tensor
+    front_index: torch.Tensor
+    front_values: torch.Tensor
+    overflow: torch.Tensor | None = None
+
+    @property
+    def capacity(self) -> int:
+        return int(self.front_index.shape[0])
+
+    def member(self) -> torch.Tensor:
+        """``[capacity]`` bool, on the device: the slot holds a front member."""
+        return torch.arange(self.capacity, device=self.tally.device) < self.tally[2]
+
+    def truncated(self) -> torch.Tensor:
+        """``[1]`` bool, on the device: the front (or one it was merged from) did not fit its capacity."""
+        over = self.tally[2:3] > self.capacity
+        return over if self.overflow is None else over | self.overflow
+
+    def merge(self, other: "EnsembleFronting") -> "EnsembleFronting":
+        """The front of the union of the two runs' front rows, by the SAME kernel over their ``front_values`` (one step, M
+        columns, the senses and targets as given), the ids through ``d_index`` and the unused slots masked by a byte table
+        built on the device from the counts - no host read.  ``seen`` and ``candidates`` add; no per-geometry ``dominated``."""
+        if not (np.array_equal(self.sense, other.sense) and np.array_equal(self.target, other.target)):
+            raise ValueError("fronts of different objectives")
+        rows = torch.cat([self.front_values, other.front_values])
+        ids = torch.cat([self.front_index, other.front_index])
+        mask = (~torch.cat([self.member(), other.member()])).to(torch.uint8)
+        objectives = [(0, i, int(s)) + ((float(t),) if s == FRONT_TARGET else ()) for i, (s, t) in enumerate(zip(self.sense, self.target))]
+        out = self.owner.front_ensemble(rows, steps_per_geometry=1, mask=mask, index=ids, objectives=objectives)
+        out.tally[:2] = self.tally[:2] + other.tally[:2]
+        out.dominated = None
+        out.overflow = self.truncated() | other.truncated()
+        return out
+
+    def finalize(self):
+        """Host copy, the only host read: ``ensemble_stats.EnsembleFront``.  Raises when the front did not fit the capacity."""
+        from .ensemble_stats import EnsembleFront
+
+        tally = self.tally.cpu().numpy()
+        n = int(tally[2])
+        if n > self.capacity or (self.overflow is not None and bool(self.overflow.item())):
+            raise RuntimeError(f"the front was truncated: {n} members, capacity {self.capacity}")
+        return EnsembleFront(None if self.dominated is None else self.dominated.cpu().numpy(), tally, self.front_index[:n].cpu().numpy(),
+                             self.front_values[:n].cpu().numpy(), self.sense.copy(), self.target.copy())
 
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
@@ -440,4 +502,72 @@ class EnsembleReductions:
         kx, origin, scale, lo, hi, degree = out.arguments
         self._ensemble_call("okx_ensemble_curves", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.abscissa), max(kx, 0), origin, scale,
                             lo, hi, degree, _ptr(f[row:]), _ptr(n[row:]))
+        return out
+
+    # ---- okx_ensemble_front: the nondominated (Pareto) front of the ensemble on up to 8 objectives (ensemble_stats.EnsembleFront) ----
+
+    def front_prepare(self, steps: int, n_columns: int, n_geometries: int, objectives, capacity: int | None = None) -> "EnsembleFronting":
+        """
+        The tables of a front pass over ``[steps, n_columns]`` entries and ``n_geometries`` geometries: ``objectives`` - a
+        sequence of ``(step, column, sense)`` or ``(step, column, "target", value)`` - are validated
+        (``okx_ensemble_front_check``) and kept as the host arrays every launch reads; ``dominated [G]``, ``tally [3]`` and the
+        front list with ``capacity`` slots (None: one per geometry) are allocated.
+        """
+        from .ensemble_stats import check_front_arguments
+
+        s, k, g = int(steps), int(n_columns), int(n_geometries)
+        if g < 0 or (capacity is not None and int(capacity) < 0):
+            raise ValueError("negative geometry count or capacity")
+        entries, sense, target = check_front_arguments(objectives, s, k, g)
+        rc = self.lib.okx_ensemble_front_check(g, s, k, entries.ctypes.data_as(C.c_void_p), sense.ctypes.data_as(C.c_void_p),
+                                               target.ctypes.data_as(C.c_void_p), entries.size)
+        _lib.check(rc, "okx_ensemble_front")
+        dev, cap = self.device, g if capacity is None else int(capacity)
+        return EnsembleFronting(self, entries, sense, target, torch.empty(g, dtype=torch.int32, device=dev), torch.zeros(3, dtype=torch.int64, device=dev),
+                                torch.empty(cap, dtype=torch.int64, device=dev), torch.empty((cap, entries.size), dtype=torch.float64, device=dev))
+
+    def front_ensemble(self, values, *, steps_per_geometry: int, objectives=None, status=None, mask=None, index=None, geometry_offset: int = 0,
+                       capacity: int | None = None, out=None):
+        """
+        ``okx_ensemble_front``: which geometries of a column table in HBM no other geometry beats on every objective at once.
+        ``objectives``: up to 8 of ``(step, column, "min" | "max")`` or ``(step, column, "target", value)``; ``values`` and
+        ``status`` as ``screen_ensemble`` takes them; ``mask [G]`` uint8 (may be strided), 0: the geometry may be a candidate -
+        ``screen_ensemble``'s ``flags`` as they lie in HBM -; ``index [G]`` int64 the ids of the geometries (None:
+        ``geometry_offset + g``).  Returns an ``EnsembleFronting`` of device tensors: ``dominated [G]`` (how many candidates
+        dominate the geometry, -1: no candidate, 0: on the front), ``tally [3]``, ``front_index [capacity]`` and ``front_values
+        [capacity, M]`` (``capacity`` defaults to the geometry count); ``.finalize()`` makes the only host read and raises if
+        the front was truncated; ``.merge(other)`` is the front of two runs' union.  ``out``: the run of an earlier call or of
+        ``front_prepare`` - it carries its own objectives and capacity; with it and a table shape seen before, the call
+        allocates nothing and is legal inside a stream capture.  Only comparisons: exact, and bit-identical from run to run.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if out is None:
+            if objectives is None:
+                raise ValueError("objectives are needed (or out=, which carries its own)")
+            out = self.front_prepare(s, k, g, objectives, capacity)
+        elif objectives is not None or capacity is not None:
+            raise ValueError("out= carries its own objectives and capacity")
+        dev = self.device
+        if out.dominated is None or out.dominated.shape[0] < g or out.tally.device != dev:
+            raise ValueError(f"out holds no dominated table for {g} geometries on {dev}")
+        m = int(out.entries.size)
+        lists = (out.front_index, out.front_values)
+        if tuple(out.front_values.shape) != (out.capacity, m) or any(t.device != dev or not t.is_contiguous() for t in (*lists, out.dominated, out.tally)) \
+                or out.front_index.dtype != torch.int64 or out.front_values.dtype != torch.float64 or out.dominated.dtype != torch.int32 \
+                or out.tally.dtype != torch.int64 or out.tally.numel() != 3:
+            raise ValueError(f"out must hold contiguous device tables dominated [G], tally [3], front_index [capacity] and front_values [capacity, {m}]")
+        mask_stride = 0
+        if mask is not None:
+            if mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev:
+                raise ValueError("mask must be a uint8 [G] device tensor")
+            mask_stride = mask.stride(0) if g > 1 else 1
+            if mask_stride < 1:
+                raise ValueError("mask must have a positive stride")
+        if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.shape[0] != g or index.device != dev or not index.is_contiguous()):
+            raise ValueError("index must be a contiguous int64 [G] device tensor")
+        scratch = self._ensemble_scratch("front", int(self.lib.okx_ensemble_front_scratch_bytes(g, m)))
+        self._ensemble_call("okx_ensemble_front", g, s, k, _ptr(values), ld, _ptr(status), stride, out.entries.ctypes.data_as(C.c_void_p),
+                            out.sense.ctypes.data_as(C.c_void_p), out.target.ctypes.data_as(C.c_void_p), m, _ptr(mask), mask_stride, _ptr(index),
+                            int(geometry_offset), _ptr(out.dominated), _ptr(out.tally), _ptr(out.front_index), _ptr(out.front_values), out.capacity,
+                            _ptr(scratch), scratch.numel())
         return out

@@ -1,7 +1,7 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
 (moments, extremes, sensitivities), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
-(``covariance=``) and ``Curves`` (``curves=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+(``covariance=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
 * ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
@@ -403,4 +403,94 @@ class Curves(_Stage):
             raise RuntimeError("no step() yet")
         if self.result is None:
             self.result = self.merged.finalize()
+        return self.result
+
+
+class Front(_Stage):
+    """``front=dict(objectives=, source=, screened=)``: the nondominated front, chunk by chunk after the screen and the curves of the
+    chunk; chunks merge into the rank's front.  At the end of a step the ranks all-gather their local front rows - id, M raw
+    values and a member byte per slot, padded to the largest shard, and one more row with seen | candidates - and every rank runs
+    the pass once more over the gathered rows: only comparisons, so the same bits on every rank."""
+
+    def __init__(self, owner, front):
+        super().__init__(owner)
+        o = owner
+        k = len(o.metric_index)
+        self.source, self.screened = front.get("source", "table"), bool(front.get("screened", False))
+        objectives = [tuple(ob) for ob in front["objectives"]]
+        self.steps, self.columns = o.steps, k
+        if self.source == "curves":
+            # (column, field, sense ...) of the feature table [G, K * 12], one step per geometry
+            self.steps, self.columns = 1, k * es.CURVE_FIELDS
+            for ob in objectives:
+                if len(ob) < 3 or any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in ob[:2]) \
+                        or not (0 <= ob[0] < k and 0 <= ob[1] < es.CURVE_FIELDS):
+                    raise ValueError(f"front=: a curves objective is (column, field, sense ...) with column in [0, {k}) and field in "
+                                     f"[0, {es.CURVE_FIELDS}), got {ob!r}")
+            objectives = [(0, int(ob[0]) * es.CURVE_FIELDS + int(ob[1])) + ob[2:] for ob in objectives]
+        self.objectives = objectives
+        _, self.sense, self.target = es.check_front_arguments(objectives, self.steps, self.columns, o.n_geom)
+        m = self.m = int(self.sense.size)
+        # the gathered rows as a table of their own: one step, M columns, the senses and targets as given
+        self.row_objectives = [(0, i, int(self.sense[i])) + ((float(self.target[i]),) if self.sense[i] == es.FRONT_TARGET else ()) for i in range(m)]
+        self.largest_shard = max(hi - lo for lo, hi in (shard_range(o.n_geom, r, o.world) for r in range(o.world)))
+        self.local = self.merged = self.result = None
+        self.bytes_per_rank = 8 * (self.largest_shard + 1) * (m + 2) if o.world > 1 else 0
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o = self.owner
+        rows = slice(a - o.geometry_range[0], b - o.geometry_range[0])
+        if self.source == "curves":
+            values, status = o.stages["curves"].local.table()[rows], None
+        mask = None
+        if self.screened:
+            screen = o.stages["screen"]
+            mask = (screen.run.flags if self.on_device else screen.part.flags)[rows]
+        if self.on_device:
+            part = o.dp.front_ensemble(values, steps_per_geometry=self.steps, objectives=self.objectives, status=status, mask=mask, geometry_offset=a)
+        else:
+            n = b - a
+            part = es.front_host(values.reshape(n, self.steps, self.columns).cpu().numpy(), None if status is None else status.reshape(n, self.steps).cpu().numpy(),
+                                 self.objectives, mask, None, a)
+        self.local = self.local.merge(part) if self.taken else part
+
+    def exchange(self) -> None:
+        o, m, n, mine = self.owner, self.m, self.largest_shard, self.local
+        self.result = None
+        if o.world == 1:
+            self.merged = mine
+            return
+        send = torch.zeros((n + 1, m + 2), dtype=torch.float64, device=o.device)
+        if self.on_device:
+            held = min(mine.capacity, n)
+            send[:held, 0] = mine.front_index[:held].view(torch.float64)  # (the id's int64 bits)
+            send[:held, 1 : m + 1] = mine.front_values[:held]
+            send[:held, m + 1] = mine.member()[:held].to(torch.float64)
+            send[n, :2] = mine.tally[:2].view(torch.float64)
+        else:
+            held = mine.index.size
+            send[:held, 0] = torch.from_numpy(mine.index.astype(np.int64)).view(torch.float64)
+            send[:held, 1 : m + 1] = torch.from_numpy(np.ascontiguousarray(mine.values))
+            send[:held, m + 1] = 1.0
+            send[n, :2] = torch.from_numpy(mine.tally[:2].astype(np.int64)).view(torch.float64)
+        table = all_gather_flat(send.view(-1), o.group).view(o.world, n + 1, m + 2)
+        rows = table[:, :n].reshape(o.world * n, m + 2)
+        ids = rows[:, 0].contiguous().view(torch.int64)
+        mask = (rows[:, m + 1] == 0).to(torch.uint8)
+        counts = table[:, n, :2].contiguous().view(torch.int64).sum(dim=0)
+        if self.on_device:
+            merged = o.dp.front_ensemble(rows[:, 1 : m + 1], steps_per_geometry=1, objectives=self.row_objectives, mask=mask, index=ids)
+            merged.tally[:2] = counts
+            merged.dominated = None
+        else:
+            merged = es.front_host(rows[:, 1 : m + 1].numpy()[:, None, :], None, self.row_objectives, mask.numpy(), ids.numpy())
+            merged.tally[:2] = counts.numpy()
+            merged.dominated = None
+        self.merged = merged
+
+    def front(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize() if self.on_device else self.merged
         return self.result

@@ -879,6 +879,140 @@ def curves_host(values, status=None, abscissa=None, origin: float = 0.0, scale: 
     return EnsembleCurves(features, count, None, (kx, origin, scale, lo, hi, degree))
 
 
+# ---- the Pareto front of the ensemble: the geometries no other geometry beats on every objective (okx_ensemble_front) ----
+
+FRONT_MIN, FRONT_MAX, FRONT_TARGET = 0, 1, 2  # OKX_FRONT_MIN / _MAX / _TARGET
+FRONT_MAX_OBJECTIVES = 8  # OKX_ENS_FRONT_MAX_OBJECTIVES
+FRONT_MAX_GEOMETRIES = 65536  # OKX_ENS_FRONT_MAX_GEOMETRIES
+FRONT_SEEN, FRONT_CANDIDATES, FRONT_MEMBERS = range(3)
+_FRONT_SENSES = {"min": FRONT_MIN, "max": FRONT_MAX, "target": FRONT_TARGET}
+
+
+def check_front_arguments(objectives, steps: int, n_columns: int, n_geometries: int = 0):
+    """``(entries [M] int32, sense [M] int32, target [M] float64)`` of ``objectives`` - a sequence of ``(step, column, sense)`` or
+    ``(step, column, "target", value)``, sense ``"min"`` / ``"max"`` / ``"target"`` or ``FRONT_MIN`` / ``FRONT_MAX`` / ``FRONT_TARGET`` -
+    or ValueError in the words of ``okx_ensemble_front_check``.  ``entries`` are ``step * n_columns + column``; the target of an
+    objective that aims at none is 0."""
+    s, k, g = int(steps), int(n_columns), int(n_geometries)
+    who = "okx_ensemble_front"
+    if g > FRONT_MAX_GEOMETRIES:
+        raise ValueError(f"{who}: {g} geometries, at most {FRONT_MAX_GEOMETRIES} in one call (chunk and merge)")
+    try:
+        objectives = [tuple(o) for o in objectives]
+    except TypeError:
+        raise ValueError(f"{who}: objectives must be a sequence of (step, column, sense) or (step, column, 'target', value)") from None
+    m = len(objectives)
+    if not 1 <= m <= FRONT_MAX_OBJECTIVES:
+        raise ValueError(f"{who}: {m} objectives, 1 to {FRONT_MAX_OBJECTIVES} allowed")
+    entries, sense, target = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.float64)
+    for i, o in enumerate(objectives):
+        if len(o) not in (3, 4):
+            raise ValueError(f"{who}: objective {i} must be (step, column, sense) or (step, column, 'target', value)")
+        step, column, kind = o[0], o[1], o[2]
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (step, column)):
+            raise ValueError(f"{who}: objective {i}: step and column must be integers")
+        if not (0 <= int(step) < s and 0 <= int(column) < k):
+            raise ValueError(f"{who}: entry {i} is (step {int(step)}, column {int(column)}), outside [0, {s}) x [0, {k})")
+        entries[i] = int(step) * k + int(column)
+        again = np.flatnonzero(entries[:i] == entries[i])
+        if again.size:
+            raise ValueError(f"{who}: entry {i} repeats entry {int(again[0])} (index {int(entries[i])})")
+        kind = _FRONT_SENSES.get(kind.lower(), -1) if isinstance(kind, str) else kind
+        if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or not FRONT_MIN <= int(kind) <= FRONT_TARGET:
+            raise ValueError(f"{who}: sense {i} is {o[2]!r}, not 0 (min), 1 (max) or 2 (target)")
+        sense[i] = int(kind)
+        if sense[i] == FRONT_TARGET:
+            if len(o) != 4:
+                raise ValueError(f"{who}: objective {i} aims at a target and no target is given")
+            if not np.isfinite(float(o[3])):
+                raise ValueError(f"{who}: target {i} is {float(o[3]):g}, not finite")
+            target[i] = float(o[3])
+        elif len(o) == 4:
+            raise ValueError(f"{who}: objective {i} gives a target and does not aim at one")
+    return entries, sense, target
+
+
+def front_objectives(raw, sense, target) -> np.ndarray:
+    """The objective values ``[n, M]`` of raw table values: ``v``, ``-v`` or ``abs(v - target)``, the subtraction rounded once."""
+    raw = np.asarray(raw, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.where(sense[None] == FRONT_MAX, -raw, np.where(sense[None] == FRONT_TARGET, np.abs(raw - target[None]), raw))
+
+
+def front_dominated(objective, candidate) -> np.ndarray:
+    """``dominated [n]`` int32 of objective vectors ``[n, M]`` (smaller is better) and the candidate bytes ``[n]``: how many
+    candidates dominate each candidate, -1 for the others.  Blocked over b: ``n = 4099`` never allocates ``n^2 M``."""
+    candidate = np.asarray(candidate, dtype=bool)
+    out = np.full(candidate.shape[0], -1, dtype=np.int32)
+    rows = np.flatnonzero(candidate)
+    c = np.ascontiguousarray(np.asarray(objective, dtype=np.float64)[rows].T)  # [M, n]
+    n = rows.size
+    block = max(1, (1 << 21) // max(n, 1))
+    for b0 in range(0, n, block):
+        b1 = min(b0 + block, n)
+        le, ge = np.ones((b1 - b0, n), dtype=bool), np.ones((b1 - b0, n), dtype=bool)
+        for col in c:  # a dominates b: a <= b everywhere and not a >= b everywhere (IEEE compares: -0.0 == +0.0)
+            le &= col[None, :] <= col[b0:b1, None]
+            ge &= col[None, :] >= col[b0:b1, None]
+        out[rows[b0:b1]] = (le & ~ge).sum(axis=1)
+    return out
+
+
+@dataclass
+class EnsembleFront:
+    """
+    The nondominated (Pareto) front of an ensemble on ``M`` objectives (NumPy, host).  A geometry is a CANDIDATE when its mask
+    byte is 0 (or there is no mask) and every selected entry counts (``status & 7 == 1`` and a finite value); a DOMINATES b when
+    a's objectives are ``<=`` b's everywhere and ``<`` somewhere.  ``dominated [G]`` int32: the number of candidates that
+    dominate the geometry, -1 when it is no candidate, 0 on the front (None for a merged front); ``tally [3]`` int64:
+    geometries seen, candidates, front members; ``index [F]`` int64 and ``values [F, M]``: the ids of the front members in
+    ascending row order and the RAW table values of their objectives, exact bits.  ``sense [M]`` / ``target [M]`` say how a
+    value column is compared, which is all ``merge`` needs.
+    """
+
+    dominated: np.ndarray | None
+    tally: np.ndarray
+    index: np.ndarray
+    values: np.ndarray
+    sense: np.ndarray
+    target: np.ndarray
+
+    def merge(self, other: "EnsembleFront") -> "EnsembleFront":
+        """The front of the union of the two fronts' rows: ``front(A u B) = front(front(A) u front(B))``.  The ids are kept,
+        ``seen`` and ``candidates`` add; a merged front carries no per-geometry ``dominated``."""
+        if self.values.shape[1] != other.values.shape[1] or not np.array_equal(self.sense, other.sense) \
+                or not np.array_equal(self.target, other.target):
+            raise ValueError("fronts of different objectives")
+        values, index = np.concatenate([self.values, other.values]), np.concatenate([self.index, other.index])
+        dominated = front_dominated(front_objectives(values, self.sense, self.target), np.ones(index.size, dtype=bool))
+        keep = dominated == 0
+        tally = np.array([self.tally[FRONT_SEEN] + other.tally[FRONT_SEEN], self.tally[FRONT_CANDIDATES] + other.tally[FRONT_CANDIDATES],
+                          int(keep.sum())], dtype=np.int64)
+        return EnsembleFront(None, tally, index[keep], values[keep], self.sense, self.target)
+
+
+def front_host(values, status=None, objectives=None, mask=None, index=None, geometry_offset: int = 0) -> EnsembleFront:
+    """
+    The definition of ``okx_ensemble_front`` in NumPy: ``values [G, S, K]``, ``status [G, S]`` or None, ``objectives`` as
+    ``check_front_arguments`` takes them, ``mask [G]`` (0: the geometry may be a candidate - the flag byte of ``screen_host``) or
+    None, ``index [G]`` the ids of the geometries (None: ``geometry_offset + g``).
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    if objectives is None:
+        raise ValueError("okx_ensemble_front: objectives are needed")
+    entries, sense, target = check_front_arguments(objectives, s, k, g)
+    raw = v.reshape(g, s * k)[:, entries]
+    candidate = ok.reshape(g, s * k)[:, entries].all(axis=1)
+    if mask is not None:
+        candidate &= np.asarray(mask).reshape(g) == 0
+    dominated = front_dominated(front_objectives(raw, sense, target), candidate)
+    keep = dominated == 0
+    ids = (int(geometry_offset) + np.arange(g, dtype=np.int64)) if index is None else np.asarray(index, dtype=np.int64).reshape(g)
+    tally = np.array([g, int(candidate.sum()), int(keep.sum())], dtype=np.int64)
+    return EnsembleFront(dominated, tally, ids[keep], raw[keep], sense, target)
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
@@ -886,4 +1020,6 @@ __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_fac
            "SELECT_ROUNDS", "SELECT_MAX_PROBS", "EnsembleScreen", "screen_host", "check_screen_arguments", "SCREEN_OUTSIDE",
            "SCREEN_UNRESOLVED", "TALLY_SEEN", "TALLY_PASSED", "TALLY_OUTSIDE", "TALLY_UNRESOLVED", "EnsembleCovariance", "CovarianceAccumulator",
            "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES", "EnsembleCurves", "curves_host", "check_curve_arguments",
-           "curve_normal_refused", "CURVE_FIELDS", "CURVE_MAX_DEGREE", "CURVE_PIVOT"]
+           "curve_normal_refused", "CURVE_FIELDS", "CURVE_MAX_DEGREE", "CURVE_PIVOT", "EnsembleFront", "front_host", "front_dominated",
+           "front_objectives", "check_front_arguments", "FRONT_MIN", "FRONT_MAX", "FRONT_TARGET", "FRONT_MAX_OBJECTIVES", "FRONT_MAX_GEOMETRIES",
+           "FRONT_SEEN", "FRONT_CANDIDATES", "FRONT_MEMBERS"]
