@@ -63,7 +63,7 @@ def _separate(axle, program, dp, positions):
     return out
 
 
-def _assert_block_matches(res, sep, roles, program, value_tol=1e-9, rate_tol=1e-8):
+def _assert_block_matches(res, sep, roles, program, value_tol=1e-9, rate_tol=1e-8, oracle_rates=True):
     from open_kinematics_amd._abi import EVAL_AXLE_METRICS, EVAL_AXLE_ROLES, EVAL_RATE_WHEEL_CENTER_X
     from open_kinematics_amd.enums import PointID, PointRef, Side
 
@@ -84,6 +84,13 @@ def _assert_block_matches(res, sep, roles, program, value_tol=1e-9, rate_tol=1e-
         assert close(block[:, 1:, col], sep["role_rates"][:, :, k].cpu().numpy(), rate_tol), name
     info = res.tangent_info()
     assert np.all(info["flags"] == sep["tinfo"]["flags"])
+    # the 7 axle-scope rates have no separate launch to compare with (okx_axle_metrics_batch writes values only): against
+    # the oracle's duals along the block's own tangents, NaN pattern included (the fixtures' sweeps: the column bounds of
+    # tests/test_gpu_metric_derivatives.py are measured on them)
+    if oracle_rates:
+        from test_gpu_metric_derivatives import assert_axle_scope_matches_the_oracle
+
+        assert_axle_scope_matches_the_oracle(res, roles, res.positions.cpu().numpy())
 
 
 AXLES = ["c3_axle_grid", "t_axle_t_bar_roll", "t_axle_t_bar_bump", "t_axle_heave_link"]

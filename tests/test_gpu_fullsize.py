@@ -376,7 +376,7 @@ def test_c3_axle_grid_evaluated_at_full_size():
     sample = dp.evaluate(plain.positions[pick].contiguous(), tangents=True)
     sep = _separate(axle, program, dp, plain.positions[pick].contiguous())
     assert set(sep["role_names"]) == set(rot_names) | set(hw_names)
-    _assert_block_matches(sample, sep, roles, program)
+    _assert_block_matches(sample, sep, roles, program, oracle_rates=False)  # (2048 states: the separate launches only)
     a, b = torch.nan_to_num(ev[pick]), torch.nan_to_num(sample.eval)
     assert float(((a - b).abs() / b.abs().clamp(min=1.0)).max()) <= 1e-9
     given = dp.evaluate(plain.positions)

@@ -72,6 +72,72 @@ def role_indices_by_name(names, mg, prefix="", side=""):
             "steer_lower": names.index(lower), "steer_upper": names.index(upper)}
 
 
+def corner_spec(names, design, mg, prefix="", side_tag=""):
+    """The ``catalog_duals`` / ``axle_metric_duals`` spec of a metrics golden's corner (design = design positions of the
+    output points; an axle golden's corner by ``prefix`` = ``side_tag`` = ``'left_'`` / ``'right_'``)."""
+    local = [n[len(side_tag):] if side_tag and n.startswith(side_tag) else ("-" if side_tag else n) for n in names]
+    g = geometry_kwargs(local, mg, prefix)
+    spec = dict(role_indices_by_name(names, mg, prefix, side_tag), side=float(mg[prefix + "side_sign"]),
+                axis_kind=g["axis_kind"], axis_idx=g["axis_idx"], damper_idx=g["damper_idx"], wheelbase=g["wheelbase"],
+                cg_z=g["cg_z"], front_brake_bias=g["front_brake_bias"], axle_position=g["axle_position"],
+                driven_axle=g["driven_axle"])
+    spec["design_wheel_center_z"] = float(design[spec["wheel_center"]][2])
+    spec["design_contact_patch_z"] = float(design[spec["contact_patch"]][2])
+    rack = str(mg[prefix + "rack"]) if prefix + "rack" in mg else ""
+    spec["rack_idx"] = names.index(side_tag + rack) if rack else None
+    spec["design_rack_y"] = float(design[spec["rack_idx"]][1]) if rack else 0.0
+    return spec
+
+
+def spec_of_roles(roles):
+    """The oracle's spec of an ``okx_corner_roles`` (``metrics.CornerRoles``): what the device was actually given."""
+    kind = {0: None, 1: "two_planes", 2: "plane_and_strut"}[roles.instant_axis_kind]
+    position = {0: None, 1: "front", 2: "rear"}
+    bias = float(roles.front_brake_bias)
+    return dict(
+        wheel_center=roles.wheel_center, contact_patch=roles.contact_patch, axle_inboard=roles.axle_inboard,
+        axle_outboard=roles.axle_outboard, steer_lower=roles.steer_lower, steer_upper=roles.steer_upper,
+        side=float(roles.side_sign), design_wheel_center_z=float(roles.design_wheel_center_z),
+        design_contact_patch_z=float(roles.design_contact_patch_z), design_rack_y=float(roles.design_rack_y),
+        rack_idx=None if roles.rack_attachment < 0 else int(roles.rack_attachment), axis_kind=kind,
+        axis_idx=[int(k) for k in roles.instant_axis_point[:{None: 0, "two_planes": 6, "plane_and_strut": 4}[kind]]],
+        damper_idx=None if roles.damper_top < 0 else (int(roles.damper_top), int(roles.damper_bottom)),
+        wheelbase=float(roles.wheelbase), cg_z=float(roles.cg_z), front_brake_bias=None if np.isnan(bias) else bias,
+        axle_position=position[roles.axle_position], driven_axle=position[roles.driven_axle])
+
+
+# metrics golden -> fixture whose program / output points its states belong to
+CORNER_GOLDENS = {"c1_dw_corner": "c1_dw_corner", "c4_macpherson_grid": "c4_macpherson_grid", "e2e_sweep": "e2e_sweep",
+                  **ANTI_FIXTURES}
+AXLE_GOLDENS = {"axle_c3": "c3_axle_grid", "axle_heave_link": "t_axle_heave_link", "axle_t_bar_bump": "t_axle_t_bar_bump",
+                "axle_t_bar_roll": "t_axle_t_bar_roll"}
+
+
+def oracle_catalog_rows(spec, pos, tan):
+    """``catalog_duals`` over states x targets: ``pos [B, n, 3]``, ``tan [B, T, n, 3]`` -> ``(values [B, 19],
+    derivatives [B, T, 19])``."""
+    from oracle.metrics_oracle import catalog_duals
+
+    values = np.empty((pos.shape[0], len(METRIC_NAMES)))
+    derivs = np.empty((pos.shape[0], tan.shape[1], len(METRIC_NAMES)))
+    for s in range(pos.shape[0]):
+        for t in range(tan.shape[1]):
+            values[s], derivs[s, t] = catalog_duals(spec, pos[s], tan[s, t])
+    return values, derivs
+
+
+def oracle_axle_rows(left, right, pos, tan):
+    """``axle_metric_duals`` over states x targets -> ``(values [B, 7], derivatives [B, T, 7])``."""
+    from oracle.metrics_oracle import axle_metric_duals
+
+    values = np.empty((pos.shape[0], len(AXLE_METRIC_NAMES)))
+    derivs = np.empty((pos.shape[0], tan.shape[1], len(AXLE_METRIC_NAMES)))
+    for s in range(pos.shape[0]):
+        for t in range(tan.shape[1]):
+            values[s], derivs[s, t] = axle_metric_duals(left, right, pos[s], tan[s, t])
+    return values, derivs
+
+
 def derivative_plan(program, deriv_names):
     """deriv column -> (metric index or ('wc', axis), target index)."""
     tnames = [program.point_keys[p].lower_name for p in program.tgt_point]
@@ -169,6 +235,130 @@ def test_axle_metric_oracle_matches_the_reference(golden):
             values, _ = corner_metrics(pos, None, side, float(design[roles["wheel_center"]][2]))
             assert np.max(np.abs(values[:8] - mg[f"{tag}_values"][s][:8])) <= 1e-10
             assert close(oracle_geometry_row(mg["pos"][s], roles, side, geometry), mg[f"{tag}_values"][s][8:], 1e-11)
+
+
+def oracle_tangents(program, pos_row):
+    """Velocity fields ``[T, n_out, 3]`` of the output points at one state (the oracle's own tangent solve)."""
+    orc = Oracle(program)
+    free_out = [list(program.out_point).index(int(p)) for p in program.free_point]
+    vel, _, _ = orc.tangents(pos_row[free_out].reshape(-1))
+    return vel[:, program.out_point]
+
+
+def richardson(f, pos, vel, h):
+    """(4 f'(h/2) - f'(h)) / 3 with central differences of the values-only ``f`` along ``vel``."""
+    slope = lambda step: (f(pos + step * vel) - f(pos - step * vel)) / (2.0 * step)  # noqa: E731
+    return (4.0 * slope(0.5 * h) - slope(h)) / 3.0
+
+
+def assert_duals_match_differences(f, dual, pos, vel, worst, label, names):
+    """One state, one direction: ``dual`` = (values, derivatives) of the dual path, ``f`` the values-only path.  Per
+    column the bound is 16 x the spread of the differences between the two step sizes, floor 1e-10, relative to
+    max(1, |d|); ``worst[name]`` keeps the largest error seen and the bound it met."""
+    values, derivs = dual
+    plain = f(pos)
+    assert close(values, plain, 1e-12), (label, values, plain)
+    assert np.array_equal(np.isnan(derivs), np.isnan(plain)), (label, derivs)  # NaN exactly where the value is NaN
+    # the same values-only code in numpy's extended precision (the goldens pin its float64 run): in float64 the rounding of
+    # an instant-centre column alone, |f| eps cond / h, reaches 2e-10 of the derivative at h = 1e-2
+    wide_pos, wide_vel = pos.astype(np.longdouble), vel.astype(np.longdouble)
+    assert close(np.asarray(f(wide_pos), dtype=np.float64), plain, 1e-12), label
+    wide, narrow = (np.asarray(richardson(f, wide_pos, wide_vel, np.longdouble(h)), dtype=np.float64) for h in ("1e-2", "4e-3"))
+    for k, name in enumerate(names):
+        if np.isnan(plain[k]):
+            continue
+        scale = max(1.0, abs(wide[k]))
+        bound = max(16.0 * abs(wide[k] - narrow[k]) / scale, 1e-10)
+        err = abs(derivs[k] - wide[k]) / scale
+        worst[name] = max(worst.get(name, (0.0, 0.0)), (err, bound))
+        if bound == 1e-10:  # ... and apart, where the differences agree so well that the floor is the bound
+            worst[name, "floor"] = max(worst.get((name, "floor"), 0.0), err)
+        assert err <= bound, (label, name, derivs[k], wide[k], narrow[k])
+
+
+def fixture_roles(arrays, program):
+    """``[(column name, kind, point, point_b, design, axis point, axis, scale)]``: the rotation and hardware roles the
+    loader declares for an axle fixture that carries its YAML."""
+    import yaml
+
+    from open_kinematics_amd.input import build_suspension, build_sweep
+    from open_kinematics_amd.metrics import hardware_roles, topology_rotation_roles
+    from open_kinematics_amd.sweep import sweep_program
+    from oracle.metrics_oracle import ROLE_KINDS
+
+    axle = build_suspension(yaml.safe_load(str(arrays["geometry_yaml"])))
+    keyed, _ = sweep_program(axle, build_sweep(yaml.safe_load(str(arrays["sweep_yaml"])), axle))
+    assert list(keyed.out_point) == list(program.out_point)
+    names, roles = topology_rotation_roles(axle, keyed)
+    hw_names, hw = hardware_roles(axle, keyed)
+    return [(n, ROLE_KINDS[r.kind], r.point, r.point_b, tuple(r.design), tuple(r.axis_point), tuple(r.axis_dir), r.scale)
+            for n, r in zip(list(names) + list(hw_names), list(roles) + list(hw))]
+
+
+def test_oracle_duals_match_richardson_differences_of_the_values_only_path(golden):
+    """
+    Every derivative column of the oracle - 19 per corner, 7 per axle, every role kind - against Richardson-extrapolated
+    central differences (h = 1e-2 mm) of the values-only path, which shares no dual arithmetic with it and is pinned to the
+    reference's goldens above.  States: every fixture (five corner goldens, both corners of the four axle goldens), 7 to 11
+    states each, along every target's tangent.  Bound per column and state: 16 x |R(1e-2) - R(4e-3)|, floor 1e-10, relative
+    to max(1, |d|).  The differences run the values-only code in numpy's extended precision: in float64 their own rounding
+    reached 1.1e-10 on fvsa_length of the MacPherson grid, where the float64 dual equals the 50-digit dual to the last bit.
+    Worst measured |dual - R(1e-2)| / max(1, |d|) per column, where the bound is the floor (and overall, with its bound):
+      camber 3.0e-12 (3.1e-12 under 1.3e-10), caster 3.7e-13, kpi 4.7e-12 (5.0e-12 under 2.5e-10), roadwheel_angle 2.7e-12,
+      wheel_travel 9.1e-13, half_track 1.5e-11, scrub_radius 3.1e-11 (4.7e-11 under 2.0e-9), mechanical_trail 2.3e-12,
+      svic_x 5.3e-12 (1.3e-8 under 2.0e-7), svic_z 7.1e-13, svsa_length 5.3e-12 (1.3e-8 under 2.0e-7),
+      fvic_y 5.2e-12 (1.3e-8 under 2.0e-7), fvic_z 1.1e-11 (6.0e-9 under 9.5e-8), fvsa_length 5.2e-12 (1.3e-8 under 2.0e-7),
+      damper_length 5.1e-15, svsa_angle 1.9e-16, anti_dive 1.4e-15, anti_lift 2.6e-16, anti_squat 1.6e-15;
+      heave 1.7e-15, roll 1.1e-16, ride_height_change 6.7e-16, track 2.7e-14, roll_center_y and roll_center_z 2.2e-12
+      (0.68 under a bound of 11 at the states of the roll sweeps where the roll centre runs off sideways, |d| to 2.8e6 mm/mm:
+      the differences say nothing there), rack_displacement 1.8e-15;
+      axis_rotation 2.8e-15, midpoint_rotation 2.6e-16, stem_twist 1.3e-16, distance 1.4e-14, midpoint_coordinate 4.4e-16.
+    """
+    from oracle.metrics_oracle import (ROLE_KINDS, axle_metric_duals, axle_sides_from_specs, catalog_duals, catalog_values,
+                                       role_dual, role_value)
+
+    worst = {}
+
+    def corner_checks(spec, pos, vel, label):
+        for t in range(vel.shape[0]):
+            assert_duals_match_differences(lambda p: catalog_values(spec, p, p.dtype.type), catalog_duals(spec, pos, vel[t]), pos, vel[t],
+                                           worst, (label, t), METRIC_NAMES)
+
+    for name, base in CORNER_GOLDENS.items():
+        _, program = golden(base)
+        mg = load_metrics_golden(name)
+        spec = corner_spec(out_names(program), program.design_pos[program.out_point], mg)
+        for s in range(0, mg["pos"].shape[0], max(1, mg["pos"].shape[0] // 8)):
+            corner_checks(spec, mg["pos"][s], oracle_tangents(program, mg["pos"][s]), (name, s))
+    kinds = set()
+    for name, base in AXLE_GOLDENS.items():
+        arrays, program = golden(base)
+        mg = load_metrics_golden(name)
+        names, design = out_names(program), program.design_pos[program.out_point]
+        left, right = (corner_spec(names, design, mg, f"{tag}_", f"{tag}_") for tag in ("left", "right"))
+        roles = fixture_roles(arrays, program)
+        for s in range(0, mg["pos"].shape[0], max(1, mg["pos"].shape[0] // 8)):
+            pos = mg["pos"][s]
+            vel = oracle_tangents(program, pos)
+            # (one corner does not move with the other's hub: its entries are the tangent solve's rounding, 1e-13, a step
+            #  of 1e-15 mm that a difference cannot resolve - both sides of the comparison get the field without them)
+            vel = np.where(np.abs(vel) < 1e-9, 0.0, vel)
+            corner_checks(left, pos, vel, (name, "left", s))
+            corner_checks(right, pos, vel, (name, "right", s))
+            for t in range(vel.shape[0]):
+                assert_duals_match_differences(lambda p: axle_metrics(axle_sides_from_specs(left, right, p), p.dtype.type),
+                                               axle_metric_duals(left, right, pos, vel[t]), pos, vel[t], worst,
+                                               (name, s, t), AXLE_METRIC_NAMES)
+                for column, kind, a, b, *rest in roles:
+                    kinds.add(kind)
+                    value = lambda p: np.array([role_value(kind, p[a], p[b], *rest)])  # noqa: E731
+                    dual = role_dual(kind, pos[a], vel[t][a], pos[b], vel[t][b], *rest)
+                    assert_duals_match_differences(value, (np.array([dual[0]]), np.array([dual[1]])), pos, vel[t], worst,
+                                                   (name, column, s, t), [kind])
+    assert kinds == set(ROLE_KINDS)
+    columns = set(METRIC_NAMES) | set(AXLE_METRIC_NAMES) | set(ROLE_KINDS)
+    assert {k for k in worst if isinstance(k, str)} == columns and {k[0] for k in worst if isinstance(k, tuple)} == columns
+    print({k: f"{worst[k][0]:.1e} (bound there {worst[k][1]:.1e}), at the floor {worst[k, 'floor']:.1e}" for k in sorted(columns)})
 
 
 def axle_rotation_specs(program):
