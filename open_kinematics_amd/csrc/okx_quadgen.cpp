@@ -802,9 +802,21 @@ class Gen : public GenBase {
       if (batches.count(i)) emit_chain_batch(batches.at(i));
       if (!row(i, &ro)) return false;
       f("    ss = fma(%s, %s, ss);", ro.r.c_str(), ro.r.c_str());
-      if (!ro.absres.empty()) f("    mres_new = fmax(mres_new, %s);", ro.absres.c_str());
+      emit_max_residual(ro);
     }
     return true;
+  }
+  // max |r| takes the row in.  The optimiser moves these maxima to where mres_new is read, a block the residuals reach as
+  // values it knows nothing about, and quiets each with a canonicalising v_max_f64 x, x before the maximum proper: two
+  // instructions per row.  bare_max_abs (the helpers' text) is the one instruction; quad_fmax_calls: fmax(m, fabs(r)).
+  // Single mode only: the pair-mode cold body lost 1 % with this and the branch-free atan2 (profiles/r07/EXPERIMENTS.md).
+  bool bare_minmax = pv == nullptr && !dev_switch("quad_fmax_calls");
+  void emit_max_residual(const RowOut& ro) {
+    if (ro.absres.empty()) return;
+    if (bare_minmax && ro.absres.compare(0, 5, "fabs(") == 0 && ro.absres.back() == ')')
+      f("    mres_new = bare_max_abs(mres_new, %s);", ro.absres.substr(5, ro.absres.size() - 6).c_str());
+    else
+      f("    mres_new = fmax(mres_new, %s);", ro.absres.c_str());
   }
 
   // pin_ata / pin_atr: every row's J^T J and J^T r contributions are made where the row is (an opaque use after the
@@ -816,6 +828,11 @@ class Gen : public GenBase {
   // in between; scheduling barriers keep the sections apart, so the marked kernel is for counting, not for timing)
   bool marks = false;
   bool tl_marks = false;  // quad_timeline: section stamps inside a pass (OKX_TL is defined per kernel body)
+  // emit_factor for a caller that reads pmin and pmax only (the cold body's fast loop): each lane follows the pivots of
+  // its OWN rows - lane k's entry of A(G, G, k) once block G is eliminated, an arithmetic result - and the quad's smallest
+  // and largest are taken once, after the last block.  On the broadcast pivot every column paid a canonicalising
+  // v_max_f64 ahead of its min and its max, on all four lanes, for a quad-uniform value.  Min and max are exact: same bits.
+  bool lane_pivot_range = false;
   void mark(int n) {
     if (marks) f("    __builtin_amdgcn_sched_barrier(0); asm volatile(\"s_nop %d\"); __builtin_amdgcn_sched_barrier(0);", 10 + n);
     if (tl_marks && n >= 5) f("    OKX_TL(%d)", n);
@@ -843,7 +860,7 @@ class Gen : public GenBase {
       if (!row(i, &ro)) return false;
       if (!jtv) {
       f("    ss = fma(%s, %s, ss);", ro.r.c_str(), ro.r.c_str());
-      if (!ro.absres.empty()) f("    mres_new = fmax(mres_new, %s);", ro.absres.c_str());
+      emit_max_residual(ro);
       }
       mark(2);
       // point partials -> free blocks
@@ -960,8 +977,10 @@ class Gen : public GenBase {
       for (int k = 0; k < 3; ++k) {
         f("    { // column %d", 3 * G + k);
         f("    const double piv = QB%d(%s);", k, A(G, G, k).c_str());
-        f("    ok = ok && piv > 0.0;  // a failed factor is never used: no need to sanitise the pivot");
-        f("    pmin = fmin(pmin, piv); pmax = fmax(pmax, piv);");
+        if (!lane_pivot_range) {
+          f("    ok = ok && piv > 0.0;  // a failed factor is never used: no need to sanitise the pivot");
+          f("    pmin = fmin(pmin, piv); pmax = fmax(pmax, piv);");
+        }
         f("    const double rinv = pivot_rcp(piv);");
         f("    dinv%d = fma(e%d, rinv, dinv%d);", G, k, G);
         // factor entries of this column (rows below the pivot)
@@ -983,7 +1002,14 @@ class Gen : public GenBase {
           }
         }
         f("    }");
+        if (lane_pivot_range && k == 2)  // (a column's pivot entry is not written again once the column is eliminated)
+          f("    { const double pd = c == 0 ? %s : (c == 1 ? %s : %s); pmin = %s(pmin, pd); pmax = %s(pmax, pd); }",
+            A(G, G, 0).c_str(), A(G, G, 1).c_str(), A(G, G, 2).c_str(), bare_minmax ? "bare_min" : "fmin", bare_minmax ? "bare_max" : "fmax");
       }
+    if (lane_pivot_range) {  // lane 3 owns no row: its entries are the padding's zeros
+      f("    pmin = PMIN(c < 3 ? pmin : 1e300); pmax = PMAX(c < 3 ? pmax : 0.0);");
+      f("    (void)ok;");
+    }
     for (int F = 0; F < nf; ++F)
       for (int G = 0; G < nf; ++G) fillf[F][G] = fill[F][G];
   }
@@ -1187,7 +1213,12 @@ __constant__ double kAtanCoef[12] = {
     4.97687799461593236017e-02, 1.62858201153657823623e-02,
     -1.99999999998764832476e-01, -1.11111104054623557880e-01, -7.69187620504482999495e-02, -5.83357013379057348645e-02,
     -3.65315727442169155270e-02, 0.0};
-template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* tab) {
+)SRC";
+
+// lean_atan2_pos, the earlier text (OKX_DEV=quad_atan_branches, and pair mode): the five reduction ranges as an if / else chain.  With
+// sixteen problems per wavefront several ranges are live in most passes, each behind its own exec-mask branch and with its own
+// reciprocal sequence.
+constexpr const char* kAtanBranches = R"SRC(template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* tab) {
   const double ax = fabs(x);
   if (!(y > 0.0)) return x >= 0.0 ? 0.0 : 3.14159265358979311600e+00;
   if (ax == 0.0) return 1.57079632679489655800e+00;
@@ -1214,8 +1245,43 @@ template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* 
   const double at = hi - ((t * (s1 + s2) - lo) - t);
   return x > 0.0 ? at : 3.14159265358979311600e+00 - (at - 1.2246467991473531772e-16);
 }
-DEV bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 )SRC";
+
+// The same function as ONE instruction stream.  Beyond the first range the reduced argument is (A t + B) / (C t + D) with
+// per-range constants, so the constants are selected, not the paths: one reciprocal sequence after the one of t itself, no
+// branch.  Every range performs its branch's IEEE operations on its values - 1 * t + b is t + b, 0 * t - 1 is -1, 1 * t + 0
+// is t, all exact, and -1 * r is -r - so the result has the branching text's bits (tests/test_gpu_angle_ranges.py).  The early
+// returns are selects at the end; what the arithmetic above them makes of y <= 0 or x = 0 is never used.
+constexpr const char* kAtanSelects = R"SRC(template <bool TAB> DEV double lean_atan2_pos(double y, double x, const double* tab) {
+  const double ax = fabs(x);
+  const double t0 = y * fast_rcp(ax);
+  const bool r0 = t0 < 0.4375, r1 = t0 < 0.6875, r2 = t0 < 1.1875, r3 = t0 < 2.4375;  // (a NaN takes the last range, as in the chain)
+  const bool m3 = r3 && !r2;
+  const double na = r1 ? 2.0 : (r3 ? 1.0 : 0.0), nb = m3 ? -1.5 : -1.0, dc = m3 ? 1.5 : 1.0;
+  const double num = na * t0 + nb, den = na + dc * t0;
+  const double hi = r0 ? 0.0 : (r1 ? 4.63647609000806093515e-01 : (r2 ? 7.85398163397448278999e-01 : (r3 ? 9.82793723247329054082e-01 : 1.57079632679489655800e+00)));
+  const double lo = r0 ? 0.0 : (r1 ? 2.26987774529616870924e-17 : (r2 ? 3.06161699786838301793e-17 : (r3 ? 1.39033110312309984516e-17 : 6.12323399573676603587e-17)));
+  const double t = r0 ? t0 : num * fast_rcp(den);
+  const double z = t * t, w = z * z;
+  double s1, s2;
+  if (TAB) {
+    int k0 = 0; asm volatile("" : "+v"(k0));
+    const double* ct = tab + k0;
+    s1 = z * (ct[0] + w * (ct[1] + w * (ct[2] + w * (ct[3] + w * (ct[4] + w * ct[5])))));
+    s2 = w * (ct[6] + w * (ct[7] + w * (ct[8] + w * (ct[9] + w * ct[10]))));
+  } else {  // kernels with registers to spare keep the coefficients as literals
+    s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 +
+         w * (6.66107313738753120669e-02 + w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
+    s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 +
+         w * (-5.83357013379057348645e-02 + w * -3.65315727442169155270e-02))));
+  }
+  const double at = hi - ((t * (s1 + s2) - lo) - t);
+  const double full = x > 0.0 ? at : 3.14159265358979311600e+00 - (at - 1.2246467991473531772e-16);
+  const double some = ax == 0.0 ? 1.57079632679489655800e+00 : full;
+  return y > 0.0 ? some : (x >= 0.0 ? 0.0 : 3.14159265358979311600e+00);
+}
+)SRC";
+constexpr const char* kPreambleEnd = "DEV bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }\n";
 
 // What differs between the two solve bodies of a module: the general one (chains, fitted model, trace) and the COLD one
 // for launches of independent solves from the design state with a first-step table (chain_len 1: the headline shape) -
@@ -1278,6 +1344,7 @@ class QuadModule {
 
   // ---- set by the preparation steps, in this order, before the first emitter runs; constant afterwards ----
   std::string eval_src, solve_src, light_src;  // make_passes: rows + normal equations, the damped step, residuals only
+  std::string solve_src_range;                 // the damped step of the cold body's fast loop (single mode; empty: solve_src)
   bool light_ok = false;
   std::string atan_decl;
   std::string couple_eval, couple_light, couple_hoist;  // make_joining_rows
@@ -1314,6 +1381,13 @@ class QuadModule {
     eval_src = ev.out;
     ev.out.clear();
     solve_src = capture(ev, [&] { ev.emit_solve(); });
+    // the cold body's fast loop asks for the pivots' range only (`factored` there is pmin > 0): Gen::lane_pivot_range.
+    // quad_column_pivots: the general loop's text there too, as before.  (Pair mode reads `ok` in both loops.)
+    if (!pv && !dev_switch("quad_column_pivots")) {
+      ev.lane_pivot_range = true;
+      solve_src_range = capture(ev, [&] { ev.emit_solve(); });
+      ev.lane_pivot_range = false;
+    }
 
     // confirming evaluation (residuals only).  Not offered for programs with the reference's
     // zero-gradient point-on-line row: along that row's valley the step length says nothing about
@@ -1701,6 +1775,18 @@ class QuadModule {
 
   void emit_preamble_and_helpers() {
     g.out += kPreamble;
+    g.out += pv || dev_switch("quad_atan_branches") ? kAtanBranches : kAtanSelects;  // (pair mode keeps the branches: see Gen::bare_minmax)
+    g.out += kPreambleEnd;
+    if (ev.bare_minmax) {
+      g.f("// v_max_f64 / v_min_f64 as they are.  fmax / fmin of a value that came through a cross-lane move, a select or from another");
+      g.f("// block cost a second instruction: the compiler quiets such an operand first (v_max_f64 x, x).  No signalling NaN is");
+      g.f("// ever made here, and the instructions pass a quiet NaN by as fmax / fmin do: the same results in half the issue slots.");
+      g.f("DEV double bare_max(double a, double b) { double o; asm(\"v_max_f64 %%0, %%1, %%2\" : \"=v\"(o) : \"v\"(a), \"v\"(b)); return o; }");
+      g.f("DEV double bare_min(double a, double b) { double o; asm(\"v_min_f64 %%0, %%1, %%2\" : \"=v\"(o) : \"v\"(a), \"v\"(b)); return o; }");
+      g.f("DEV double bare_max_abs(double a, double b) { double o; asm(\"v_max_f64 %%0, %%1, |%%2|\" : \"=v\"(o) : \"v\"(a), \"v\"(b)); return o; }");
+      g.f("DEV double qmax_bare(double v) { v = bare_max(v, qperm<0xB1>(v)); v = bare_max(v, qperm<0x4E>(v)); return v; }");
+      g.f("DEV double qmin_bare(double v) { v = bare_min(v, qperm<0xB1>(v)); v = bare_min(v, qperm<0x4E>(v)); return v; }");
+    }
     if (EV) {
       g.out += eval_metrics_source(*es);
       if (EVP) {
@@ -1734,7 +1820,11 @@ class QuadModule {
       g.f("#define PJOIN_SUM(v) ((v) + xq(v))");
     } else {
       g.f("#define PSUM(v) qsum(v)");
-      g.f("#define PMAX(v) qmax(v)");
+      g.f("#define PMAX(v) %s(v)", ev.bare_minmax ? "qmax_bare" : "qmax");
+      if (!solve_src_range.empty()) {
+        if (!ev.bare_minmax) g.f("DEV double qmin(double v) { v = fmin(v, qperm<0xB1>(v)); v = fmin(v, qperm<0x4E>(v)); return v; }");
+        g.f("#define PMIN(v) %s(v)", ev.bare_minmax ? "qmin_bare" : "qmin");
+      }
       g.f("#define PJOIN_SUM(v) (v)");
     }
     if (ev.batched_any) {
@@ -2109,9 +2199,10 @@ class QuadModule {
   // One damped step from the normal equations in hand: declarations of the factor's registers, then (single mode) LDL^T +
   // substitutions, or (pair mode) each half's factorisation and the Woodbury system of the joining rows.  Leaves nx{F}, ok,
   // pmin, pmax (pair mode also pcoup, kc).  Emitted in the general loop and in the cold body's fast loop: the same text.
-  void solve_step() {
+  // (range_only: the caller reads pmin and pmax but not `ok` - the fast loop)
+  void solve_step(bool range_only = false) {
     declare_factor_registers(g);
-    if (!pv) g.out += solve_src;
+    if (!pv) g.out += range_only && !solve_src_range.empty() ? solve_src_range : solve_src;
     else if (NK > 1) solve_step_joins();
     else solve_step_one_join();
   }
@@ -2812,9 +2903,9 @@ class QuadModule {
     g.f("    { const double t = 2.0 * rho - 1.0;");
     g.f("      lambda *= (rho > 0.99 && (step_len <= 1.0 || Ft <= 1e-2)) ? 1e-3 : (rho > 0.9 ? 0.1 : fmax(1.0 / 3.0, 1.0 - t * t * t)); }");
     if (b.timeline) g.f("    OKX_TL(10)");
-    solve_step();
+    solve_step(true);
     g.f("    double sl = 0.0, pr = 0.0, dd = 0.0;");
-    for (int F = 0; F < nf; ++F) g.f("    sl = fmax(sl, fabs(nx%d));", F);
+    for (int F = 0; F < nf; ++F) g.f(ev.bare_minmax ? "    sl = bare_max_abs(sl, nx%d);" : "    sl = fmax(sl, fabs(nx%d));", F);
     g.f("    sl = PMAX(sl);");
     for (int F = 0; F < nf; ++F) g.f("    pr = fma(nx%d, fma(lambda, nx%d, -gn%d), pr); dd = fma(nx%d, nx%d, dd);", F, F, F, F, F);
     g.f("    pr = 0.5 * PSUM(pr);");
