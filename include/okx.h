@@ -1047,6 +1047,77 @@ int32_t okx_ensemble_front_check(int64_t n_geometries, int64_t steps, int32_t n_
                                  const int32_t* entries, const int32_t* sense,
                                  const double* target, int32_t n_objectives);
 
+/*
+ * Ensemble sampler on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): the head of the ensemble
+ * chain - the hardpoint table [n_geometries][n_points][3] that okx_rebind_design reads, drawn in HBM by a COUNTER-BASED
+ * generator.  Geometry g's draw is a pure function of (seed, g, latent index, attempt): any chunk, device or rank writes the
+ * same bits for the rows [geometry_offset, geometry_offset + n_geometries) it asks for.  The definition is
+ * open_kinematics_amd/ensemble_sample.py (NumPy); the pass equals it bit for bit in all four outputs - integer arithmetic and
+ * fp64 add, multiply, divide and sqrt, each rounded on its own (no fused multiply-add, no libm call).
+ *
+ * BITS.  Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and the counter words
+ *   c0 = g & 0xffffffff      c1 = g >> 32      c2 = latent index z      c3 = attempt | purpose << 8
+ * (g the GLOBAL geometry index, attempt 0 .. 15 in bits 0-7, purpose in bits 8-15, bits 16-31 zero).  OKX_SAMPLE_PURPOSE_DRAW:
+ * output words w0, w1 give 52 bits k = w0 << 20 | w1 >> 12 and u' = (k + 0.5) * 2^-52, exact and never 0 or 1 (w2, w3 are
+ * unused).  OKX_SAMPLE_PURPOSE_STRATA (c0 = c1 = 0, attempt 0): the four output words are the round keys of latent z's
+ * stratum permutation.
+ * STRATA.  OKX_SAMPLE_IID: u = u'.  OKX_SAMPLE_LHS: u = (pi_z(g) + u') / n_total, one rounded add and one rounded divide,
+ * clamped into [2^-53, 1 - 2^-53]; pi_z is a bijection of [0, n_total), n_total <= 2^32: a four-round Feistel network on b
+ * bits (the smallest even b >= 2 with 2^b >= n_total), L, R <- R, L ^ (mix(R + key_r) & (2^(b/2) - 1)), walked until the value
+ * is below n_total; mix is x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16 on 32 bits.  A redraw
+ * keeps pi_z(g) and draws u' again, so every stratum of every latent holds exactly one geometry of the whole ensemble.
+ * KINDS (d_kind [n_latents]).  OKX_SAMPLE_UNIFORM: 2 u - 1.  OKX_SAMPLE_NORMAL: the inverse normal CDF of u by Wichura's
+ * AS241 (PPND16, within 1e-12 of the true value), Horner sums, the tail's logarithm by exponent split and a polynomial.
+ * OKX_SAMPLE_TRUNCATED to [-k, k]: the same of Phi(-k) + u (Phi(k) - Phi(-k)), clamped into [-k, k].  d_bound is
+ * [n_latents][3] = k, Phi(-k), Phi(k) - Phi(-k), the two constants computed by the caller (ignored for the other kinds).
+ * DELTA.  With d_mixing [n_coords][n_latents]: delta_f = sum over z ascending from 0.0 of mixing[f][z] * latent_z.  Without
+ * (NULL; then n_latents == n_coords): delta_f = d_scale[f] * latent_f.  The row is d_nominal [n_points][3] with
+ * nominal[c] + delta_f at the flat index c = d_coords[f] = point * 3 + axis (distinct, in range).
+ * GUARDS (HOST array of n_guards <= 16 items; they travel as kernel arguments).  OKX_SAMPLE_GUARD_SIGN: sign * row[a] > eps,
+ * a a flat coordinate index.  _DISTINCT: points a and b are more than eps apart.  _OFF_LINE: a and b are, and point c is more
+ * than eps from the line through them.  Attempt 0, 1, ... enter the counter; the first attempt every guard accepts is kept.
+ *   d_hardpoints [n_geometries][n_points][3]
+ *   d_latents [n_geometries][n_latents], d_delta [n_geometries][n_coords], d_flags [n_geometries] uint8   (each may be NULL)
+ *        flags bit 0: no attempt was valid and the last one stands - the sense of the screen's flag byte, so the table can be
+ *        the mask of okx_ensemble_front; bits 4-7: the attempt that was kept.
+ * Launch-only, stream-ordered, no host read-back, no allocation, legal inside a stream capture; n_geometries = 0 is legal.
+ * okx_ensemble_sample_check validates HOST copies of the tables without a launch (a coordinate out of range or repeated, an
+ * unknown kind, a TRUNCATED bound - the k alone, [n_latents] - that is not finite and greater than 0, counts over the caps,
+ * a bad guard, n_total over 2^32 or geometry_offset + n_geometries > n_total under LHS: OKX_ERR_INVALID with okx_last_error
+ * text); the launch repeats the checks that need no device table, and the kernel never writes outside a row.
+ */
+enum { OKX_SAMPLE_NORMAL = 0, OKX_SAMPLE_UNIFORM = 1, OKX_SAMPLE_TRUNCATED = 2,
+       OKX_SAMPLE_IID = 0, OKX_SAMPLE_LHS = 1,
+       OKX_SAMPLE_GUARD_SIGN = 0, OKX_SAMPLE_GUARD_DISTINCT = 1, OKX_SAMPLE_GUARD_OFF_LINE = 2,
+       OKX_SAMPLE_PURPOSE_DRAW = 0, OKX_SAMPLE_PURPOSE_STRATA = 1,
+       OKX_ENS_SAMPLE_MAX_COORDS = 288, OKX_ENS_SAMPLE_MAX_LATENTS = 288,
+       OKX_ENS_SAMPLE_MAX_GUARDS = 16, OKX_ENS_SAMPLE_MAX_ATTEMPTS = 16 };
+
+typedef struct okx_sample_guard {
+  int32_t kind;      /* OKX_SAMPLE_GUARD_*                                                          */
+  int32_t a, b, c;   /* SIGN: a = flat coordinate index; DISTINCT: points a, b; OFF_LINE: a, b, c   */
+  double eps;
+  double sign;       /* SIGN: +1 or -1                                                              */
+} okx_sample_guard;
+
+int32_t okx_ensemble_sample(int64_t n_geometries, int64_t geometry_offset, int64_t n_total, uint64_t seed,
+                            int32_t n_points, const double* d_nominal,         /* [n_points][3]                           */
+                            const int32_t* d_coords, int32_t n_coords,         /* [n_coords]                              */
+                            const int32_t* d_kind, const double* d_bound,      /* [n_latents], [n_latents][3]             */
+                            int32_t n_latents,
+                            const double* d_mixing, const double* d_scale,     /* [n_coords][n_latents] or NULL, [n_coords] */
+                            const okx_sample_guard* guards, int32_t n_guards,  /* HOST [n_guards] or NULL                 */
+                            int32_t stratify, int32_t max_attempts,
+                            double* d_hardpoints,                              /* [n_geometries][n_points][3]             */
+                            double* d_latents, double* d_delta, uint8_t* d_flags, /* or NULL                              */
+                            void* stream);
+/* host only */
+int32_t okx_ensemble_sample_check(int64_t n_geometries, int64_t geometry_offset, int64_t n_total, int32_t n_points,
+                                  const int32_t* coords, int32_t n_coords,
+                                  const int32_t* kind, const double* bound, int32_t n_latents, int32_t has_mixing,
+                                  const okx_sample_guard* guards, int32_t n_guards,
+                                  int32_t stratify, int32_t max_attempts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,8 @@ EXPORTS = (
     "okx_ensemble_front",
     "okx_ensemble_front_scratch_bytes",
     "okx_ensemble_front_check",
+    "okx_ensemble_sample",
+    "okx_ensemble_sample_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -279,6 +281,10 @@ def load() -> C.CDLL:
     lib.okx_ensemble_front_scratch_bytes.restype = C.c_size_t
     lib.okx_ensemble_front_check.argtypes = [i64, i64, i32, vp, vp, vp, i32]
     lib.okx_ensemble_front_check.restype = i32
+    lib.okx_ensemble_sample.argtypes = [i64, i64, i64, C.c_uint64, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.okx_ensemble_sample.restype = i32
+    lib.okx_ensemble_sample_check.argtypes = [i64, i64, i64, i32, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32]
+    lib.okx_ensemble_sample_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -258,6 +258,36 @@ def chunk_pieces(n_geom: int, world: int, chunks: int) -> list:
     return table
 
 
+class PlanTable:
+    """
+    A ``SamplePlan`` where ``ShardedEnsemble`` takes a hardpoint table ``[G, P, 3]``: a slice of geometries is DRAWN when it is
+    asked for - by ``DeviceProgram.sample_ensemble`` into HBM, or by ``ensemble_sample.sample_host`` for a program without it (the
+    CPU tests' stand-in) - so a rank draws only the geometries it rebinds.
+    """
+
+    def __init__(self, device_program, plan):
+        self.dp, self.plan = device_program, plan
+        self.shape = (int(plan.n_total), plan.n_points, 3)
+        self.on_device = hasattr(device_program, "sample_ensemble")
+        self.device = device_program.device if self.on_device else torch.device("cpu")
+
+    def draw(self, lo: int, hi: int, latents: bool = False):
+        """``(hardpoints [n, P, 3], latents [n, Z] or None)`` of geometries ``[lo, hi)``, tensors on ``device``."""
+        if self.on_device:
+            run = self.dp.sample_ensemble(self.plan, lo, hi, latents=latents)
+            return run.hardpoints, run.latents
+        from .ensemble_sample import sample_host
+
+        table, lat, _, _ = sample_host(self.plan, lo, hi)
+        return torch.as_tensor(table), torch.as_tensor(lat) if latents else None
+
+    def __getitem__(self, rows):
+        if not isinstance(rows, slice) or rows.step not in (None, 1):
+            raise TypeError("a plan's table is read in slices of geometries")
+        lo, hi, _ = rows.indices(self.shape[0])
+        return self.draw(lo, max(lo, hi))[0]
+
+
 class ShardedEnsemble:
     """
     BASELINE config 5 on N GPUs as a PIPELINE (geometry-major contiguous shards, one exchange of the
@@ -302,6 +332,17 @@ class ShardedEnsemble:
     geometries never change: they are summed once, here, on the host in ascending geometry order - so ``factor_acc`` repeats
     bit for bit from step to step, rank to rank and chunking to chunking, but agrees with a direct
     ``reduce_ensemble(factor_moments=True)`` of the same table (summed per slab on the device) to rounding only.
+
+    ``hardpoints`` may be an ``ensemble_sample.SamplePlan`` instead of a table: the ensemble is then the plan's ``n_total``
+    geometries and every rank DRAWS the rows it rebinds (``okx_ensemble_sample``: geometry g's draw depends on the seed and g
+    alone, so the rows carry the same bits on every rank and for every world size) - no table is built on the host, uploaded
+    or sent.  ``factors="sampled"`` (with a plan) takes the plan's latents as the factors, named ``"latent<z>"`` or, for a plan
+    without ``mixing``, by its coordinates; they come out of the same draw as the rank's rows and stay on the device (one host
+    copy feeds the factor moments).  Two routes still hold ALL geometries on every rank, as they do with a table: with records
+    and more than one rank every rank rebinds (so draws) the whole ensemble, and ``curves=`` with factors reduces every rank's
+    feature rows against the factors of all geometries, which each rank then draws once more, whole, and copies to the host.
+    Either way the run equals, bit for bit, the run over the materialised table (``sample_host(plan)``) with the materialised
+    latents as ``factors``.
 
     ``quantiles=(p, ...)`` (with ``reduce=True``; ``limits`` optional, ``[S, K, 2]`` / ``[K, 2]`` / ``[2]`` = (lo, hi)) adds the
     band and the yield: after the last chunk of a step the rank runs the select rounds (``okx_ensemble_select_count`` /
@@ -361,6 +402,13 @@ class ShardedEnsemble:
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
                  covariance=None, curves=None, front=None, **solve_kw):
+        from .ensemble_sample import SamplePlan
+
+        self.plan = hardpoints if isinstance(hardpoints, SamplePlan) else None
+        if self.plan is not None:
+            hardpoints = PlanTable(device_program, self.plan)  # rows are drawn where they are asked for
+        elif isinstance(factors, str) and factors == "sampled":
+            raise ValueError("factors='sampled' takes the latents of a SamplePlan: pass the plan where the hardpoints go")
         if (reduce or factors is not None or shift is not None) and (metric_columns is None or not reduce):
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
         if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
@@ -407,7 +455,7 @@ class ShardedEnsemble:
             # with most SIMDs idle, and the pipeline loses more on its solve stage than it hides of the exchange
             # (tools/c5_pipeline_model.py: a rank's 131072 problems at N = 8 solve in 0.09 ms as one launch or two halves, in
             # 0.40 ms as 8 eighths).  Without a GPU (the CPU tests' stand-in) a round is 4096.
-            dev = torch.as_tensor(hardpoints).device
+            dev = hardpoints.device if self.plan is not None else torch.as_tensor(hardpoints).device
             one_round = torch.cuda.get_device_properties(dev).multi_processor_count * 256 if dev.type == "cuda" else 4096
             # (the evaluated ensemble sends 33 B instead of 145 B per state and computes 1.5 x as long: its exchange hides
             #  behind the solve with two chunks, more only lengthen the solve - tools/c5_pipeline_model.py)
@@ -432,7 +480,15 @@ class ShardedEnsemble:
         # per-geometry emission: the expand on the receiving side needs every geometry's fixed points (a small table,
         # replicated as SURVEY.md section 8e allows); without records only this rank's slice is rebound
         everyone = self.records and self.world > 1
-        table = hardpoints if everyone else hardpoints[glo:ghi]
+        self.sampled_latents = None  # factors="sampled": this rank's rows of the plan's latents, where they were drawn
+        if self.plan is not None:
+            # ONE draw: the rows this rank rebinds and, when they are the factors, their latents beside them
+            lo, hi = (0, self.n_geom) if everyone else (glo, ghi)
+            table, drawn = hardpoints.draw(lo, hi, latents=isinstance(factors, str) and factors == "sampled")
+            if drawn is not None:
+                self.sampled_latents = drawn[glo - lo : ghi - lo]
+        else:
+            table = hardpoints if everyone else hardpoints[glo:ghi]
         gpos, gparam = device_program.rebind(table)
         self.gpos_all = gpos if everyone else None
         self.my_pos = gpos[glo:ghi] if everyone else gpos

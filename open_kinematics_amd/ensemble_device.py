@@ -2,7 +2,8 @@
 The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce`` (moments, extremes, sensitivities),
 ``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry),
 ``okx_ensemble_covariance``, ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry) and
-``okx_ensemble_front`` (the nondominated front of the ensemble).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+``okx_ensemble_front`` (the nondominated front of the ensemble) - and the pass at the head of the chain, ``okx_ensemble_sample`` (the
+hardpoint table of a ``SamplePlan`` drawn in HBM, ``ensemble_sample.py``).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
 is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
 """
 
@@ -143,6 +144,28 @@ class EnsembleFronting:
             raise RuntimeError(f"the front was truncated: {n} members, capacity {self.capacity}")
         return EnsembleFront(None if self.dominated is None else self.dominated.cpu().numpy(), tally, self.front_index[:n].cpu().numpy(),
                              self.front_values[:n].cpu().numpy(), self.sense.copy(), self.target.copy())
+
+
+class SampleGuard(C.Structure):
+    """``okx_sample_guard``."""
+
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("eps", C.c_double), ("sign", C.c_double)]
+
+
+@dataclass
+class EnsembleSample:
+    """
+    What ``DeviceProgram.sample_ensemble`` returns, device tensors of the geometries ``[lo, hi)`` of a plan's ensemble:
+    ``hardpoints [n, P, 3]`` (what ``rebind`` and ``ShardedEnsemble`` take), ``latents [n, Z]`` and ``delta [n, F]`` (None unless
+    asked for; ``latents`` feed ``reduce_ensemble(factors=...)``) and ``flags [n]`` uint8 (None when an ``out=`` without them was passed; bit 0: no attempt satisfied the guards -
+    a ``mask`` for ``front_ensemble``; bits 4-7: the attempt kept).
+    """
+
+    hardpoints: torch.Tensor
+    latents: torch.Tensor | None
+    delta: torch.Tensor | None
+    flags: torch.Tensor | None
+    lo: int = 0
 
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
@@ -570,4 +593,67 @@ class EnsembleReductions:
                             out.sense.ctypes.data_as(C.c_void_p), out.target.ctypes.data_as(C.c_void_p), m, _ptr(mask), mask_stride, _ptr(index),
                             int(geometry_offset), _ptr(out.dominated), _ptr(out.tally), _ptr(out.front_index), _ptr(out.front_values), out.capacity,
                             _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_sample: the hardpoint table of a plan's ensemble, drawn on device (ensemble_sample.SamplePlan) ----
+
+    def _sample_tables(self, plan):
+        """The plan's tables on the device and its guards as the host array a launch reads, validated (``okx_ensemble_sample_check``)
+        and uploaded ONCE per plan.  They are held for as long as the plan object lives and dropped with it (a search loop makes a
+        plan per generation); whoever keeps a captured graph of a launch keeps its plan."""
+        import weakref
+
+        if not hasattr(self, "_sample_plans"):
+            self._sample_plans = {}
+        held = self._sample_plans.get(id(plan))
+        if held is not None and held[0]() is plan:
+            return held[1]
+        ints, reals = plan.guard_table()
+        guards = (SampleGuard * max(1, len(plan.guards)))()
+        for i in range(len(plan.guards)):
+            guards[i] = SampleGuard(*(int(v) for v in ints[i]), float(reals[i, 0]), float(reals[i, 1]))
+        rc = self.lib.okx_ensemble_sample_check(0, 0, plan.n_total, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
+                                                plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
+                                                0 if plan.mixing is None else 1, guards, len(plan.guards), plan.stratify, plan.max_attempts)
+        _lib.check(rc, "okx_ensemble_sample")
+        dev = self.device
+        up = lambda a: None if a is None else torch.tensor(np.asarray(a), device=dev)  # noqa: E731
+        tables = dict(nominal=up(plan.nominal), coords=up(plan.coords), kind=up(plan.kind), bound=up(plan.bound_table()), mixing=up(plan.mixing),
+                      scale=up(plan.scale), guards=guards)
+        plans, key = self._sample_plans, id(plan)
+        ref = weakref.ref(plan, lambda r, plans=plans, key=key: plans.pop(key, None) if plans.get(key, (None,))[0] is r else None)
+        plans[key] = (ref, tables)
+        return tables
+
+    def sample_ensemble(self, plan, lo: int = 0, hi: int | None = None, *, latents: bool = False, delta: bool = False, out=None) -> "EnsembleSample":
+        """
+        ``okx_ensemble_sample``: geometries ``[lo, hi)`` (``hi`` None: ``plan.n_total``) of the ensemble of ``plan``
+        (``ensemble_sample.SamplePlan``), drawn in HBM - the bits of ``ensemble_sample.sample_host(plan, lo, hi)``, whatever the
+        range is cut into and wherever it is drawn.  Returns an ``EnsembleSample`` of device tensors; ``latents`` / ``delta`` ask for
+        those tables too.  ``out``: the ``EnsembleSample`` of an earlier call of the same shape to write into - with it (and a
+        plan seen before) the call allocates nothing and is legal inside a stream capture.
+        """
+        lo = int(lo)
+        hi = int(plan.n_total) if hi is None else int(hi)
+        n = hi - lo
+        if n < 0 or lo < 0:
+            raise ValueError(f"okx_ensemble_sample: bad range [{lo}, {hi})")
+        tables = self._sample_tables(plan)
+        dev, p, f, z = self.device, plan.n_points, plan.n_coords, plan.n_latents
+        if out is None:
+            out = EnsembleSample(torch.empty((n, p, 3), dtype=torch.float64, device=dev),
+                                 torch.empty((n, z), dtype=torch.float64, device=dev) if latents else None,
+                                 torch.empty((n, f), dtype=torch.float64, device=dev) if delta else None,
+                                 torch.empty(n, dtype=torch.uint8, device=dev), lo)
+        else:
+            for t, shape, dtype in ((out.hardpoints, (n, p, 3), torch.float64), (out.latents, (n, z), torch.float64), (out.delta, (n, f), torch.float64),
+                                    (out.flags, (n,), torch.uint8)):
+                if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous()):
+                    raise ValueError(f"out must hold contiguous device tables hardpoints [{n}, {p}, 3], latents [{n}, {z}], delta [{n}, {f}] and flags [{n}]")
+            if out.hardpoints is None:
+                raise ValueError("out holds no hardpoint table")
+            out.lo = lo
+        self._ensemble_call("okx_ensemble_sample", n, lo, int(plan.n_total), C.c_uint64(plan.seed), p, _ptr(tables["nominal"]), _ptr(tables["coords"]), f,
+                            _ptr(tables["kind"]), _ptr(tables["bound"]), z, _ptr(tables["mixing"]), _ptr(tables["scale"]), tables["guards"],
+                            len(plan.guards), plan.stratify, plan.max_attempts, _ptr(out.hardpoints), _ptr(out.latents), _ptr(out.delta), _ptr(out.flags))
         return out

@@ -1,0 +1,487 @@
+"""
+The definition of ``okx_ensemble_sample`` in NumPy: perturbed-geometry ensembles drawn by a COUNTER-BASED sampler.  Geometry
+``g``'s draw is a pure function of ``(seed, g, latent index, attempt)`` - no draw depends on another - so a rank makes its
+own shard, a chunk its own rows, and every split of an ensemble carries the same bits.  The device pass equals this module
+bit for bit in all four outputs; every step below is IEEE add, multiply, divide or sqrt, each rounded on its own (no fused
+multiply-add, no libm call), or integer arithmetic.
+
+Bits: Philox4x32-10, key = (seed low word, seed high word), counter = (g low word, g high word, latent index z,
+attempt | purpose << 8) with purpose ``PURPOSE_DRAW`` for a latent's uniform and ``PURPOSE_STRATA`` (g = 0, attempt = 0) for
+the four round keys of latent z's stratum permutation.  Output words 0 and 1 of a draw give 52 bits ``k = w0 << 20 | w1 >> 12``
+and ``u' = (k + 0.5) * 2^-52``, exact and never 0 or 1.
+
+Strata (``LHS``): latent z's stratum of geometry g is ``pi_z(g)``, a keyed bijection of ``[0, n_total)``: a four-round Feistel
+network on ``b`` bits - the smallest even b >= 2 with ``2^b >= n_total`` - walked until the value lies below ``n_total``;
+the round function is a 32-bit integer mix of the right half plus the round key.  ``u = (pi + u') / n_total`` (one rounded
+add, one rounded divide), clamped into ``[2^-53, 1 - 2^-53]``.  A redraw keeps the stratum and redraws ``u'`` only, so the
+strata of a latent stay a permutation whatever the guards do.  ``IID``: ``u = u'``.
+
+Kinds: ``UNIFORM`` is ``2 u - 1``; ``NORMAL`` is ``ppnd16(u)``, Wichura's AS241 inverse normal CDF with the tail's logarithm
+written out (``log_unit``); ``TRUNCATED`` (to ``[-k, k]``) is ``ppnd16(Phi(-k) + u (Phi(k) - Phi(-k)))`` clamped into
+``[-k, k]`` - the two constants come from the host's ``erfc`` once per plan (``SamplePlan.bound_table``) and travel with it.
+
+Delta: ``delta_f = sum_z mixing[f][z] * latent_z``, ascending in z from 0.0, every product and sum rounded; without ``mixing``
+``delta_f = scale_f * latent_f``.  ``hardpoints`` is ``nominal`` with ``nominal[c] + delta_f`` at ``c = coords[f]``.
+
+Guards: a draw that fails one is drawn again with the next attempt number; the first valid attempt is kept.
+``flags[g]`` bit 0: no attempt was valid and the last one stands (the sense of the screen's flag byte: 0 passes); bits 4-7:
+the attempt kept.
+"""
+
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+
+NORMAL, UNIFORM, TRUNCATED = 0, 1, 2
+IID, LHS = 0, 1
+GUARD_SIGN, GUARD_DISTINCT, GUARD_OFF_LINE = 0, 1, 2
+PURPOSE_DRAW, PURPOSE_STRATA = 0, 1
+MAX_COORDS = 288      # OKX_ENS_SAMPLE_MAX_COORDS (= 3 * OKX_MAX_POINTS)
+MAX_LATENTS = 288     # OKX_ENS_SAMPLE_MAX_LATENTS
+MAX_GUARDS = 16       # OKX_ENS_SAMPLE_MAX_GUARDS
+MAX_ATTEMPTS = 16     # OKX_ENS_SAMPLE_MAX_ATTEMPTS
+MAX_POINTS = 96       # OKX_MAX_POINTS
+
+_M32 = np.uint64(0xFFFFFFFF)
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+
+U_MIN = 2.0 ** -53
+U_MAX = 1.0 - 2.0 ** -53
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 of ``counter`` (four uint32 arrays that broadcast) under ``key`` (two): four uint32 arrays."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in counter)
+    k0, k1 = (np.asarray(k, dtype=np.uint64) & _M32 for k in key)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return tuple(np.asarray(c).astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def _seed_key(seed: int):
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed & 0xFFFFFFFF, seed >> 32
+
+
+def draw_bits(seed: int, g, z, attempt):
+    """The 52 bits ``k`` of (seed, g, z, attempt), uint64; the arguments broadcast."""
+    g = np.asarray(g, dtype=np.uint64)
+    c3 = (np.asarray(attempt, dtype=np.uint64) & np.uint64(0xFF)) | np.uint64(PURPOSE_DRAW << 8)
+    w0, w1, _, _ = philox4x32_10((g & _M32, g >> np.uint64(32), np.asarray(z, dtype=np.uint64), c3), _seed_key(seed))
+    return (w0.astype(np.uint64) << np.uint64(20)) | (w1.astype(np.uint64) >> np.uint64(12))
+
+
+def unit_from_bits(k):
+    """``u' = (k + 0.5) * 2^-52`` of 52 bits k: exact, inside (0, 1)."""
+    return (np.asarray(k, dtype=np.uint64).astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def strata_bits(n_total: int) -> int:
+    """The Feistel network's width: the smallest even b >= 2 with 2^b >= n_total."""
+    b = 2
+    while (1 << b) < int(n_total):
+        b += 2
+    return b
+
+
+def _mix32(x):
+    x = np.asarray(x, dtype=np.uint64) & _M32
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def strata_keys(seed: int, z):
+    """The four round keys of latent z's permutation (uint64 arrays holding 32-bit words)."""
+    z = np.asarray(z, dtype=np.uint64)
+    zero = np.zeros_like(z)
+    return tuple(w.astype(np.uint64) for w in philox4x32_10((zero, zero, z, zero + np.uint64(PURPOSE_STRATA << 8)), _seed_key(seed)))
+
+
+def stratum(seed: int, n_total: int, g, z):
+    """``pi_z(g)``: the stratum of geometry g (< n_total <= 2^32) under latent z, uint64; g and z broadcast."""
+    n_total = int(n_total)
+    half = np.uint64(strata_bits(n_total) // 2)
+    mask = np.uint64((1 << int(half)) - 1)
+    keys = strata_keys(seed, z)  # (per latent; broadcast over the geometries below)
+    g, z = np.broadcast_arrays(np.asarray(g, dtype=np.uint64), np.asarray(z, dtype=np.uint64))
+    keys = tuple(np.broadcast_to(k, g.shape) for k in keys)
+    x = g.copy()
+    walking = np.ones(x.shape, dtype=bool)
+    while walking.any():
+        v = x[walking]
+        left, right = v >> half, v & mask
+        for r in range(4):
+            left, right = right, left ^ (_mix32(right + keys[r][walking]) & mask)
+        v = (left << half) | right
+        x[walking] = v
+        walking[walking] = v >= np.uint64(n_total)
+    return x
+
+
+# ---- the inverse normal CDF: AS241 (PPND16), the tail's log written out ----
+
+_A = (3.3871328727963666080e0, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
+      4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3)
+_B = (1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3, 2.1213794301586595867e+4,
+      3.9307895800092710610e+4, 2.8729085735721942674e+4, 5.2264952788528545610e+3)
+_C = (1.42343711074968357734e0, 4.63033784615654529590e0, 5.76949722146069140550e0, 3.64784832476320460504e0,
+      1.27045825245236838258e0, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4)
+_D = (1.0, 2.05319162663775882187e0, 1.67638483018380384940e0, 6.89767334985100004550e-1, 1.48103976427480074590e-1,
+      1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9)
+_E = (6.65790464350110377720e0, 5.46378491116411436990e0, 1.78482653991729133580e0, 2.96560571828504891230e-1,
+      2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7)
+_F = (1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2, 7.86869131145613259100e-4,
+      1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15)
+PPND_SPLIT1, PPND_CONST1, PPND_CONST2, PPND_SPLIT2 = 0.425, 0.180625, 1.6, 5.0
+
+LN2 = 0.6931471805599453
+SQRT_HALF = 0.7071067811865476
+# log(m) = 2 s (1 + s^2 / 3 + s^4 / 5 + ...), s = (m - 1) / (m + 1): the coefficients 1 / (2 n + 1), n = 0 .. 10
+_LOG = tuple(1.0 / (2 * n + 1) for n in range(11))
+
+
+def _horner(coefficients, r):
+    acc = np.full_like(r, coefficients[-1])
+    for c in coefficients[-2::-1]:
+        acc = acc * r + c
+    return acc
+
+
+def log_unit(x):
+    """``log(x)`` of normal positive doubles by frexp and a polynomial in + - * / alone: x = m 2^e with m in [sqrt(1/2), sqrt(2)),
+    ``log x = e ln2 + 2 s P(s^2)``, ``s = (m - 1) / (m + 1)``; |error| below 1e-14 on [2^-53, 1]."""
+    m, e = np.frexp(np.asarray(x, dtype=np.float64))
+    small = m < SQRT_HALF
+    m = np.where(small, m * 2.0, m)
+    e = np.where(small, e - 1, e).astype(np.float64)
+    s = (m - 1.0) / (m + 1.0)
+    return e * LN2 + (2.0 * s) * _horner(_LOG, s * s)
+
+
+def ppnd16(u):
+    """``Phi^-1(u)`` for u in (0, 1): AS241's three regions, Horner sums, one divide each; within 1e-12 of the true value."""
+    u = np.asarray(u, dtype=np.float64)
+    q = u - 0.5
+    with np.errstate(all="ignore"):
+        central = np.abs(q) <= PPND_SPLIT1
+        r0 = PPND_CONST1 - q * q
+        v0 = q * _horner(_A, r0) / _horner(_B, r0)
+        tail = np.where(central, 0.5, np.where(q < 0.0, u, 1.0 - u))
+        r = np.sqrt(-log_unit(tail))
+        r1 = r - PPND_CONST2
+        v1 = _horner(_C, r1) / _horner(_D, r1)
+        r2 = r - PPND_SPLIT2
+        v2 = _horner(_E, r2) / _horner(_F, r2)
+        v = np.where(r <= PPND_SPLIT2, v1, v2)
+        v = np.where(q < 0.0, -v, v)
+    return np.where(central, v0, v)
+
+
+@dataclass(frozen=True)
+class SamplePlan:
+    """
+    What an ensemble is drawn from.  ``nominal [P, 3]``; ``coords [F]`` int32, distinct flat indices ``p * 3 + axis`` of the
+    perturbed coordinates; ``kind [Z]`` (``NORMAL`` / ``UNIFORM`` / ``TRUNCATED``) and ``bound [Z]`` (the k of ``TRUNCATED``, ignored
+    otherwise) of the latents; ``mixing [F, Z]`` or None - then ``Z == F`` and ``scale [F]`` multiplies latent f; ``stratify``
+    ``IID`` or ``LHS`` with ``n_total`` strata (the size of the WHOLE ensemble); ``seed`` a uint64; ``guards`` a tuple of at most 16
+    ``(GUARD_SIGN, coordinate, sign, eps)``, ``(GUARD_DISTINCT, a, b, eps)`` or ``(GUARD_OFF_LINE, a, b, c, eps)`` over point
+    indices; ``max_attempts`` 1 .. 16.  ``names``: the factor names of the latents (optional; see ``factor_names``).
+    """
+
+    nominal: np.ndarray
+    coords: np.ndarray
+    kind: np.ndarray
+    bound: np.ndarray | None = None
+    mixing: np.ndarray | None = None
+    scale: np.ndarray | None = None
+    stratify: int = IID
+    n_total: int = 0
+    seed: int = 0
+    guards: tuple = ()
+    max_attempts: int = 1
+    names: tuple | None = field(default=None, compare=False)
+
+    def __post_init__(self):
+        who = "okx_ensemble_sample"
+        put = lambda name, value: object.__setattr__(self, name, value)  # noqa: E731
+        nominal = np.ascontiguousarray(np.asarray(self.nominal, dtype=np.float64))
+        if nominal.ndim != 2 or nominal.shape[1] != 3 or not 1 <= nominal.shape[0] <= MAX_POINTS:
+            raise ValueError(f"{who}: nominal must be [P, 3] with 1 <= P <= {MAX_POINTS}")
+        coords = np.ascontiguousarray(np.asarray(self.coords, dtype=np.int32).reshape(-1))
+        kind = np.asarray(self.kind, dtype=np.int32)
+        if kind.ndim == 0:  # one kind for every latent
+            kind = np.broadcast_to(kind, (coords.size if self.mixing is None else np.shape(self.mixing)[1],))
+        kind = np.ascontiguousarray(kind.reshape(-1))
+        z = kind.size
+        bound = np.ones(z) if self.bound is None else np.ascontiguousarray(np.broadcast_to(np.asarray(self.bound, dtype=np.float64), (z,)))
+        mixing = None if self.mixing is None else np.ascontiguousarray(np.asarray(self.mixing, dtype=np.float64))
+        scale = None
+        if mixing is None:
+            scale = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if self.scale is None else self.scale, dtype=np.float64), (coords.size,)))
+            if z != coords.size:
+                raise ValueError(f"{who}: without mixing every coordinate has its own latent ({z} latents, {coords.size} coordinates)")
+        elif mixing.shape != (coords.size, z):
+            raise ValueError(f"{who}: mixing must be [{coords.size}, {z}], got {list(mixing.shape)}")
+        elif self.scale is not None:
+            raise ValueError(f"{who}: scale applies without mixing only")
+        guards = tuple(_normal_guard(gd) for gd in self.guards)
+        for name, value in (("nominal", nominal), ("coords", coords), ("kind", kind), ("bound", bound), ("mixing", mixing), ("scale", scale),
+                            ("guards", guards), ("stratify", int(self.stratify)), ("n_total", int(self.n_total)),
+                            ("seed", int(self.seed) & 0xFFFFFFFFFFFFFFFF), ("max_attempts", int(self.max_attempts))):
+            put(name, value)
+        for a in (nominal, coords, kind, bound, mixing, scale):
+            if a is not None:
+                a.setflags(write=False)
+        check_plan(self)
+
+    n_points = property(lambda self: int(self.nominal.shape[0]))
+    n_coords = property(lambda self: int(self.coords.size))
+    n_latents = property(lambda self: int(self.kind.size))
+
+    def bound_table(self) -> np.ndarray:
+        """``[Z, 3]``: k, ``Phi(-k)`` and ``Phi(k) - Phi(-k)`` of every latent (the table the device reads; (1, 0, 1) where the kind
+        is not ``TRUNCATED``).  The two constants are the host's ``erfc``, taken once: they are part of the plan."""
+        table = np.zeros((self.n_latents, 3))
+        table[:, 0], table[:, 2] = 1.0, 1.0
+        for i in np.flatnonzero(self.kind == TRUNCATED):
+            k = float(self.bound[i])
+            below = 0.5 * math.erfc(k / math.sqrt(2.0))
+            table[i] = k, below, (1.0 - below) - below
+        return table
+
+    def guard_table(self):
+        """``(ints [n, 4] int32: kind, a, b, c; reals [n, 2]: eps, sign)``, the form the guards travel in."""
+        ints, reals = np.zeros((len(self.guards), 4), dtype=np.int32), np.zeros((len(self.guards), 2))
+        for i, (kind, a, b, c, eps, sign) in enumerate(self.guards):
+            ints[i], reals[i] = (kind, a, b, c), (eps, sign)
+        return ints, reals
+
+    def factor_names(self) -> list:
+        """The names of the latents as factors: ``names`` when the plan carries them; else, without ``mixing``, the coordinate each
+        latent moves (``"point7.x"``, as ``ensemble_stats.hardpoint_factors`` names them); else ``"latent<z>"``."""
+        if self.names is not None:
+            return list(self.names)
+        if self.mixing is None:
+            return [f"point{int(c) // 3}.{'xyz'[int(c) % 3]}" for c in self.coords]
+        return [f"latent{z}" for z in range(self.n_latents)]
+
+
+def _normal_guard(guard) -> tuple:
+    """A guard as ``(kind, a, b, c, eps, sign)``."""
+    guard = tuple(guard)
+    kind = int(guard[0]) if guard else -1
+    if kind == GUARD_SIGN and len(guard) == 4:
+        return kind, int(guard[1]), 0, 0, float(guard[3]), float(guard[2])
+    if kind == GUARD_DISTINCT and len(guard) == 4:
+        return kind, int(guard[1]), int(guard[2]), 0, float(guard[3]), 1.0
+    if kind == GUARD_OFF_LINE and len(guard) == 5:
+        return kind, int(guard[1]), int(guard[2]), int(guard[3]), float(guard[4]), 1.0
+    if len(guard) == 6:
+        return kind, int(guard[1]), int(guard[2]), int(guard[3]), float(guard[4]), float(guard[5])
+    raise ValueError(f"okx_ensemble_sample: a guard is (SIGN, coordinate, sign, eps), (DISTINCT, a, b, eps) or (OFF_LINE, a, b, c, eps), got {guard!r}")
+
+
+def check_arguments(n_geometries, geometry_offset, n_total, n_points, coords, kind, bound, has_mixing, guards, stratify, max_attempts) -> None:
+    """``okx_ensemble_sample_check`` on the host: ValueError in its words."""
+    who = "okx_ensemble_sample"
+    n, off, n_total, p = int(n_geometries), int(geometry_offset), int(n_total), int(n_points)
+    coords, kind, bound = np.asarray(coords).reshape(-1), np.asarray(kind).reshape(-1), np.asarray(bound, dtype=np.float64).reshape(-1)
+    f, z = coords.size, kind.size
+    if n < 0 or off < 0 or n_total < 0:
+        raise ValueError(f"{who}: negative n_geometries, geometry_offset or n_total")
+    if not 1 <= p <= MAX_POINTS:
+        raise ValueError(f"{who}: {p} points, 1 to {MAX_POINTS} allowed")
+    if not 1 <= f <= MAX_COORDS:
+        raise ValueError(f"{who}: {f} coordinates, 1 to {MAX_COORDS} allowed")
+    if not 1 <= z <= MAX_LATENTS:
+        raise ValueError(f"{who}: {z} latents, 1 to {MAX_LATENTS} allowed")
+    if not has_mixing and z != f:
+        raise ValueError(f"{who}: without mixing every coordinate has its own latent ({z} latents, {f} coordinates)")
+    seen = set()
+    for i, c in enumerate(coords.tolist()):
+        if not 0 <= c < 3 * p:
+            raise ValueError(f"{who}: coordinate {i} is {c}, outside [0, {3 * p})")
+        if c in seen:
+            raise ValueError(f"{who}: coordinate {i} repeats index {c}")
+        seen.add(c)
+    for i, (k, b) in enumerate(zip(kind.tolist(), bound.tolist())):
+        if k not in (NORMAL, UNIFORM, TRUNCATED):
+            raise ValueError(f"{who}: kind {i} is {k}, not 0 (normal), 1 (uniform) or 2 (truncated)")
+        if k == TRUNCATED and not (math.isfinite(b) and b > 0.0):
+            raise ValueError(f"{who}: bound {i} is {b:g}, not finite and greater than 0")
+    if len(guards) > MAX_GUARDS:
+        raise ValueError(f"{who}: {len(guards)} guards, at most {MAX_GUARDS}")
+    for i, (gk, a, b, c, eps, sign) in enumerate(guards):
+        if gk not in (GUARD_SIGN, GUARD_DISTINCT, GUARD_OFF_LINE):
+            raise ValueError(f"{who}: guard {i} has kind {gk}, not 0 (sign), 1 (distinct) or 2 (off line)")
+        limit = 3 * p if gk == GUARD_SIGN else p
+        used = (a,) if gk == GUARD_SIGN else (a, b) if gk == GUARD_DISTINCT else (a, b, c)
+        if any(not 0 <= v < limit for v in used):
+            raise ValueError(f"{who}: guard {i} names an index outside [0, {limit})")
+        if not math.isfinite(eps) or (gk == GUARD_SIGN and sign not in (1.0, -1.0)):
+            raise ValueError(f"{who}: guard {i} needs a finite eps (and a sign of +1 or -1)")
+    if stratify not in (IID, LHS):
+        raise ValueError(f"{who}: stratify is {stratify}, not 0 (iid) or 1 (lhs)")
+    if not 1 <= int(max_attempts) <= MAX_ATTEMPTS:
+        raise ValueError(f"{who}: max_attempts is {max_attempts}, 1 to {MAX_ATTEMPTS} allowed")
+    if stratify == LHS:
+        if n_total > 1 << 32:
+            raise ValueError(f"{who}: {n_total} strata, at most 2^32 under LHS")
+        if off + n > n_total:
+            raise ValueError(f"{who}: geometries [{off}, {off + n}) lie outside the {n_total} strata")
+
+
+def check_plan(plan: SamplePlan, lo: int = 0, hi: int = 0) -> None:
+    check_arguments(hi - lo, lo, plan.n_total, plan.n_points, plan.coords, plan.kind, plan.bound, plan.mixing is not None, plan.guards,
+                    plan.stratify, plan.max_attempts)
+
+
+def latents_from_units(plan: SamplePlan, u) -> np.ndarray:
+    """The latents ``[n, Z]`` of the uniforms ``u [n, Z]`` by the plan's kinds."""
+    u = np.asarray(u, dtype=np.float64)
+    out = np.empty_like(u)
+    table = plan.bound_table()
+    for kind in (NORMAL, UNIFORM, TRUNCATED):
+        cols = np.flatnonzero(plan.kind == kind)
+        if not cols.size:
+            continue
+        v = u[:, cols]
+        if kind == UNIFORM:
+            out[:, cols] = 2.0 * v - 1.0
+        elif kind == NORMAL:
+            out[:, cols] = ppnd16(v)
+        else:
+            k, below, width = table[cols, 0], table[cols, 1], table[cols, 2]
+            v = np.minimum(np.maximum(below + v * width, U_MIN), U_MAX)
+            out[:, cols] = np.minimum(np.maximum(ppnd16(v), -k), k)
+    return out
+
+
+def stratified_unit(strata, up, n_total: int) -> np.ndarray:
+    """``u = (pi + u') / n_total`` - one rounded add, one rounded divide - clamped into ``[2^-53, 1 - 2^-53]``: without the clamp
+    ``pi = n - 1`` with ``u'`` near 1 rounds to 1 and the normal map returns infinity."""
+    u = (np.asarray(strata).astype(np.float64) + np.asarray(up, dtype=np.float64)) / float(n_total)
+    return np.minimum(np.maximum(u, U_MIN), U_MAX)
+
+
+def units(plan: SamplePlan, g, attempt, strata=None) -> np.ndarray:
+    """The uniforms ``[n, Z]`` of geometries ``g [n]`` (global indices) at ``attempt`` (a number or ``[n]``); ``strata [n, Z]``
+    under ``LHS`` (None: computed)."""
+    g = np.asarray(g, dtype=np.uint64).reshape(-1, 1)
+    z = np.arange(plan.n_latents, dtype=np.uint64)[None]
+    up = unit_from_bits(draw_bits(plan.seed, g, z, np.asarray(attempt, dtype=np.uint64).reshape(-1, 1)))
+    if plan.stratify != LHS:
+        return up
+    if strata is None:
+        strata = stratum(plan.seed, plan.n_total, g, z)
+    return stratified_unit(strata, up, plan.n_total)
+
+
+def contract(plan: SamplePlan, latents) -> np.ndarray:
+    """``delta [n, F]`` of ``latents [n, Z]``."""
+    if plan.mixing is None:
+        return plan.scale[None] * latents
+    acc = np.zeros((latents.shape[0], plan.n_coords))
+    for z in range(plan.n_latents):
+        acc = acc + plan.mixing[None, :, z] * latents[:, z, None]
+    return acc
+
+
+def guards_hold(plan: SamplePlan, points) -> np.ndarray:
+    """``[n]`` bool: every guard of the plan holds for ``points [n, P, 3]``.  Sums of three squares are ``(x^2 + y^2) + z^2``."""
+    ok = np.ones(points.shape[0], dtype=bool)
+    flat = points.reshape(points.shape[0], -1)
+
+    def norm(v):
+        return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+
+    with np.errstate(all="ignore"):
+        for kind, a, b, c, eps, sign in plan.guards:
+            if kind == GUARD_SIGN:
+                ok &= sign * flat[:, a] > eps
+            elif kind == GUARD_DISTINCT:
+                ok &= norm(points[:, b] - points[:, a]) > eps
+            else:
+                d = points[:, b] - points[:, a]
+                span = norm(d)
+                t = d / span[:, None]
+                w = points[:, c] - points[:, a]
+                cross = np.stack([w[:, 1] * t[:, 2] - w[:, 2] * t[:, 1], w[:, 2] * t[:, 0] - w[:, 0] * t[:, 2],
+                                  w[:, 0] * t[:, 1] - w[:, 1] * t[:, 0]], axis=1)
+                ok &= (span > eps) & (norm(cross) > eps)
+    return ok
+
+
+def sample_host(plan: SamplePlan, lo: int = 0, hi: int | None = None):
+    """
+    Geometries ``[lo, hi)`` of the plan's ensemble (``hi`` None: ``n_total``): ``(hardpoints [n, P, 3], latents [n, Z], delta [n, F],
+    flags [n] uint8)``.  The definition the device pass equals bit for bit.
+    """
+    lo = int(lo)
+    hi = plan.n_total if hi is None else int(hi)
+    check_plan(plan, lo, hi)
+    n, p = hi - lo, plan.n_points
+    g = np.arange(n, dtype=np.uint64) + np.uint64(lo)
+    hardpoints = np.repeat(plan.nominal[None], n, axis=0)
+    latents, delta = np.zeros((n, plan.n_latents)), np.zeros((n, plan.n_coords))
+    flags = np.zeros(n, dtype=np.uint8)
+    strata = stratum(plan.seed, plan.n_total, g[:, None], np.arange(plan.n_latents, dtype=np.uint64)[None]) if plan.stratify == LHS and n else None
+    pending = np.arange(n)
+    base = plan.nominal.reshape(-1)
+    for attempt in range(plan.max_attempts):
+        if not pending.size:
+            break
+        lat = latents_from_units(plan, units(plan, g[pending], attempt, None if strata is None else strata[pending]))
+        dlt = contract(plan, lat)
+        rows = np.repeat(base[None], pending.size, axis=0)
+        rows[:, plan.coords] = base[plan.coords][None] + dlt
+        points = rows.reshape(-1, p, 3)
+        ok = guards_hold(plan, points)
+        keep = ok | (attempt == plan.max_attempts - 1)
+        idx = pending[keep]
+        hardpoints[idx], latents[idx], delta[idx] = points[keep], lat[keep], dlt[keep]
+        flags[idx] = (attempt << 4) | np.where(ok[keep], 0, 1)
+        pending = pending[~keep]
+    return hardpoints, latents, delta, flags
+
+
+def hardpoint_plan(program, points, *, sigma=None, half_width=None, kind: int | None = None, bound=None, mixing=None, stratify: int = IID,
+                   n_total: int = 0, seed: int = 0, guards=(), max_attempts: int = 1) -> SamplePlan:
+    """
+    A plan that perturbs all three coordinates of ``points`` (indices into the program's point table, or names) about the
+    program's design positions: ``sigma`` (a number or ``[F]``) scales ``NORMAL`` / ``TRUNCATED`` latents, ``half_width`` ``UNIFORM`` ones -
+    give exactly one; ``kind`` defaults to the one that goes with it.  With ``mixing [F, Z]`` the latents move the coordinates
+    together (``kind`` / ``bound`` then describe the Z latents and ``sigma`` / ``half_width`` must be left out).
+    """
+    from .program import key_name
+
+    # (a PointID is an int too: plain integers alone are indices, everything else is a key of the program's point table)
+    index = [int(pt) if type(pt) is int or isinstance(pt, np.integer) else program.point_index(pt) for pt in points]
+    coords = np.asarray([3 * i + axis for i in index for axis in range(3)], dtype=np.int32)
+    if mixing is None:
+        if (sigma is None) == (half_width is None):
+            raise ValueError("hardpoint_plan takes sigma or half_width, one of them")
+        kind = (UNIFORM if sigma is None else NORMAL) if kind is None else kind
+        names = tuple(f"{key_name(program.point_keys[i]).lower()}.{'xyz'[axis]}" for i in index for axis in range(3))
+        return SamplePlan(program.design_pos, coords, np.full(coords.size, kind, dtype=np.int32), bound, None, half_width if sigma is None else sigma,
+                          stratify, n_total, seed, tuple(guards), max_attempts, names)
+    if sigma is not None or half_width is not None:
+        raise ValueError("with mixing the scales are its entries: leave sigma and half_width out")
+    z = np.shape(mixing)[1]
+    return SamplePlan(program.design_pos, coords, np.broadcast_to(np.asarray(NORMAL if kind is None else kind, dtype=np.int32), (z,)), bound, mixing, None,
+                      stratify, n_total, seed, tuple(guards), max_attempts)
+
+
+__all__ = ["SamplePlan", "sample_host", "hardpoint_plan", "philox4x32_10", "draw_bits", "unit_from_bits", "stratum", "strata_bits", "strata_keys",
+           "ppnd16", "log_unit", "units", "stratified_unit", "latents_from_units", "contract", "guards_hold", "check_arguments", "check_plan",
+           "NORMAL", "UNIFORM", "TRUNCATED", "IID", "LHS", "GUARD_SIGN", "GUARD_DISTINCT", "GUARD_OFF_LINE", "PURPOSE_DRAW", "PURPOSE_STRATA",
+           "MAX_COORDS", "MAX_LATENTS", "MAX_GUARDS", "MAX_ATTEMPTS", "U_MIN", "U_MAX"]

@@ -86,10 +86,26 @@ class Reduction(_AccumulatorStage):
         glo, ghi = o.geometry_range
         device, k = o.device, len(o.metric_index)
         self.factor_names = None
+        plan = getattr(o, "plan", None)
+        self._all_factors = None
+        if isinstance(factors, str) and factors == "sampled":
+            # the plan's latents ARE the factors: the owner drew this rank's rows of them beside the rows it rebound, and they stay
+            # where they are (one host copy for the moments below); a stage that reduces rows of every rank draws the whole table
+            # when it asks for it (all_factors)
+            mine = o.sampled_latents.contiguous()
+            factors = mine.detach().cpu().numpy()
+            self.factor_names = plan.factor_names()
+            self._sampled = hardpoints
+            if glo == 0 and ghi == o.n_geom:
+                self._all_factors = factors
+            self._finish(o, hardpoints, targets, relative_targets, factors, shift, glo, ghi, 0, mine)
+            return
         if isinstance(factors, str):
             if factors != "hardpoints":
-                raise ValueError("factors must be None, 'hardpoints' or a [G, P] table")
+                raise ValueError("factors must be None, 'hardpoints', 'sampled' (with a SamplePlan) or a [G, P] table")
             program = o.dp.program
+            if plan is not None:
+                hardpoints = hardpoints[0 : o.n_geom]
             table = torch.as_tensor(hardpoints).detach().cpu().numpy()
             # (derived points are recomputed from the authored ones by rebind: their coordinates are no factors)
             from .program import key_name
@@ -99,15 +115,30 @@ class Reduction(_AccumulatorStage):
             factors, self.factor_names = es.hardpoint_factors(table[:, authored], names)
         if factors is not None:
             factors = np.ascontiguousarray(torch.as_tensor(factors).detach().cpu().numpy(), dtype=np.float64).reshape(o.n_geom, -1)
+        self._all_factors = factors  # [G, P] on the host (or None): a stage that reduces rows of every rank takes them from here
+        self._finish(o, hardpoints, targets, relative_targets, factors, shift, glo, ghi, glo)
+
+    @property
+    def all_factors(self):
+        """``[G, P]`` on the host (or None): the factors of EVERY geometry, for a stage that reduces rows of every rank."""
+        if self._all_factors is None and self.n_factors and getattr(self, "_sampled", None) is not None:
+            self._all_factors = self._sampled.draw(0, self.owner.n_geom, latents=True)[1].detach().cpu().numpy()
+        return self._all_factors
+
+    def _finish(self, o, hardpoints, targets, relative_targets, factors, shift, glo, ghi, row0, resident=None):
+        """The rest of the set-up; ``factors [*, P]`` on the host hold this rank's rows from row ``row0`` on (``resident``: the same
+        rows already on the ensemble's device)."""
+        device, k = o.device, len(o.metric_index)
+        if factors is not None:
+            factors = np.ascontiguousarray(factors, dtype=np.float64)[row0 : row0 + ghi - glo]
         p = 0 if factors is None else factors.shape[1]
         self.n_factors = p
-        self.all_factors = factors  # [G, P] on the host (or None): a stage that reduces rows of every rank takes them from here
-        self.my_factors = torch.as_tensor(factors[glo:ghi], device=device).contiguous() if p else None
+        self.my_factors = (resident if resident is not None else torch.as_tensor(factors, device=device).contiguous()) if p else None
         # the shift: ONE table for every partial that is ever merged
         if shift is None:
             shift = torch.zeros((o.steps, k), dtype=torch.float64, device=device)
             if o.rank == 0 and o.n_geom > 0:
-                gpos, gparam = o.dp.rebind(torch.as_tensor(hardpoints)[:1])
+                gpos, gparam = o.dp.rebind(hardpoints[:1] if getattr(o, "plan", None) is not None else torch.as_tensor(hardpoints)[:1])
                 first = o.dp.ensemble_targets(gpos, targets) if relative_targets else targets[: o.steps]
                 res = o.dp.solve_evaluated(first, geom_pos=gpos, geom_row_param=gparam, steps_per_geometry=o.steps,
                                            output="none", **o.solve_kw)
@@ -121,7 +152,7 @@ class Reduction(_AccumulatorStage):
         # the unmasked factor moments of this rank's geometries, once: the factors never change (ascending order, as the device sums)
         factor_acc = None
         if p:
-            mine = factors[glo:ghi]
+            mine = factors
             rows, cols = np.tril_indices(p)
             moments = np.zeros(es.factor_moment_count(p))
             if ghi > glo:

@@ -98,3 +98,32 @@ def ensemble_problem(n_geometries: int = 4096, n_steps: int = 256, sigma: float 
         g += 1
     relative = np.stack([np.zeros(n_steps), np.linspace(-60.0, 80.0, n_steps)], axis=1)
     return program, table, relative
+
+
+def ensemble_plan(n_geometries: int = 4096, sigma: float = 1.0, seed: int = 0, *, n_steps: int = 256, line_mode: str = "pinned",
+                  kind: int | None = None, bound=None, stratify: int = 0, max_attempts: int = 16):
+    """
+    C5 as a ``SamplePlan`` (``ensemble_sample.py``): the geometry of ``ensemble_problem`` - every authored coordinate of the
+    double-wishbone corner perturbed with scale ``sigma`` - drawn by the counter-based sampler instead of a sequential host
+    loop, with ``ensemble_problem``'s two validators as guards: the side sign (``AXLE_OUTBOARD`` y > 0) and the track rod's
+    rigid anchors (the first two distinct, the third off their line, to ``EPS_GEOMETRIC``).  Returns the base program, the
+    plan (``DeviceProgram.sample_ensemble`` / ``ShardedEnsemble`` take it where they take a table) and the relative targets
+    ``[S, T]``.  The draws are not ``ensemble_problem``'s: that table is only reproducible drawn whole and in order.
+    """
+    import yaml
+
+    from .ensemble_sample import GUARD_OFF_LINE, GUARD_SIGN, hardpoint_plan
+    from .topology import EPS_GEOMETRIC
+
+    with open(geometry_path("geometry.yaml"), "r", encoding="utf-8") as fh:
+        base_map = yaml.safe_load(fh)
+    sus = build_suspension(base_map)
+    program, _ = target_rows(sus, [(P.TRACKROD_INBOARD, Y), (P.WHEEL_CENTER, Z)], line_mode)
+    authored = [program.point_index(k) for k in sus.hardpoints]
+    axle_outboard = program.point_index(P.AXLE_OUTBOARD)
+    a, b, c = (program.point_index(k) for k in sus.UPRIGHT_BODY[:3])
+    guards = ((GUARD_SIGN, 3 * axle_outboard + 1, 1.0, 0.0), (GUARD_OFF_LINE, a, b, c, EPS_GEOMETRIC))
+    plan = hardpoint_plan(program, authored, sigma=sigma, kind=kind, bound=bound, stratify=stratify, n_total=n_geometries, seed=seed,
+                          guards=guards, max_attempts=max_attempts)
+    relative = np.stack([np.zeros(n_steps), np.linspace(-60.0, 80.0, n_steps)], axis=1)
+    return program, plan, relative
