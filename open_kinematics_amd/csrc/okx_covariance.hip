@@ -1,6 +1,6 @@
 // Ensemble covariance (okx_ensemble_covariance*, include/okx.h): over the geometries of a table of metric columns
 // [G * S][ld], the Gram matrix sum d_n d_m and the sums sum d_n of N selected (step, column) entries, d = value - shift,
-// over the COMPLETE cases - the geometries whose every selected entry counts by the rule of okx_ensemble_reduce.
+// over the COMPLETE cases - the geometries whose every selected entry counts by the acceptance rule (okx_enstable.hpp).
 //
 // The first ensemble pass with real arithmetic: a symmetric rank-G update, N^2 G flop for the lower triangle, where
 // okx_ensemble.hip / okx_select.hip / okx_screen.hip stream.  Three launches:
@@ -71,9 +71,7 @@ inline Plan plan_for(long long n_geom, long long n) {
   len = (len + kBlock - 1) / kBlock * kBlock;
   p.slab_len = len < kMinSlab ? kMinSlab : len;
   p.slabs = n_geom > 0 ? (n_geom + p.slab_len - 1) / p.slab_len : 0;
-  long long gpb = (n_geom + kWantGroups - 1) / kWantGroups;
-  gpb = (gpb + kWaves - 1) / kWaves * kWaves;
-  p.gpb = gpb < kWaves ? kWaves : gpb;
+  p.gpb = enstable::geometries_per_group(n_geom, kWantGroups, kWaves);
   p.ugroups = n_geom > 0 ? (n_geom + p.gpb - 1) / p.gpb : 0;
   return p;
 }
@@ -122,18 +120,18 @@ __global__ __launch_bounds__(kThreads) void okx_cov_used(UsedArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long g0 = (long long)blockIdx.x * a.gpb;
   const long long g1 = g0 + a.gpb < a.n_geom ? g0 + a.gpb : a.n_geom;
+  const enstable::Table tab = OKX_ENS_TABLE_OF(a);
   unsigned count = 0u;  // wave-uniform
   for (long long g = g0 + wave; g < g1; g += kWaves) {
-    const double* vp = a.values + g * a.steps * a.ld;
-    const unsigned char* sp = a.status ? a.status + g * a.steps * a.status_stride : nullptr;
+    const double* vp = enstable::geometry_values(tab, g);
+    const unsigned char* sp = enstable::geometry_status(tab, g);
     bool ok = true;
     for (int n = lane; n < a.n; n += 64) {
       const long long o = off[n];
       if (o < 0) { ok = false; continue; }
       const double v = vp[o];
-      const unsigned st = sp ? sp[(long long)stp[n] * a.status_stride] : 1u;
-      // the rule of okx_ensemble_reduce: converged, not residual-exceeded, not failed, and a finite value
-      ok = ok && (st & 7u) == 1u && __builtin_isfinite(v);
+      const unsigned st = OKX_ENS_STATUS_AT(sp, stp[n], a.status_stride);
+      ok = ok && OKX_ENS_ACCEPTED(st, v);
     }
     const bool all = __ballot(!ok) == 0ull;
     if (lane == 0) {
@@ -314,7 +312,7 @@ __global__ __launch_bounds__(kThreads) void okx_cov_merge(MergeArgs a) {
       a.sum[n] = t;
     }
   }
-  if (blockIdx.x == 0) {
+  if (blockIdx.x == 0) {  // (its own workgroup sum: only thread 0 wants it, so one barrier and no broadcast - enstable::block_sum has two)
     long long used = 0;
     for (long long i = threadIdx.x; i < a.ugroups; i += kThreads) used += a.totals[i];
     for (int o = 32; o > 0; o >>= 1) used += __shfl_xor(used, o);
@@ -331,7 +329,7 @@ __global__ __launch_bounds__(kThreads) void okx_cov_merge(MergeArgs a) {
 
 inline int check_sizes(const char* who, long long n_geom, long long steps, int n_columns, long long n) {
   if (int rc = enstable::check_counts(who, n_geom, steps, n_columns)) return rc;
-  if (steps > 0x7fffffffll || (long long)steps * n_columns > kMaxTable) return fail(OKX_ERR_LIMIT, "%s: too many entries in the table for one call", who);
+  if (int rc = enstable::check_entries(who, steps, n_columns, kMaxTable, "entries in the table")) return rc;
   if (n < 1 || n > OKX_ENS_COV_MAX_ENTRIES)
     return fail(OKX_ERR_INVALID, "%s: %lld entries selected, 1 to %d allowed", who, n, (int)OKX_ENS_COV_MAX_ENTRIES);
   return OKX_OK;
@@ -405,28 +403,25 @@ int32_t okx_ensemble_covariance(int64_t n_geometries, int64_t steps, int32_t n_c
   double* sums = reinterpret_cast<double*>(base + lay.sums);
   double* part = reinterpret_cast<double*>(base + lay.tiles);
   if (n_geometries > 0) {
+    const et::Table table = et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns);
     cv::UsedArgs u{};
-    u.values = d_values; u.status = d_status; u.entries = d_entries; u.used = used; u.used_out = d_used; u.totals = totals;
-    u.ld = ld; u.status_stride = d_status ? status_stride : 0; u.n_geom = n_geometries; u.steps = steps; u.gpb = plan.gpb;
-    u.n = n_entries; u.n_columns = n_columns; u.n_table = (int)n_table;
-    hipLaunchKernelGGL(cv::okx_cov_used, dim3((unsigned)plan.ugroups), dim3(cv::kThreads), 0, (hipStream_t)stream, u);
-    HIP_TRY(hipGetLastError());
+    et::set_table(&u, table);
+    u.entries = d_entries; u.used = used; u.used_out = d_used; u.totals = totals;
+    u.gpb = plan.gpb; u.n = n_entries; u.n_table = (int)n_table;
+    OKX_LAUNCH(cv::okx_cov_used, dim3((unsigned)plan.ugroups), dim3(cv::kThreads), 0, (hipStream_t)stream, u);
     cv::GramArgs g{};
-    g.values = d_values; g.entries = d_entries; g.shift = d_shift; g.used = used; g.part = part; g.sums = sums;
-    g.ld = ld; g.n_geom = n_geometries; g.steps = steps; g.slab_len = plan.slab_len; g.slabs = plan.slabs;
-    g.n = n_entries; g.n_columns = n_columns; g.n_table = (int)n_table;
+    et::set_rows(&g, table);  // (the used bytes stand for the status table)
+    g.entries = d_entries; g.shift = d_shift; g.used = used; g.part = part; g.sums = sums;
+    g.slab_len = plan.slab_len; g.slabs = plan.slabs; g.n = n_entries; g.n_columns = n_columns; g.n_table = (int)n_table;
     const bool valu = std::getenv("OKX_DEV") != nullptr && okx::dev_switch("cov_valu");  // (one look at the environment per launch)
-    if (valu)
-      hipLaunchKernelGGL(cv::okx_cov_gram<false>, dim3((unsigned)plan.pairs, (unsigned)plan.slabs), dim3(cv::kThreads), 0, (hipStream_t)stream, g);
-    else
-      hipLaunchKernelGGL(cv::okx_cov_gram<true>, dim3((unsigned)plan.pairs, (unsigned)plan.slabs), dim3(cv::kThreads), 0, (hipStream_t)stream, g);
-    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)plan.pairs, (unsigned)plan.slabs);
+    if (valu) OKX_LAUNCH(cv::okx_cov_gram<false>, grid, dim3(cv::kThreads), 0, (hipStream_t)stream, g);
+    else OKX_LAUNCH(cv::okx_cov_gram<true>, grid, dim3(cv::kThreads), 0, (hipStream_t)stream, g);
   }
   cv::MergeArgs m{};
   m.part = part; m.sums = sums; m.totals = totals; m.gram = d_gram; m.sum = d_sum; m.counts = reinterpret_cast<long long*>(d_counts);
   m.slabs = plan.slabs; m.ugroups = plan.ugroups; m.n_geom = n_geometries; m.n = n_entries; m.accumulate = accumulate != 0;
-  hipLaunchKernelGGL(cv::okx_cov_merge, dim3((unsigned)plan.pairs, cv::kTile * cv::kTile / cv::kThreads), dim3(cv::kThreads), 0, (hipStream_t)stream, m);
-  HIP_TRY(hipGetLastError());
+  OKX_LAUNCH(cv::okx_cov_merge, dim3((unsigned)plan.pairs, cv::kTile * cv::kTile / cv::kThreads), dim3(cv::kThreads), 0, (hipStream_t)stream, m);
   return OKX_OK;
 }
 

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void okx_curves_fit(Args a) {
     for (int k0 = 0; k0 < K; k0 += CL) {  // (wave-uniform: every lane takes every shuffle)
       const int k = k0 + kc;
       const bool live = g < a.n_geom && k < K;
-      const double* vp = a.values + g * S * a.ld;
+      const double* vp = a.values + g * S * a.ld;  // (enstable's walk 2, written out: through the view this kernel's text moves)
       const unsigned char* sp = a.status ? a.status + g * S * a.status_stride : nullptr;
       // ---- first walk: this lane's steps of its column ----
       double su[2 * D + 1], sy[D + 1];
@@ -157,9 +157,9 @@ __global__ __launch_bounds__(kThreads) void okx_curves_fit(Args a) {
           const double* row = vp + s * a.ld;
           const double y = row[k];
           const double x = a.abscissa ? a.abscissa[s] : row[a.x_column];
-          const unsigned st = sp ? sp[s * a.status_stride] : 1u;
-          // the rule of okx_ensemble_reduce for the state and the value; the abscissa finite and inside the closed window
-          if (!((st & 7u) == 1u && __builtin_isfinite(y) && __builtin_isfinite(x) && x >= a.lo && x <= a.hi)) continue;
+          const unsigned st = OKX_ENS_STATUS_AT(sp, s, a.status_stride);
+          // a used step: the state and the value accepted; the abscissa finite and inside the closed window
+          if (!(OKX_ENS_ACCEPTED(st, y) && __builtin_isfinite(x) && x >= a.lo && x <= a.hi)) continue;
           if (n == 0) { y0 = y; first = (int)s; }
           ++n;
           take_lower(ymin, y, (int)s, x);
@@ -217,8 +217,8 @@ __global__ __launch_bounds__(kThreads) void okx_curves_fit(Args a) {
           const double* row = vp + s * a.ld;
           const double y = row[k];
           const double x = a.abscissa ? a.abscissa[s] : row[a.x_column];
-          const unsigned st = sp ? sp[s * a.status_stride] : 1u;
-          if (!((st & 7u) == 1u && __builtin_isfinite(y) && __builtin_isfinite(x) && x >= a.lo && x <= a.hi)) continue;
+          const unsigned st = OKX_ENS_STATUS_AT(sp, s, a.status_stride);
+          if (!(OKX_ENS_ACCEPTED(st, y) && __builtin_isfinite(x) && x >= a.lo && x <= a.hi)) continue;
           const double u = (x - a.origin) * a.inv_scale;
           double q = c[D];
 #pragma unroll
@@ -301,21 +301,20 @@ int32_t okx_ensemble_curves(int64_t n_geometries, int64_t steps, int32_t n_colum
   long long groups = (tasks + cv::kWaves - 1) / cv::kWaves;
   if (groups > cv::kMaxGroups) groups = cv::kMaxGroups;
   cv::Args a{};
-  a.values = d_values; a.status = d_status; a.abscissa = d_abscissa; a.features = d_features; a.count = d_count;
-  a.ld = ld; a.status_stride = d_status ? status_stride : 0; a.n_geom = n_geometries; a.steps = steps;
+  et::set_table(&a, et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns));
+  a.abscissa = d_abscissa; a.features = d_features; a.count = d_count;
   a.origin = origin; a.scale = scale; a.inv_scale = 1.0 / scale; a.lo = window_lo; a.hi = window_hi;
-  a.n_columns = n_columns; a.x_column = d_abscissa ? 0 : x_column; a.col_lanes = plan.col_lanes; a.slices = plan.slices;
+  a.x_column = d_abscissa ? 0 : x_column; a.col_lanes = plan.col_lanes; a.slices = plan.slices;
   a.col_shift = 0;
   while ((1 << a.col_shift) < plan.col_lanes) ++a.col_shift;
   const dim3 grid((unsigned)groups), block(cv::kThreads);
   hipStream_t st = (hipStream_t)stream;
   switch (degree) {
-    case 0: hipLaunchKernelGGL(cv::okx_curves_fit<0>, grid, block, 0, st, a); break;
-    case 1: hipLaunchKernelGGL(cv::okx_curves_fit<1>, grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL(cv::okx_curves_fit<2>, grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL(cv::okx_curves_fit<3>, grid, block, 0, st, a); break;
+    case 0: OKX_LAUNCH(cv::okx_curves_fit<0>, grid, block, 0, st, a); break;
+    case 1: OKX_LAUNCH(cv::okx_curves_fit<1>, grid, block, 0, st, a); break;
+    case 2: OKX_LAUNCH(cv::okx_curves_fit<2>, grid, block, 0, st, a); break;
+    default: OKX_LAUNCH(cv::okx_curves_fit<3>, grid, block, 0, st, a); break;
   }
-  HIP_TRY(hipGetLastError());
   return OKX_OK;
 }
 

@@ -43,14 +43,7 @@ struct EnsArgs {
 
 // slabs of a call: from the problem size only
 inline void slab_plan(long long n_geom, long long n_entries, long long* n_slabs, long long* slab_len) {
-  if (n_geom <= 0) { *n_slabs = 0; *slab_len = 1; return; }
-  const long long tiles = n_entries > 0 ? (n_entries + kTile - 1) / kTile : 1;
-  const long long want = (kWantGroups + tiles - 1) / tiles;
-  const long long most = (n_geom + kMinSlab - 1) / kMinSlab;
-  long long slabs = want < most ? want : most;
-  if (slabs < 1) slabs = 1;
-  *slab_len = (n_geom + slabs - 1) / slabs;
-  *n_slabs = (n_geom + *slab_len - 1) / *slab_len;
+  enstable::slab_plan(n_geom, n_entries, kTile, kWantGroups, kMinSlab, enstable::kNoCap, n_slabs, slab_len);
 }
 
 inline long long factor_moments(int p) { return p > 0 ? (long long)p + (long long)p * (p + 1) / 2 + 1 : 0; }
@@ -80,10 +73,10 @@ __global__ __launch_bounds__(kThreads) void okx_ensemble_partial(EnsArgs a) {
   const long long quarter = (g1 - g0 + kWaves - 1) / kWaves;
   const long long ga = g0 + wave * quarter < g1 ? g0 + wave * quarter : g1;
   const long long gb = ga + quarter < g1 ? ga + quarter : g1;
-  const long long s = er / a.n_columns;
-  const double* vp = a.values + s * a.ld + er % a.n_columns;
-  const unsigned char* sp = a.status ? a.status + s * a.status_stride : nullptr;
-  const long long v_step = a.steps * a.ld, s_step = a.steps * a.status_stride;
+  const enstable::Table t = OKX_ENS_TABLE_OF(a);
+  const double* vp = enstable::entry_values(t, er);
+  const unsigned char* sp = enstable::entry_status(t, er);
+  const long long v_step = enstable::value_step(t), s_step = enstable::status_step(t);
   const double sh = a.shift[er];
   double count = 0.0, rejected = 0.0, sum = 0.0, sumsq = 0.0;
   double mn = __builtin_inf(), mx = -__builtin_inf(), amin = -1.0, amax = -1.0;
@@ -97,9 +90,7 @@ __global__ __launch_bounds__(kThreads) void okx_ensemble_partial(EnsArgs a) {
   auto geometry = [&](long long g, auto whole) {
     constexpr bool kWhole = decltype(whole)::value;
     const double v = vp[g * v_step];
-    const unsigned st = sp ? sp[g * s_step] : 1u;
-    // BatchResult.accepted: converged, not residual-exceeded, not failed; and a value the reference would not report as None
-    const bool ok = (st & 7u) == 1u && __builtin_isfinite(v);
+    const bool ok = OKX_ENS_ACCEPTED(OKX_ENS_STATUS_AT(sp, g, s_step), v);
     const double d = ok ? v - sh : 0.0;
     count += ok ? 1.0 : 0.0;
     rejected += ok ? 0.0 : 1.0;
@@ -251,8 +242,7 @@ int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_colum
   if (n_factors < 0 || n_factors > OKX_ENS_MAX_FACTORS) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: at most %d factors", OKX_ENS_MAX_FACTORS);
   if (geometry_offset < 0 || geometry_offset + n_geometries > (1ll << 53)) return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: geometry indices beyond 2^53");
   const long long n_entries = (long long)steps * n_columns;
-  if (steps > 0x7fffffffll || n_entries * (long long)(okx::ens::kFields + n_factors) > (1ll << 38))
-    return fail(OKX_ERR_LIMIT, "okx_ensemble_reduce: too many entries for one call");
+  if (int rc = et::check_entries("okx_ensemble_reduce", steps, n_columns, (1ll << 38) / (en::kFields + n_factors))) return rc;
   if (n_entries > 0 && (!d_acc || !d_shift)) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: null accumulator or shift table");
   if (int rc = et::check_table("okx_ensemble_reduce", n_entries > 0 && n_geometries > 0, d_values, ld, n_columns, d_status, status_stride)) return rc;
   if (n_factors > 0 && n_geometries > 0 && !d_factors) return fail(OKX_ERR_INVALID, "okx_ensemble_reduce: n_factors > 0 without a factor table");
@@ -269,10 +259,9 @@ int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_colum
   if (n_entries > 0) {
     if (n_slabs > 0) {
       en::EnsArgs a{};
-      a.values = d_values; a.status = d_status; a.factors = d_factors; a.shift = d_shift; a.partial = partial;
-      a.ld = ld; a.status_stride = d_status ? status_stride : 0;
-      a.n_geom = n_geometries; a.steps = steps; a.n_entries = n_entries; a.slab_len = slab_len; a.geometry_offset = geometry_offset;
-      a.n_columns = n_columns; a.n_factors = n_factors;
+      et::set_table(&a, et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns));
+      a.factors = d_factors; a.shift = d_shift; a.partial = partial;
+      a.n_entries = n_entries; a.slab_len = slab_len; a.geometry_offset = geometry_offset; a.n_factors = n_factors;
       // the cross sums of a lane stay in registers: blocks of 8, 16 or 32 factors, more than 32 as further workgroups
       if (n_factors == 0) HIP_TRY(en::launch_partial<0>(a, n_slabs, st));
       else if (n_factors <= 8) HIP_TRY(en::launch_partial<8>(a, n_slabs, st));
@@ -280,21 +269,18 @@ int32_t okx_ensemble_reduce(int64_t n_geometries, int64_t steps, int32_t n_colum
       else HIP_TRY(en::launch_partial<en::kFactorBlock>(a, n_slabs, st));
     }
     const long long threads = n_entries * rows;
-    hipLaunchKernelGGL(en::okx_ensemble_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, partial, n_slabs, n_entries, rows,
-                       accumulate ? 1 : 0, d_acc);
-    HIP_TRY(hipGetLastError());
+    OKX_LAUNCH(en::okx_ensemble_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, partial, n_slabs, n_entries, rows,
+               accumulate ? 1 : 0, d_acc);
   }
   if (d_factor_acc) {
     const long long n_moments = en::factor_moments(n_factors);
     double* fpart = partial + (size_t)n_slabs * (size_t)rows * (size_t)n_entries;
     if (n_slabs > 0) {
-      hipLaunchKernelGGL(en::okx_ensemble_factor_partial, dim3((unsigned)n_slabs), dim3(256), 0, st, d_factors, n_factors,
-                         (long long)n_geometries, slab_len, n_moments, fpart);
-      HIP_TRY(hipGetLastError());
+      OKX_LAUNCH(en::okx_ensemble_factor_partial, dim3((unsigned)n_slabs), dim3(256), 0, st, d_factors, n_factors, (long long)n_geometries,
+                 slab_len, n_moments, fpart);
     }
-    hipLaunchKernelGGL(en::okx_ensemble_factor_merge, dim3((unsigned)((n_moments + 255) / 256)), dim3(256), 0, st, fpart, n_slabs, n_moments,
-                       accumulate ? 1 : 0, d_factor_acc);
-    HIP_TRY(hipGetLastError());
+    OKX_LAUNCH(en::okx_ensemble_factor_merge, dim3((unsigned)((n_moments + 255) / 256)), dim3(256), 0, st, fpart, n_slabs, n_moments,
+               accumulate ? 1 : 0, d_factor_acc);
   }
   return OKX_OK;
 }

@@ -7,7 +7,7 @@
 //
 // Three launches, all sized by plan_for(n_geometries, n_objectives) alone (it never looks at the device):
 // Gather pass (okx_front_gather): one lane per geometry reads its M selected entries, decides whether it is a CANDIDATE
-// (mask byte 0, every selected entry counts by the rule of okx_ensemble_reduce) and writes its objective vector - v, -v or
+// (mask byte 0, every selected entry counts by the acceptance rule of okx_enstable.hpp) and writes its objective vector - v, -v or
 // |v - target|, the subtraction rounded once - into d_scratch, double [rows][MP]: rows = G rounded up to a tile of kTile,
 // MP = M rounded up to even (M = 1: 1) so that a row of an even M is 16-byte aligned.  The vector of a geometry that is no
 // candidate, and of the padding rows, is all NaN: a NaN compares false both ways, so such a row neither dominates nor is
@@ -22,7 +22,7 @@
 // (grid 16 x 64); every split adds its int32 count into d_dominated[b] with one integer atomic per lane - integer sums carry
 // the same bits in any order.
 // Compaction pass (okx_front_compact): a workgroup owns gpb consecutive geometries, counts the front members before them
-// (d_dominated == 0) and walks its own in ascending order with ballot + prefix counts, as okx_screen_compact does: a
+// (d_dominated == 0) and walks its own in ascending order with ballot + prefix counts (enstable::kept_before): a
 // member's slot is what lies before it - no atomic decides a position.  It writes the id and the raw table values of the
 // member's objectives; the last workgroup writes the tally (seen, candidates, front members).
 #include <hip/hip_runtime.h>
@@ -45,8 +45,6 @@ constexpr int kTile = 64;                 // a-vectors per LDS tile
 constexpr int kMaxM = OKX_ENS_FRONT_MAX_OBJECTIVES;
 constexpr long long kWantGroups = 1024;   // workgroups the all-pairs pass aims at (four per CU of a 256-CU part, from the sizes alone)
 constexpr long long kCompactRows = 1024;  // geometries per workgroup of the compaction pass
-
-typedef unsigned long long u64;
 
 constexpr int padded(int m) { return m == 1 ? 1 : (m + 1) & ~1; }
 
@@ -103,9 +101,7 @@ __global__ __launch_bounds__(kThreads) void okx_front_gather(GatherArgs a) {
     if (ok && m < a.o.n) {
       const long long row = g * a.steps + a.o.step[m];
       const double v = a.values[row * a.ld + a.o.column[m]];
-      const unsigned st = a.status ? a.status[row * a.status_stride] : 1u;
-      // the rule of okx_ensemble_reduce: converged, not residual-exceeded, not failed, and a finite value
-      if (!((st & 7u) == 1u && __builtin_isfinite(v))) ok = false;
+      if (!OKX_ENS_ACCEPTED(OKX_ENS_STATUS_AT(a.status, row, a.status_stride), v)) ok = false;
       const int sense = a.o.sense[m];
       o[m] = sense == OKX_FRONT_MAX ? -v : sense == OKX_FRONT_TARGET ? __builtin_fabs(v - a.o.target[m]) : v;
     }
@@ -149,17 +145,6 @@ __global__ __launch_bounds__(kThreads) void okx_front_pairs(const double* __rest
   if (count != 0) atomicAdd(&dominated[b], count);
 }
 
-// the sum of one value per thread over the workgroup, in every thread (integers: the order does not matter)
-__device__ inline long long block_sum(long long x, long long* lds) {
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  __syncthreads();  // (lds may still be read from the call before)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = x;
-  __syncthreads();
-  long long sum = 0;
-  for (int w = 0; w < kWaves; ++w) sum += lds[w];
-  return sum;
-}
-
 struct CompactArgs {
   const int* dominated;
   const double* values;
@@ -184,25 +169,15 @@ __global__ __launch_bounds__(kThreads) void okx_front_compact(CompactArgs a) {
     before += d == 0 ? 1 : 0;
     candidates += d >= 0 ? 1 : 0;
   }
-  before = block_sum(before, sums);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  before = enstable::block_sum<kWaves>(before, sums);
   long long at = before;  // the slot of the next front member of this workgroup
   for (long long gc = g0; gc < g1; gc += kThreads) {
     const long long g = gc + threadIdx.x;
     const int d = g < g1 ? a.dominated[g] : -1;
     const bool member = d == 0;
     candidates += d >= 0 ? 1 : 0;
-    const u64 mask = __ballot(member);
-    const unsigned mine = (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wave_n[wave] = (unsigned)__popcll(mask);
-    __syncthreads();
-    unsigned ahead = 0u, all = 0u;
-    for (int w = 0; w < kWaves; ++w) {
-      if (w < wave) ahead += wave_n[w];
-      all += wave_n[w];
-    }
-    const long long slot = at + ahead + mine;
+    unsigned all;
+    const long long slot = at + enstable::kept_before<kWaves>(member, wave_n, &all);
     if (member) {
       if (a.front_index && slot < a.cap_index) a.front_index[slot] = a.index ? a.index[g] : a.geometry_offset + g;
       if (a.front_values && slot < a.cap_values) {
@@ -215,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void okx_front_compact(CompactArgs a) {
     at += all;
   }
   if (last) {
-    candidates = block_sum(candidates, sums);
+    candidates = enstable::block_sum<kWaves>(candidates, sums);
     if (threadIdx.x == 0) {
       a.tally[0] = a.n_geom;
       a.tally[1] = candidates;
@@ -225,9 +200,10 @@ __global__ __launch_bounds__(kThreads) void okx_front_compact(CompactArgs a) {
 }
 
 template <int M>
-void launch_pairs(const Plan& p, const double* obj, int* dominated, long long n_geom, hipStream_t stream) {
-  hipLaunchKernelGGL(okx_front_pairs<M>, dim3((unsigned)p.b_blocks, (unsigned)p.splits), dim3(kThreads), 0, stream, obj, dominated, n_geom, p.tiles,
-                     p.tiles_per_split);
+int launch_pairs(const Plan& p, const double* obj, int* dominated, long long n_geom, hipStream_t stream) {
+  OKX_LAUNCH(okx_front_pairs<M>, dim3((unsigned)p.b_blocks, (unsigned)p.splits), dim3(kThreads), 0, stream, obj, dominated, n_geom, p.tiles,
+             p.tiles_per_split);
+  return OKX_OK;
 }
 
 // what okx_ensemble_front_check reports; `o` (or null) takes the entries apart for the kernels
@@ -300,32 +276,25 @@ int32_t okx_ensemble_front(int64_t n_geometries, int64_t steps, int32_t n_column
   const fr::Plan plan = fr::plan_for(n_geometries, n_objectives);
   hipStream_t st = (hipStream_t)stream;
   double* obj = static_cast<double*>(d_scratch);
+  const et::Table table = et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns);
   if (n_geometries > 0) {
     fr::GatherArgs g{};
-    g.values = d_values; g.status = d_status; g.mask = d_mask; g.obj = obj; g.dominated = d_dominated;
-    g.ld = ld; g.status_stride = d_status ? status_stride : 0; g.mask_stride = d_mask ? mask_stride : 0;
-    g.n_geom = n_geometries; g.steps = steps; g.rows = plan.rows; g.mp = fr::padded(n_objectives); g.o = o;
-    hipLaunchKernelGGL(fr::okx_front_gather, dim3((unsigned)((plan.rows + fr::kThreads - 1) / fr::kThreads)), dim3(fr::kThreads), 0, st, g);
-    HIP_TRY(hipGetLastError());
-    switch (n_objectives) {
-      case 1: fr::launch_pairs<1>(plan, obj, d_dominated, n_geometries, st); break;
-      case 2: fr::launch_pairs<2>(plan, obj, d_dominated, n_geometries, st); break;
-      case 3: fr::launch_pairs<3>(plan, obj, d_dominated, n_geometries, st); break;
-      case 4: fr::launch_pairs<4>(plan, obj, d_dominated, n_geometries, st); break;
-      case 5: fr::launch_pairs<5>(plan, obj, d_dominated, n_geometries, st); break;
-      case 6: fr::launch_pairs<6>(plan, obj, d_dominated, n_geometries, st); break;
-      case 7: fr::launch_pairs<7>(plan, obj, d_dominated, n_geometries, st); break;
-      default: fr::launch_pairs<8>(plan, obj, d_dominated, n_geometries, st); break;
-    }
-    HIP_TRY(hipGetLastError());
+    et::set_rows(&g, table);  // (the objectives carry their own step and column)
+    g.status = table.status; g.status_stride = table.status_stride; g.mask = d_mask; g.mask_stride = d_mask ? mask_stride : 0;
+    g.obj = obj; g.dominated = d_dominated; g.rows = plan.rows; g.mp = fr::padded(n_objectives); g.o = o;
+    OKX_LAUNCH(fr::okx_front_gather, dim3((unsigned)((plan.rows + fr::kThreads - 1) / fr::kThreads)), dim3(fr::kThreads), 0, st, g);
+    static constexpr decltype(&fr::launch_pairs<1>) kPairs[fr::kMaxM] = {  // (check_objectives: 1 <= n_objectives <= kMaxM)
+        fr::launch_pairs<1>, fr::launch_pairs<2>, fr::launch_pairs<3>, fr::launch_pairs<4>,
+        fr::launch_pairs<5>, fr::launch_pairs<6>, fr::launch_pairs<7>, fr::launch_pairs<8>};
+    if (int rc = kPairs[n_objectives - 1](plan, obj, d_dominated, n_geometries, st)) return rc;
   }
   fr::CompactArgs c{};
-  c.dominated = d_dominated; c.values = d_values; c.index = reinterpret_cast<const long long*>(d_index);
+  et::set_rows(&c, table);
+  c.dominated = d_dominated; c.index = reinterpret_cast<const long long*>(d_index);
   c.tally = reinterpret_cast<long long*>(d_tally); c.front_index = reinterpret_cast<long long*>(d_front_index); c.front_values = d_front_values;
-  c.ld = ld; c.n_geom = n_geometries; c.steps = steps; c.groups = plan.groups;
-  c.cap_index = d_front_index ? capacity : 0; c.cap_values = d_front_values ? capacity : 0; c.geometry_offset = geometry_offset; c.o = o;
-  hipLaunchKernelGGL(fr::okx_front_compact, dim3((unsigned)(plan.groups > 0 ? plan.groups : 1)), dim3(fr::kThreads), 0, st, c);
-  HIP_TRY(hipGetLastError());
+  c.groups = plan.groups; c.cap_index = d_front_index ? capacity : 0; c.cap_values = d_front_values ? capacity : 0;
+  c.geometry_offset = geometry_offset; c.o = o;
+  OKX_LAUNCH(fr::okx_front_compact, dim3((unsigned)(plan.groups > 0 ? plan.groups : 1)), dim3(fr::kThreads), 0, st, c);
   return OKX_OK;
 }
 

@@ -7,7 +7,8 @@
 //   okx_evaluation.cpp  the evaluated modules: enabling, precompiling, okx_evaluate_batch (HIP runtime API only)
 //   okx_predictor.cpp   okx_program_fit_predictor (on top of the public okx_solve_batch)
 //   okx_metrics.hip, okx_shim_api.hip (kernel: okx_shim.hip), okx_diagnose.hip, okx_ensemble.hip, okx_select.hip,
-//   okx_screen.hip, okx_covariance.hip: one pass each - kernels, launch plan, argument checks and entry points together
+//   okx_screen.hip, okx_covariance.hip, okx_curves.hip, okx_front.hip, okx_sample.hip: one pass each - kernels, launch plan,
+//   argument checks and entry points together (what the six passes over an ensemble table share: okx_enstable.hpp)
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -58,9 +58,7 @@ inline Plan plan_for(long long n_geom, long long n_entries) {
   p.lanes = 1;
   while (p.lanes < 64 && p.lanes < n_entries) p.lanes <<= 1;
   const long long per_iter = (long long)kWaves * (64 / p.lanes);
-  long long gpb = (n_geom + kWantGroups - 1) / kWantGroups;
-  gpb = (gpb + per_iter - 1) / per_iter * per_iter;
-  p.gpb = gpb < per_iter ? per_iter : gpb;
+  p.gpb = enstable::geometries_per_group(n_geom, kWantGroups, per_iter);
   p.groups = n_geom > 0 ? (n_geom + p.gpb - 1) / p.gpb : 0;
   p.lds_blame = n_entries * 2 * 4 <= kLdsBlameBytes ? 1 : 0;
   return p;
@@ -103,6 +101,7 @@ __global__ __launch_bounds__(kThreads) void okx_screen_verdict(VerdictArgs a) {
   const int s0 = t / K, k0 = t % K, ds = L / K, dk = L % K;  // entry e = t, t + L, ...: (s, k) by additions
   const long long g0 = (long long)blockIdx.x * a.gpb;
   const long long g1 = g0 + a.gpb < a.n_geom ? g0 + a.gpb : a.n_geom;
+  const enstable::Table tab = OKX_ENS_TABLE_OF(a);
   unsigned n_pass = 0u, n_out = 0u, n_unres = 0u;  // wave-uniform
   for (long long gb = g0 + (long long)wave * pack; gb < g1; gb += (long long)kWaves * pack) {
     const long long g = gb + sub;
@@ -111,20 +110,19 @@ __global__ __launch_bounds__(kThreads) void okx_screen_verdict(VerdictArgs a) {
     int key = kNoEntry;  // entry * 2 + (value below lo)
     unsigned fl = 0u;
     if (live) {
-      const double* vp = a.values + g * a.steps * a.ld;
-      const unsigned char* sp = a.status ? a.status + g * a.steps * a.status_stride : nullptr;
+      const double* vp = enstable::geometry_values(tab, g);
+      const unsigned char* sp = enstable::geometry_status(tab, g);
       int s = s0, k = k0;
 #pragma unroll 4
       for (int e = t; e < E; e += L) {
         const double lo = a.limits[2 * (long long)e], hi = a.limits[2 * (long long)e + 1];
         const double v = vp[(long long)s * a.ld + k];
-        const unsigned st = sp ? sp[(long long)s * a.status_stride] : 1u;
+        const unsigned st = OKX_ENS_STATUS_AT(sp, s, a.status_stride);
         const double sc = a.scale ? a.scale[e] : 1.0;
         s += ds; k += dk;
         if (k >= K) { k -= K; ++s; }
         if (!(__builtin_isfinite(lo) || __builtin_isfinite(hi))) continue;  // not looked at
-        // the rule of okx_ensemble_reduce: converged, not residual-exceeded, not failed, and a finite value
-        if (!((st & 7u) == 1u && __builtin_isfinite(v))) { fl |= OKX_SCREEN_UNRESOLVED; continue; }
+        if (!OKX_ENS_ACCEPTED(st, v)) { fl |= OKX_SCREEN_UNRESOLVED; continue; }
         const bool below = v < lo;
         if (below || v > hi) fl |= OKX_SCREEN_OUTSIDE;
         double x = v - lo, y = hi - v;
@@ -161,17 +159,6 @@ __global__ __launch_bounds__(kThreads) void okx_screen_verdict(VerdictArgs a) {
   if (threadIdx.x < 3 && blockIdx.x < a.groups) a.totals[3 * (long long)blockIdx.x + threadIdx.x] = (long long)scr_lds[threadIdx.x];
 }
 
-// the sum of one value per thread over the workgroup, in every thread (integers: the order does not matter)
-__device__ inline long long block_sum(long long x, long long* lds) {
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  __syncthreads();  // (lds may still be read from the call before)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = x;
-  __syncthreads();
-  long long sum = 0;
-  for (int w = 0; w < kWaves; ++w) sum += lds[w];
-  return sum;
-}
-
 struct CompactArgs {
   const unsigned char* flags;
   const int* blame_key;     // [n_geom]
@@ -195,11 +182,11 @@ __global__ __launch_bounds__(kThreads) void okx_screen_compact(CompactArgs a) {
   const bool last = b + 1 >= a.groups;  // (groups == 0: the one workgroup launched)
   long long before = 0;
   for (long long i = threadIdx.x; i < b && i < a.groups; i += kThreads) before += a.totals[3 * i];
-  before = block_sum(before, sums);
+  before = enstable::block_sum<kWaves>(before, sums);
   const long long base = *a.base;
   const long long g0 = b * a.gpb;
   const long long g1 = g0 + a.gpb < a.n_geom ? g0 + a.gpb : a.n_geom;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   long long at = base + before;  // the slot of the next survivor of this workgroup
   for (long long gc = g0; gc < g1; gc += kThreads) {
     const long long g = gc + threadIdx.x;
@@ -217,17 +204,8 @@ __global__ __launch_bounds__(kThreads) void okx_screen_compact(CompactArgs a) {
         if (blamed == k0) blamed = -1;
       }
     }
-    const u64 mask = __ballot(pass);
-    const unsigned mine = (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
-    __syncthreads();
-    if (lane == 0) wave_n[wave] = (unsigned)__popcll(mask);
-    __syncthreads();
-    unsigned ahead = 0u, all = 0u;
-    for (int w = 0; w < kWaves; ++w) {
-      if (w < wave) ahead += wave_n[w];
-      all += wave_n[w];
-    }
-    const long long slot = at + ahead + mine;
+    unsigned all;
+    const long long slot = at + enstable::kept_before<kWaves>(pass, wave_n, &all);
     if (pass && a.pass_index && slot >= 0 && slot < a.capacity) a.pass_index[slot] = a.geometry_offset + g;
     at += all;
   }
@@ -239,8 +217,8 @@ __global__ __launch_bounds__(kThreads) void okx_screen_compact(CompactArgs a) {
   if (last) {
     long long n_out = 0, n_unres = 0;
     for (long long i = threadIdx.x; i < a.groups; i += kThreads) { n_out += a.totals[3 * i + 1]; n_unres += a.totals[3 * i + 2]; }
-    n_out = block_sum(n_out, sums);
-    n_unres = block_sum(n_unres, sums);
+    n_out = enstable::block_sum<kWaves>(n_out, sums);
+    n_unres = enstable::block_sum<kWaves>(n_unres, sums);
     if (threadIdx.x == 0) {
       const long long passed = at - base;  // what passed before this workgroup and in it
       const long long add[4] = {a.n_geom, passed, n_out, n_unres};
@@ -252,8 +230,7 @@ __global__ __launch_bounds__(kThreads) void okx_screen_compact(CompactArgs a) {
 
 inline int check_sizes(const char* who, long long n_geom, long long steps, int n_columns) {
   if (int rc = enstable::check_counts(who, n_geom, steps, n_columns)) return rc;
-  if (steps > 0x7fffffffll || (long long)steps * n_columns > kMaxEntries) return fail(OKX_ERR_LIMIT, "%s: too many entries for one call", who);
-  return OKX_OK;
+  return enstable::check_entries(who, steps, n_columns, kMaxEntries);
 }
 
 }  // namespace scr
@@ -302,14 +279,13 @@ int32_t okx_ensemble_screen(int64_t n_geometries, int64_t steps, int32_t n_colum
   const unsigned grid = (unsigned)(plan.groups > 0 ? plan.groups : 1);  // (no geometry: the one workgroup zeroes and keeps the count)
   {
     sc::VerdictArgs a{};
-    a.values = d_values; a.status = d_status; a.limits = d_limits; a.scale = d_scale;
+    et::set_table(&a, et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns));
+    a.limits = d_limits; a.scale = d_scale;
     a.flags = d_flags; a.margin = d_margin; a.entry = d_entry;
     a.blame_key = blame_key; a.blame = reinterpret_cast<sc::u64*>(d_blame); a.totals = totals;
     a.pass_count = reinterpret_cast<const long long*>(d_pass_count); a.base = base;
-    a.ld = ld; a.status_stride = d_status ? status_stride : 0; a.n_geom = n_geometries; a.steps = steps; a.gpb = plan.gpb; a.groups = plan.groups;
-    a.n_entries = (int)n_entries; a.n_columns = n_columns; a.lanes = plan.lanes; a.accumulate = accumulate != 0;
-    hipLaunchKernelGGL(sc::okx_screen_verdict, dim3(grid), dim3(sc::kThreads), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
+    a.gpb = plan.gpb; a.groups = plan.groups; a.n_entries = (int)n_entries; a.lanes = plan.lanes; a.accumulate = accumulate != 0;
+    OKX_LAUNCH(sc::okx_screen_verdict, dim3(grid), dim3(sc::kThreads), 0, (hipStream_t)stream, a);
   }
   sc::CompactArgs c{};
   c.flags = d_flags; c.blame_key = blame_key; c.blame = reinterpret_cast<sc::u64*>(d_blame); c.totals = totals; c.base = base;
@@ -317,8 +293,7 @@ int32_t okx_ensemble_screen(int64_t n_geometries, int64_t steps, int32_t n_colum
   c.pass_count = reinterpret_cast<long long*>(d_pass_count);
   c.n_geom = n_geometries; c.gpb = plan.gpb; c.groups = plan.groups; c.capacity = d_pass_index ? capacity : 0;
   c.geometry_offset = geometry_offset; c.accumulate = accumulate != 0; c.n_entries = (int)n_entries; c.lds_blame = plan.lds_blame;
-  hipLaunchKernelGGL(sc::okx_screen_compact, dim3(grid), dim3(sc::kThreads), plan.lds_blame ? 8 * (size_t)n_entries : 0, (hipStream_t)stream, c);
-  HIP_TRY(hipGetLastError());
+  OKX_LAUNCH(sc::okx_screen_compact, dim3(grid), dim3(sc::kThreads), plan.lds_blame ? 8 * (size_t)n_entries : 0, (hipStream_t)stream, c);
   return OKX_OK;
 }
 

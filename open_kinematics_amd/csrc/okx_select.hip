@@ -70,19 +70,6 @@ inline int tile_for(int n_sel) {
 
 inline size_t lds_bytes(int n_sel, int tile) { return (size_t)n_sel * kBins * (tile + 1) * 4 + (size_t)n_sel * tile * 8; }
 
-// slabs of a count call: from the problem size only
-inline void slab_plan(long long n_geom, long long n_entries, int tile, long long* n_slabs, long long* slab_len) {
-  if (n_geom <= 0 || n_entries <= 0) { *n_slabs = 0; *slab_len = 1; return; }
-  const long long tiles = (n_entries + tile - 1) / tile;
-  const long long want = (kWantGroups + tiles - 1) / tiles;
-  const long long most = (n_geom + kMinSlab - 1) / kMinSlab;
-  long long slabs = want < most ? want : most;
-  if (slabs < 1) slabs = 1;
-  if (slabs > 65535) slabs = 65535;
-  *slab_len = (n_geom + slabs - 1) / slabs;
-  *n_slabs = (n_geom + *slab_len - 1) / *slab_len;
-}
-
 __device__ inline u64 key_of(double v) {
   const u64 b = (u64)__double_as_longlong(v);
   return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
@@ -127,10 +114,10 @@ __global__ __launch_bounds__(kThreads) void okx_select_count(CountArgs a) {
   const long long er = live ? e : 0;  // a lane past the table walks entry 0 and counts nothing
   const long long g0 = (long long)blockIdx.y * a.slab_len;
   const long long g1 = g0 + a.slab_len < a.n_geom ? g0 + a.slab_len : a.n_geom;
-  const long long s = er / a.n_columns;
-  const double* vp = a.values + s * a.ld + er % a.n_columns;
-  const unsigned char* sp = a.status ? a.status + s * a.status_stride : nullptr;
-  const long long v_step = a.steps * a.ld, s_step = a.steps * a.status_stride;
+  const enstable::Table t = OKX_ENS_TABLE_OF(a);
+  const double* vp = enstable::entry_values(t, er);
+  const unsigned char* sp = enstable::entry_status(t, er);
+  const long long v_step = enstable::value_step(t), s_step = enstable::status_step(t);
   const int shift = 64 - kBits * (a.round + 1);
   const int fixed_shift = 64 - kBits * a.round;  // (round > 0) key >> fixed_shift: the bits already fixed
   const bool limited = a.round == 0 && a.limits != nullptr;
@@ -138,9 +125,8 @@ __global__ __launch_bounds__(kThreads) void okx_select_count(CountArgs a) {
   unsigned below = 0u, above = 0u;
   auto geometry = [&](long long g) {
     const double v = vp[g * v_step];
-    const unsigned st = sp ? sp[g * s_step] : 1u;
-    // the rule of okx_ensemble_reduce: converged, not residual-exceeded, not failed, and a finite value
-    const bool ok = live && (st & 7u) == 1u && __builtin_isfinite(v);
+    const unsigned st = OKX_ENS_STATUS_AT(sp, g, s_step);
+    const bool ok = live && OKX_ENS_ACCEPTED(st, v);
     if (!ok) return;
     const u64 key = key_of(v);
     const unsigned bin = (unsigned)(key >> shift) & (unsigned)(kBins - 1);
@@ -246,9 +232,7 @@ inline int check_sizes(const char* who, long long steps, int n_columns, int n_pr
   if (steps < 0 || n_columns < 0) return fail(OKX_ERR_INVALID, "%s: negative step or column count", who);
   if (n_probs < 1 || n_probs > OKX_ENS_SELECT_MAX_PROBS || tile_for(2 * n_probs) < 1)
     return fail(OKX_ERR_LIMIT, "%s: 1 to %d probabilities", who, OKX_ENS_SELECT_MAX_PROBS);
-  if (steps > 0x7fffffffll || (long long)steps * n_columns > (1ll << 38) / (2ll * n_probs * kBins))
-    return fail(OKX_ERR_LIMIT, "%s: too many entries for one call", who);
-  return OKX_OK;
+  return enstable::check_entries(who, steps, n_columns, (1ll << 38) / (2ll * n_probs * kBins));
 }
 
 }  // namespace sel
@@ -294,9 +278,8 @@ int32_t okx_ensemble_select_begin(int64_t steps, int32_t n_columns, int32_t n_pr
   if (!d_state || !d_hist) return fail(OKX_ERR_INVALID, "okx_ensemble_select_begin: null state or histogram");
   const long long state_len = sl::state_words(n_entries, 2 * n_probs), hist_len = okx_ensemble_select_hist_len(steps, n_columns, n_probs);
   const long long blocks = (state_len + hist_len + 255) / 256;
-  hipLaunchKernelGGL(sl::okx_select_init, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream,
-                     static_cast<sl::u64*>(d_state), state_len, reinterpret_cast<sl::u64*>(d_hist), hist_len);
-  HIP_TRY(hipGetLastError());
+  OKX_LAUNCH(sl::okx_select_init, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream,
+             static_cast<sl::u64*>(d_state), state_len, reinterpret_cast<sl::u64*>(d_hist), hist_len);
   return OKX_OK;
 }
 
@@ -313,19 +296,16 @@ int32_t okx_ensemble_select_count(int32_t round, int64_t n_geometries, int64_t s
   if (int rc = et::check_table("okx_ensemble_select_count", true, d_values, ld, n_columns, d_status, status_stride)) return rc;
   const int n_sel = 2 * n_probs, tile = sl::tile_for(n_sel);
   long long n_slabs, slab_len;
-  sl::slab_plan(n_geometries, n_entries, tile, &n_slabs, &slab_len);
+  et::slab_plan(n_geometries, n_entries, tile, sl::kWantGroups, sl::kMinSlab, 65535, &n_slabs, &slab_len);  // from the sizes alone
   const long long tiles = (n_entries + tile - 1) / tile;
   if (tiles > 0x7fffffffll) return fail(OKX_ERR_LIMIT, "okx_ensemble_select_count: too many entries for one call");
   sl::CountArgs a{};
-  a.values = d_values; a.status = d_status; a.limits = d_limits;
+  et::set_table(&a, et::table_view(d_values, ld, d_status, status_stride, n_geometries, steps, n_columns));
+  a.limits = d_limits;
   a.prefix = sl::state_of(const_cast<void*>(d_state), n_entries, n_sel).prefix;
   a.hist = reinterpret_cast<sl::u64*>(d_hist);
-  a.ld = ld; a.status_stride = d_status ? status_stride : 0;
-  a.n_geom = n_geometries; a.steps = steps; a.n_entries = n_entries; a.slab_len = slab_len;
-  a.n_columns = n_columns; a.n_sel = n_sel; a.round = round; a.tile = tile;
-  hipLaunchKernelGGL(sl::okx_select_count, dim3((unsigned)tiles, (unsigned)n_slabs), dim3(sl::kThreads), sl::lds_bytes(n_sel, tile),
-                     (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
+  a.n_entries = n_entries; a.slab_len = slab_len; a.n_sel = n_sel; a.round = round; a.tile = tile;
+  OKX_LAUNCH(sl::okx_select_count, dim3((unsigned)tiles, (unsigned)n_slabs), dim3(sl::kThreads), sl::lds_bytes(n_sel, tile), (hipStream_t)stream, a);
   return OKX_OK;
 }
 
@@ -338,9 +318,8 @@ int32_t okx_ensemble_select_descend(int32_t round, int64_t steps, int32_t n_colu
   if (n_entries == 0) return OKX_OK;
   if (!d_state || !d_hist || !d_probs) return fail(OKX_ERR_INVALID, "okx_ensemble_select_descend: null state, histogram or probabilities");
   const int n_sel = 2 * n_probs, per_block = 256 / n_sel;
-  hipLaunchKernelGGL(sl::okx_select_descend, dim3((unsigned)((n_entries + per_block - 1) / per_block)), dim3(256), 0, (hipStream_t)stream, d_state,
-                     reinterpret_cast<sl::u64*>(d_hist), d_probs, n_entries, n_sel, (int)round, per_block);
-  HIP_TRY(hipGetLastError());
+  OKX_LAUNCH(sl::okx_select_descend, dim3((unsigned)((n_entries + per_block - 1) / per_block)), dim3(256), 0, (hipStream_t)stream, d_state,
+             reinterpret_cast<sl::u64*>(d_hist), d_probs, n_entries, n_sel, (int)round, per_block);
   return OKX_OK;
 }
 
@@ -353,9 +332,8 @@ int32_t okx_ensemble_select_finish(int64_t steps, int32_t n_columns, int32_t n_p
   if (!d_state) return fail(OKX_ERR_INVALID, "okx_ensemble_select_finish: null state");
   if (!d_order || !d_count) return fail(OKX_ERR_INVALID, "okx_ensemble_select_finish: null order-statistic or count table");
   const long long threads = n_entries * 2 * n_probs;
-  hipLaunchKernelGGL(sl::okx_select_finish, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_state, n_entries,
-                     2 * n_probs, d_order, reinterpret_cast<long long*>(d_count), reinterpret_cast<long long*>(d_outside));
-  HIP_TRY(hipGetLastError());
+  OKX_LAUNCH(sl::okx_select_finish, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_state, n_entries, 2 * n_probs,
+             d_order, reinterpret_cast<long long*>(d_count), reinterpret_cast<long long*>(d_outside));
   return OKX_OK;
 }
 

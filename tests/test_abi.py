@@ -64,6 +64,54 @@ def test_library_exports_nothing_undeclared():
         assert hasattr(lib, name), f"libokx.so does not export {name}"
 
 
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "size_t": C.c_size_t, "uint64_t": C.c_uint64}
+
+
+def _prototypes(path):
+    """{name: (return type, [parameter types])} of a header's okx_* prototypes, types as written less `const` and the name."""
+    with open(path, "r", encoding="utf-8") as fh:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", fh.read(), flags=re.S)
+    found = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+(?:\s*\*)?)\s*\b(okx_\w+)\s*\(([^;{}()]*)\)\s*;", text, flags=re.M):
+        kinds = []
+        for param in (p.strip() for p in params.split(",")):
+            if param in ("", "void"):
+                continue
+            kinds.append("*" if "*" in param else " ".join(w for w in param.split()[:-1] if w != "const"))
+        found[name] = (" ".join(ret.replace("*", " * ").split()), kinds)
+    return found
+
+
+def test_ctypes_signatures_match_the_headers():
+    """Every prototype of include/okx.h and include/okx_debug.h against the argtypes / restype the loaded library carries:
+    the count, a pointer for a pointer, the exact scalar for a scalar; void <-> None and const char* <-> c_char_p."""
+    lib = _lib.load()
+    protos = _prototypes(HEADER)
+    debug = _prototypes(os.path.join(REPO, "include", "okx_debug.h"))
+    assert set(protos) == set(_lib.EXPORTS) and set(debug) == set(_lib.DEBUG_EXPORTS), "header parse failed"
+    protos.update(debug)
+    pointer_type = type(C.POINTER(C.c_int))
+    for name, (ret, kinds) in sorted(protos.items()):
+        fn = getattr(lib, name)
+        got = list(fn.argtypes or [])
+        if kinds:
+            assert fn.argtypes is not None, f"{name}: no argtypes for {len(kinds)} parameters"
+        assert len(got) == len(kinds), f"{name}: {len(kinds)} parameters declared, {len(got)} argtypes"
+        for i, (kind, ctype) in enumerate(zip(kinds, got)):
+            if kind == "*":
+                assert ctype in (C.c_void_p, C.c_char_p) or isinstance(ctype, pointer_type), f"{name}: parameter {i} is a pointer, argtype {ctype}"
+            else:
+                assert kind in _SCALARS, f"{name}: parameter {i} has the type {kind!r}, which this test does not know"
+                assert ctype is _SCALARS[kind], f"{name}: parameter {i} is {kind}, argtype {ctype}"
+        if ret == "void":
+            assert fn.restype is None, f"{name}: returns void, restype {fn.restype}"
+        elif ret == "const char *":
+            assert fn.restype is C.c_char_p, f"{name}: returns const char*, restype {fn.restype}"
+        else:
+            assert ret in _SCALARS, f"{name}: returns {ret!r}, which this test does not know"
+            assert fn.restype is _SCALARS[ret], f"{name}: returns {ret}, restype {fn.restype}"
+
+
 @pytest.mark.parametrize("name", STEERED + UNSTEERED)
 def test_plan_building_on_host(golden, name):
     _, program = golden(name)
