@@ -1118,6 +1118,82 @@ int32_t okx_ensemble_sample_check(int64_t n_geometries, int64_t geometry_offset,
                                   const okx_sample_guard* guards, int32_t n_guards,
                                   int32_t stratify, int32_t max_attempts);
 
+/*
+ * Pick-freeze families on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): the structured
+ * ensemble a variance decomposition (okx_ensemble_sobol) needs, drawn by the sampler above with ONE counter word changed.
+ * d_group [n_latents] int32 puts every latent into a factor group in [0, n_groups), or -1: never swapped;
+ * 1 <= n_groups <= OKX_ENS_SOBOL_MAX_GROUPS and every group holds a latent.  A family has M = n_groups + 2 members and
+ * geometry g is member b = g % M of family i = g / M (interleaved: a family's rows are contiguous, a chunk of whole families
+ * is self-contained): member 0 is A, member 1 is B, member 2 + j is A with the latents of group j taken from B.
+ * Latent z of geometry g is the draw of SOURCE ROW src = 2 i + s, always at attempt 0 - the Philox counter
+ * (src lo, src hi, z, 0 | OKX_SAMPLE_PURPOSE_DRAW << 8) - with s = 1 when b == 1, or when b >= 2 and d_group[z] == b - 2,
+ * else 0.  Under OKX_SAMPLE_LHS the stratum is pi_z(src) over 2 n_families strata: A and B together are one Latin hypercube
+ * of the source ensemble.  Kinds, mixing / scale, delta, the row and the guards are those of okx_ensemble_sample; there is
+ * one attempt (a redraw of one member would break the coordinates it shares with the others), so d_flags[g] is 1 when a
+ * guard fails and 0 otherwise - bits 4-7 are always 0.  Members 0 and 1 of family i are rows 2 i and 2 i + 1 of
+ * okx_ensemble_sample with n_total = 2 n_families, bit for bit, and any range of geometries carries the bits of the whole.
+ * Launch-only, stream-ordered, no allocation, legal inside a stream capture; n_geometries = 0 is legal.
+ * okx_ensemble_sample_families_check validates HOST copies (what okx_ensemble_sample_check does, a group outside
+ * [-1, n_groups), a group without a latent, n_groups outside the cap, max_attempts other than 1, under LHS a range beyond
+ * the n_families families: OKX_ERR_INVALID with okx_last_error text).
+ */
+enum { OKX_ENS_SOBOL_MAX_GROUPS = 288 };
+
+int32_t okx_ensemble_sample_families(int64_t n_geometries, int64_t geometry_offset, int64_t n_families, uint64_t seed,
+                                     int32_t n_points, const double* d_nominal,
+                                     const int32_t* d_coords, int32_t n_coords,
+                                     const int32_t* d_kind, const double* d_bound,
+                                     int32_t n_latents,
+                                     const double* d_mixing, const double* d_scale,
+                                     const int32_t* d_group, int32_t n_groups,            /* [n_latents]                 */
+                                     const okx_sample_guard* guards, int32_t n_guards,    /* HOST [n_guards] or NULL     */
+                                     int32_t stratify,
+                                     double* d_hardpoints,
+                                     double* d_latents, double* d_delta, uint8_t* d_flags, /* or NULL                    */
+                                     void* stream);
+/* host only */
+int32_t okx_ensemble_sample_families_check(int64_t n_geometries, int64_t geometry_offset, int64_t n_families, int32_t n_points,
+                                           const int32_t* coords, int32_t n_coords,
+                                           const int32_t* kind, const double* bound, int32_t n_latents, int32_t has_mixing,
+                                           const int32_t* group, int32_t n_groups,
+                                           const okx_sample_guard* guards, int32_t n_guards,
+                                           int32_t stratify, int32_t max_attempts);
+
+/*
+ * Sobol' accumulators on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): the variance
+ * decomposition of an evaluated pick-freeze ensemble, per (step, column) entry of the table [n_families * M * steps][ld],
+ * M = n_groups + 2, laid out as okx_ensemble_sample_families draws it (geometry g = i M + b).  A member COUNTS at an entry by
+ * the rule of okx_ensemble_reduce (status & 7 == 1 and a finite value) and, with d_mask [n_families * M] uint8, when bit 0
+ * of its byte is clear (the sampler's d_flags).  A family counts at an entry when all M members do; otherwise it is dropped
+ * for that entry alone.  With dA, dB, dj = value - d_shift[step][column] of members 0, 1 and 2 + j,
+ * d_acc [steps][n_columns][OKX_SOBOL_FIELDS + 3 n_groups], every field a double, sums over the families that count:
+ *   OKX_SOBOL_COUNT, OKX_SOBOL_DROPPED        families that count / do not
+ *   OKX_SOBOL_SUM_A, OKX_SOBOL_SUM_B          sum dA, sum dB
+ *   OKX_SOBOL_SUMSQ_A, OKX_SOBOL_SUMSQ_B      sum dA dA, sum dB dB
+ *   OKX_SOBOL_FIELDS + 3 j + 0 / 1 / 2        P_j = sum dB (dj - dA), Q_j = sum (dA - dj)^2, R_j = sum (dB - dj)^2
+ * Every difference and product is rounded on its own (no fused multiply-add) and there is no floating-point atomic: partial
+ * sums go per slab of families into d_scratch (okx_ensemble_sobol_scratch_bytes), families ascending inside a slab, slabs
+ * merged ascending, the slab count from the sizes alone - bit-identical from run to run and from device to device.
+ * accumulate = 1 adds into what d_acc holds (all partials need ONE shift); chunkings agree to rounding, exactly when the
+ * sums are exact.  The host turns the fields into first-order (Saltelli 2010, Jansen) and total-order (Jansen) indices
+ * (ensemble_stats.SobolAccumulator.finalize).  Launch-only, stream-ordered, no allocation, legal inside a stream capture;
+ * n_families = 0 leaves zeros (or, accumulating, what was there).  Errors (okx_last_error text): a negative count,
+ * ld < n_columns or a null table, n_groups outside [1, OKX_ENS_SOBOL_MAX_GROUPS], too many entries for one call, short
+ * scratch.
+ */
+enum { OKX_SOBOL_COUNT = 0, OKX_SOBOL_DROPPED = 1, OKX_SOBOL_SUM_A = 2, OKX_SOBOL_SUM_B = 3, OKX_SOBOL_SUMSQ_A = 4,
+       OKX_SOBOL_SUMSQ_B = 5, OKX_SOBOL_FIELDS = 6 };
+
+int32_t okx_ensemble_sobol(int64_t n_families, int32_t n_groups, int64_t steps, int32_t n_columns,
+                           const double* d_values, int64_t ld,              /* [n_families * M * steps][ld]           */
+                           const uint8_t* d_status, int64_t status_stride,  /* or NULL                                */
+                           const uint8_t* d_mask,                           /* [n_families * M] or NULL               */
+                           const double* d_shift,                           /* [steps][n_columns]                     */
+                           int32_t accumulate,
+                           double* d_acc,                                   /* [steps][n_columns][6 + 3 n_groups]     */
+                           void* d_scratch, size_t scratch_bytes, void* stream);
+size_t okx_ensemble_sobol_scratch_bytes(int64_t n_families, int32_t n_groups, int64_t steps, int32_t n_columns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,10 @@ EXPORTS = (
     "okx_ensemble_front_check",
     "okx_ensemble_sample",
     "okx_ensemble_sample_check",
+    "okx_ensemble_sample_families",
+    "okx_ensemble_sample_families_check",
+    "okx_ensemble_sobol",
+    "okx_ensemble_sobol_scratch_bytes",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -285,6 +289,14 @@ def load() -> C.CDLL:
     lib.okx_ensemble_sample.restype = i32
     lib.okx_ensemble_sample_check.argtypes = [i64, i64, i64, i32, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32]
     lib.okx_ensemble_sample_check.restype = i32
+    lib.okx_ensemble_sample_families.argtypes = [i64, i64, i64, C.c_uint64, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.okx_ensemble_sample_families.restype = i32
+    lib.okx_ensemble_sample_families_check.argtypes = [i64, i64, i64, i32, vp, i32, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32]
+    lib.okx_ensemble_sample_families_check.restype = i32
+    lib.okx_ensemble_sobol.argtypes = [i64, i32, i64, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_sobol.restype = i32
+    lib.okx_ensemble_sobol_scratch_bytes.argtypes = [i64, i32, i64, i32]
+    lib.okx_ensemble_sobol_scratch_bytes.restype = C.c_size_t
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -17,6 +17,8 @@
 //    before the first attempt; a redraw only moves the draw inside its stratum.
 // A workgroup of one wavefront makes the barriers between the phases cheap.  Device tables are indexed defensively: a
 // coordinate index outside the row is skipped, never written.
+// okx_sample_draw_families (okx_ensemble_sample_families) is the same mapping for a pick-freeze ensemble: one attempt, and a
+// latent's counter names the source row of its family instead of the geometry (further down, with its own comment).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -326,6 +328,108 @@ inline int check_arguments(const char* who, long long n_geom, long long offset, 
   return OKX_OK;
 }
 
+// ---- the pick-freeze draw (okx_ensemble_sample_families): families of M = n_groups + 2 geometries, interleaved ----
+//
+// Geometry g is member b = g % M of family i = g / M.  Member 0 is A, member 1 is B, member 2 + j is A with the latents of
+// group j taken from B: latent z of g is the draw of SOURCE ROW src = 2 i + s at attempt 0, s = 1 for B and for a latent of
+// the member's own group, else 0 - one counter word differs from okx_sample_draw.  Under LHS the stratum is pi_z(src) over
+// the 2 n_families source rows.  One attempt: a redraw of one member would break the coordinates it shares with the others.
+struct FamilyArgs {
+  Args a;            // n_total = 2 n_families (the source rows), max_attempts unused
+  const int* group;  // [z]: the latent's group in [0, n_groups), -1: never swapped
+  u64 members;       // M
+};
+
+__global__ __launch_bounds__(kThreads) void okx_sample_draw_families(FamilyArgs fa) {
+  __shared__ double row[kMaxRow];
+  __shared__ double lat[kMaxZ];
+  __shared__ double dlt[kMaxF];
+  const Args& a = fa.a;
+  const int lane = threadIdx.x;
+  const u64 local = blockIdx.x;
+  const u64 g = a.offset + local;
+  const u64 family = g / fa.members;
+  const int member = (int)(g - family * fa.members);
+  for (int z = lane; z < a.z; z += kThreads) {
+    const int gr = fa.group[z];
+    const bool from_b = member == 1 || (member >= 2 && gr == member - 2);
+    const u64 src = 2ull * family + (from_b ? 1ull : 0ull);
+    u32 w[4];
+    philox4x32_10((u32)src, (u32)(src >> 32), (u32)z, (u32)OKX_SAMPLE_PURPOSE_DRAW << 8, a.key0, a.key1, w);
+    const u64 k = ((u64)w[0] << 20) | (u64)(w[1] >> 12);
+    double u = ((double)k + 0.5) * 0x1.0p-52;
+    if (a.lhs) {  // (src < n_total: the entry point checked the range, so the walk returns)
+      u32 keys[4];
+      philox4x32_10(0u, 0u, (u32)z, (u32)OKX_SAMPLE_PURPOSE_STRATA << 8, a.key0, a.key1, keys);
+      u = clamp(__ddiv_rn((double)stratum(src, a.n_total, a.half_bits, keys) + u, a.n_total_f), kUMin, kUMax);
+    }
+    const int kind = a.kind[z];
+    double x;
+    if (kind == OKX_SAMPLE_UNIFORM) {
+      x = 2.0 * u - 1.0;
+    } else if (kind == OKX_SAMPLE_TRUNCATED) {
+      const double bound = a.bound[3 * z], below = a.bound[3 * z + 1], width = a.bound[3 * z + 2];
+      x = clamp(ppnd16(clamp(below + u * width, kUMin, kUMax)), -bound, bound);
+    } else {
+      x = ppnd16(u);
+    }
+    lat[z] = x;
+  }
+  for (int i = lane; i < a.p3; i += kThreads) row[i] = a.nominal[i];
+  __syncthreads();
+  for (int f = lane; f < a.f; f += kThreads) {
+    double d;
+    if (a.mixing) {
+      const double* m = a.mixing + (size_t)f * a.z;
+      d = 0.0;
+      for (int z = 0; z < a.z; ++z) d = d + m[z] * lat[z];
+    } else {
+      d = a.scale[f] * lat[f];
+    }
+    dlt[f] = d;
+    const int c = a.coords[f];
+    if ((unsigned)c < (unsigned)a.p3) row[c] = a.nominal[c] + d;
+  }
+  __syncthreads();
+  const bool ok = guards_hold(a.guards, row);
+  double* out = a.hardpoints + local * (u64)a.p3;
+  for (int i = lane; i < a.p3; i += kThreads) out[i] = row[i];
+  if (a.latents)
+    for (int z = lane; z < a.z; z += kThreads) a.latents[local * (u64)a.z + z] = lat[z];
+  if (a.delta)
+    for (int f = lane; f < a.f; f += kThreads) a.delta[local * (u64)a.f + f] = dlt[f];
+  if (a.flags && lane == 0) a.flags[local] = (unsigned char)(ok ? 0 : 1);
+}
+
+// what okx_ensemble_sample_families_check reports: the plan's own checks, then the families'
+inline int check_families(const char* who, long long n_geom, long long offset, long long n_families, int n_points, const int32_t* coords, int n_coords,
+                          const int32_t* kind, const double* bound, int n_latents, int has_mixing, const int32_t* group, int n_groups,
+                          const okx_sample_guard* guards, int n_guards, int stratify, int max_attempts) {
+  if (n_geom < 0 || offset < 0 || n_families < 0) return fail(OKX_ERR_INVALID, "%s: negative n_geometries, geometry_offset or n_families", who);
+  if (n_groups < 1 || n_groups > OKX_ENS_SOBOL_MAX_GROUPS)
+    return fail(OKX_ERR_INVALID, "%s: %d groups, 1 to %d allowed", who, n_groups, (int)OKX_ENS_SOBOL_MAX_GROUPS);
+  if (max_attempts != 1)
+    return fail(OKX_ERR_INVALID, "%s: max_attempts is %d; a family is drawn once (a redraw of one member would break the frozen coordinates)", who,
+                max_attempts);
+  if (n_families > (1ll << 52)) return fail(OKX_ERR_INVALID, "%s: %lld families, at most 2^52", who, n_families);
+  if (int rc = check_arguments(who, 0, 0, 2 * n_families, n_points, coords, n_coords, kind, bound, n_latents, has_mixing, guards, n_guards, stratify, 1))
+    return rc;
+  if (group) {
+    bool seen[OKX_ENS_SOBOL_MAX_GROUPS] = {};
+    for (int z = 0; z < n_latents; ++z) {
+      if (group[z] < -1 || group[z] >= n_groups)
+        return fail(OKX_ERR_INVALID, "%s: group %d is %d, outside [-1, %d)", who, z, (int)group[z], n_groups);
+      if (group[z] >= 0) seen[group[z]] = true;
+    }
+    for (int j = 0; j < n_groups; ++j)
+      if (!seen[j]) return fail(OKX_ERR_INVALID, "%s: group %d has no latent", who, j);
+  }
+  const long long members = n_groups + 2;
+  if (stratify == OKX_SAMPLE_LHS && (offset + n_geom + members - 1) / members > n_families)
+    return fail(OKX_ERR_INVALID, "%s: geometries [%lld, %lld) lie outside the %lld families of %lld", who, offset, offset + n_geom, n_families, members);
+  return OKX_OK;
+}
+
 }  // namespace smp
 }  // namespace okx
 
@@ -366,6 +470,48 @@ int32_t okx_ensemble_sample(int64_t n_geometries, int64_t geometry_offset, int64
   a.guards.n = n_guards;
   for (int i = 0; i < n_guards; ++i) a.guards.g[i] = guards[i];
   hipLaunchKernelGGL(sm::okx_sample_draw, dim3((unsigned)n_geometries), dim3(sm::kThreads), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return OKX_OK;
+}
+
+int32_t okx_ensemble_sample_families_check(int64_t n_geometries, int64_t geometry_offset, int64_t n_families, int32_t n_points, const int32_t* coords,
+                                           int32_t n_coords, const int32_t* kind, const double* bound, int32_t n_latents, int32_t has_mixing,
+                                           const int32_t* group, int32_t n_groups, const okx_sample_guard* guards, int32_t n_guards, int32_t stratify,
+                                           int32_t max_attempts) {
+  return okx::smp::check_families("okx_ensemble_sample_families", n_geometries, geometry_offset, n_families, n_points, coords, n_coords, kind, bound,
+                                  n_latents, has_mixing, group, n_groups, guards, n_guards, stratify, max_attempts);
+}
+
+int32_t okx_ensemble_sample_families(int64_t n_geometries, int64_t geometry_offset, int64_t n_families, uint64_t seed, int32_t n_points,
+                                     const double* d_nominal, const int32_t* d_coords, int32_t n_coords, const int32_t* d_kind, const double* d_bound,
+                                     int32_t n_latents, const double* d_mixing, const double* d_scale, const int32_t* d_group, int32_t n_groups,
+                                     const okx_sample_guard* guards, int32_t n_guards, int32_t stratify, double* d_hardpoints, double* d_latents,
+                                     double* d_delta, uint8_t* d_flags, void* stream) {
+  namespace sm = okx::smp;
+  const char* who = "okx_ensemble_sample_families";
+  // (the device tables cannot be read here: okx_ensemble_sample_families_check takes their host copies; the kernel compares a
+  //  latent's group with the member's and never indexes by it)
+  if (int rc = sm::check_families(who, n_geometries, geometry_offset, n_families, n_points, nullptr, n_coords, nullptr, nullptr, n_latents,
+                                  d_mixing != nullptr, nullptr, n_groups, guards, n_guards, stratify, 1))
+    return rc;
+  if (n_geometries > 0x7FFFFFFFll) return fail(OKX_ERR_INVALID, "%s: %lld geometries, at most 2^31 - 1 in one call", who, (long long)n_geometries);
+  if (!d_nominal || !d_coords || !d_kind || !d_bound || !d_group) return fail(OKX_ERR_INVALID, "%s: null nominal, coords, kind, bound or group table", who);
+  if (!d_mixing && !d_scale) return fail(OKX_ERR_INVALID, "%s: neither mixing nor scale", who);
+  if (n_geometries == 0) return OKX_OK;
+  if (!d_hardpoints) return fail(OKX_ERR_INVALID, "%s: null hardpoint table", who);
+  sm::FamilyArgs fa{};
+  sm::Args& a = fa.a;
+  a.nominal = d_nominal; a.coords = d_coords; a.kind = d_kind; a.bound = d_bound; a.mixing = d_mixing; a.scale = d_scale;
+  a.hardpoints = d_hardpoints; a.latents = d_latents; a.delta = d_delta; a.flags = d_flags;
+  a.offset = (unsigned long long)geometry_offset; a.n_total = 2ull * (unsigned long long)n_families; a.n_total_f = (double)a.n_total;
+  a.key0 = (unsigned)(seed & 0xFFFFFFFFull); a.key1 = (unsigned)(seed >> 32);
+  a.p3 = 3 * n_points; a.f = n_coords; a.z = n_latents; a.lhs = stratify == OKX_SAMPLE_LHS ? 1 : 0; a.max_attempts = 1;
+  a.half_bits = sm::half_bits_for(a.n_total);
+  a.guards.n = n_guards;
+  for (int i = 0; i < n_guards; ++i) a.guards.g[i] = guards[i];
+  fa.group = d_group;
+  fa.members = (unsigned long long)n_groups + 2ull;
+  hipLaunchKernelGGL(sm::okx_sample_draw_families, dim3((unsigned)n_geometries), dim3(sm::kThreads), 0, (hipStream_t)stream, fa);
   HIP_TRY(hipGetLastError());
   return OKX_OK;
 }

@@ -241,18 +241,27 @@ def _world(group):
     return world, (dist.get_rank(group) if world > 1 else 0)
 
 
-def chunk_pieces(n_geom: int, world: int, chunks: int) -> list:
+def aligned_shard_range(n_items: int, rank: int, world_size: int, align: int = 1) -> tuple[int, int]:
+    """``shard_range`` in units of ``align`` items: both ends are multiples of ``align`` (the last end is ``n_items``)."""
+    if align <= 1:
+        return shard_range(n_items, rank, world_size)
+    lo, hi = shard_range(-(-n_items // align), rank, world_size)
+    return min(lo * align, n_items), min(hi * align, n_items)
+
+
+def chunk_pieces(n_geom: int, world: int, chunks: int, align: int = 1) -> list:
     """
     The piece table of a chunked ensemble exchange, the same on every rank: ``pieces[k][r] = (g_lo, g_hi)`` - the
     geometries rank ``r`` solves in chunk ``k`` (its ``shard_range`` block cut into ``chunks`` contiguous runs; runs may
-    be empty when a rank has fewer geometries than chunks).
+    be empty when a rank has fewer geometries than chunks).  ``align``: shards and runs are cut in units of ``align``
+    geometries - every boundary is a multiple of it (whole pick-freeze families); 1 is the plain table.
     """
     table = []
     for k in range(chunks):
         row = []
         for r in range(world):
-            lo, hi = shard_range(n_geom, r, world)
-            a, b = shard_range(hi - lo, k, chunks)
+            lo, hi = aligned_shard_range(n_geom, r, world, align)
+            a, b = aligned_shard_range(hi - lo, k, chunks, align)
             row.append((lo + a, lo + b))
         table.append(row)
     return table
@@ -262,24 +271,30 @@ class PlanTable:
     """
     A ``SamplePlan`` where ``ShardedEnsemble`` takes a hardpoint table ``[G, P, 3]``: a slice of geometries is DRAWN when it is
     asked for - by ``DeviceProgram.sample_ensemble`` into HBM, or by ``ensemble_sample.sample_host`` for a program without it (the
-    CPU tests' stand-in) - so a rank draws only the geometries it rebinds.
+    CPU tests' stand-in) - so a rank draws only the geometries it rebinds.  A ``FamilyPlan`` (the pick-freeze ensemble of
+    ``sobol=True``) is drawn through ``sample_families`` / ``families_host`` in the same way.
     """
 
     def __init__(self, device_program, plan):
+        from .ensemble_sample import FamilyPlan
+
         self.dp, self.plan = device_program, plan
+        self.families = isinstance(plan, FamilyPlan)
         self.shape = (int(plan.n_total), plan.n_points, 3)
-        self.on_device = hasattr(device_program, "sample_ensemble")
+        self.on_device = hasattr(device_program, "sample_families" if self.families else "sample_ensemble")
         self.device = device_program.device if self.on_device else torch.device("cpu")
 
-    def draw(self, lo: int, hi: int, latents: bool = False):
-        """``(hardpoints [n, P, 3], latents [n, Z] or None)`` of geometries ``[lo, hi)``, tensors on ``device``."""
+    def draw(self, lo: int, hi: int, latents: bool = False, flags: bool = False):
+        """``(hardpoints [n, P, 3], latents [n, Z] or None)`` of geometries ``[lo, hi)``, tensors on ``device``; with ``flags`` a third
+        item, the sampler's flag bytes ``[n]`` uint8."""
         if self.on_device:
-            run = self.dp.sample_ensemble(self.plan, lo, hi, latents=latents)
-            return run.hardpoints, run.latents
-        from .ensemble_sample import sample_host
+            run = (self.dp.sample_families if self.families else self.dp.sample_ensemble)(self.plan, lo, hi, latents=latents)
+            return (run.hardpoints, run.latents, run.flags) if flags else (run.hardpoints, run.latents)
+        from .ensemble_sample import families_host, sample_host
 
-        table, lat, _, _ = sample_host(self.plan, lo, hi)
-        return torch.as_tensor(table), torch.as_tensor(lat) if latents else None
+        table, lat, _, byte = (families_host if self.families else sample_host)(self.plan, lo, hi)
+        out = (torch.as_tensor(table), torch.as_tensor(lat) if latents else None)
+        return (*out, torch.as_tensor(byte)) if flags else out
 
     def __getitem__(self, rows):
         if not isinstance(rows, slice) or rows.step not in (None, 1):
@@ -396,15 +411,30 @@ class ShardedEnsemble:
     shard - and every rank runs the pass once more over the gathered rows.  All comparisons: the same bits on every rank and
     for every world size and chunking.  ``front()`` returns the ensemble's ``ensemble_stats.EnsembleFront``, ``front_local()`` this
     rank's run, ``front_exchange_bytes_per_rank`` what the rank sends.  At most 65536 geometries.
+
+    ``sobol=True`` (with ``reduce=True`` and an ``ensemble_sample.FamilyPlan`` where the hardpoints go) adds WHICH FACTOR GROUP
+    explains the variance (``okx_ensemble_sobol``): the ensemble is the plan's pick-freeze families, ``M = D + 2`` geometries
+    each, drawn by ``okx_ensemble_sample_families``; shards and chunks are cut in whole families (``chunk_pieces(..., align=M)``),
+    and right after a chunk's reduction its rows of ``metric_local`` are accumulated with the reduction's shift and the chunk's
+    sampler flags as the mask.  ``step()`` then ends with one all-gather of the accumulators, added on every rank in ascending
+    rank order - the same bits on every rank; world sizes and chunkings agree to rounding, exactly when the sums are exact.
+    ``sobol()`` returns the ``ensemble_stats.EnsembleSobol`` (first-order and total-order indices per group and entry),
+    ``sobol_accumulator`` the merged tables, ``sobol_exchange_bytes_per_rank`` what the rank sends.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
-                 covariance=None, curves=None, front=None, **solve_kw):
-        from .ensemble_sample import SamplePlan
+                 covariance=None, curves=None, front=None, sobol: bool = False, **solve_kw):
+        from .ensemble_sample import FamilyPlan, SamplePlan
 
-        self.plan = hardpoints if isinstance(hardpoints, SamplePlan) else None
+        self.plan = hardpoints if isinstance(hardpoints, (SamplePlan, FamilyPlan)) else None
+        if sobol and not isinstance(self.plan, FamilyPlan):
+            raise ValueError("sobol=True decomposes a pick-freeze ensemble: pass an ensemble_sample.FamilyPlan where the hardpoints go")
+        if sobol and not reduce:
+            raise ValueError("sobol=True accumulates the reduced ensemble: it needs reduce=True")
+        # sobol=True: shards and chunks are cut in whole families
+        self.align = self.plan.family_size if sobol else 1
         if self.plan is not None:
             hardpoints = PlanTable(device_program, self.plan)  # rows are drawn where they are asked for
         elif isinstance(factors, str) and factors == "sampled":
@@ -447,7 +477,9 @@ class ShardedEnsemble:
         program = device_program.program
         self.n_geom = int(hardpoints.shape[0])
         self.n_total = self.n_geom * self.steps
-        glo, ghi = shard_range(self.n_geom, self.rank, self.world)
+        if self.n_geom % self.align:
+            raise ValueError(f"sobol=True: {self.n_geom} geometries are no whole families of {self.align}")
+        glo, ghi = self.shard_of(self.rank)
         self.geometry_range = (glo, ghi)
         if chunks is None:
             # Up to 8 chunks, but never a chunk below ONE FULL ROUND of the solve kernel over the chip (one 64-problem
@@ -462,8 +494,8 @@ class ShardedEnsemble:
             most = 2 if metric_columns is not None else 8
             # (from the SMALLEST shard, a rank-independent number: the piece tables and the grouped send / receive calls
             #  must have the same chunk count on every rank, and uneven shards differ by one geometry)
-            least = min(hi - lo for lo, hi in (shard_range(self.n_geom, r, self.world) for r in range(self.world)))
-            chunks = max(1, min(most, (least * self.steps) // one_round, least)) if self.world > 1 else 1
+            least = min(hi - lo for lo, hi in (self.shard_of(r) for r in range(self.world)))
+            chunks = max(1, min(most, (least * self.steps) // one_round, least // self.align)) if self.world > 1 else 1
         self.chunks = max(1, int(chunks))
         # Kernel family and chain length are chosen ONCE, for the whole ensemble as one launch on one GPU (auto selection
         # goes by the problem count: a 16384-problem chunk of a million-problem ensemble would otherwise run the quad kernel
@@ -476,17 +508,19 @@ class ShardedEnsemble:
                                                            evaluated=metric_columns is not None, **solve_kw)
             solve_kw = {**solve_kw, "kernel": kernel, "chain_len": chain_len}
         self.solve_kw = solve_kw
-        self.pieces = chunk_pieces(self.n_geom, self.world, self.chunks)
+        self.pieces = chunk_pieces(self.n_geom, self.world, self.chunks, self.align)
         # per-geometry emission: the expand on the receiving side needs every geometry's fixed points (a small table,
         # replicated as SURVEY.md section 8e allows); without records only this rank's slice is rebound
         everyone = self.records and self.world > 1
         self.sampled_latents = None  # factors="sampled": this rank's rows of the plan's latents, where they were drawn
+        self.sampled_flags = None    # a plan: this rank's rows of the sampler's flag bytes
         if self.plan is not None:
             # ONE draw: the rows this rank rebinds and, when they are the factors, their latents beside them
             lo, hi = (0, self.n_geom) if everyone else (glo, ghi)
-            table, drawn = hardpoints.draw(lo, hi, latents=isinstance(factors, str) and factors == "sampled")
+            table, drawn, byte = hardpoints.draw(lo, hi, latents=isinstance(factors, str) and factors == "sampled", flags=True)
             if drawn is not None:
                 self.sampled_latents = drawn[glo - lo : ghi - lo]
+            self.sampled_flags = byte[glo - lo : ghi - lo]
         else:
             table = hardpoints if everyone else hardpoints[glo:ghi]
         gpos, gparam = device_program.rebind(table)
@@ -562,6 +596,8 @@ class ShardedEnsemble:
             first = self.stages["reduce"] = stages.Reduction(self, hardpoints, targets, relative_targets, factors, shift)
             self.local_accumulator, self.exchange_bytes_per_rank = first.local, first.bytes_per_rank
             self.factor_names, self.n_factors, self.my_factors = first.factor_names, first.n_factors, first.my_factors
+            if sobol:
+                self.stages["sobol"] = stages.Sobol(self)
             if quantiles is not None:
                 stage = self.stages["select"] = stages.Selection(self, quantiles, limits)
                 self.select_probs, self.select_limits = stage.probs, stage.limits
@@ -580,11 +616,25 @@ class ShardedEnsemble:
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
         self.front_exchange_bytes_per_rank = sent.get("front", 0)
+        self.sobol_exchange_bytes_per_rank = sent.get("sobol", 0)
 
     # ---- reduce=True: the stages of ensemble_stages.py; what they hold and answer, by the names it has always had ----
 
     accumulator = property(lambda self: self.stages["reduce"].merged, doc="The merged accumulator of the last ``step()`` (``reduce=True``).")
     covariance_accumulator = property(lambda self: self.stages["covariance"].merged, doc="The merged covariance tables of the last ``step()``; None before.")
+
+    def shard_of(self, rank: int) -> tuple:
+        """``[lo, hi)`` of the geometries rank ``rank`` owns: ``shard_range``, cut in whole families with ``sobol=True``."""
+        return aligned_shard_range(self.n_geom, rank, self.world, self.align)
+
+    sobol_accumulator = property(lambda self: self.stages["sobol"].merged, doc="The merged Sobol' accumulator of the last ``step()`` (``sobol=True``); None before.")
+
+    def sobol(self):
+        """``ensemble_stats.EnsembleSobol`` of the WHOLE ensemble after the last ``step()`` (``sobol=True``): first-order and total-order
+        indices of every factor group per (step, column) entry.  The same bits on every rank."""
+        if "sobol" not in self.stages:
+            raise ValueError("sobol() needs sobol=True")
+        return self.stages["sobol"].sobol()
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""
@@ -872,7 +922,7 @@ class ShardedEnsemble:
         if self.expand_stream is not None:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
         if self.reduce:
-            # every rank, with or without a geometry, in this order: the accumulators' all-gather, the select rounds' all-reduces,
+            # every rank, with or without a geometry, in this order: the accumulators' all-gather, the Sobol' accumulators' all-gather, the select rounds' all-reduces,
             # the screen's all-reduce and all-gather, the covariance's all-gather, the curve features' all-gather, the front
             # rows' all-gather
             for stage in self.stages.values():

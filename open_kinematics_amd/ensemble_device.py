@@ -3,7 +3,8 @@ The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce``
 ``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry),
 ``okx_ensemble_covariance``, ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry) and
 ``okx_ensemble_front`` (the nondominated front of the ensemble) - and the pass at the head of the chain, ``okx_ensemble_sample`` (the
-hardpoint table of a ``SamplePlan`` drawn in HBM, ``ensemble_sample.py``).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+hardpoint table of a ``SamplePlan`` drawn in HBM, ``ensemble_sample.py``) with its pick-freeze form ``okx_ensemble_sample_families`` (a ``FamilyPlan``'s
+families) and the pass that reads their evaluated table, ``okx_ensemble_sobol`` (first-order and total-order Sobol' indices per factor group).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
 is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
 """
 
@@ -656,4 +657,107 @@ class EnsembleReductions:
         self._ensemble_call("okx_ensemble_sample", n, lo, int(plan.n_total), C.c_uint64(plan.seed), p, _ptr(tables["nominal"]), _ptr(tables["coords"]), f,
                             _ptr(tables["kind"]), _ptr(tables["bound"]), z, _ptr(tables["mixing"]), _ptr(tables["scale"]), tables["guards"],
                             len(plan.guards), plan.stratify, plan.max_attempts, _ptr(out.hardpoints), _ptr(out.latents), _ptr(out.delta), _ptr(out.flags))
+        return out
+
+    # ---- okx_ensemble_sample_families: the pick-freeze ensemble of a FamilyPlan, drawn on device (ensemble_sample.FamilyPlan) ----
+
+    def _family_tables(self, fplan):
+        """The wrapped plan's tables (``_sample_tables``) and the group table on the device, validated
+        (``okx_ensemble_sample_families_check``) and uploaded ONCE per plan object; dropped with it."""
+        import weakref
+
+        if not hasattr(self, "_family_plans"):
+            self._family_plans = {}
+        held = self._family_plans.get(id(fplan))
+        if held is not None and held[0]() is fplan:
+            return held[1]
+        plan = fplan.plan
+        tables = dict(self._sample_tables(plan))
+        rc = self.lib.okx_ensemble_sample_families_check(0, 0, fplan.n_families, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
+                                                         plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
+                                                         0 if plan.mixing is None else 1, fplan.group.ctypes.data_as(C.c_void_p), fplan.n_groups,
+                                                         tables["guards"], len(plan.guards), plan.stratify, plan.max_attempts)
+        _lib.check(rc, "okx_ensemble_sample_families")
+        tables["group"] = torch.tensor(np.asarray(fplan.group), device=self.device)
+        plans, key = self._family_plans, id(fplan)
+        ref = weakref.ref(fplan, lambda r, plans=plans, key=key: plans.pop(key, None) if plans.get(key, (None,))[0] is r else None)
+        plans[key] = (ref, tables)
+        return tables
+
+    def sample_families(self, plan, lo: int = 0, hi: int | None = None, *, latents: bool = False, delta: bool = False, out=None) -> "EnsembleSample":
+        """
+        ``okx_ensemble_sample_families``: geometries ``[lo, hi)`` (``hi`` None: ``plan.n_total = n_families * M``) of the pick-freeze
+        ensemble of ``plan`` (``ensemble_sample.FamilyPlan``), drawn in HBM - the bits of ``ensemble_sample.families_host(plan, lo, hi)``,
+        whatever the range is cut into (family-aligned or not) and wherever it is drawn.  Returns an ``EnsembleSample`` of device
+        tensors; ``flags`` is 1 where a guard fails (the ``mask`` of ``sobol_ensemble``).  ``out``: the ``EnsembleSample`` of an earlier
+        call of the same shape - with it (and a plan seen before) the call allocates nothing and is legal inside a stream capture.
+        """
+        lo = int(lo)
+        hi = int(plan.n_total) if hi is None else int(hi)
+        n = hi - lo
+        if n < 0 or lo < 0:
+            raise ValueError(f"okx_ensemble_sample_families: bad range [{lo}, {hi})")
+        tables = self._family_tables(plan)
+        base = plan.plan
+        dev, p, f, z = self.device, base.n_points, base.n_coords, base.n_latents
+        if out is None:
+            out = EnsembleSample(torch.empty((n, p, 3), dtype=torch.float64, device=dev),
+                                 torch.empty((n, z), dtype=torch.float64, device=dev) if latents else None,
+                                 torch.empty((n, f), dtype=torch.float64, device=dev) if delta else None,
+                                 torch.empty(n, dtype=torch.uint8, device=dev), lo)
+        else:
+            for t, shape, dtype in ((out.hardpoints, (n, p, 3), torch.float64), (out.latents, (n, z), torch.float64), (out.delta, (n, f), torch.float64),
+                                    (out.flags, (n,), torch.uint8)):
+                if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous()):
+                    raise ValueError(f"out must hold contiguous device tables hardpoints [{n}, {p}, 3], latents [{n}, {z}], delta [{n}, {f}] and flags [{n}]")
+            if out.hardpoints is None:
+                raise ValueError("out holds no hardpoint table")
+            out.lo = lo
+        self._ensemble_call("okx_ensemble_sample_families", n, lo, int(plan.n_families), C.c_uint64(base.seed), p, _ptr(tables["nominal"]),
+                            _ptr(tables["coords"]), f, _ptr(tables["kind"]), _ptr(tables["bound"]), z, _ptr(tables["mixing"]), _ptr(tables["scale"]),
+                            _ptr(tables["group"]), int(plan.n_groups), tables["guards"], len(base.guards), base.stratify, _ptr(out.hardpoints),
+                            _ptr(out.latents), _ptr(out.delta), _ptr(out.flags))
+        return out
+
+    # ---- okx_ensemble_sobol: the variance decomposition of an evaluated pick-freeze ensemble (ensemble_stats.EnsembleSobol) ----
+
+    def sobol_ensemble(self, values, *, steps_per_geometry: int, n_groups: int, status=None, mask=None, shift=None, out=None, accumulate: bool = False,
+                       group_names=None):
+        """
+        ``okx_ensemble_sobol``: the Sobol' accumulator (``ensemble_stats.SobolAccumulator``, device tensors: ``acc [S, K, 6 + 3 D]``,
+        ``shift [S, K]``) of a column table in HBM whose geometries are the families of ``sample_families`` - ``M = n_groups + 2``
+        consecutive geometries each.  ``values`` and ``status`` as ``reduce_ensemble`` takes them (unit column stride; strided rows and
+        a strided status byte are passed on, nothing is copied); ``mask [G]`` contiguous uint8, bit 0 set: the member does not
+        count - the sampler's ``flags`` as they lie in HBM; a family counts at an entry when all its members do.  ``shift [S, K]``
+        the common shift (None: the table's own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift,
+        pass it or pass ``out=``).  ``out``: the accumulator of an earlier call - it carries its own shift - to write
+        (``accumulate=False``) or add into (``True``); with it and a table shape seen before, the call allocates nothing and is
+        legal inside a stream capture.  ``.finalize()`` copies to the host: first-order and total-order indices per group.
+        Bit-identical from run to run; different chunkings agree to rounding, exactly when the sums are exact.
+        """
+        from .ensemble_stats import SOBOL_FIELDS, SOBOL_MAX_GROUPS, SobolAccumulator
+
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        d = int(n_groups)
+        if not 1 <= d <= SOBOL_MAX_GROUPS:
+            raise ValueError(f"okx_ensemble_sobol: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
+        if g % (d + 2):
+            raise ValueError(f"okx_ensemble_sobol: {g} geometries are no whole families of {d + 2}")
+        dev = self.device
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+            out = SobolAccumulator(torch.empty((s, k, SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=dev), self._ensemble_shift(shift, values, g, s, k),
+                                   group_names)
+        elif shift is not None:
+            raise ValueError("out= carries its own shift")
+        if tuple(out.acc.shape) != (s, k, SOBOL_FIELDS + 3 * d) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != torch.float64 for t in (out.acc, out.shift)):
+            raise ValueError(f"out must hold contiguous device tables acc [S, K, {SOBOL_FIELDS + 3 * d}] and shift [S, K] = [{s}, {k}]")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev or not mask.is_contiguous()):
+            raise ValueError("mask must be a contiguous uint8 [G] device tensor")
+        n = g // (d + 2)
+        scratch = self._ensemble_scratch("sobol", int(self.lib.okx_ensemble_sobol_scratch_bytes(n, d, s, k)))
+        self._ensemble_call("okx_ensemble_sobol", n, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift),
+                            1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())
         return out

@@ -481,7 +481,130 @@ def hardpoint_plan(program, points, *, sigma=None, half_width=None, kind: int | 
                       stratify, n_total, seed, tuple(guards), max_attempts)
 
 
-__all__ = ["SamplePlan", "sample_host", "hardpoint_plan", "philox4x32_10", "draw_bits", "unit_from_bits", "stratum", "strata_bits", "strata_keys",
+# ---- pick-freeze families (okx_ensemble_sample_families): the structured ensemble of a variance decomposition ----
+
+SOBOL_MAX_GROUPS = 288  # OKX_ENS_SOBOL_MAX_GROUPS
+
+
+@dataclass(frozen=True)
+class FamilyPlan:
+    """
+    A pick-freeze (Saltelli) ensemble over a ``SamplePlan``: ``group [Z]`` int32 puts every latent into a factor group in
+    ``[0, D)`` or ``-1`` (never swapped), ``n_families`` families of ``M = D + 2`` geometries each.  Geometry ``g`` is member
+    ``b = g % M`` of family ``i = g // M``: member 0 is A, member 1 is B, member ``2 + j`` is A with group j's latents taken from
+    B.  Latent z of g is the wrapped plan's draw of SOURCE ROW ``2 i + s`` at attempt 0 (``s = 1`` for B and for a latent of the
+    member's own group); under ``LHS`` over ``2 n_families`` strata, whatever the wrapped plan's ``n_total`` says.  The wrapped plan
+    has ``max_attempts == 1``: a redraw of one member would break the coordinates it shares with the others.
+    ``n_total = n_families * M`` is the ensemble every consumer sees.  ``group_names``: the names of the groups (optional).
+    """
+
+    plan: SamplePlan
+    group: np.ndarray
+    n_families: int
+    group_names: tuple | None = field(default=None, compare=False)
+
+    def __post_init__(self):
+        group = np.ascontiguousarray(np.asarray(self.group, dtype=np.int32).reshape(-1))
+        group.setflags(write=False)
+        object.__setattr__(self, "group", group)
+        object.__setattr__(self, "n_families", int(self.n_families))
+        if self.group_names is not None:
+            object.__setattr__(self, "group_names", tuple(self.group_names))
+        check_families(self)
+
+    n_groups = property(lambda self: int(self.group.max()) + 1 if self.group.size else 0)
+    family_size = property(lambda self: self.n_groups + 2)
+    n_total = property(lambda self: self.n_families * self.family_size)
+    n_points = property(lambda self: self.plan.n_points)
+    n_coords = property(lambda self: self.plan.n_coords)
+    n_latents = property(lambda self: self.plan.n_latents)
+
+    def source_plan(self) -> SamplePlan:
+        """The plain ensemble the families are cut from: the wrapped plan with ``n_total = 2 n_families``; members 0 and 1 of family
+        i are its rows ``2 i`` and ``2 i + 1``."""
+        import dataclasses
+
+        return dataclasses.replace(self.plan, n_total=2 * self.n_families)
+
+    def factor_names(self) -> list:
+        return self.plan.factor_names()
+
+    def names(self) -> list:
+        """The names of the groups: ``group_names``, else ``"group<j>"``."""
+        return list(self.group_names) if self.group_names is not None else [f"group{j}" for j in range(self.n_groups)]
+
+
+def check_families(fplan: FamilyPlan, lo: int = 0, hi: int = 0) -> None:
+    """``okx_ensemble_sample_families_check`` on the host: ValueError in its words."""
+    who = "okx_ensemble_sample_families"
+    plan, group, n, off, n_fam = fplan.plan, fplan.group, int(hi) - int(lo), int(lo), fplan.n_families
+    if not isinstance(plan, SamplePlan):
+        raise ValueError(f"{who}: a FamilyPlan wraps a SamplePlan")
+    if n < 0 or off < 0 or n_fam < 0:
+        raise ValueError(f"{who}: negative n_geometries, geometry_offset or n_families")
+    d = fplan.n_groups
+    if not 1 <= d <= SOBOL_MAX_GROUPS:
+        raise ValueError(f"{who}: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
+    if plan.max_attempts != 1:
+        raise ValueError(f"{who}: max_attempts is {plan.max_attempts}; a family is drawn once (a redraw of one member would break the frozen coordinates)")
+    if group.size != plan.n_latents:
+        raise ValueError(f"{who}: {group.size} groups for {plan.n_latents} latents")
+    if plan.stratify == LHS and 2 * n_fam > 1 << 32:
+        raise ValueError(f"{who}: {2 * n_fam} strata, at most 2^32 under LHS")
+    for z, gr in enumerate(group.tolist()):
+        if not -1 <= gr < d:
+            raise ValueError(f"{who}: group {z} is {gr}, outside [-1, {d})")
+    for j in range(d):
+        if not np.any(group == j):
+            raise ValueError(f"{who}: group {j} has no latent")
+    if fplan.group_names is not None and len(fplan.group_names) != d:
+        raise ValueError(f"{who}: {len(fplan.group_names)} group names for {d} groups")
+    m = d + 2
+    if plan.stratify == LHS and -(-(off + n) // m) > n_fam:
+        raise ValueError(f"{who}: geometries [{off}, {off + n}) lie outside the {n_fam} families of {m}")
+
+
+def families_host(fplan: FamilyPlan, lo: int = 0, hi: int | None = None):
+    """
+    Geometries ``[lo, hi)`` of the pick-freeze ensemble (``hi`` None: ``n_total``): ``(hardpoints [n, P, 3], latents [n, Z], delta [n, F],
+    flags [n] uint8)``.  The definition ``okx_ensemble_sample_families`` equals bit for bit; ``flags`` is 1 where a guard fails.
+    """
+    lo = int(lo)
+    hi = fplan.n_total if hi is None else int(hi)
+    check_families(fplan, lo, hi)
+    plan, m, n_src = fplan.plan, fplan.family_size, 2 * fplan.n_families
+    n, p = hi - lo, plan.n_points
+    g = np.arange(n, dtype=np.uint64) + np.uint64(lo)
+    family, member = g // np.uint64(m), (g % np.uint64(m)).astype(np.int64)
+    from_b = (member[:, None] == 1) | ((member[:, None] >= 2) & (fplan.group[None].astype(np.int64) == member[:, None] - 2))
+    src = (np.uint64(2) * family)[:, None] + from_b.astype(np.uint64)                                 # [n, Z]
+    z = np.arange(plan.n_latents, dtype=np.uint64)[None]
+    u = unit_from_bits(draw_bits(plan.seed, src, z, 0))
+    if plan.stratify == LHS and n:
+        u = stratified_unit(stratum(plan.seed, n_src, src, z), u, n_src)
+    lat = latents_from_units(plan, u)
+    dlt = contract(plan, lat)
+    base = plan.nominal.reshape(-1)
+    rows = np.repeat(base[None], n, axis=0)
+    rows[:, plan.coords] = base[plan.coords][None] + dlt
+    points = rows.reshape(-1, p, 3)
+    flags = np.where(guards_hold(plan, points) if n else np.ones(0, dtype=bool), 0, 1).astype(np.uint8)
+    return points, lat, dlt, flags
+
+
+def group_by_point(plan: SamplePlan) -> tuple:
+    """``(group [Z], names)`` of a plan without ``mixing``: one group per perturbed POINT, in the order the points first appear."""
+    if plan.mixing is not None:
+        raise ValueError("group_by_point needs a plan without mixing: a latent then moves one coordinate of one point")
+    points = [int(c) // 3 for c in plan.coords]
+    order = list(dict.fromkeys(points))
+    names = plan.factor_names()
+    first = {pt: names[points.index(pt)].rsplit(".", 1)[0] for pt in order}
+    return np.asarray([order.index(pt) for pt in points], dtype=np.int32), tuple(first[pt] for pt in order)
+
+
+__all__ = ["SamplePlan", "sample_host", "hardpoint_plan", "FamilyPlan", "families_host", "check_families", "group_by_point",
+           "SOBOL_MAX_GROUPS", "philox4x32_10", "draw_bits", "unit_from_bits", "stratum", "strata_bits", "strata_keys",
            "ppnd16", "log_unit", "units", "stratified_unit", "latents_from_units", "contract", "guards_hold", "check_arguments", "check_plan",
            "NORMAL", "UNIFORM", "TRUNCATED", "IID", "LHS", "GUARD_SIGN", "GUARD_DISTINCT", "GUARD_OFF_LINE", "PURPOSE_DRAW", "PURPOSE_STRATA",
            "MAX_COORDS", "MAX_LATENTS", "MAX_GUARDS", "MAX_ATTEMPTS", "U_MIN", "U_MAX"]

@@ -1,6 +1,6 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
-(moments, extremes, sensitivities), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
+(moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
 (``covariance=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import ensemble_stats as es
-from .dist import all_gather_flat, all_reduce_sum, broadcast_from_rank_zero, shard_range
+from .dist import all_gather_flat, all_reduce_sum, broadcast_from_rank_zero
 
 
 class _Stage:
@@ -189,6 +189,46 @@ class Reduction(_AccumulatorStage):
         self.merged = self.merged_over_ranks(mine, (mine.acc, mine.factor_acc) if self.n_factors else (mine.acc,), unpack)
 
 
+class Sobol(_AccumulatorStage):
+    """``sobol=True`` (the ensemble is a ``FamilyPlan``'s): the Sobol' accumulators, chunk by chunk right after the reduction, with the
+    reduction's shift and the chunk's sampler flags as the mask; chunks and shards are whole families (``ShardedEnsemble.align``)."""
+
+    def __init__(self, owner):
+        super().__init__(owner)
+        o = owner
+        k, d = len(o.metric_index), o.plan.n_groups
+        self.n_groups, self.group_names = d, o.plan.names()
+        shift = o.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's (itself, no copy)
+        self.flags = o.sampled_flags.contiguous()
+        self.local = es.SobolAccumulator(torch.zeros((o.steps, k, es.SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=o.device), shift, self.group_names)
+        self.merged = self.result = None
+        self.allocate_exchange(self.local.acc.numel())
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        mask = self.flags[a - glo : b - glo]
+        if self.on_device:
+            o.dp.sobol_ensemble(values, steps_per_geometry=o.steps, n_groups=self.n_groups, status=status, mask=mask, out=mine, accumulate=self.taken)
+            return
+        part = es.sobol_host(*self.host_tables(a, b, values, status), mask.cpu().numpy(), self.n_groups, mine.shift.cpu().numpy())
+        if not self.taken:
+            mine.acc.zero_()
+        mine.acc += torch.from_numpy(part.acc)
+
+    def exchange(self) -> None:
+        mine = self.local
+        self.result = None
+        self.merged = self.merged_over_ranks(mine, (mine.acc,), lambda row: es.SobolAccumulator(row.reshape(mine.acc.shape), mine.shift, self.group_names))
+
+    def sobol(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result
+
+
 class Selection(_Stage):
     """``quantiles=...``: the select rounds over the rank's whole shard at the end of a step, the histograms summed over the ranks."""
 
@@ -250,7 +290,7 @@ class Screening(_Stage):
         glo, ghi = o.geometry_range
         k = len(o.metric_index)
         self.limits, self.scale = es.check_screen_arguments(limits, scale, o.steps, k)
-        self.largest_shard = max(hi - lo for lo, hi in (shard_range(o.n_geom, r, o.world) for r in range(o.world)))
+        self.largest_shard = max(hi - lo for lo, hi in (o.shard_of(r) for r in range(o.world)))
         self.run = self.part = self.result = self.counts = self.flags = None
         if self.on_device:
             self.run = o.dp.screen_prepare(o.steps, k, self.limits, self.scale, ghi - glo)
@@ -279,7 +319,7 @@ class Screening(_Stage):
             padded[: flags.shape[0]] = flags
             all_reduce_sum(counts, o.group)
             table = all_gather_flat(padded, o.group)
-            spans = [shard_range(o.n_geom, r, o.world) for r in range(o.world)]
+            spans = [o.shard_of(r) for r in range(o.world)]
             flags = torch.cat([table[r, : hi - lo] for r, (lo, hi) in enumerate(spans)])
         self.counts, self.flags = counts, flags
 
@@ -394,7 +434,7 @@ class Curves(_Stage):
         self.factors = torch.as_tensor(reduction.all_factors, device=device).contiguous() if p else None  # [G, P]: every rank reduces every row
         self.acc = es.EnsembleAccumulator(torch.empty((1, n, es.ENS_FIELDS + p), dtype=torch.float64, device=device), shift.reshape(1, n).contiguous(),
                                           torch.empty(es.factor_moment_count(p), dtype=torch.float64, device=device) if p else None, self.factor_names)
-        self.spans = [shard_range(o.n_geom, r, o.world) for r in range(o.world)]
+        self.spans = [o.shard_of(r) for r in range(o.world)]
         self.largest_shard = max(hi - lo for lo, hi in self.spans)
         self.send = torch.empty((self.largest_shard, n), dtype=torch.float64, device=device) if o.world > 1 else None
         self.recv = torch.empty((o.world, self.largest_shard * n), dtype=torch.float64, device=device) if o.world > 1 else None
@@ -464,7 +504,7 @@ class Front(_Stage):
         m = self.m = int(self.sense.size)
         # the gathered rows as a table of their own: one step, M columns, the senses and targets as given
         self.row_objectives = [(0, i, int(self.sense[i])) + ((float(self.target[i]),) if self.sense[i] == es.FRONT_TARGET else ()) for i in range(m)]
-        self.largest_shard = max(hi - lo for lo, hi in (shard_range(o.n_geom, r, o.world) for r in range(o.world)))
+        self.largest_shard = max(hi - lo for lo, hi in (o.shard_of(r) for r in range(o.world)))
         self.local = self.merged = self.result = None
         self.bytes_per_rank = 8 * (self.largest_shard + 1) * (m + 2) if o.world > 1 else 0
 

@@ -17,6 +17,8 @@ and how the entries move TOGETHER over the geometries: covariance and correlatio
 ALONG the sweep inside one geometry: the curve characteristics of every (geometry, column) - fitted value, gradient and
 curvature at an origin, departure from the fitted shape, extremes and where they occur (``curves_host`` / ``EnsembleCurves``,
 ``okx_ensemble_curves``); their table ``[G, K * 12]`` is again a column table for every pass above.
+WHICH FACTOR GROUP explains the variance: the Sobol' accumulators of a pick-freeze ensemble (``ensemble_sample.FamilyPlan``) and
+their first-order and total-order indices (``sobol_host`` / ``SobolAccumulator`` / ``EnsembleSobol``, ``okx_ensemble_sobol``).
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -1013,6 +1015,151 @@ def front_host(values, status=None, objectives=None, mask=None, index=None, geom
     return EnsembleFront(dominated, tally, ids[keep], raw[keep], sense, target)
 
 
+# ---- Sobol' indices of a pick-freeze ensemble: which factor group explains the variance (okx_ensemble_sobol) ----
+
+SOBOL_COUNT, SOBOL_DROPPED, SOBOL_SUM_A, SOBOL_SUM_B, SOBOL_SUMSQ_A, SOBOL_SUMSQ_B = range(6)
+SOBOL_FIELDS = 6  # OKX_SOBOL_FIELDS; then per group j: P_j, Q_j, R_j at SOBOL_FIELDS + 3 j + 0 / 1 / 2
+SOBOL_MAX_GROUPS = 288  # OKX_ENS_SOBOL_MAX_GROUPS
+
+
+@dataclass
+class EnsembleSobol:
+    """
+    What ``SobolAccumulator.finalize`` returns (NumPy, host): per (step, column) entry ``count`` the families whose every member
+    counts and ``dropped`` the others ``[S, K]``, ``mean`` and ``variance`` ``[S, K]`` of the response over A and B together, and per
+    factor group ``[S, K, D]``: ``first`` the first-order index (Saltelli 2010: ``(P_j / n) / V``), ``first_jansen`` the same by
+    Jansen's form (``1 - (R_j / 2n) / V``) and ``total`` the total-order index (Jansen: ``(Q_j / 2n) / V``).  NaN where no family
+    counts or the variance is not positive.
+    """
+
+    count: np.ndarray
+    dropped: np.ndarray
+    mean: np.ndarray
+    variance: np.ndarray
+    first: np.ndarray
+    first_jansen: np.ndarray
+    total: np.ndarray
+    group_names: list | None = None
+
+
+class SobolAccumulator:
+    """
+    The raw tables of ``okx_ensemble_sobol``: ``acc [S, K, SOBOL_FIELDS + 3 D]`` float64 and ``shift [S, K]`` - NumPy arrays or torch
+    tensors (host or device), whatever produced them.
+    """
+
+    def __init__(self, acc, shift, group_names=None):
+        self.acc, self.shift = acc, shift
+        self.group_names = list(group_names) if group_names is not None else None
+        if acc.ndim != 3 or acc.shape[2] < SOBOL_FIELDS + 3 or (acc.shape[2] - SOBOL_FIELDS) % 3 or tuple(shift.shape) != tuple(acc.shape[:2]):
+            raise ValueError("acc must be [S, K, SOBOL_FIELDS + 3 D] and shift [S, K]")
+
+    @property
+    def n_groups(self) -> int:
+        return (int(self.acc.shape[2]) - SOBOL_FIELDS) // 3
+
+    @classmethod
+    def empty(cls, steps: int, n_columns: int, n_groups: int, shift, group_names=None) -> "SobolAccumulator":
+        """The accumulator of no family at all (the neutral element of ``merge``), NumPy."""
+        return cls(np.zeros((steps, n_columns, SOBOL_FIELDS + 3 * n_groups)), np.asarray(shift, dtype=np.float64).reshape(steps, n_columns), group_names)
+
+    def numpy(self) -> "SobolAccumulator":
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(self.acc):
+            return self
+        return SobolAccumulator(self.acc.detach().cpu().numpy(), self.shift.detach().cpu().numpy(), self.group_names)
+
+    def merge(self, other: "SobolAccumulator") -> "SobolAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been taken
+        with the same shift.  Works on NumPy arrays and on torch tensors alike."""
+        if tuple(self.acc.shape) != tuple(other.acc.shape):
+            raise ValueError("accumulators of different shapes")
+        xp = __import__("torch") if _is_tensor(self.acc) else np
+        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
+        if not bool(same):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        return SobolAccumulator(self.acc + other.acc, self.shift, self.group_names)
+
+    def finalize(self) -> EnsembleSobol:
+        """Mean, variance and the indices on the host in fp64."""
+        h = self.numpy()
+        acc, shift = np.asarray(h.acc, dtype=np.float64), np.asarray(h.shift, dtype=np.float64)
+        n = acc[..., SOBOL_COUNT]
+        groups = acc[..., SOBOL_FIELDS:].reshape(acc.shape[0], acc.shape[1], self.n_groups, 3)
+        p, q, r = groups[..., 0], groups[..., 1], groups[..., 2]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_d = (acc[..., SOBOL_SUM_A] + acc[..., SOBOL_SUM_B]) / (2.0 * n)
+            v = (acc[..., SOBOL_SUMSQ_A] + acc[..., SOBOL_SUMSQ_B]) / (2.0 * n) - mean_d * mean_d
+            defined = (n > 0) & (v > 0.0)
+            nn, vv = n[..., None], v[..., None]
+            first = np.where(defined[..., None], (p / nn) / vv, np.nan)
+            first_jansen = np.where(defined[..., None], 1.0 - (r / (2.0 * nn)) / vv, np.nan)
+            total = np.where(defined[..., None], (q / (2.0 * nn)) / vv, np.nan)
+            mean = np.where(n > 0, mean_d + shift, np.nan)
+        return EnsembleSobol(n.astype(np.int64), acc[..., SOBOL_DROPPED].astype(np.int64), mean, np.where(defined, v, np.nan), first, first_jansen,
+                             total, self.group_names)
+
+
+def sobol_terms(values, status=None, mask=None, n_groups: int = 1, shift=None):
+    """
+    The terms ``okx_ensemble_sobol`` sums, per family: ``(counts [N, S, K] bool, terms [N, S, K, SOBOL_FIELDS + 3 D], shift [S, K])`` of
+    ``values [N * M, S, K]`` (``M = D + 2``, family i's members contiguous), ``status [N * M, S]`` uint8 or None and ``mask [N * M]``
+    uint8 or None (bit 0 set: the member does not count).  Every difference and product is rounded on its own; the terms of a
+    family that does not count are 0 (its DROPPED term 1).
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    d = int(n_groups)
+    if not 1 <= d <= SOBOL_MAX_GROUPS:
+        raise ValueError(f"okx_ensemble_sobol: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
+    m = d + 2
+    if g % m:
+        raise ValueError(f"okx_ensemble_sobol: {g} geometries are no whole families of {m}")
+    n = g // m
+    if shift is None:
+        shift = clean_shift(v[0]) if g else np.zeros((s, k))
+    shift = np.asarray(shift, dtype=np.float64).reshape(s, k)
+    if not np.all(np.isfinite(shift)):
+        raise ValueError("the shift must be finite (clean_shift replaces undefined entries)")
+    if mask is not None:
+        ok = ok & ((np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0)[:, None, None]
+    counts = ok.reshape(n, m, s, k).all(axis=1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dv = np.where(counts[:, None], v.reshape(n, m, s, k) - shift[None, None], 0.0)
+        da, db, dj = dv[:, 0], dv[:, 1], np.moveaxis(dv[:, 2:], 1, -1)  # [N, S, K], [N, S, K], [N, S, K, D]
+        terms = np.zeros((n, s, k, SOBOL_FIELDS + 3 * d))
+        terms[..., SOBOL_COUNT], terms[..., SOBOL_DROPPED] = counts, ~counts
+        terms[..., SOBOL_SUM_A], terms[..., SOBOL_SUM_B] = da, db
+        terms[..., SOBOL_SUMSQ_A], terms[..., SOBOL_SUMSQ_B] = da * da, db * db
+        ua, ub = da[..., None] - dj, db[..., None] - dj
+        terms[..., SOBOL_FIELDS + 0 :: 3] = db[..., None] * (dj - da[..., None])
+        terms[..., SOBOL_FIELDS + 1 :: 3] = ua * ua
+        terms[..., SOBOL_FIELDS + 2 :: 3] = ub * ub
+    return counts, terms, shift
+
+
+def sobol_host(values, status=None, mask=None, n_groups: int = 1, shift=None, group_names=None) -> SobolAccumulator:
+    """
+    The accumulator of ``okx_ensemble_sobol`` in NumPy (arguments as ``sobol_terms`` takes them; ``shift`` None: the values of
+    geometry 0, undefined entries 0).  The sums run over the families in ascending order, one after the other.
+    """
+    v = np.asarray(values, dtype=np.float64)
+    m = int(n_groups) + 2
+    _, terms, shift = sobol_terms(v[:0], None if status is None else np.asarray(status)[:0], None, n_groups,
+                                  (clean_shift(v[0]) if v.shape[0] else None) if shift is None else shift)
+    if v.ndim == 3 and v.shape[0] % m:
+        sobol_terms(v, status, mask, n_groups, shift)  # (raises: no whole families)
+    acc = np.zeros(terms.shape[1:])
+    block = 64 * m  # (the terms of 64 families at a time: a C5 table's would not fit the host otherwise)
+    for lo in range(0, v.shape[0], block):
+        rows = slice(lo, lo + block)
+        _, terms, _ = sobol_terms(v[rows], None if status is None else np.asarray(status)[rows], None if mask is None else np.asarray(mask).reshape(-1)[rows],
+                                  n_groups, shift)
+        for i in range(terms.shape[0]):  # ascending family order, as the device walks a slab
+            acc += terms[i]
+    return SobolAccumulator(acc, shift, group_names)
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
@@ -1022,4 +1169,5 @@ __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_fac
            "covariance_host", "check_covariance_arguments", "COV_MAX_ENTRIES", "EnsembleCurves", "curves_host", "check_curve_arguments",
            "curve_normal_refused", "CURVE_FIELDS", "CURVE_MAX_DEGREE", "CURVE_PIVOT", "EnsembleFront", "front_host", "front_dominated",
            "front_objectives", "check_front_arguments", "FRONT_MIN", "FRONT_MAX", "FRONT_TARGET", "FRONT_MAX_OBJECTIVES", "FRONT_MAX_GEOMETRIES",
-           "FRONT_SEEN", "FRONT_CANDIDATES", "FRONT_MEMBERS"]
+           "FRONT_SEEN", "FRONT_CANDIDATES", "FRONT_MEMBERS", "EnsembleSobol", "SobolAccumulator", "sobol_host", "sobol_terms", "SOBOL_COUNT",
+           "SOBOL_DROPPED", "SOBOL_SUM_A", "SOBOL_SUM_B", "SOBOL_SUMSQ_A", "SOBOL_SUMSQ_B", "SOBOL_FIELDS", "SOBOL_MAX_GROUPS"]

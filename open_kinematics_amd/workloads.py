@@ -127,3 +127,25 @@ def ensemble_plan(n_geometries: int = 4096, sigma: float = 1.0, seed: int = 0, *
                           guards=guards, max_attempts=max_attempts)
     relative = np.stack([np.zeros(n_steps), np.linspace(-60.0, 80.0, n_steps)], axis=1)
     return program, plan, relative
+
+
+def ensemble_family_plan(n_families: int = 4096, sigma: float = 1.0, seed: int = 0, *, n_steps: int = 256, n_points: int | None = None,
+                         by_point: bool = True, stratify: int = 0, line_mode: str = "pinned"):
+    """
+    C5 as a pick-freeze ensemble (``ensemble_sample.FamilyPlan``): the plan of ``ensemble_plan`` with one attempt, over the first
+    ``n_points`` authored points (None: all ten), its latents grouped by point (``by_point``: D = points, 10 for C5) or one
+    group per coordinate (D = 3 points, 30 for C5).  Returns the base program, the family plan and the relative targets.
+    """
+    from .ensemble_sample import FamilyPlan, group_by_point
+
+    program, whole, relative = ensemble_plan(2 * n_families, sigma, seed, n_steps=n_steps, line_mode=line_mode, stratify=stratify, max_attempts=1)
+    plan = whole
+    if n_points is not None:
+        from .ensemble_sample import hardpoint_plan
+
+        points = sorted({int(c) // 3 for c in whole.coords})[:n_points]
+        plan = hardpoint_plan(program, points, sigma=sigma, stratify=stratify, n_total=2 * n_families, seed=seed, guards=whole.guards, max_attempts=1)
+    group, names = group_by_point(plan)
+    if not by_point:
+        group, names = np.arange(plan.n_latents, dtype=np.int32), tuple(plan.factor_names())
+    return program, FamilyPlan(plan, group, n_families, names), relative
