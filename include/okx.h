@@ -193,7 +193,20 @@ typedef struct okx_solve_opts {
 
 enum { OKX_OUTPUT_RECORDS = 0, OKX_OUTPUT_FREE = 1, OKX_OUTPUT_NONE = 2 };
 
-/* Per-problem result, the device analogue of SolverInfo (solver.py:83-96). */
+/* Per-problem result, the device analogue of SolverInfo (solver.py:83-96).
+ * max_residual and cost describe the ACCEPTED point that was written out, never a rejected trial point.  One documented
+ * exception: a nested start of the lane kernel without confirm_full_pass may take the step after a lane's first as it
+ * is - a Gauss-Newton step of at most 1e-5 mm whose PREDICTED successor is below a thousandth of step_tol - without
+ * evaluating the point it lands on; the two fields are then those of the point that step started from (at most
+ * max_i |J_i|_1 * last_step from the rows of the returned state; ~1e-8 mm in practice), last_step is that step.
+ * Non-finite input (a NaN or infinite target, a NaN or infinite entry of the geometry's tables): the problem is never
+ * accepted - bit0 stays clear.  bit2 is set as soon as a non-finite cost is met at a point the problem stands on: at its
+ * first evaluation, in the shared first step's table entry when that step is NaN, or at the re-evaluation of the accepted
+ * point after a non-finite trial point was rejected (an infinite target under the shared first step takes that way: a
+ * launch with max_iter = 1 ends before it, with neither bit0 nor bit2); likewise when a computed correction is NaN.
+ * cost is then that non-finite value and the positions are the state the problem stood on.  max_residual is formed
+ * with NaN-dropping maxima: in such a record it may be finite and small, and says nothing.  Other problems of the
+ * launch are not affected, and a chain restarts from the design state at the next problem. */
 typedef struct okx_info {
   double max_residual;    /* max |r_i| at the returned state, reference row definitions    */
   double cost;            /* 0.5 * sum r_i^2 at the returned state                         */

@@ -1068,6 +1068,13 @@ __global__ void __launch_bounds__(GroupWidth<NREG>::value, NREG <= 24 ? OKX_WAVE
         double rho = 1.0;
         if (first) {
           accept = true;
+          if (!(Ft < 1e300)) {
+            // a non-finite cost at the start point (a NaN / infinite target or geometry entry): nothing to iterate on
+            F = Ft;
+            cur ^= 1;  // (the record's max_residual is taken from the rows just evaluated)
+            flags |= OKX_INFO_FAILED;
+            break;
+          }
         } else {
           const double pred = 0.5 * grp_sum<W>(S.red, lane < n ? dx * (lambda * dx - g) : 0.0);
           const bool finite = Ft == Ft && step_len == step_len && Ft < 1e300;
@@ -1153,7 +1160,12 @@ __global__ void __launch_bounds__(GroupWidth<NREG>::value, NREG <= 24 ? OKX_WAVE
         piv_lo = pmin - lambda;  // what the damping did not put there
         piv_hi = pmax;
         OKX_STAMP(7)
-        step_len = grp_max<W>(S.red, lane < n ? fabs(dx) : 0.0);
+        // (fmax drops a NaN: a non-finite correction must not read as a step of length 0)
+        step_len = grp_max<W>(S.red, lane < n ? (dx == dx ? fabs(dx) : 1e301) : 0.0);
+        if (!(step_len < 1e300)) {
+          flags |= OKX_INFO_FAILED;
+          break;
+        }
         if (step_len <= args.step_tol) {
           // the Newton-type correction is already below tolerance: x is the answer and the
           // residuals in hand belong to it (no confirming evaluation of x + dx)

@@ -107,6 +107,14 @@ class LGen : public GenBase {
   // which kernel family wrote it: lane solve, quad solve and okx_expand_positions_batch of the same free coordinates give
   // the same bits (what dist.ShardedEnsemble relies on: one rank writes records, N ranks gather coordinates and expand)
   bool quad_order = false;
+  // A derived point is base + unit vector x length, and rows are evaluated ON it: fast_sqrt_rsqrt's reciprocal root is good
+  // to ~4e-15, which on a 240 mm arm moves the point - and a distance row through it - by ~1e-12 mm, past the 2.5e-13 the
+  // rows are held to (tests/test_gpu_info_record.py: the MacPherson strut's bottom end).  One Newton step against the root
+  // (exact to the last bit or so) brings it to rounding, in the passes the rows and the info record come from; the final
+  // state's derived points keep the quad kernels' bits.
+  void refine_inverse(const std::string& inv, const std::string& root) {
+    if (!quad_order) f("    %s = fma(%s, fma(-%s, %s, 1.0), %s);", inv.c_str(), inv.c_str(), inv.c_str(), root.c_str(), inv.c_str());
+  }
   std::string norm2(const S3& v) {
     if (!quad_order) return dot(v, v);
     std::string e;
@@ -289,6 +297,7 @@ class LGen : public GenBase {
       const std::string s2 = norm2(v);
       const std::string nrm = tmp("nr"), inrm = tmp("in");
       f("    double %s, %s; fast_sqrt_rsqrt(%s, &%s, &%s);", nrm.c_str(), inrm.c_str(), s2.c_str(), nrm.c_str(), inrm.c_str());
+      refine_inverse(inrm, nrm);
       const S3 u = scale(inrm, v);
       const S3 base = pt(pts[0]);
       for (int k = 0; k < 3; ++k) f("    %s = fma(%s, %s, %s);", o.c[k].c_str(), u.c[k].c_str(), dp(e).c_str(), base.c[k].c_str());
@@ -334,6 +343,7 @@ class LGen : public GenBase {
       const std::string vv = norm2(v);
       const std::string vn = tmp("vn"), ivn = tmp("iv");
       f("    double %s, %s; fast_sqrt_rsqrt(%s, &%s, &%s);", vn.c_str(), ivn.c_str(), vv.c_str(), vn.c_str(), ivn.c_str());
+      refine_inverse(ivn, vn);
       const S3 ax = scale(ivn, v);
       const std::string az = ax.c[2];
       S3 wd;  // -ga a - e_z with ga = -a_z
@@ -343,6 +353,7 @@ class LGen : public GenBase {
       const std::string ww = norm2(wd);
       const std::string wn = tmp("wn"), iwn = tmp("iw");
       f("    double %s, %s; fast_sqrt_rsqrt(%s, &%s, &%s);", wn.c_str(), iwn.c_str(), ww.c_str(), wn.c_str(), iwn.c_str());
+      refine_inverse(iwn, wn);
       const S3 wc = pt(pts[0]);
       const std::string rk = emit("rk", iwn + " * " + dp(e));
       if (quad_order && !with_blocks) {  // (wd / |wd|) * R + wc, the unit vector rounded first (okx_quadgen.cpp)
@@ -1965,7 +1976,9 @@ class LaneModule {
     g.f("          Fc = 0.5 * hss; mres = hmr; dmax = hs0; lambda = a.lambda0 * dmax;");
     g.f("          step_len = hstep; pred = 0.5 * fma(lambda, hN, hM); iters = 1; mode = 1;");
     g.f("          piv_lo = hs1 - lambda; piv_hi = hs5;");
-    g.f("          if (hstep <= a.step_tol) { flags |= INFO_CONVERGED; last_step = hstep; done = true; }");
+    // (a NaN target leaves every entry of the step NaN, which the NaN-dropping maximum reads as a step of length 0:
+    //  the sum of squares tells the two apart, inside the branch that a sweep takes once)
+    g.f("          if (hstep <= a.step_tol) { if (hN == hN) { flags |= INFO_CONVERGED; last_step = hstep; } else flags |= INFO_FAILED; done = true; }");
     g.f("          else {");
     g.f("            want_light = hstep <= 1e-3 && (100.0 * lambda * fast_rcp(hs1) + hstep) * hstep <= a.step_tol;");
     g.f("            prev_sl = hstep;");
@@ -2048,6 +2061,11 @@ class LaneModule {
     g.f("    }");
     g.f("    if (!done) {");
     g.f("      ++nfev;");
+    // a non-finite cost at a point the problem STANDS ON - its first evaluation (mode 0) or the re-evaluation of the accepted
+    // point after a rejected trial (mode 2: where an infinite target under the shared first step ends up) - leaves nothing to
+    // iterate on (a NaN / infinite target or geometry entry): the NaN-dropping maxima of the step length and the row maximum
+    // would otherwise read it as a converged solve
+    g.f("      if (mode != 1 && !(Ft < 1e300)) { Fc = Ft; mres = mres_new; flags |= INFO_FAILED; done = true; accept = false; }");
     g.f("      if (stop) flags |= INFO_CONVERGED;");
     // a solve that ends on the cost test without meeting its rows sits at a compromise point (okx_quadgen.cpp): advisory bit
     g.f("      if (compromise && mres_new > 0.01 * a.residual_tolerance) flags |= INFO_ILL_CONDITIONED;");
@@ -2091,7 +2109,7 @@ class LaneModule {
     g.f("    const double rq = dd > 0.0 ? (2.0 * pr - lambda * dd) * fast_rcp(dd) - lambda : 1e300;");
     g.f("    if (solve_now) {");
     g.f("      ++iters;");
-    g.f("      if (ok) {");
+    g.f("      if (ok && dd == dd) {  // (a NaN anywhere in the matrix reaches the step, hence dd)");
     g.f("        piv_lo = fmin(pmin - lambda, rq); piv_hi = pmax;");
     for (int i = 0; i < n; ++i) g.f("        dx%d = nx%d;", i, i);
     g.f("        step_len = sl; pred = pr;");

@@ -294,6 +294,13 @@ __global__ void __launch_bounds__(kWave, 2) okx_solve_packed_kernel(const DevPro
         double rho = 1.0;
         if (first) {
           accept = true;
+          if (!done && !(Ft < 1e300)) {
+            // a non-finite cost at the start point (a NaN / infinite target or geometry entry): nothing to iterate on
+            F = Ft;
+            cur ^= 1;  // (the record's max_residual is taken from the rows just evaluated)
+            flags |= OKX_INFO_FAILED;
+            done = true;
+          }
         } else {
           const bool finite = Ft == Ft && step_len == step_len && Ft < 1e300;
           const bool small = finite && step_len <= 1e-8 && Ft <= F * (1.0 + 1e-6) + 1e-28;
@@ -385,7 +392,13 @@ __global__ void __launch_bounds__(kWave, 2) okx_solve_packed_kernel(const DevPro
         }
         OKX_STAMP(6)
         dx = done ? 0.0 : dx_new;
-        step_len = group_max(is_var ? fabs(dx) : 0.0, L.scratch, lane, gbase, W);
+        // (fmax drops a NaN: a non-finite correction must not read as a step of length 0)
+        step_len = group_max(is_var ? (dx == dx ? fabs(dx) : 1e301) : 0.0, L.scratch, lane, gbase, W);
+        if (!done && !(step_len < 1e300)) {
+          flags |= OKX_INFO_FAILED;
+          done = true;
+          dx = 0.0;
+        }
         if (!done && step_len <= args.step_tol) {  // correction below tolerance: x is the answer
           flags |= OKX_INFO_CONVERGED;
           last_step = step_len;

@@ -2833,7 +2833,9 @@ class QuadModule {
     g.f("          Fc = 0.5 * hc_ss; mres = hc_mr; dmax = hc_dmax; lambda = a.lambda0 * dmax;");
     g.f("          step_len = hstep; pred = 0.5 * fma(lambda, hc_N, hc_M); iters = 1; mode = 1;");
     g.f("          piv_lo = hc_pmin - lambda; piv_hi = hc_pmax;");
-    g.f("          if (hstep <= a.step_tol) { flags |= INFO_CONVERGED; last_step = hstep; done = true; }");
+    // (a NaN target leaves every entry of the step NaN, which the NaN-dropping maximum reads as a step of length 0:
+    //  the sum of squares tells the two apart, inside the branch that a sweep takes once)
+    g.f("          if (hstep <= a.step_tol) { if (hc_N == hc_N) { flags |= INFO_CONVERGED; last_step = hstep; } else flags |= INFO_FAILED; done = true; }");
     g.f("          else {");
     g.f("            want_light = hstep <= 1e-3 && (100.0 * lambda * fast_rcp(hc_pmin) + hstep) * hstep <= a.step_tol;");
     g.f("            prev_sl = hstep;");
@@ -2865,7 +2867,9 @@ class QuadModule {
     g.f("          Fc = 0.5 * hsc[48 + hq_]; mres = hsc[64 + hq_]; dmax = hsc[80 + hq_]; lambda = a.lambda0 * dmax;");
     g.f("          step_len = hstep; pred = 0.5 * fma(lambda, hsc[32 + hq_], hsc[16 + hq_]); iters = 1; mode = 1;");
     g.f("          piv_lo = hsc[96 + hq_] - lambda; piv_hi = hsc[112 + hq_];");
-    g.f("          if (hstep <= a.step_tol) { flags |= INFO_CONVERGED; last_step = hstep; done = true; }");
+    // (a NaN target leaves every entry of the step NaN, which the NaN-dropping maximum reads as a step of length 0:
+    //  the sum of squares tells the two apart, inside the branch that a sweep takes once)
+    g.f("          if (hstep <= a.step_tol) { if (hsc[32 + hq_] == hsc[32 + hq_]) { flags |= INFO_CONVERGED; last_step = hstep; } else flags |= INFO_FAILED; done = true; }");
     g.f("          else {");
     g.f("            want_light = hstep <= 1e-3 && (100.0 * lambda * fast_rcp(hsc[96 + hq_]) + hstep) * hstep <= a.step_tol;");
     g.f("            prev_sl = hstep;");
@@ -3023,6 +3027,11 @@ class QuadModule {
     g.f("    }");
     g.f("    if (!done) {");
     g.f("      ++nfev;");
+    // a non-finite cost at a point the problem STANDS ON - its first evaluation (mode 0) or the re-evaluation of the accepted
+    // point after a rejected trial (mode 2: where an infinite target under the shared first step ends up) - leaves nothing to
+    // iterate on (a NaN / infinite target or geometry entry): the NaN-dropping maxima of the step length and the row maximum
+    // would otherwise read it as a converged solve
+    g.f("      if (mode != 1 && !(Ft < 1e300)) { Fc = Ft; mres = mres_new; flags |= INFO_FAILED; done = true; accept = false; }");
     g.f("      if (stop) flags |= INFO_CONVERGED;");
     // A solve that ends on the cost test (no further reduction, actual or predicted) WITHOUT meeting its rows to a hundredth
     // of the acceptance tolerance sits at a compromise point: a local minimum with a residual, i.e. beyond kinematic
@@ -3091,7 +3100,7 @@ class QuadModule {
     g.f("    const double rq = dd > 0.0 ? (2.0 * pr - lambda * dd) * fast_rcp(dd) - lambda : 1e300;");
     g.f("    if (solve_now) {");
     g.f("      ++iters;");
-    g.f("      if (ok) {");
+    g.f("      if (ok && dd == dd) {  // (a NaN anywhere in the matrix reaches the step, hence dd)");
     if (pv) {
       g.f("        piv_lo = fmin(fmin(pmin - lambda, pcoup), rq); piv_hi = pmax;  // what the damping did not put there (halves' pivots, tied mode, Rayleigh bound)");
     }
