@@ -16,7 +16,8 @@ namespace okx {
 // source are part of its text and therefore of the kernel cache key.
 //   generators   quad_mark, quad_timeline, quad_no_light, quad_no_head, quad_no_fast, quad_two_waves, pair_no_head, pair_first_order_head,
 //                pair_lds_homes, pair_cold_lds, quad_serial_chains, lane_mark, lane_timeline, lane_lds_tables, lane_nested, lane_refine,
-//                lane_g_scalar, quad_atan_branches, quad_column_pivots, quad_fmax_calls (these three: tests/test_quad_lean_passes.py)
+//                lane_g_scalar, quad_atan_branches, quad_column_pivots, quad_fmax_calls (these three: tests/test_quad_lean_passes.py),
+//                quad_full_diag_update, quad_full_diag_rows (tests/test_quad_owner_lane.py)
 //   library     no_quad, no_lane, no_cold, tangent_generic, evaluate_quad, evaluate_lane, keep_source, cov_valu
 bool dev_switch(const char* name);
 

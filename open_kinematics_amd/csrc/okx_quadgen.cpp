@@ -824,6 +824,13 @@ class Gen : public GenBase {
   // its broadcasts alive until then - in AGPRs, at a v_accvgpr move per use (measured: DW corner -4 %, MacPherson -7 %,
   // axle -6 % per sweep; tools/quad_sections.py shows where a pass's instructions are).
   bool pin_ata = false, pin_atr = false;
+  // Entry 2 of a diagonal block - A(F, F, 2), of J^T J and of the trailing matrix - is read on lane 2 alone: the blocks are
+  // symmetric and only their lower triangle is used (the pivot QB2, the lane's pivot range, diag, the scaled gradient
+  // norm).  An update of that entry whose other factor is a broadcast FROM lane 2 therefore takes the lane's own value:
+  // lane 2 computes what it computed, the other lanes' entries are dead.  full_diag_rows (emit_rows) and
+  // full_diag_update (emit_factor, the joining rows' rank-one terms) keep every lane's entry valid, as before:
+  // OKX_DEV=quad_full_diag_rows / quad_full_diag_update, and the rows of okx_quad_eval, which stores whole blocks.
+  bool full_diag_rows = dev_switch("quad_full_diag_rows"), full_diag_update = dev_switch("quad_full_diag_update");
   // OKX_QUAD_MARK=1: `s_nop 11..17` between the sections of a pass (tools/quad_sections.py counts the instructions
   // in between; scheduling barriers keep the sections apart, so the marked kernel is for counting, not for timing)
   bool marks = false;
@@ -926,7 +933,8 @@ class Gen : public GenBase {
           const LV& jG = jv[ib].second;
           nz[F][G] = true;
           for (int k = 0; k < 3; ++k) {
-            std::string b = bcast(jG.n, k);
+            // (a row with one free block writes entry 2 of a diagonal block only: lane 2's own operand, no broadcast)
+            std::string b = jv.size() == 1 && k == 2 && !full_diag_rows ? jG.n : bcast(jG.n, k);
             const int sg = jF.sg * jG.sg;
             std::string an = A(F, G, k);
             if (!declared.count(an)) {
@@ -991,6 +999,14 @@ class Gen : public GenBase {
         for (int H = G; H < nf; ++H) {
           if (H > G && !fill[H][G]) continue;
           for (int j = (H == G ? k + 1 : 0); j < 3; ++j) {
+            int consumers = 0, only = -1;
+            for (int F = H; F < nf; ++F)
+              if (!(F > G && !fill[F][G]) && !(F == G && k == 2)) ++consumers, only = F;
+            if (consumers == 0 && !full_diag_update) continue;
+            // (column 2 into the diagonal block alone: lane 2 holds the operand already - see full_diag_update)
+            if (consumers == 1 && only == H && j == 2 && !full_diag_update)
+              f("    { const double cu = %s;", A(H, G, k).c_str());
+            else
             f("    { const double cu = QB%d(%s);", j, A(H, G, k).c_str());
             for (int F = H; F < nf; ++F) {
               if (F > G && !fill[F][G]) continue;
@@ -1344,6 +1360,7 @@ class QuadModule {
 
   // ---- set by the preparation steps, in this order, before the first emitter runs; constant afterwards ----
   std::string eval_src, solve_src, light_src;  // make_passes: rows + normal equations, the damped step, residuals only
+  std::string eval_src_blocks;                 // eval_src with every lane's entry of the diagonal blocks valid (okx_quad_eval)
   std::string solve_src_range;                 // the damped step of the cold body's fast loop (single mode; empty: solve_src)
   bool light_ok = false;
   std::string atan_decl;
@@ -1360,26 +1377,43 @@ class QuadModule {
 
   // ---- evaluation body (rows + normal equations), generated first to learn the sparsity ----
   bool make_passes() {
-    ev.lds_constants = pv != nullptr;
-    ev.scalars_in_regs = ev.lanes_in_regs = pv != nullptr && !lds_homes;
-    ev.pin_ata = ev.pin_atr = true;
-    ev.marks = dev_switch("quad_mark");
-    ev.tl_marks = dev_switch("quad_timeline");
-    for (int e = 0; e < P.n_derived; ++e) ev.dp(e);  // every derived-op parameter is chain-constant
-    ev.f("    // ---- active derived points with chain-rule blocks ----");
-    for (int idx = 0; idx < P.n_active; ++idx)
-      if (!ev.derived_op(P.active_op[idx], true)) {
-        why = ev.why;
+    auto evaluation = [&](Gen& gen) {
+      gen.lds_constants = pv != nullptr;
+      gen.scalars_in_regs = gen.lanes_in_regs = pv != nullptr && !lds_homes;
+      gen.pin_ata = gen.pin_atr = true;
+      gen.marks = dev_switch("quad_mark");
+      gen.tl_marks = dev_switch("quad_timeline");
+      for (int e = 0; e < P.n_derived; ++e) gen.dp(e);  // every derived-op parameter is chain-constant
+      gen.f("    // ---- active derived points with chain-rule blocks ----");
+      for (int idx = 0; idx < P.n_active; ++idx)
+        if (!gen.derived_op(P.active_op[idx], true)) {
+          why = gen.why;
+          return false;
+        }
+      gen.mark(8);  // (derived points done)
+      if (!gen.emit_rows()) {
+        why = gen.why;
         return false;
       }
-    ev.mark(8);  // (derived points done)
-    if (!ev.emit_rows()) {
-      why = ev.why;
-      return false;
-    }
-    ev.mark(9);  // (rows done)
+      gen.mark(9);  // (rows done)
+      return true;
+    };
+    if (!evaluation(ev)) return false;
     eval_src = ev.out;
     ev.out.clear();
+    // okx_quad_eval stores whole diagonal blocks of J^T J: its rows keep every lane's entry valid (Gen::full_diag_rows),
+    // emitted by a generator of their own - same loads, same tables, nothing of it enters another kernel
+    eval_src_blocks = eval_src;
+    if (!pv && !EV && !ev.full_diag_rows) {
+      Gen full(P, pv);
+      full.full_diag_rows = true;
+      if (!evaluation(full)) return false;
+      if (full.hoisted != ev.hoisted) {
+        why = "okx_quad_eval: the evaluation with whole diagonal blocks asks for other loads";
+        return false;
+      }
+      eval_src_blocks = full.out;
+    }
     solve_src = capture(ev, [&] { ev.emit_solve(); });
     // the cold body's fast loop asks for the pivots' range only (`factored` there is pmin > 0): Gen::lane_pivot_range.
     // quad_column_pivots: the general loop's text there too, as before.  (Pair mode reads `ok` in both loops.)
@@ -1517,6 +1551,9 @@ class QuadModule {
     std::string out;
     for (int j = 0; j < NK; ++j)
       for (int k = 0; k < 3; ++k)
+        if (k == 2 && !ev.full_diag_update)  // (entry 2 of a diagonal block is lane 2's alone: Gen::full_diag_update)
+          out += sfmt("    %s = fma(cu%d, cu%d, %s);\n", Gen::A(FUj[j], FUj[j], k).c_str(), j, j, Gen::A(FUj[j], FUj[j], k).c_str());
+        else
         out += sfmt("    %s = fma(cu%d, QB%d(cu%d), %s);\n", Gen::A(FUj[j], FUj[j], k).c_str(), j, k, j, Gen::A(FUj[j], FUj[j], k).c_str());
     return out;
   }
@@ -1595,6 +1632,9 @@ class QuadModule {
   // one joining row: each half takes its own part of the row's rank-one term (see solve_step_one_join)
   void single_join_rank_one(Gen& sink) const {
     for (int k = 0; k < 3; ++k)
+      if (k == 2 && !ev.full_diag_update)  // (entry 2 of a diagonal block is lane 2's alone: Gen::full_diag_update)
+        sink.f("    %s = fma(cu, cu, %s);", Gen::A(FU, FU, k).c_str(), Gen::A(FU, FU, k).c_str());
+      else
       sink.f("    %s = fma(cu, QB%d(cu), %s);", Gen::A(FU, FU, k).c_str(), k, Gen::A(FU, FU, k).c_str());
   }
   void halves_must_factor(Gen& sink) const {
@@ -3587,7 +3627,7 @@ class QuadModule {
       if (used[p]) g.f("    double p%d = c < 3 ? gp[%d + cc] : 0.0;", p, 3 * p);
     for (int F = 0; F < nf; ++F) g.f("    p%d = c < 3 ? a.x[bb * %d + %d + cc] : 0.0;", ev.fp(F), 3 * nf, 3 * ev.perm[F]);
     for (int t = 0; t < T; ++t) g.f("    const double tv%d = a.targets[bb * %d + %d];", t, T, t);
-    g.out += eval_src;
+    g.out += eval_src_blocks;  // (whole diagonal blocks: `ata` below stores every lane's entries)
     g.f("    if (valid && c == 0) {");
     for (int i = 0; i < P.m; ++i) g.f("      a.r[bb * %d + %d] = r%d;", P.m, i, i);
     g.f("    }");
