@@ -1102,7 +1102,7 @@ int32_t okx_ensemble_front_check(int64_t n_geometries, int64_t steps, int32_t n_
 enum { OKX_SAMPLE_NORMAL = 0, OKX_SAMPLE_UNIFORM = 1, OKX_SAMPLE_TRUNCATED = 2,
        OKX_SAMPLE_IID = 0, OKX_SAMPLE_LHS = 1,
        OKX_SAMPLE_GUARD_SIGN = 0, OKX_SAMPLE_GUARD_DISTINCT = 1, OKX_SAMPLE_GUARD_OFF_LINE = 2,
-       OKX_SAMPLE_PURPOSE_DRAW = 0, OKX_SAMPLE_PURPOSE_STRATA = 1,
+       OKX_SAMPLE_PURPOSE_DRAW = 0, OKX_SAMPLE_PURPOSE_STRATA = 1, OKX_SAMPLE_PURPOSE_BOOTSTRAP = 2,
        OKX_ENS_SAMPLE_MAX_COORDS = 288, OKX_ENS_SAMPLE_MAX_LATENTS = 288,
        OKX_ENS_SAMPLE_MAX_GUARDS = 16, OKX_ENS_SAMPLE_MAX_ATTEMPTS = 16 };
 
@@ -1206,6 +1206,60 @@ int32_t okx_ensemble_sobol(int64_t n_families, int32_t n_groups, int64_t steps, 
                            double* d_acc,                                   /* [steps][n_columns][6 + 3 n_groups]     */
                            void* d_scratch, size_t scratch_bytes, void* stream);
 size_t okx_ensemble_sobol_scratch_bytes(int64_t n_families, int32_t n_groups, int64_t steps, int32_t n_columns);
+
+/*
+ * Poisson bootstrap weights on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): what a
+ * bootstrap of an ensemble statistic resamples with.  Replicate r gives GLOBAL row i (for the Sobol' pass a row is a
+ * family) an independent Poisson(1) weight that is a pure function of (seed, i, r), so every chunk, device and rank forms
+ * the same replicates and their accumulators merge by addition.  The sampler's generator with its purpose word changed:
+ *   u = word r % 4 of Philox4x32-10, key = (seed & 0xffffffff, seed >> 32),
+ *       counter = (i & 0xffffffff, i >> 32, r / 4, OKX_SAMPLE_PURPOSE_BOOTSTRAP << 8)
+ *   w = the number of k in 0 .. 12 with u >= T[k],   T[k] = floor(2^32 sum over j <= k of e^-1 / j!):
+ *       0x5e2d58d8 0xbc5ab1b1 0xeb715e1d 0xfb239797 0xff1025f5 0xffd90f3b 0xfffa8b71
+ *       0xffff540c 0xffffed1f 0xfffffe21 0xffffffd4 0xfffffffc 0xffffffff
+ * Integers only: the pass equals ensemble_stats.bootstrap_weights (NumPy) byte for byte, and w <= 13.
+ *   d_weights [n_rows][n_replicates] uint8, row i = row_offset + its index
+ * 1 <= n_replicates <= OKX_ENS_BOOTSTRAP_MAX_REPLICATES (1024).  Launch-only, stream-ordered, no allocation, legal inside
+ * a stream capture; n_rows = 0 is legal.  Errors (okx_last_error text): a negative count or offset, n_replicates outside
+ * the cap, a null table, too many rows for one call.
+ */
+enum { OKX_ENS_BOOTSTRAP_MAX_REPLICATES = 1024, OKX_ENS_BOOTSTRAP_MAX_WEIGHT = 13 };
+
+int32_t okx_ensemble_bootstrap_weights(int64_t n_rows, int64_t row_offset, uint64_t seed, int32_t n_replicates,
+                                       uint8_t* d_weights,                    /* [n_rows][n_replicates]                */
+                                       void* stream);
+
+/*
+ * Bootstrap replicates of the Sobol' accumulators on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols
+ * up): how far to trust the indices of okx_ensemble_sobol.  Table, counting rule, d_mask and d_shift are exactly those of
+ * okx_ensemble_sobol; replicate r holds its fields with every family's term multiplied by the family's weight
+ * w = weight of GLOBAL family family_offset + i in replicate r (okx_ensemble_bootstrap_weights with the same seed):
+ *   d_acc [n_replicates][steps][n_columns][OKX_SOBOL_FIELDS + 3 n_groups]
+ *   COUNT_r = sum w over the families that count, DROPPED_r = sum w over those that do not, SUM_A_r = sum w dA, ...,
+ *   P_j,r = sum w (dB (dj - dA)), Q_j,r = sum w (dA - dj)^2, R_j,r = sum w (dB - dj)^2
+ * FAMILIES are resampled as independent units.  Under OKX_SAMPLE_LHS they are not quite independent (the strata spread
+ * them more evenly than independent draws would), so the intervals the host forms from the replicates
+ * (ensemble_stats.SobolBootstrapAccumulator.finalize) are on the conservative side.
+ * ROUNDING.  A term is formed as okx_ensemble_sobol forms it (every difference and product rounded on its own), then
+ * multiplied by (double)w, rounded, then added, rounded; a family whose weight is 0 in a replicate is skipped there.
+ * Families ascend inside a slab, slab partials (d_scratch, okx_ensemble_sobol_bootstrap_scratch_bytes) merge in ascending
+ * order after what d_acc holds when accumulate = 1, the slab plan comes from the sizes alone and there is no
+ * floating-point atomic: bit-identical from run to run and from device to device; chunkings (with the right family_offset)
+ * agree to rounding, exactly when the sums are exact.  d_scratch also takes the weights of the call and one counting byte
+ * per (family, entry).  Launch-only, stream-ordered, no allocation, legal inside a stream capture; n_families = 0 leaves
+ * zeros (or, accumulating, what was there).  Errors (okx_last_error text): what okx_ensemble_sobol reports, a negative
+ * family_offset, n_replicates outside [1, OKX_ENS_BOOTSTRAP_MAX_REPLICATES], too many entries for one call, short scratch.
+ */
+int32_t okx_ensemble_sobol_bootstrap(int64_t n_families, int64_t family_offset, int32_t n_groups, int64_t steps, int32_t n_columns,
+                                     const double* d_values, int64_t ld,              /* [n_families * M * steps][ld]  */
+                                     const uint8_t* d_status, int64_t status_stride,  /* or NULL                       */
+                                     const uint8_t* d_mask,                           /* [n_families * M] or NULL      */
+                                     const double* d_shift,                           /* [steps][n_columns]            */
+                                     uint64_t seed, int32_t n_replicates, int32_t accumulate,
+                                     double* d_acc,            /* [n_replicates][steps][n_columns][6 + 3 n_groups]     */
+                                     void* d_scratch, size_t scratch_bytes, void* stream);
+size_t okx_ensemble_sobol_bootstrap_scratch_bytes(int64_t n_families, int32_t n_groups, int64_t steps, int32_t n_columns,
+                                                  int32_t n_replicates);
 
 #ifdef __cplusplus
 }

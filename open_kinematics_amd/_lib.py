@@ -87,6 +87,9 @@ EXPORTS = (
     "okx_ensemble_sample_families_check",
     "okx_ensemble_sobol",
     "okx_ensemble_sobol_scratch_bytes",
+    "okx_ensemble_bootstrap_weights",
+    "okx_ensemble_sobol_bootstrap",
+    "okx_ensemble_sobol_bootstrap_scratch_bytes",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -297,6 +300,12 @@ def load() -> C.CDLL:
     lib.okx_ensemble_sobol.restype = i32
     lib.okx_ensemble_sobol_scratch_bytes.argtypes = [i64, i32, i64, i32]
     lib.okx_ensemble_sobol_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_bootstrap_weights.argtypes = [i64, i64, C.c_uint64, i32, vp, vp]
+    lib.okx_ensemble_bootstrap_weights.restype = i32
+    lib.okx_ensemble_sobol_bootstrap.argtypes = [i64, i64, i32, i64, i32, vp, i64, vp, i64, vp, vp, C.c_uint64, i32, i32, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_sobol_bootstrap.restype = i32
+    lib.okx_ensemble_sobol_bootstrap_scratch_bytes.argtypes = [i64, i32, i64, i32, i32]
+    lib.okx_ensemble_sobol_bootstrap_scratch_bytes.restype = C.c_size_t
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "../../include/okx.h"
+#include "okx_philox.hpp"
 #include "okx_program.hpp"
 
 #pragma clang fp contract(off)
@@ -89,20 +90,7 @@ struct Args {
   Guards guards;
 };
 
-__device__ inline void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const u32 hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const u32 hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+using rng::philox4x32_10;  // (okx_philox.hpp: the bootstrap draws from it too)
 
 __device__ inline u32 mix32(u32 x) {
   x ^= x >> 16;

@@ -420,12 +420,22 @@ class ShardedEnsemble:
     rank order - the same bits on every rank; world sizes and chunkings agree to rounding, exactly when the sums are exact.
     ``sobol()`` returns the ``ensemble_stats.EnsembleSobol`` (first-order and total-order indices per group and entry),
     ``sobol_accumulator`` the merged tables, ``sobol_exchange_bytes_per_rank`` what the rank sends.
+
+    ``bootstrap=R`` (with ``sobol=True``; ``bootstrap_seed`` None: the plan's seed) adds HOW FAR TO TRUST those indices
+    (``okx_ensemble_sobol_bootstrap``): ``R`` Poisson-bootstrap replicates of the Sobol' accumulators, each chunk right after the
+    Sobol' stage took it.  A family's weight in a replicate is a pure function of (seed, global family index, replicate) - the
+    chunk's ``family_offset`` is ``a // family_size`` - so every rank and chunking forms the same replicates, and ``step()`` ends with
+    one more all-gather, added in ascending rank order.  ``sobol_bootstrap(level=0.95)`` returns the
+    ``ensemble_stats.EnsembleSobolBootstrap`` (the replicates' indices, their standard deviations and percentile intervals),
+    ``sobol_bootstrap_accumulator`` the merged tables, ``sobol_bootstrap_exchange_bytes_per_rank`` what the rank sends.  Families are
+    resampled as independent units; under ``LHS`` they are not quite, so the intervals are on the conservative side.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
-                 covariance=None, curves=None, front=None, sobol: bool = False, **solve_kw):
+                 covariance=None, curves=None, front=None, sobol: bool = False, bootstrap: int | None = None, bootstrap_seed: int | None = None,
+                 **solve_kw):
         from .ensemble_sample import FamilyPlan, SamplePlan
 
         self.plan = hardpoints if isinstance(hardpoints, (SamplePlan, FamilyPlan)) else None
@@ -433,6 +443,12 @@ class ShardedEnsemble:
             raise ValueError("sobol=True decomposes a pick-freeze ensemble: pass an ensemble_sample.FamilyPlan where the hardpoints go")
         if sobol and not reduce:
             raise ValueError("sobol=True accumulates the reduced ensemble: it needs reduce=True")
+        if (bootstrap is not None or bootstrap_seed is not None) and (not sobol or bootstrap is None):
+            raise ValueError("bootstrap= resamples the families of the Sobol' accumulators: it needs sobol=True (and bootstrap_seed needs bootstrap=)")
+        if bootstrap is not None:
+            from .ensemble_stats import check_replicates
+
+            bootstrap = check_replicates("bootstrap=", bootstrap)
         # sobol=True: shards and chunks are cut in whole families
         self.align = self.plan.family_size if sobol else 1
         if self.plan is not None:
@@ -598,6 +614,8 @@ class ShardedEnsemble:
             self.factor_names, self.n_factors, self.my_factors = first.factor_names, first.n_factors, first.my_factors
             if sobol:
                 self.stages["sobol"] = stages.Sobol(self)
+                if bootstrap is not None:
+                    self.stages["sobol_bootstrap"] = stages.SobolBootstrap(self, bootstrap, self.plan.plan.seed if bootstrap_seed is None else bootstrap_seed)
             if quantiles is not None:
                 stage = self.stages["select"] = stages.Selection(self, quantiles, limits)
                 self.select_probs, self.select_limits = stage.probs, stage.limits
@@ -617,6 +635,7 @@ class ShardedEnsemble:
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
         self.front_exchange_bytes_per_rank = sent.get("front", 0)
         self.sobol_exchange_bytes_per_rank = sent.get("sobol", 0)
+        self.sobol_bootstrap_exchange_bytes_per_rank = sent.get("sobol_bootstrap", 0)
 
     # ---- reduce=True: the stages of ensemble_stages.py; what they hold and answer, by the names it has always had ----
 
@@ -635,6 +654,16 @@ class ShardedEnsemble:
         if "sobol" not in self.stages:
             raise ValueError("sobol() needs sobol=True")
         return self.stages["sobol"].sobol()
+
+    sobol_bootstrap_accumulator = property(lambda self: self.stages["sobol_bootstrap"].merged,
+                                           doc="The merged bootstrap replicates of the Sobol' accumulator of the last ``step()`` (``bootstrap=R``); None before.")
+
+    def sobol_bootstrap(self, level: float = 0.95):
+        """``ensemble_stats.EnsembleSobolBootstrap`` of the WHOLE ensemble after the last ``step()`` (``sobol=True, bootstrap=R``): the indices of
+        every replicate, their standard deviations and the percentile intervals at ``level``.  The same bits on every rank."""
+        if "sobol_bootstrap" not in self.stages:
+            raise ValueError("sobol_bootstrap() needs sobol=True and bootstrap=R")
+        return self.stages["sobol_bootstrap"].sobol_bootstrap(level)
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""

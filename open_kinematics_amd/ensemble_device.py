@@ -4,7 +4,7 @@ The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce``
 ``okx_ensemble_covariance``, ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry) and
 ``okx_ensemble_front`` (the nondominated front of the ensemble) - and the pass at the head of the chain, ``okx_ensemble_sample`` (the
 hardpoint table of a ``SamplePlan`` drawn in HBM, ``ensemble_sample.py``) with its pick-freeze form ``okx_ensemble_sample_families`` (a ``FamilyPlan``'s
-families) and the pass that reads their evaluated table, ``okx_ensemble_sobol`` (first-order and total-order Sobol' indices per factor group).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
+families) and the pass that reads their evaluated table, ``okx_ensemble_sobol`` (first-order and total-order Sobol' indices per factor group), with ``okx_ensemble_sobol_bootstrap`` (Poisson-bootstrap replicates of it: standard deviations and intervals of the indices).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
 is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
 """
 
@@ -759,5 +759,70 @@ class EnsembleReductions:
         n = g // (d + 2)
         scratch = self._ensemble_scratch("sobol", int(self.lib.okx_ensemble_sobol_scratch_bytes(n, d, s, k)))
         self._ensemble_call("okx_ensemble_sobol", n, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift),
+                            1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_bootstrap_weights / okx_ensemble_sobol_bootstrap: how far to trust the indices (ensemble_stats.EnsembleSobolBootstrap) ----
+
+    def bootstrap_weights(self, n_rows: int, n_replicates: int, seed: int, row_offset: int = 0, out=None) -> torch.Tensor:
+        """
+        ``okx_ensemble_bootstrap_weights``: the Poisson(1) bootstrap weights ``uint8 [n_rows, R]`` of GLOBAL rows
+        ``[row_offset, row_offset + n_rows)`` in HBM - the bytes of ``ensemble_stats.bootstrap_weights(seed, row_offset, row_offset + n_rows, R)``,
+        a pure function of ``(seed, row, replicate)`` wherever and in whatever ranges they are drawn.  ``out``: the tensor of an earlier
+        call of the same shape (then the call allocates nothing and is legal inside a stream capture).
+        """
+        from .ensemble_stats import check_replicates
+
+        n, r, lo = int(n_rows), check_replicates("okx_ensemble_bootstrap_weights", n_replicates), int(row_offset)
+        if n < 0 or lo < 0:
+            raise ValueError(f"okx_ensemble_bootstrap_weights: bad range [{lo}, {lo + n})")
+        if out is None:
+            out = torch.empty((n, r), dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (n, r) or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 [{n}, {r}] device tensor")
+        self._ensemble_call("okx_ensemble_bootstrap_weights", n, lo, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), r, _ptr(out))
+        return out
+
+    def sobol_bootstrap_ensemble(self, values, *, steps_per_geometry: int, n_groups: int, n_replicates: int, seed: int, family_offset: int = 0,
+                                 status=None, mask=None, shift=None, out=None, accumulate: bool = False, group_names=None):
+        """
+        ``okx_ensemble_sobol_bootstrap``: ``n_replicates`` Poisson-bootstrap replicates of the Sobol' accumulator of ``sobol_ensemble`` over
+        the same table (``ensemble_stats.SobolBootstrapAccumulator``, device tensors: ``acc [R, S, K, 6 + 3 D]``, ``shift [S, K]``) - replicate
+        ``r`` weighs family ``i`` of the table, GLOBAL family ``family_offset + i``, with ``bootstrap_weights(...)[i, r]`` of ``seed``.
+        ``values``, ``status``, ``mask``, ``shift``, ``out`` and ``accumulate`` as ``sobol_ensemble`` takes them; chunks that are accumulated
+        pass their ``family_offset`` (and ONE shift and seed: ``out=`` carries both).  ``.finalize(level)`` copies to the host: the
+        replicates' indices, their standard deviations and percentile intervals.  Bit-identical from run to run; different chunkings
+        agree to rounding, exactly when the sums are exact.
+        """
+        from .ensemble_stats import SOBOL_FIELDS, SOBOL_MAX_GROUPS, SobolBootstrapAccumulator, check_replicates
+
+        who = "okx_ensemble_sobol_bootstrap"
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        d, r, first = int(n_groups), check_replicates(who, n_replicates), int(family_offset)
+        if not 1 <= d <= SOBOL_MAX_GROUPS:
+            raise ValueError(f"{who}: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
+        if g % (d + 2):
+            raise ValueError(f"{who}: {g} geometries are no whole families of {d + 2}")
+        if first < 0:
+            raise ValueError(f"{who}: negative family_offset")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        dev = self.device
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+            out = SobolBootstrapAccumulator(torch.empty((r, s, k, SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=dev),
+                                            self._ensemble_shift(shift, values, g, s, k), seed, group_names)
+        elif shift is not None:
+            raise ValueError("out= carries its own shift")
+        elif out.seed != seed:
+            raise ValueError(f"out= was taken with seed {out.seed}, not {seed}")
+        if tuple(out.acc.shape) != (r, s, k, SOBOL_FIELDS + 3 * d) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous()
+                                                                         or t.dtype != torch.float64 for t in (out.acc, out.shift)):
+            raise ValueError(f"out must hold contiguous device tables acc [R, S, K, {SOBOL_FIELDS + 3 * d}] = [{r}, {s}, {k}, .] and shift [S, K]")
+        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev or not mask.is_contiguous()):
+            raise ValueError("mask must be a contiguous uint8 [G] device tensor")
+        n = g // (d + 2)
+        scratch = self._ensemble_scratch("sobol_bootstrap", int(self.lib.okx_ensemble_sobol_bootstrap_scratch_bytes(n, d, s, k, r)))
+        self._ensemble_call(who, n, first, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift), C.c_uint64(seed), r,
                             1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())
         return out

@@ -39,6 +39,7 @@ NORMAL, UNIFORM, TRUNCATED = 0, 1, 2
 IID, LHS = 0, 1
 GUARD_SIGN, GUARD_DISTINCT, GUARD_OFF_LINE = 0, 1, 2
 PURPOSE_DRAW, PURPOSE_STRATA = 0, 1
+PURPOSE_BOOTSTRAP = 2  # OKX_SAMPLE_PURPOSE_BOOTSTRAP: the Poisson weights of ensemble_stats.bootstrap_weights
 MAX_COORDS = 288      # OKX_ENS_SAMPLE_MAX_COORDS (= 3 * OKX_MAX_POINTS)
 MAX_LATENTS = 288     # OKX_ENS_SAMPLE_MAX_LATENTS
 MAX_GUARDS = 16       # OKX_ENS_SAMPLE_MAX_GUARDS
@@ -606,5 +607,5 @@ def group_by_point(plan: SamplePlan) -> tuple:
 __all__ = ["SamplePlan", "sample_host", "hardpoint_plan", "FamilyPlan", "families_host", "check_families", "group_by_point",
            "SOBOL_MAX_GROUPS", "philox4x32_10", "draw_bits", "unit_from_bits", "stratum", "strata_bits", "strata_keys",
            "ppnd16", "log_unit", "units", "stratified_unit", "latents_from_units", "contract", "guards_hold", "check_arguments", "check_plan",
-           "NORMAL", "UNIFORM", "TRUNCATED", "IID", "LHS", "GUARD_SIGN", "GUARD_DISTINCT", "GUARD_OFF_LINE", "PURPOSE_DRAW", "PURPOSE_STRATA",
+           "NORMAL", "UNIFORM", "TRUNCATED", "IID", "LHS", "GUARD_SIGN", "GUARD_DISTINCT", "GUARD_OFF_LINE", "PURPOSE_DRAW", "PURPOSE_STRATA", "PURPOSE_BOOTSTRAP",
            "MAX_COORDS", "MAX_LATENTS", "MAX_GUARDS", "MAX_ATTEMPTS", "U_MIN", "U_MAX"]

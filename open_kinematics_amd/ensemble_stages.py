@@ -1,6 +1,6 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
-(moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
+(moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``SobolBootstrap`` (``bootstrap=``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
 (``covariance=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
@@ -226,6 +226,53 @@ class Sobol(_AccumulatorStage):
             raise RuntimeError("no step() yet")
         if self.result is None:
             self.result = self.merged.finalize()
+        return self.result
+
+
+class SobolBootstrap(_AccumulatorStage):
+    """``sobol=True, bootstrap=R``: ``R`` Poisson-bootstrap replicates of the Sobol' accumulators, each chunk right after the Sobol' stage
+    took it, with the same shift and mask; the chunk's first family ``a // family_size`` is its ``family_offset``, so the replicates do
+    not depend on how the ensemble is sharded or chunked."""
+
+    def __init__(self, owner, n_replicates: int, seed: int):
+        super().__init__(owner)
+        o = owner
+        k, d = len(o.metric_index), o.plan.n_groups
+        self.n_groups, self.group_names, self.family_size = d, o.plan.names(), o.plan.family_size
+        self.n_replicates, self.seed = es.check_replicates("bootstrap=", n_replicates), int(seed) & 0xFFFFFFFFFFFFFFFF
+        sobol = o.stages["sobol"]
+        self.flags = sobol.flags
+        self.local = es.SobolBootstrapAccumulator(torch.zeros((self.n_replicates, o.steps, k, es.SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=o.device),
+                                                  sobol.local.shift, self.seed, self.group_names)  # ONE shift: the reduction's (itself, no copy)
+        self.merged = self.result = None
+        self.allocate_exchange(self.local.acc.numel())
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        mask = self.flags[a - glo : b - glo]
+        first = a // self.family_size
+        if self.on_device:
+            o.dp.sobol_bootstrap_ensemble(values, steps_per_geometry=o.steps, n_groups=self.n_groups, n_replicates=self.n_replicates, seed=self.seed,
+                                          family_offset=first, status=status, mask=mask, out=mine, accumulate=self.taken)
+            return
+        part = es.sobol_bootstrap_host(*self.host_tables(a, b, values, status), mask.cpu().numpy(), self.n_groups, mine.shift.cpu().numpy(),
+                                       seed=self.seed, n_replicates=self.n_replicates, family_offset=first)
+        if not self.taken:
+            mine.acc.zero_()
+        mine.acc += torch.from_numpy(part.acc)
+
+    def exchange(self) -> None:
+        mine = self.local
+        self.result = None
+        self.merged = self.merged_over_ranks(mine, (mine.acc,), lambda row: es.SobolBootstrapAccumulator(row.reshape(mine.acc.shape), mine.shift, self.seed,
+                                                                                                        self.group_names))
+
+    def sobol_bootstrap(self, level: float = 0.95):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None or self.result.level != float(level):
+            self.result = self.merged.finalize(level)
         return self.result
 
 

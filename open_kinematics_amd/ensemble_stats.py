@@ -18,7 +18,9 @@ ALONG the sweep inside one geometry: the curve characteristics of every (geometr
 curvature at an origin, departure from the fitted shape, extremes and where they occur (``curves_host`` / ``EnsembleCurves``,
 ``okx_ensemble_curves``); their table ``[G, K * 12]`` is again a column table for every pass above.
 WHICH FACTOR GROUP explains the variance: the Sobol' accumulators of a pick-freeze ensemble (``ensemble_sample.FamilyPlan``) and
-their first-order and total-order indices (``sobol_host`` / ``SobolAccumulator`` / ``EnsembleSobol``, ``okx_ensemble_sobol``).
+their first-order and total-order indices (``sobol_host`` / ``SobolAccumulator`` / ``EnsembleSobol``, ``okx_ensemble_sobol``), and
+HOW FAR TO TRUST them: Poisson-bootstrap replicates of those accumulators, their standard deviations and percentile intervals
+(``bootstrap_weights`` / ``sobol_bootstrap_host`` / ``SobolBootstrapAccumulator`` / ``EnsembleSobolBootstrap``, ``okx_ensemble_sobol_bootstrap``).
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -1160,6 +1162,178 @@ def sobol_host(values, status=None, mask=None, n_groups: int = 1, shift=None, gr
     return SobolAccumulator(acc, shift, group_names)
 
 
+# ---- Poisson bootstrap of the Sobol' indices: how far to trust them (okx_ensemble_bootstrap_weights, okx_ensemble_sobol_bootstrap) ----
+
+BOOTSTRAP_MAX_REPLICATES = 1024  # OKX_ENS_BOOTSTRAP_MAX_REPLICATES
+# T[k] = floor(2^32 sum_{j <= k} e^-1 / j!), k = 0 .. 12: the weight of a 32-bit word u is the number of k with u >= T[k]
+BOOTSTRAP_THRESHOLDS = np.array([0x5E2D58D8, 0xBC5AB1B1, 0xEB715E1D, 0xFB239797, 0xFF1025F5, 0xFFD90F3B, 0xFFFA8B71, 0xFFFF540C, 0xFFFFED1F, 0xFFFFFE21,
+                                 0xFFFFFFD4, 0xFFFFFFFC, 0xFFFFFFFF], dtype=np.uint32)
+BOOTSTRAP_MAX_WEIGHT = 13  # OKX_ENS_BOOTSTRAP_MAX_WEIGHT
+
+
+def check_replicates(who: str, n_replicates) -> int:
+    r = int(n_replicates)
+    if not 1 <= r <= BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"{who}: {r} replicates, 1 to {BOOTSTRAP_MAX_REPLICATES} allowed")
+    return r
+
+
+def bootstrap_weights(seed: int, lo: int, hi: int, n_replicates: int) -> np.ndarray:
+    """
+    The definition of ``okx_ensemble_bootstrap_weights`` in NumPy: ``uint8 [hi - lo, R]``, the Poisson(1) weight of GLOBAL row ``i`` in
+    ``[lo, hi)`` (for the Sobol' bootstrap a row is a family) in replicate ``r`` - a pure function of ``(seed, i, r)``, so any range is
+    the slice of the whole and every chunk, device and rank forms the same replicates.  ``u`` is word ``r % 4`` of
+    ``philox4x32_10((i & 0xffffffff, i >> 32, r // 4, PURPOSE_BOOTSTRAP << 8), key of the seed)`` and the weight the number of
+    ``BOOTSTRAP_THRESHOLDS`` that ``u`` reaches: integers only, at most 13.
+    """
+    from .ensemble_sample import PURPOSE_BOOTSTRAP, _seed_key, philox4x32_10
+
+    r = check_replicates("okx_ensemble_bootstrap_weights", n_replicates)
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi < lo:
+        raise ValueError(f"okx_ensemble_bootstrap_weights: bad range [{lo}, {hi})")
+    rows = (np.uint64(lo) + np.arange(hi - lo, dtype=np.uint64))[:, None]
+    quads = np.arange((r + 3) // 4, dtype=np.uint64)[None, :]
+    words = philox4x32_10((rows & np.uint64(0xFFFFFFFF), rows >> np.uint64(32), quads, np.uint64(PURPOSE_BOOTSTRAP << 8)), _seed_key(seed))
+    u = np.stack(np.broadcast_arrays(*words), axis=-1).reshape(hi - lo, 4 * ((r + 3) // 4))[:, :r]
+    return np.searchsorted(BOOTSTRAP_THRESHOLDS, u, side="right").astype(np.uint8)
+
+
+@dataclass
+class EnsembleSobolBootstrap:
+    """
+    What ``SobolBootstrapAccumulator.finalize`` returns (NumPy, host): ``SobolAccumulator.finalize`` of every replicate - ``first``,
+    ``first_jansen``, ``total`` ``[R, S, K, D]`` and ``mean``, ``variance`` ``[R, S, K]``, NaN where a replicate leaves the quantity
+    undefined - with, over the replicates and NaN-aware, ``<name>_std`` (``ddof = 1``) and the percentile interval
+    ``interval(name, level)``.  ``defined [S, K]``: the replicates in which the entry's indices are defined.  Families are
+    resampled as independent units; under ``LHS`` they are not quite independent, so the intervals are on the conservative side.
+    """
+
+    first: np.ndarray
+    first_jansen: np.ndarray
+    total: np.ndarray
+    mean: np.ndarray
+    variance: np.ndarray
+    first_std: np.ndarray
+    first_jansen_std: np.ndarray
+    total_std: np.ndarray
+    mean_std: np.ndarray
+    variance_std: np.ndarray
+    defined: np.ndarray
+    level: float = 0.95
+    group_names: list | None = None
+
+    NAMES = ("first", "first_jansen", "total", "mean", "variance")
+
+    def interval(self, name: str, level: float | None = None):
+        """``(lo, hi)``: ``np.nanquantile`` of the replicates of ``name`` at ``(1 - level) / 2`` and ``(1 + level) / 2`` (linear rule)."""
+        if name not in self.NAMES:
+            raise ValueError(f"no replicates of {name!r}: one of {self.NAMES}")
+        level = self.level if level is None else float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie inside (0, 1)")
+        import warnings
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)  # (an entry no replicate defines: NaN)
+            lo, hi = np.nanquantile(getattr(self, name), [(1.0 - level) / 2.0, (1.0 + level) / 2.0], axis=0)
+        return lo, hi
+
+
+class SobolBootstrapAccumulator:
+    """
+    The raw tables of ``okx_ensemble_sobol_bootstrap``: ``acc [R, S, K, SOBOL_FIELDS + 3 D]`` float64 - replicate ``r`` holds the fields
+    of a ``SobolAccumulator`` with every family's term multiplied by the family's weight - ``shift [S, K]`` and the ``seed`` of the
+    weights; NumPy arrays or torch tensors (host or device).
+    """
+
+    def __init__(self, acc, shift, seed: int, group_names=None):
+        self.acc, self.shift, self.seed = acc, shift, int(seed)
+        self.group_names = list(group_names) if group_names is not None else None
+        if acc.ndim != 4 or acc.shape[0] < 1 or acc.shape[3] < SOBOL_FIELDS + 3 or (acc.shape[3] - SOBOL_FIELDS) % 3 \
+                or tuple(shift.shape) != tuple(acc.shape[1:3]):
+            raise ValueError("acc must be [R, S, K, SOBOL_FIELDS + 3 D] and shift [S, K]")
+
+    @property
+    def n_groups(self) -> int:
+        return (int(self.acc.shape[3]) - SOBOL_FIELDS) // 3
+
+    @property
+    def n_replicates(self) -> int:
+        return int(self.acc.shape[0])
+
+    def numpy(self) -> "SobolBootstrapAccumulator":
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(self.acc):
+            return self
+        return SobolBootstrapAccumulator(self.acc.detach().cpu().numpy(), self.shift.detach().cpu().numpy(), self.seed, self.group_names)
+
+    def merge(self, other: "SobolBootstrapAccumulator") -> "SobolBootstrapAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one): additions only, which is why both must have been taken with the same
+        shift and - the weights of a family are a function of the seed - the same seed."""
+        if tuple(self.acc.shape) != tuple(other.acc.shape):
+            raise ValueError("accumulators of different shapes")
+        if self.seed != other.seed:
+            raise ValueError("accumulators taken with different seeds cannot be merged")
+        xp = __import__("torch") if _is_tensor(self.acc) else np
+        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
+        if not bool(same):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        return SobolBootstrapAccumulator(self.acc + other.acc, self.shift, self.seed, self.group_names)
+
+    def finalize(self, level: float = 0.95) -> EnsembleSobolBootstrap:
+        """``SobolAccumulator.finalize`` of every replicate (``COUNT_r`` plays the part of ``n``), their standard deviations and the
+        percentile intervals at ``level``, on the host in fp64."""
+        import warnings
+
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("level must lie inside (0, 1)")
+        h = self.numpy()
+        parts = [SobolAccumulator(np.asarray(h.acc[r], dtype=np.float64), h.shift).finalize() for r in range(h.n_replicates)]
+        tables = {name: np.stack([getattr(part, name) for part in parts]) for name in EnsembleSobolBootstrap.NAMES}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)  # (fewer than two defined replicates: NaN)
+            std = {f"{name}_std": np.nanstd(table, axis=0, ddof=1) for name, table in tables.items()}
+        defined = np.isfinite(tables["variance"]).sum(axis=0).astype(np.int64)
+        return EnsembleSobolBootstrap(**tables, **std, defined=defined, level=float(level), group_names=self.group_names)
+
+
+def sobol_bootstrap_host(values, status=None, mask=None, n_groups: int = 1, shift=None, *, seed: int, n_replicates: int, family_offset: int = 0,
+                         weights=None, group_names=None) -> SobolBootstrapAccumulator:
+    """
+    The accumulator of ``okx_ensemble_sobol_bootstrap`` in NumPy (table arguments as ``sobol_terms`` takes them): family ``i`` of the
+    table is GLOBAL family ``family_offset + i`` and enters replicate ``r`` with the weight ``bootstrap_weights(seed, ...)[i, r]`` -
+    families ascending, ``acc[r] += w * term`` with the product rounded, then the sum; a replicate in which the family's weight is 0
+    is left alone (adding +0 changes no bit).  ``weights [N, R]``: these instead of the seed's (a test's all-ones table).
+    """
+    r = check_replicates("okx_ensemble_sobol_bootstrap", n_replicates)
+    if int(family_offset) < 0:
+        raise ValueError("okx_ensemble_sobol_bootstrap: negative family_offset")
+    v = np.asarray(values, dtype=np.float64)
+    m = int(n_groups) + 2
+    _, terms, shift = sobol_terms(v[:0], None if status is None else np.asarray(status)[:0], None, n_groups,
+                                  (clean_shift(v[0]) if v.shape[0] else None) if shift is None else shift)
+    if v.ndim == 3 and v.shape[0] % m:
+        sobol_terms(v, status, mask, n_groups, shift)  # (raises: no whole families)
+    n = v.shape[0] // m
+    if weights is None:
+        weights = bootstrap_weights(seed, int(family_offset), int(family_offset) + n, r)
+    weights = np.asarray(weights)
+    if weights.shape != (n, r):
+        raise ValueError(f"weights must be [{n}, {r}]")
+    acc = np.zeros((r,) + terms.shape[1:])
+    block = 64 * m
+    for lo in range(0, v.shape[0], block):
+        rows = slice(lo, lo + block)
+        _, terms, _ = sobol_terms(v[rows], None if status is None else np.asarray(status)[rows], None if mask is None else np.asarray(mask).reshape(-1)[rows],
+                                  n_groups, shift)
+        for i in range(terms.shape[0]):  # ascending family order, as the device walks a slab
+            w = weights[lo // m + i]
+            drawn = np.flatnonzero(w)
+            acc[drawn] += w[drawn].astype(np.float64)[:, None, None, None] * terms[i][None]
+    return SobolBootstrapAccumulator(acc, shift, seed, group_names)
+
+
 __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_factors", "clean_shift", "factor_moment_count",
            "ENS_FIELDS", "ENS_COUNT", "ENS_REJECTED", "ENS_SUM", "ENS_SUMSQ", "ENS_MIN", "ENS_MAX", "ENS_ARGMIN", "ENS_ARGMAX",
            "EnsembleQuantiles", "SelectState", "select_host", "select_rounds_host", "select_begin", "select_count_round", "select_descend_round",
@@ -1170,4 +1344,6 @@ __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_fac
            "curve_normal_refused", "CURVE_FIELDS", "CURVE_MAX_DEGREE", "CURVE_PIVOT", "EnsembleFront", "front_host", "front_dominated",
            "front_objectives", "check_front_arguments", "FRONT_MIN", "FRONT_MAX", "FRONT_TARGET", "FRONT_MAX_OBJECTIVES", "FRONT_MAX_GEOMETRIES",
            "FRONT_SEEN", "FRONT_CANDIDATES", "FRONT_MEMBERS", "EnsembleSobol", "SobolAccumulator", "sobol_host", "sobol_terms", "SOBOL_COUNT",
-           "SOBOL_DROPPED", "SOBOL_SUM_A", "SOBOL_SUM_B", "SOBOL_SUMSQ_A", "SOBOL_SUMSQ_B", "SOBOL_FIELDS", "SOBOL_MAX_GROUPS"]
+           "SOBOL_DROPPED", "SOBOL_SUM_A", "SOBOL_SUM_B", "SOBOL_SUMSQ_A", "SOBOL_SUMSQ_B", "SOBOL_FIELDS", "SOBOL_MAX_GROUPS", "EnsembleSobolBootstrap",
+           "SobolBootstrapAccumulator", "sobol_bootstrap_host", "bootstrap_weights", "check_replicates", "BOOTSTRAP_MAX_REPLICATES", "BOOTSTRAP_THRESHOLDS",
+           "BOOTSTRAP_MAX_WEIGHT"]
