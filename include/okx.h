@@ -303,6 +303,18 @@ int32_t okx_eval_batch(okx_program* prog, int64_t n_problems,
  * with every row's design-state target recomputed (distance L, angle alpha, triple
  * product V and scale=|V|, point-on-line / line-pin anchor = the point's design position);
  * rows whose parameters are authored constants (fixed axis, planes) are copied through.
+ *
+ * Derived-op parameters are PROGRAM CONSTANTS: every geometry's derived points are recomputed
+ * with the program's own dop_param - the ALONG offset (wheel offset, half wheel width, the
+ * MacPherson strut clamp's distance from the lower ball joint) and the contact-patch radius.
+ * The reference reads the clamp offset off the AUTHORED clamp of each geometry
+ * (macpherson.py:199-204, :302-323: the clamp projected onto the strut axis); here an authored
+ * clamp entry in d_hardpoints is ignored like every other derived entry, and the clamp is
+ * placed at LBJ + normalize(STRUT_TOP - LBJ) * d0 with the program's d0.  A table whose
+ * clamps keep the distance d0 along their own perturbed axis describes the same mechanisms as
+ * the reference builds; one that moves the clamp along the axis does not (the solve kernels
+ * read the same constant), and DeviceProgram.rebind(strict=True) refuses it.  Both are pinned
+ * against the reference on every topology by tests/test_gpu_rebind_topologies.py.
  */
 int32_t okx_rebind_design(okx_program* prog, int64_t n_geometries,
                           const double* d_hardpoints,     /* [G][P][3] */

@@ -745,8 +745,14 @@ class DeviceProgram(EnsembleReductions):
         base = (geom_pos[:, pts, :] * dirs[None]).sum(dim=2)                                           # [G, T]
         return (base[:, None, :] + rel[None]).reshape(-1, p.n_targets).contiguous()
 
-    def rebind(self, hardpoints):
-        """Per-geometry design positions ``[G, P, 3]`` and row parameters ``[G, Mc, 8]``."""
+    def rebind(self, hardpoints, strict: bool = False):
+        """
+        Per-geometry design positions ``[G, P, 3]`` and row parameters ``[G, Mc, 8]`` (``okx_rebind_design``).  Derived
+        entries of the table are ignored and recomputed with the PROGRAM's derived-op parameters (the ``ALONG`` offset, the
+        contact-patch radius): an authored MacPherson strut clamp does not move the clamp offset the way it does in the
+        reference.  ``strict=True`` compares, on the host after the kernel (one synchronising copy), every authored derived
+        entry with the recomputed point and raises ``ValueError`` where they differ by more than 1e-9 mm.
+        """
         p = self.program
         hp = _as_f64(hardpoints, self.device).reshape(-1, p.n_points, 3)
         g = hp.shape[0]
@@ -756,4 +762,7 @@ class DeviceProgram(EnsembleReductions):
         with torch.cuda.device(self.device):
             rc = self.lib.okx_rebind_design(self._handle, g, _ptr(hp), _ptr(pos), _ptr(rq), C.c_void_p(stream))
         _lib.check(rc, "okx_rebind_design")
+        points = p.authored_derived_points() if strict else []
+        if points:
+            p.check_authored_derived(hp.cpu().numpy(), pos.cpu().numpy())
         return pos, rq

@@ -229,6 +229,35 @@ class ConstraintProgram:
         clone.line_mode = line_mode
         return clone
 
+    def authored_derived_points(self) -> list[int]:
+        """
+        Derived points the reference takes an AUTHORED value for: the outputs of ``get_point_along_line`` (a MacPherson's
+        strut clamp, whose offset along the strut axis the reference reads off the authored clamp).  Every other derived
+        point (wheel centre, wheel faces, contact patch, axle midpoint) has no authored value.
+        """
+        return [int(self.dop_out[e]) for e in range(self.n_derived)
+                if int(self.dop_type[e]) == DOP_ALONG and self.dop_pts[e][0] == self.dop_pts[e][2] != self.dop_pts[e][1]]
+
+    def check_authored_derived(self, hardpoints: np.ndarray, rebound_pos: np.ndarray, tol: float = 1e-9) -> None:
+        """
+        ``rebind(strict=True)``: derived-op parameters are program constants (``okx_rebind_design``), so an authored
+        derived entry of a hardpoint table ``[G, P, 3]`` that is not where the recomputed point ``rebound_pos [G, P, 3]``
+        lies (to ``tol`` mm) describes a mechanism this program cannot express.  Raises ``ValueError`` naming the first.
+        """
+        points = self.authored_derived_points()
+        if not points:
+            return
+        hp = np.asarray(hardpoints, dtype=np.float64).reshape(-1, self.n_points, 3)[:, points]
+        gap = np.abs(hp - np.asarray(rebound_pos, dtype=np.float64).reshape(-1, self.n_points, 3)[:, points]).max(axis=2)
+        bad = np.argwhere(~(gap <= tol))   # (a NaN entry disagrees too)
+        if len(bad):
+            g, k = (int(v) for v in bad[0])
+            raise ValueError(
+                f"geometry {g}: the authored {key_name(self.point_keys[points[k]])} lies {gap[g, k]:.3e} mm from where the "
+                f"program's constant derived-op parameter puts it ({len(bad)} such entries in the table); rebind keeps "
+                "the program's offset and ignores the authored entry"
+            )
+
     def validate(self) -> None:
         """Static checks shared by the oracle and the device library."""
         if self.n_points > MAX_POINTS or self.n_vars > MAX_VARS:
