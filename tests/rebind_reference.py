@@ -1,6 +1,7 @@
 """
 What the ``rebind_<name>.npz`` fixtures (oracle/gen_golden_rebind.py) say, in the shapes the tests of per-geometry problem
-emission need: shared by tests/test_rebind_topologies.py (the oracle) and tests/test_gpu_rebind_topologies.py (the device).
+emission need: shared by tests/test_rebind_topologies.py (the oracle), tests/test_gpu_rebind_topologies.py (the device) and
+the tangent tests on the same geometries (tests/test_tangents_oracle.py, tests/test_gpu_tangent_topologies.py).
 Everything here is the reference's recorded data, re-arranged; nothing of the code under test computes an expectation.
 
 Bounds (the project's existing ones, DESIGN.md section 4 and the C5 tests):
