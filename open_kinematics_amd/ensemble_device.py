@@ -1,23 +1,43 @@
 """
-The device passes over an evaluated ensemble, host side: ``okx_ensemble_reduce`` (moments, extremes, sensitivities),
-``okx_ensemble_select`` (exact quantiles, spec-limit counts), ``okx_ensemble_screen`` (the joint verdict per geometry),
-``okx_ensemble_covariance``, ``okx_ensemble_curves`` (the curve characteristics along the sweep of every geometry) and
-``okx_ensemble_front`` (the nondominated front of the ensemble) - and the pass at the head of the chain, ``okx_ensemble_sample`` (the
-hardpoint table of a ``SamplePlan`` drawn in HBM, ``ensemble_sample.py``) with its pick-freeze form ``okx_ensemble_sample_families`` (a ``FamilyPlan``'s
-families) and the pass that reads their evaluated table, ``okx_ensemble_sobol`` (first-order and total-order Sobol' indices per factor group), with ``okx_ensemble_sobol_bootstrap`` (Poisson-bootstrap replicates of it: standard deviations and intervals of the indices).  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them from; what they return
-is described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a table to the host.
+The device passes over an evaluated ensemble, host side.  ``EnsembleReductions`` is the mixin ``batch.DeviceProgram`` takes them
+from; the host forms of what they return are described in ``ensemble_stats.py``.  Tensors stay in HBM; nothing here copies a
+table to the host.
+
+=============================  ====================  ==============================================
+pass (``okx_ensemble_...``)    prepare call          result
+=============================  ====================  ==============================================
+``sample_ensemble``            -                     ``EnsembleSample`` (of a ``SamplePlan``)
+``sample_families``            -                     ``EnsembleSample`` (of a ``FamilyPlan``)
+``reduce_ensemble``            -                     ``ensemble_stats.EnsembleAccumulator``
+``select_ensemble``            ``select_prepare``    ``EnsembleSelection``
+``screen_ensemble``            ``screen_prepare``    ``EnsembleScreening``
+``covariance_ensemble``        -                     ``ensemble_stats.CovarianceAccumulator``
+``curves_ensemble``            ``curves_prepare``    ``ensemble_stats.EnsembleCurves``
+``front_ensemble``             ``front_prepare``     ``EnsembleFronting``
+``sobol_ensemble``             -                     ``ensemble_stats.SobolAccumulator``
+``bootstrap_weights``          -                     ``uint8 [n_rows, R]`` tensor
+``sobol_bootstrap_ensemble``   -                     ``ensemble_stats.SobolBootstrapAccumulator``
+=============================  ====================  ==============================================
+
+Every pass takes ``out=``, the result of an earlier call or of its prepare call; the tables it holds are checked in one place
+(``EnsembleReductions._check_tables``) before anything is launched.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _lib
-from .ensemble_stats import FRONT_TARGET, _host_f64
+from .ensemble_stats import (CURVE_FIELDS, ENS_FIELDS, FRONT_TARGET, SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS, CovarianceAccumulator,
+                             EnsembleAccumulator, EnsembleCurves, SobolAccumulator, SobolBootstrapAccumulator, _host_f64, broadcast_limits,
+                             broadcast_scale, check_covariance_arguments, check_front_arguments, check_replicates, factor_moment_count)
+
+F64, I64, I32, U8 = torch.float64, torch.int64, torch.int32, torch.uint8
 
 
 @dataclass
@@ -169,8 +189,16 @@ class EnsembleSample:
     lo: int = 0
 
 
-def _ptr(t: torch.Tensor | None) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
+def _ptr(t: torch.Tensor | None, row: int = 0) -> C.c_void_p:
+    """The address of ``t`` (None: 0); with ``row``, of that row of a contiguous table - what ``t[row:]`` starts at, without making the view."""
+    if t is None:
+        return C.c_void_p(0)
+    return C.c_void_p(t.data_ptr() + row * t.stride(0) * t.element_size() if row else t.data_ptr())
+
+
+def _rows(t) -> int:
+    """The row count of a table that sets its own; of anything without rows -1, a size no tensor has."""
+    return t.shape[0] if isinstance(t, torch.Tensor) and t.dim() else -1
 
 
 def _as_f64(t, device) -> torch.Tensor:
@@ -227,6 +255,43 @@ class EnsembleReductions:
             rc = getattr(self.lib, name)(*args, C.c_void_p(stream))
         _lib.check(rc, name)
 
+    def _check_tables(self, message: str, tables, optional=()) -> None:
+        """The ``out=`` contract, checked HERE for every pass: each ``(tensor, shape or None, dtype)`` of ``tables`` is a
+        contiguous torch tensor of that dtype (and shape) on ``self.device``; those of ``optional`` may also be None.  Metadata
+        only - no allocation, no device work -, so a checked call stays legal inside a stream capture."""
+        dev = self.device
+        for specs, needed in ((tables, True), (optional, False)):
+            for t, shape, dtype in specs:
+                if t is None and not needed:
+                    continue
+                if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.is_contiguous() and (shape is None or t.shape == shape)):
+                    raise ValueError(message)
+
+    def _check_mask(self, mask, g: int, contiguous: bool) -> int:
+        """The stride of ``mask`` (None: 0), a uint8 ``[G]`` device tensor: contiguous, or strided with a positive stride."""
+        if mask is None:
+            return 0
+        if mask.dtype != U8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != self.device or (contiguous and not mask.is_contiguous()):
+            raise ValueError("mask must be a contiguous uint8 [G] device tensor" if contiguous else "mask must be a uint8 [G] device tensor")
+        stride = mask.stride(0) if g > 1 else 1
+        if stride < 1:
+            raise ValueError("mask must have a positive stride")
+        return stride
+
+    @staticmethod
+    def _new_result(out, carried: tuple, what: str, accumulate: bool = False,
+                    needs: str = "accumulate=True needs the accumulator to merge into (out=)") -> bool:
+        """The "new or given" rule of every pass.  True: there is no ``out=`` and the result is to be made - then
+        ``accumulate=True`` is refused; False: ``out=`` is given - then the arguments it ``carried`` itself must be None."""
+        if out is None:
+            if accumulate:
+                raise ValueError(needs)
+            return True
+        for x in carried:
+            if x is not None:
+                raise ValueError(f"out= carries its own {what}")
+        return False
+
     def reduce_ensemble(self, values, *, steps_per_geometry: int, status=None, factors=None, shift=None, geometry_offset: int = 0,
                         out=None, accumulate: bool = False, factor_moments: bool = True):
         """
@@ -241,8 +306,6 @@ class EnsembleReductions:
         allocates nothing and is legal inside a stream capture.  ``factor_moments=False`` skips the factor moments (a caller
         that merges chunks of fixed factors takes them once).
         """
-        from .ensemble_stats import ENS_FIELDS, EnsembleAccumulator, factor_moment_count
-
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         p = 0
         if factors is not None:
@@ -251,18 +314,12 @@ class EnsembleReductions:
                 raise ValueError("factors must be [G, P]")
             factors = factors.contiguous()
             p = factors.shape[1]
-        if out is None:
-            shift = self._ensemble_shift(shift, values, g, s, k)
-            out = EnsembleAccumulator(torch.empty((s, k, ENS_FIELDS + p), dtype=torch.float64, device=self.device), shift,
-                                      torch.empty(factor_moment_count(p), dtype=torch.float64, device=self.device) if p and factor_moments else None)
-            if accumulate:
-                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
-        elif shift is not None:
-            raise ValueError("out= carries its own shift")
-        if tuple(out.acc.shape) != (s, k, ENS_FIELDS + p) or not out.acc.is_contiguous() or not out.shift.is_contiguous() \
-                or out.acc.device != self.device or out.shift.device != self.device:
-            raise ValueError(f"out must hold contiguous device tables [S, K, {ENS_FIELDS + p}] and [S, K]")
+        if self._new_result(out, (shift,), "shift", accumulate):
+            out = EnsembleAccumulator(torch.empty((s, k, ENS_FIELDS + p), dtype=F64, device=self.device), self._ensemble_shift(shift, values, g, s, k),
+                                      torch.empty(factor_moment_count(p), dtype=F64, device=self.device) if p and factor_moments else None)
         factor_acc = out.factor_acc if factor_moments and p else None
+        self._check_tables(f"out must hold contiguous device tables [S, K, {ENS_FIELDS + p}] and [S, K]",
+                           [(out.acc, (s, k, ENS_FIELDS + p), F64), (out.shift, (s, k), F64)], [(factor_acc, (factor_moment_count(p),), F64)])
         scratch = self._ensemble_scratch("reduce", int(self.lib.okx_ensemble_scratch_bytes(g, s, k, p)))
         self._ensemble_call("okx_ensemble_reduce", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(factors), p, _ptr(out.shift),
                             int(geometry_offset), 1 if accumulate else 0, _ptr(out.acc), _ptr(factor_acc), _ptr(scratch), scratch.numel())
@@ -277,8 +334,6 @@ class EnsembleReductions:
         ``okx_ensemble_select_check`` on the host and uploaded ONCE; outputs are allocated.  ``rounds=True`` adds the state and
         the histogram the round-level calls (``select_begin`` / ``select_count`` / ``select_descend`` / ``select_finish``) work on.
         """
-        from .ensemble_stats import SELECT_MAX_PROBS, broadcast_limits
-
         s, k = int(steps), int(n_columns)
         p = np.ascontiguousarray(np.atleast_1d(_host_f64(probs)).reshape(-1))
         lim = None if limits is None else broadcast_limits(limits, s, k)
@@ -299,9 +354,27 @@ class EnsembleReductions:
     def select_rounds(self) -> int:
         return int(self.lib.okx_ensemble_select_rounds())
 
+    def _select_tables(self, run: "EnsembleSelection", rounds: bool) -> tuple:
+        """``(S, K, Q)`` of ``run``, its tables checked: those of ``select_ensemble``, and with ``rounds`` the state and the
+        histogram the round-level calls work on."""
+        message = "out must hold contiguous device tables probs [Q], limits [S, K, 2], order [S, K, Q, 2], count [S, K] and outside [S, K, 2]" \
+            + (", state and hist [S, K, 2 Q, bins]" if rounds else "")
+        order = run.order
+        if not isinstance(order, torch.Tensor) or order.dim() != 4 or (run.outside is None) != (run.limits is None):
+            raise ValueError(message)
+        s, k, q = order.shape[:3]
+        tables = [(run.probs, (q,), F64), (order, (s, k, q, 2), F64), (run.count, (s, k), I64)]
+        if rounds:
+            bins = int(self.lib.okx_ensemble_select_hist_len(s, k, q)) // max(1, s * k * 2 * q)
+            tables += [(run.state, None, U8), (run.hist, (s, k, 2 * q, bins), I64)]
+        self._check_tables(message, tables, [(run.limits, (s, k, 2), F64), (run.outside, (s, k, 2), I64)])
+        if rounds and run.state.numel() < int(self.lib.okx_ensemble_select_state_bytes(s, k, q)):
+            raise ValueError(message)
+        return s, k, q
+
     def select_begin(self, run: "EnsembleSelection") -> None:
         """State and histogram of ``run`` zeroed on the stream (``okx_ensemble_select_begin``)."""
-        s, k, q = run.shape
+        s, k, q = self._select_tables(run, True)
         self._ensemble_call("okx_ensemble_select_begin", s, k, q, _ptr(run.state), _ptr(run.hist))
 
     def select_count(self, run: "EnsembleSelection", rnd: int, values, *, steps_per_geometry: int, status=None) -> None:
@@ -309,17 +382,18 @@ class EnsembleReductions:
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         if (s, k) != run.shape[:2]:
             raise ValueError(f"the select was prepared for [S, K] = {list(run.shape[:2])}")
+        self._select_tables(run, True)
         self._ensemble_call("okx_ensemble_select_count", int(rnd), g, s, k, _ptr(values), ld, _ptr(status), stride, run.shape[2],
                             _ptr(run.limits), _ptr(run.state), _ptr(run.hist))
 
     def select_descend(self, run: "EnsembleSelection", rnd: int) -> None:
         """``run.hist`` consumed and re-zeroed, the state advanced by one round (``okx_ensemble_select_descend``)."""
-        s, k, q = run.shape
+        s, k, q = self._select_tables(run, True)
         self._ensemble_call("okx_ensemble_select_descend", int(rnd), s, k, _ptr(run.probs), q, _ptr(run.state), _ptr(run.hist))
 
     def select_finish(self, run: "EnsembleSelection") -> "EnsembleSelection":
         """``run.order`` / ``count`` / ``outside`` written from the state (``okx_ensemble_select_finish``)."""
-        s, k, q = run.shape
+        s, k, q = self._select_tables(run, True)
         self._ensemble_call("okx_ensemble_select_finish", s, k, q, _ptr(run.state), _ptr(run.order), _ptr(run.count), _ptr(run.outside))
         return run
 
@@ -336,15 +410,13 @@ class EnsembleReductions:
         is legal inside a stream capture.  Bit-identical from run to run: integer counting only.
         """
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
-        if out is None:
+        if self._new_result(out, (probs, limits), "probabilities and limits"):
             if probs is None:
                 raise ValueError("probs is needed (or out=, which carries its own)")
             out = self.select_prepare(s, k, probs, limits)
-        elif probs is not None or limits is not None:
-            raise ValueError("out= carries its own probabilities and limits")
         if out.shape[:2] != (s, k) or out.order.device != self.device:
             raise ValueError(f"out was prepared for [S, K] = {list(out.shape[:2])} on {out.order.device}")
-        q = out.shape[2]
+        q = self._select_tables(out, False)[2]
         scratch = self._ensemble_scratch("select", int(self.lib.okx_ensemble_select_scratch_bytes(s, k, q)))
         self._ensemble_call("okx_ensemble_select", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.probs), q, _ptr(out.limits),
                             _ptr(out.order), _ptr(out.count), _ptr(out.outside), _ptr(scratch), scratch.numel())
@@ -359,8 +431,6 @@ class EnsembleReductions:
         and > 0; None: 1) are validated by ``okx_ensemble_screen_check`` on the host and uploaded ONCE; the outputs are
         allocated, the survivor list with ``capacity`` slots (None: one per geometry).
         """
-        from .ensemble_stats import broadcast_limits, broadcast_scale
-
         s, k, g = int(steps), int(n_columns), int(n_geometries)
         if limits is None:
             raise ValueError("limits are needed: [S, K, 2], [K, 2] or [2] (lo, hi)")
@@ -395,21 +465,23 @@ class EnsembleReductions:
         """
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         row = int(first_row) if first_row is not None else (0 if out is None else int(geometry_offset))
-        if out is None:
-            if limits is None:
-                raise ValueError("limits are needed (or out=, which carries its own)")
-            if accumulate:
-                raise ValueError("accumulate=True adds to out=")
+        if out is None and limits is None:
+            raise ValueError("limits are needed (or out=, which carries its own)")
+        if self._new_result(out, (limits, scale, capacity), "limits, scale and capacity", accumulate, "accumulate=True adds to out="):
             out = self.screen_prepare(s, k, limits, scale, row + g, capacity)
-        elif limits is not None or scale is not None or capacity is not None:
-            raise ValueError("out= carries its own limits, scale and capacity")
         if out.shape != (s, k) or out.blame.device != self.device:
             raise ValueError(f"out was prepared for [S, K] = {list(out.shape)} on {out.blame.device}")
+        rows = (_rows(out.flags),)
+        self._check_tables("out must hold contiguous device tables limits [S, K, 2], scale [S, K], flags [G], margin [G], entry [G], tally [4], "
+                           "blame [S, K, 2], pass_index [capacity] and pass_count [1]",
+                           [(out.limits, (s, k, 2), F64), (out.flags, rows, U8), (out.margin, rows, F64), (out.entry, rows, I32), (out.tally, (4,), I64),
+                            (out.blame, (s, k, 2), I64), (out.pass_index, (_rows(out.pass_index),), I64), (out.pass_count, (1,), I64)],
+                           [(out.scale, (s, k), F64)])
         if row < 0 or row + g > out.flags.shape[0]:
             raise ValueError(f"out holds {out.flags.shape[0]} geometries: rows [{row}, {row + g}) do not fit")
         scratch = self._ensemble_scratch("screen", int(self.lib.okx_ensemble_screen_scratch_bytes(g, s, k)))
         self._ensemble_call("okx_ensemble_screen", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.limits), _ptr(out.scale),
-                            int(geometry_offset), 1 if accumulate else 0, _ptr(out.flags[row:]), _ptr(out.margin[row:]), _ptr(out.entry[row:]),
+                            int(geometry_offset), 1 if accumulate else 0, _ptr(out.flags, row), _ptr(out.margin, row), _ptr(out.entry, row),
                             _ptr(out.tally), _ptr(out.blame), _ptr(out.pass_index), out.pass_index.shape[0], _ptr(out.pass_count),
                             _ptr(scratch), scratch.numel())
         return out
@@ -430,13 +502,9 @@ class EnsembleReductions:
         ``.finalize()`` copies to the host: mean, covariance, std, correlation.  Bit-identical from run to run; different
         chunkings agree to rounding.
         """
-        from .ensemble_stats import CovarianceAccumulator, check_covariance_arguments
-
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         dev = self.device
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
+        if self._new_result(out, (shift, entries), "shift and entries", accumulate):
             host = None if entries is None else np.ascontiguousarray(check_covariance_arguments(
                 entries.detach().cpu().numpy() if isinstance(entries, torch.Tensor) else entries, s * k))
             n = s * k if host is None else host.size
@@ -447,14 +515,12 @@ class EnsembleReductions:
             out = CovarianceAccumulator(torch.empty((n, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
                                         torch.empty(2, dtype=torch.int64, device=dev), shift, index, torch.empty(g, dtype=torch.uint8, device=dev),
                                         natural=host is None)  # (all entries in natural order: the call passes no entry list)
-        elif shift is not None or entries is not None:
-            raise ValueError("out= carries its own shift and entries")
-        n = int(out.entries.shape[0])
-        tables = (out.gram, out.sum, out.counts, out.shift, out.entries)
-        if tuple(out.shift.shape) != (s, k) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous() for t in tables) \
-                or out.entries.dtype != torch.int32 or out.gram.dtype != torch.float64 or out.sum.dtype != torch.float64 or out.counts.dtype != torch.int64:
-            raise ValueError(f"out must hold contiguous device tables gram [N, N], sum [N], counts [2], entries [N] and shift [S, K] = [{s}, {k}]")
-        used = out.used if out.used is not None and out.used.shape[0] >= g and out.used.is_contiguous() and out.used.device == dev else None
+        n = _rows(out.entries)
+        self._check_tables(f"out must hold contiguous device tables gram [N, N], sum [N], counts [2], entries [N] and shift [S, K] = [{s}, {k}]",
+                           [(out.gram, (n, n), F64), (out.sum, (n,), F64), (out.counts, (2,), I64), (out.shift, (s, k), F64), (out.entries, (n,), I32)])
+        used = out.used  # (written when it holds a byte per geometry of the call)
+        if used is not None and (used.dtype != U8 or used.shape[0] < g or not used.is_contiguous() or used.device != dev):
+            used = None
         scratch = self._ensemble_scratch("covariance", int(self.lib.okx_ensemble_covariance_scratch_bytes(g, s, k, n)))
         index = None if out.natural and n == s * k else _ptr(out.entries)
         self._ensemble_call("okx_ensemble_covariance", g, s, k, _ptr(values), ld, _ptr(status), stride, index, n, _ptr(out.shift),
@@ -469,8 +535,6 @@ class EnsembleReductions:
         validated (``okx_ensemble_curves_check``), a shared abscissa ``[S]`` is uploaded ONCE (an integer ``abscissa`` names a
         column of the table) and ``features [G, K, 12]`` / ``count [G, K]`` are allocated.
         """
-        from .ensemble_stats import CURVE_FIELDS, EnsembleCurves
-
         s, k, g = int(steps), int(n_columns), int(n_geometries)
         if g < 0:
             raise ValueError("negative geometry count")
@@ -508,24 +572,22 @@ class EnsembleReductions:
         """
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         row = int(first_row)
-        if out is None:
+        if self._new_result(out, (abscissa, scale, origin, degree, window), "abscissa, origin, scale, degree and window"):
             if scale is None:
                 raise ValueError("abscissa and scale are needed (or out=, which carries its own)")
             out = self.curves_prepare(s, k, row + g, abscissa=abscissa, scale=scale, origin=0.0 if origin is None else origin,
                                       degree=2 if degree is None else degree, window=window)
-        elif any(x is not None for x in (abscissa, scale, origin, degree, window)):
-            raise ValueError("out= carries its own abscissa, origin, scale, degree and window")
         f, n = out.features, out.count
-        if f.dim() != 3 or tuple(f.shape[1:]) != (k, 12) or tuple(n.shape) != (f.shape[0], k) or f.device != self.device or n.device != self.device \
-                or f.dtype != torch.float64 or n.dtype != torch.int32 or not f.is_contiguous() or not n.is_contiguous():
-            raise ValueError(f"out must hold contiguous device tables features [G, {k}, 12] and count [G, {k}]")
+        rows = _rows(f)
+        self._check_tables(f"out must hold contiguous device tables features [G, {k}, 12] and count [G, {k}]",
+                           [(f, (rows, k, CURVE_FIELDS), F64), (n, (rows, k), I32)], [(out.abscissa, (_rows(out.abscissa),), F64)])
         if out.abscissa is not None and out.abscissa.shape[0] != s:
             raise ValueError(f"out was prepared for {out.abscissa.shape[0]} steps")
         if row < 0 or row + g > f.shape[0]:
             raise ValueError(f"out holds {f.shape[0]} geometries: rows [{row}, {row + g}) do not fit")
         kx, origin, scale, lo, hi, degree = out.arguments
         self._ensemble_call("okx_ensemble_curves", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(out.abscissa), max(kx, 0), origin, scale,
-                            lo, hi, degree, _ptr(f[row:]), _ptr(n[row:]))
+                            lo, hi, degree, _ptr(f, row), _ptr(n, row))
         return out
 
     # ---- okx_ensemble_front: the nondominated (Pareto) front of the ensemble on up to 8 objectives (ensemble_stats.EnsembleFront) ----
@@ -537,8 +599,6 @@ class EnsembleReductions:
         (``okx_ensemble_front_check``) and kept as the host arrays every launch reads; ``dominated [G]``, ``tally [3]`` and the
         front list with ``capacity`` slots (None: one per geometry) are allocated.
         """
-        from .ensemble_stats import check_front_arguments
-
         s, k, g = int(steps), int(n_columns), int(n_geometries)
         if g < 0 or (capacity is not None and int(capacity) < 0):
             raise ValueError("negative geometry count or capacity")
@@ -565,28 +625,19 @@ class EnsembleReductions:
         allocates nothing and is legal inside a stream capture.  Only comparisons: exact, and bit-identical from run to run.
         """
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
-        if out is None:
+        if self._new_result(out, (objectives, capacity), "objectives and capacity"):
             if objectives is None:
                 raise ValueError("objectives are needed (or out=, which carries its own)")
             out = self.front_prepare(s, k, g, objectives, capacity)
-        elif objectives is not None or capacity is not None:
-            raise ValueError("out= carries its own objectives and capacity")
         dev = self.device
         if out.dominated is None or out.dominated.shape[0] < g or out.tally.device != dev:
             raise ValueError(f"out holds no dominated table for {g} geometries on {dev}")
         m = int(out.entries.size)
-        lists = (out.front_index, out.front_values)
-        if tuple(out.front_values.shape) != (out.capacity, m) or any(t.device != dev or not t.is_contiguous() for t in (*lists, out.dominated, out.tally)) \
-                or out.front_index.dtype != torch.int64 or out.front_values.dtype != torch.float64 or out.dominated.dtype != torch.int32 \
-                or out.tally.dtype != torch.int64 or out.tally.numel() != 3:
-            raise ValueError(f"out must hold contiguous device tables dominated [G], tally [3], front_index [capacity] and front_values [capacity, {m}]")
-        mask_stride = 0
-        if mask is not None:
-            if mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev:
-                raise ValueError("mask must be a uint8 [G] device tensor")
-            mask_stride = mask.stride(0) if g > 1 else 1
-            if mask_stride < 1:
-                raise ValueError("mask must have a positive stride")
+        capacity = _rows(out.front_index)
+        self._check_tables(f"out must hold contiguous device tables dominated [G], tally [3], front_index [capacity] and front_values [capacity, {m}]",
+                           [(out.dominated, (_rows(out.dominated),), I32), (out.tally, (3,), I64), (out.front_index, (capacity,), I64),
+                            (out.front_values, (capacity, m), F64)])
+        mask_stride = self._check_mask(mask, g, contiguous=False)
         if index is not None and (index.dtype != torch.int64 or index.dim() != 1 or index.shape[0] != g or index.device != dev or not index.is_contiguous()):
             raise ValueError("index must be a contiguous int64 [G] device tensor")
         scratch = self._ensemble_scratch("front", int(self.lib.okx_ensemble_front_scratch_bytes(g, m)))
@@ -598,33 +649,70 @@ class EnsembleReductions:
 
     # ---- okx_ensemble_sample: the hardpoint table of a plan's ensemble, drawn on device (ensemble_sample.SamplePlan) ----
 
-    def _sample_tables(self, plan):
+    def _plan_tables(self, plan, build) -> dict:
+        """``build(plan)``, made ONCE per plan object: the entry is keyed by ``id(plan)``, guarded by a weak reference (an id may be
+        reused) and dropped when the plan dies."""
+        plans, key = self.__dict__.setdefault("_sample_plans", {}), id(plan)
+        held = plans.get(key)
+        if held is not None and held[0]() is plan:
+            return held[1]
+        tables = build(plan)
+        plans[key] = (weakref.ref(plan, lambda r: plans.pop(key, None) if plans.get(key, (None,))[0] is r else None), tables)
+        return tables
+
+    def _sample_tables(self, plan) -> dict:
         """The plan's tables on the device and its guards as the host array a launch reads, validated (``okx_ensemble_sample_check``)
         and uploaded ONCE per plan.  They are held for as long as the plan object lives and dropped with it (a search loop makes a
         plan per generation); whoever keeps a captured graph of a launch keeps its plan."""
-        import weakref
+        def build(plan):
+            ints, reals = plan.guard_table()
+            guards = (SampleGuard * max(1, len(plan.guards)))()
+            for i in range(len(plan.guards)):
+                guards[i] = SampleGuard(*(int(v) for v in ints[i]), float(reals[i, 0]), float(reals[i, 1]))
+            rc = self.lib.okx_ensemble_sample_check(0, 0, plan.n_total, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
+                                                    plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
+                                                    0 if plan.mixing is None else 1, guards, len(plan.guards), plan.stratify, plan.max_attempts)
+            _lib.check(rc, "okx_ensemble_sample")
+            up = lambda a: None if a is None else torch.tensor(np.asarray(a), device=self.device)  # noqa: E731
+            return dict(nominal=up(plan.nominal), coords=up(plan.coords), kind=up(plan.kind), bound=up(plan.bound_table()), mixing=up(plan.mixing),
+                        scale=up(plan.scale), guards=guards)
 
-        if not hasattr(self, "_sample_plans"):
-            self._sample_plans = {}
-        held = self._sample_plans.get(id(plan))
-        if held is not None and held[0]() is plan:
-            return held[1]
-        ints, reals = plan.guard_table()
-        guards = (SampleGuard * max(1, len(plan.guards)))()
-        for i in range(len(plan.guards)):
-            guards[i] = SampleGuard(*(int(v) for v in ints[i]), float(reals[i, 0]), float(reals[i, 1]))
-        rc = self.lib.okx_ensemble_sample_check(0, 0, plan.n_total, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
-                                                plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
-                                                0 if plan.mixing is None else 1, guards, len(plan.guards), plan.stratify, plan.max_attempts)
-        _lib.check(rc, "okx_ensemble_sample")
-        dev = self.device
-        up = lambda a: None if a is None else torch.tensor(np.asarray(a), device=dev)  # noqa: E731
-        tables = dict(nominal=up(plan.nominal), coords=up(plan.coords), kind=up(plan.kind), bound=up(plan.bound_table()), mixing=up(plan.mixing),
-                      scale=up(plan.scale), guards=guards)
-        plans, key = self._sample_plans, id(plan)
-        ref = weakref.ref(plan, lambda r, plans=plans, key=key: plans.pop(key, None) if plans.get(key, (None,))[0] is r else None)
-        plans[key] = (ref, tables)
-        return tables
+        return self._plan_tables(plan, build)
+
+    def _family_tables(self, fplan) -> dict:
+        """The wrapped plan's tables (``_sample_tables``) and the group table on the device, validated
+        (``okx_ensemble_sample_families_check``) and uploaded ONCE per plan object; dropped with it."""
+        def build(fplan):
+            plan = fplan.plan
+            tables = dict(self._sample_tables(plan))
+            rc = self.lib.okx_ensemble_sample_families_check(0, 0, fplan.n_families, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
+                                                             plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
+                                                             0 if plan.mixing is None else 1, fplan.group.ctypes.data_as(C.c_void_p), fplan.n_groups,
+                                                             tables["guards"], len(plan.guards), plan.stratify, plan.max_attempts)
+            _lib.check(rc, "okx_ensemble_sample_families")
+            tables["group"] = torch.tensor(np.asarray(fplan.group), device=self.device)
+            return tables
+
+        return self._plan_tables(fplan, build)
+
+    def _sample_out(self, who: str, plan, base, lo, hi, latents: bool, delta: bool, out) -> tuple:
+        """``(n, lo, out)`` of a draw of geometries ``[lo, hi)`` of ``plan`` (``base``: the ``SamplePlan`` that sets the table shapes):
+        the range checked, the ``EnsembleSample`` made or - ``out=`` - its tables checked, and ``out.lo`` set."""
+        lo = int(lo)
+        hi = int(plan.n_total) if hi is None else int(hi)
+        n = hi - lo
+        if n < 0 or lo < 0:
+            raise ValueError(f"{who}: bad range [{lo}, {hi})")
+        dev, p, f, z = self.device, base.n_points, base.n_coords, base.n_latents
+        if out is None:
+            return n, lo, EnsembleSample(torch.empty((n, p, 3), dtype=F64, device=dev), torch.empty((n, z), dtype=F64, device=dev) if latents else None,
+                                         torch.empty((n, f), dtype=F64, device=dev) if delta else None, torch.empty(n, dtype=U8, device=dev), lo)
+        self._check_tables(f"out must hold contiguous device tables hardpoints [{n}, {p}, 3], latents [{n}, {z}], delta [{n}, {f}] and flags [{n}]", [],
+                           [(out.hardpoints, (n, p, 3), F64), (out.latents, (n, z), F64), (out.delta, (n, f), F64), (out.flags, (n,), U8)])
+        if out.hardpoints is None:
+            raise ValueError("out holds no hardpoint table")
+        out.lo = lo
+        return n, lo, out
 
     def sample_ensemble(self, plan, lo: int = 0, hi: int | None = None, *, latents: bool = False, delta: bool = False, out=None) -> "EnsembleSample":
         """
@@ -634,55 +722,14 @@ class EnsembleReductions:
         those tables too.  ``out``: the ``EnsembleSample`` of an earlier call of the same shape to write into - with it (and a
         plan seen before) the call allocates nothing and is legal inside a stream capture.
         """
-        lo = int(lo)
-        hi = int(plan.n_total) if hi is None else int(hi)
-        n = hi - lo
-        if n < 0 or lo < 0:
-            raise ValueError(f"okx_ensemble_sample: bad range [{lo}, {hi})")
-        tables = self._sample_tables(plan)
-        dev, p, f, z = self.device, plan.n_points, plan.n_coords, plan.n_latents
-        if out is None:
-            out = EnsembleSample(torch.empty((n, p, 3), dtype=torch.float64, device=dev),
-                                 torch.empty((n, z), dtype=torch.float64, device=dev) if latents else None,
-                                 torch.empty((n, f), dtype=torch.float64, device=dev) if delta else None,
-                                 torch.empty(n, dtype=torch.uint8, device=dev), lo)
-        else:
-            for t, shape, dtype in ((out.hardpoints, (n, p, 3), torch.float64), (out.latents, (n, z), torch.float64), (out.delta, (n, f), torch.float64),
-                                    (out.flags, (n,), torch.uint8)):
-                if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous()):
-                    raise ValueError(f"out must hold contiguous device tables hardpoints [{n}, {p}, 3], latents [{n}, {z}], delta [{n}, {f}] and flags [{n}]")
-            if out.hardpoints is None:
-                raise ValueError("out holds no hardpoint table")
-            out.lo = lo
-        self._ensemble_call("okx_ensemble_sample", n, lo, int(plan.n_total), C.c_uint64(plan.seed), p, _ptr(tables["nominal"]), _ptr(tables["coords"]), f,
-                            _ptr(tables["kind"]), _ptr(tables["bound"]), z, _ptr(tables["mixing"]), _ptr(tables["scale"]), tables["guards"],
+        n, lo, out = self._sample_out("okx_ensemble_sample", plan, plan, lo, hi, latents, delta, out)
+        t = self._sample_tables(plan)
+        self._ensemble_call("okx_ensemble_sample", n, lo, int(plan.n_total), C.c_uint64(plan.seed), plan.n_points, _ptr(t["nominal"]), _ptr(t["coords"]),
+                            plan.n_coords, _ptr(t["kind"]), _ptr(t["bound"]), plan.n_latents, _ptr(t["mixing"]), _ptr(t["scale"]), t["guards"],
                             len(plan.guards), plan.stratify, plan.max_attempts, _ptr(out.hardpoints), _ptr(out.latents), _ptr(out.delta), _ptr(out.flags))
         return out
 
     # ---- okx_ensemble_sample_families: the pick-freeze ensemble of a FamilyPlan, drawn on device (ensemble_sample.FamilyPlan) ----
-
-    def _family_tables(self, fplan):
-        """The wrapped plan's tables (``_sample_tables``) and the group table on the device, validated
-        (``okx_ensemble_sample_families_check``) and uploaded ONCE per plan object; dropped with it."""
-        import weakref
-
-        if not hasattr(self, "_family_plans"):
-            self._family_plans = {}
-        held = self._family_plans.get(id(fplan))
-        if held is not None and held[0]() is fplan:
-            return held[1]
-        plan = fplan.plan
-        tables = dict(self._sample_tables(plan))
-        rc = self.lib.okx_ensemble_sample_families_check(0, 0, fplan.n_families, plan.n_points, plan.coords.ctypes.data_as(C.c_void_p), plan.n_coords,
-                                                         plan.kind.ctypes.data_as(C.c_void_p), plan.bound.ctypes.data_as(C.c_void_p), plan.n_latents,
-                                                         0 if plan.mixing is None else 1, fplan.group.ctypes.data_as(C.c_void_p), fplan.n_groups,
-                                                         tables["guards"], len(plan.guards), plan.stratify, plan.max_attempts)
-        _lib.check(rc, "okx_ensemble_sample_families")
-        tables["group"] = torch.tensor(np.asarray(fplan.group), device=self.device)
-        plans, key = self._family_plans, id(fplan)
-        ref = weakref.ref(fplan, lambda r, plans=plans, key=key: plans.pop(key, None) if plans.get(key, (None,))[0] is r else None)
-        plans[key] = (ref, tables)
-        return tables
 
     def sample_families(self, plan, lo: int = 0, hi: int | None = None, *, latents: bool = False, delta: bool = False, out=None) -> "EnsembleSample":
         """
@@ -692,30 +739,12 @@ class EnsembleReductions:
         tensors; ``flags`` is 1 where a guard fails (the ``mask`` of ``sobol_ensemble``).  ``out``: the ``EnsembleSample`` of an earlier
         call of the same shape - with it (and a plan seen before) the call allocates nothing and is legal inside a stream capture.
         """
-        lo = int(lo)
-        hi = int(plan.n_total) if hi is None else int(hi)
-        n = hi - lo
-        if n < 0 or lo < 0:
-            raise ValueError(f"okx_ensemble_sample_families: bad range [{lo}, {hi})")
-        tables = self._family_tables(plan)
         base = plan.plan
-        dev, p, f, z = self.device, base.n_points, base.n_coords, base.n_latents
-        if out is None:
-            out = EnsembleSample(torch.empty((n, p, 3), dtype=torch.float64, device=dev),
-                                 torch.empty((n, z), dtype=torch.float64, device=dev) if latents else None,
-                                 torch.empty((n, f), dtype=torch.float64, device=dev) if delta else None,
-                                 torch.empty(n, dtype=torch.uint8, device=dev), lo)
-        else:
-            for t, shape, dtype in ((out.hardpoints, (n, p, 3), torch.float64), (out.latents, (n, z), torch.float64), (out.delta, (n, f), torch.float64),
-                                    (out.flags, (n,), torch.uint8)):
-                if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous()):
-                    raise ValueError(f"out must hold contiguous device tables hardpoints [{n}, {p}, 3], latents [{n}, {z}], delta [{n}, {f}] and flags [{n}]")
-            if out.hardpoints is None:
-                raise ValueError("out holds no hardpoint table")
-            out.lo = lo
-        self._ensemble_call("okx_ensemble_sample_families", n, lo, int(plan.n_families), C.c_uint64(base.seed), p, _ptr(tables["nominal"]),
-                            _ptr(tables["coords"]), f, _ptr(tables["kind"]), _ptr(tables["bound"]), z, _ptr(tables["mixing"]), _ptr(tables["scale"]),
-                            _ptr(tables["group"]), int(plan.n_groups), tables["guards"], len(base.guards), base.stratify, _ptr(out.hardpoints),
+        n, lo, out = self._sample_out("okx_ensemble_sample_families", plan, base, lo, hi, latents, delta, out)
+        t = self._family_tables(plan)
+        self._ensemble_call("okx_ensemble_sample_families", n, lo, int(plan.n_families), C.c_uint64(base.seed), base.n_points, _ptr(t["nominal"]),
+                            _ptr(t["coords"]), base.n_coords, _ptr(t["kind"]), _ptr(t["bound"]), base.n_latents, _ptr(t["mixing"]), _ptr(t["scale"]),
+                            _ptr(t["group"]), int(plan.n_groups), t["guards"], len(base.guards), base.stratify, _ptr(out.hardpoints),
                             _ptr(out.latents), _ptr(out.delta), _ptr(out.flags))
         return out
 
@@ -735,32 +764,32 @@ class EnsembleReductions:
         legal inside a stream capture.  ``.finalize()`` copies to the host: first-order and total-order indices per group.
         Bit-identical from run to run; different chunkings agree to rounding, exactly when the sums are exact.
         """
-        from .ensemble_stats import SOBOL_FIELDS, SOBOL_MAX_GROUPS, SobolAccumulator
-
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
         d = int(n_groups)
-        if not 1 <= d <= SOBOL_MAX_GROUPS:
-            raise ValueError(f"okx_ensemble_sobol: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
-        if g % (d + 2):
-            raise ValueError(f"okx_ensemble_sobol: {g} geometries are no whole families of {d + 2}")
-        dev = self.device
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
-            out = SobolAccumulator(torch.empty((s, k, SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=dev), self._ensemble_shift(shift, values, g, s, k),
-                                   group_names)
-        elif shift is not None:
-            raise ValueError("out= carries its own shift")
-        if tuple(out.acc.shape) != (s, k, SOBOL_FIELDS + 3 * d) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != torch.float64 for t in (out.acc, out.shift)):
-            raise ValueError(f"out must hold contiguous device tables acc [S, K, {SOBOL_FIELDS + 3 * d}] and shift [S, K] = [{s}, {k}]")
-        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev or not mask.is_contiguous()):
-            raise ValueError("mask must be a contiguous uint8 [G] device tensor")
-        n = g // (d + 2)
+        n, out = self._sobol_out("okx_ensemble_sobol", (g, s, k), d, 0, mask, shift, values, out, accumulate, (s, k, SOBOL_FIELDS + 3 * d),
+                                 f"out must hold contiguous device tables acc [S, K, {SOBOL_FIELDS + 3 * d}] and shift [S, K] = [{s}, {k}]",
+                                 lambda acc, shift: SobolAccumulator(acc, shift, group_names))
         scratch = self._ensemble_scratch("sobol", int(self.lib.okx_ensemble_sobol_scratch_bytes(n, d, s, k)))
         self._ensemble_call("okx_ensemble_sobol", n, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift),
                             1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())
         return out
+
+    def _sobol_out(self, who: str, table: tuple, d: int, family_offset: int, mask, shift, values, out, accumulate: bool, acc_shape: tuple, message: str,
+                   new) -> tuple:
+        """The front end ``sobol_ensemble`` and ``sobol_bootstrap_ensemble`` share: the group count, whole families, the accumulator
+        - ``new(acc, shift)`` or ``out=``, its tables checked (``message``) - and the mask.  Returns ``(families, out)``."""
+        g, s, k = table
+        if not 1 <= d <= SOBOL_MAX_GROUPS:
+            raise ValueError(f"{who}: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
+        if g % (d + 2):
+            raise ValueError(f"{who}: {g} geometries are no whole families of {d + 2}")
+        if family_offset < 0:
+            raise ValueError(f"{who}: negative family_offset")
+        if self._new_result(out, (shift,), "shift", accumulate):
+            out = new(torch.empty(acc_shape, dtype=F64, device=self.device), self._ensemble_shift(shift, values, g, s, k))
+        self._check_tables(message, [(out.acc, acc_shape, F64), (out.shift, (s, k), F64)])
+        self._check_mask(mask, g, contiguous=True)
+        return g // (d + 2), out
 
     # ---- okx_ensemble_bootstrap_weights / okx_ensemble_sobol_bootstrap: how far to trust the indices (ensemble_stats.EnsembleSobolBootstrap) ----
 
@@ -771,15 +800,12 @@ class EnsembleReductions:
         a pure function of ``(seed, row, replicate)`` wherever and in whatever ranges they are drawn.  ``out``: the tensor of an earlier
         call of the same shape (then the call allocates nothing and is legal inside a stream capture).
         """
-        from .ensemble_stats import check_replicates
-
         n, r, lo = int(n_rows), check_replicates("okx_ensemble_bootstrap_weights", n_replicates), int(row_offset)
         if n < 0 or lo < 0:
             raise ValueError(f"okx_ensemble_bootstrap_weights: bad range [{lo}, {lo + n})")
         if out is None:
-            out = torch.empty((n, r), dtype=torch.uint8, device=self.device)
-        elif tuple(out.shape) != (n, r) or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 [{n}, {r}] device tensor")
+            out = torch.empty((n, r), dtype=U8, device=self.device)
+        self._check_tables(f"out must be a contiguous uint8 [{n}, {r}] device tensor", [(out, (n, r), U8)])
         self._ensemble_call("okx_ensemble_bootstrap_weights", n, lo, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), r, _ptr(out))
         return out
 
@@ -794,34 +820,14 @@ class EnsembleReductions:
         replicates' indices, their standard deviations and percentile intervals.  Bit-identical from run to run; different chunkings
         agree to rounding, exactly when the sums are exact.
         """
-        from .ensemble_stats import SOBOL_FIELDS, SOBOL_MAX_GROUPS, SobolBootstrapAccumulator, check_replicates
-
         who = "okx_ensemble_sobol_bootstrap"
         g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
-        d, r, first = int(n_groups), check_replicates(who, n_replicates), int(family_offset)
-        if not 1 <= d <= SOBOL_MAX_GROUPS:
-            raise ValueError(f"{who}: {d} groups, 1 to {SOBOL_MAX_GROUPS} allowed")
-        if g % (d + 2):
-            raise ValueError(f"{who}: {g} geometries are no whole families of {d + 2}")
-        if first < 0:
-            raise ValueError(f"{who}: negative family_offset")
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        dev = self.device
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs the accumulator to merge into (out=)")
-            out = SobolBootstrapAccumulator(torch.empty((r, s, k, SOBOL_FIELDS + 3 * d), dtype=torch.float64, device=dev),
-                                            self._ensemble_shift(shift, values, g, s, k), seed, group_names)
-        elif shift is not None:
-            raise ValueError("out= carries its own shift")
-        elif out.seed != seed:
+        d, r, first, seed = int(n_groups), check_replicates(who, n_replicates), int(family_offset), int(seed) & 0xFFFFFFFFFFFFFFFF
+        n, out = self._sobol_out(who, (g, s, k), d, first, mask, shift, values, out, accumulate, (r, s, k, SOBOL_FIELDS + 3 * d),
+                                 f"out must hold contiguous device tables acc [R, S, K, {SOBOL_FIELDS + 3 * d}] = [{r}, {s}, {k}, .] and shift [S, K]",
+                                 lambda acc, shift: SobolBootstrapAccumulator(acc, shift, seed, group_names))
+        if out.seed != seed:
             raise ValueError(f"out= was taken with seed {out.seed}, not {seed}")
-        if tuple(out.acc.shape) != (r, s, k, SOBOL_FIELDS + 3 * d) or any(not isinstance(t, torch.Tensor) or t.device != dev or not t.is_contiguous()
-                                                                         or t.dtype != torch.float64 for t in (out.acc, out.shift)):
-            raise ValueError(f"out must hold contiguous device tables acc [R, S, K, {SOBOL_FIELDS + 3 * d}] = [{r}, {s}, {k}, .] and shift [S, K]")
-        if mask is not None and (mask.dtype != torch.uint8 or mask.dim() != 1 or mask.shape[0] != g or mask.device != dev or not mask.is_contiguous()):
-            raise ValueError("mask must be a contiguous uint8 [G] device tensor")
-        n = g // (d + 2)
         scratch = self._ensemble_scratch("sobol_bootstrap", int(self.lib.okx_ensemble_sobol_bootstrap_scratch_bytes(n, d, s, k, r)))
         self._ensemble_call(who, n, first, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift), C.c_uint64(seed), r,
                             1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())

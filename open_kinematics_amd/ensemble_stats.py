@@ -47,6 +47,40 @@ def _is_tensor(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+def _same_table(a, b) -> bool:
+    """One table object on both sides (the sharded exchange) needs no comparison - on a device that would be a sync -; else by content."""
+    return a is b or bool(__import__("torch").equal(a, b) if _is_tensor(a) else np.array_equal(a, b))
+
+
+def _same_shape(a, b) -> bool:
+    return tuple(a.shape) == tuple(b.shape)
+
+
+class _Accumulator:
+    """What the four accumulators share.  A class names its tables once (``TABLES``, constructor arguments; the first is never None)
+    and the other constructor arguments a copy carries over (``CARRIED``; ``DEVICE_ONLY``: those a host copy drops)."""
+
+    TABLES: tuple = ()
+    CARRIED: tuple = ()
+    DEVICE_ONLY: tuple = ()
+
+    def _copy(self, convert, carried):
+        return type(self)(**{name: None if getattr(self, name) is None else convert(getattr(self, name)) for name in self.TABLES},
+                          **{name: getattr(self, name) for name in carried})
+
+    def numpy(self):
+        """Host NumPy copy (self when it is one already)."""
+        if not _is_tensor(getattr(self, self.TABLES[0])):
+            return self
+        return self._copy(lambda t: t.detach().cpu().numpy(), [name for name in self.CARRIED if name not in self.DEVICE_ONLY])
+
+    def to(self, device):
+        """The tables as torch tensors on ``device``."""
+        import torch
+
+        return self._copy(lambda t: torch.as_tensor(t).to(device), self.CARRIED)
+
+
 @dataclass
 class EnsembleStats:
     """
@@ -74,11 +108,13 @@ class EnsembleStats:
     factor_names: list | None = None
 
 
-class EnsembleAccumulator:
+class EnsembleAccumulator(_Accumulator):
     """
     The raw tables of ``okx_ensemble_reduce``: ``acc [S, K, ENS_FIELDS + P]`` float64, ``shift [S, K]`` and, with factors,
     ``factor_acc [P + P (P + 1) / 2 + 1]`` - NumPy arrays or torch tensors (host or device), whatever produced them.
     """
+
+    TABLES, CARRIED = ("acc", "shift", "factor_acc"), ("factor_names",)
 
     def __init__(self, acc, shift, factor_acc=None, factor_names=None):
         self.acc = acc
@@ -103,20 +139,6 @@ class EnsembleAccumulator:
         shift = np.asarray(shift, dtype=np.float64).reshape(steps, n_columns)
         return cls(acc, shift, np.zeros(factor_moment_count(n_factors)) if n_factors else None, factor_names)
 
-    def numpy(self) -> "EnsembleAccumulator":
-        """Host NumPy copy (self when it is one already)."""
-        if not _is_tensor(self.acc):
-            return self
-        host = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
-        return EnsembleAccumulator(host(self.acc), host(self.shift), host(self.factor_acc), self.factor_names)
-
-    def to(self, device) -> "EnsembleAccumulator":
-        """The tables as torch tensors on ``device``."""
-        import torch
-
-        move = lambda t: None if t is None else torch.as_tensor(t).to(device)  # noqa: E731
-        return EnsembleAccumulator(move(self.acc), move(self.shift), move(self.factor_acc), self.factor_names)
-
     def merge(self, other: "EnsembleAccumulator") -> "EnsembleAccumulator":
         """
         ``self`` then ``other`` as one accumulator (a new one; both stay): sums add, an extreme that is strictly better
@@ -124,13 +146,11 @@ class EnsembleAccumulator:
         makes a merge additions and comparisons only.  Works on NumPy arrays and on torch tensors alike.
         """
         a, b = self.acc, other.acc
-        if tuple(a.shape) != tuple(b.shape):
+        if not _same_shape(a, b):
             raise ValueError("accumulators of different shapes")
-        xp = __import__("torch") if _is_tensor(a) else np
-        # (one table object on both sides - the sharded exchange - needs no comparison: on a device that would be a sync)
-        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
-        if not bool(same):
+        if not _same_table(self.shift, other.shift):
             raise ValueError("accumulators taken with different shifts cannot be merged")
+        xp = __import__("torch") if _is_tensor(a) else np
         out = a + b
         for value, arg, better in ((ENS_MIN, ENS_ARGMIN, lambda x, y: x < y), (ENS_MAX, ENS_ARGMAX, lambda x, y: x > y)):
             av, ai, bv, bi = a[..., value], a[..., arg], b[..., value], b[..., arg]
@@ -662,12 +682,14 @@ def check_covariance_arguments(entries, n_table_entries: int) -> np.ndarray:
     return e.astype(np.int32)
 
 
-class CovarianceAccumulator:
+class CovarianceAccumulator(_Accumulator):
     """
     The raw tables of ``okx_ensemble_covariance``: ``gram [N, N]`` and ``sum [N]`` float64, ``counts [2]`` int64 (used,
     dropped), ``shift [S, K]`` and ``entries [N]`` int32 - NumPy arrays or torch tensors (host or device), whatever produced
     them.  ``used [G]`` uint8 (or None) is the per-geometry byte of the LAST call that filled it.
     """
+
+    TABLES, CARRIED, DEVICE_ONLY = ("gram", "sum", "counts", "shift", "entries", "used"), ("natural",), ("natural",)
 
     def __init__(self, gram, sum, counts, shift, entries, used=None, *, natural: bool = False):  # noqa: A002
         self.gram, self.sum, self.counts, self.shift, self.entries, self.used = gram, sum, counts, shift, entries, used
@@ -683,21 +705,12 @@ class CovarianceAccumulator:
         e = check_covariance_arguments(entries, shift.size)
         return cls(np.zeros((e.size, e.size)), np.zeros(e.size), np.zeros(2, dtype=np.int64), shift, e)
 
-    def numpy(self) -> "CovarianceAccumulator":
-        """Host NumPy copy (self when it is one already)."""
-        if not _is_tensor(self.gram):
-            return self
-        host = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
-        return CovarianceAccumulator(host(self.gram), host(self.sum), host(self.counts), host(self.shift), host(self.entries), host(self.used))
-
     def merge(self, other: "CovarianceAccumulator") -> "CovarianceAccumulator":
         """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been
         taken with the same shift and the same entries.  Works on NumPy arrays and on torch tensors alike."""
-        xp = __import__("torch") if _is_tensor(self.gram) else np
-        equal = (lambda a, b: a is b or bool(xp.equal(a, b))) if xp is not np else (lambda a, b: a is b or np.array_equal(a, b))
-        if tuple(self.entries.shape) != tuple(other.entries.shape) or not equal(self.entries, other.entries):
+        if not (_same_shape(self.entries, other.entries) and _same_table(self.entries, other.entries)):
             raise ValueError("accumulators of different entries cannot be merged")
-        if tuple(self.shift.shape) != tuple(other.shift.shape) or not equal(self.shift, other.shift):
+        if not (_same_shape(self.shift, other.shift) and _same_table(self.shift, other.shift)):
             raise ValueError("accumulators taken with different shifts cannot be merged")
         return CovarianceAccumulator(self.gram + other.gram, self.sum + other.sum, self.counts + other.counts, self.shift, self.entries)
 
@@ -1044,11 +1057,13 @@ class EnsembleSobol:
     group_names: list | None = None
 
 
-class SobolAccumulator:
+class SobolAccumulator(_Accumulator):
     """
     The raw tables of ``okx_ensemble_sobol``: ``acc [S, K, SOBOL_FIELDS + 3 D]`` float64 and ``shift [S, K]`` - NumPy arrays or torch
     tensors (host or device), whatever produced them.
     """
+
+    TABLES, CARRIED = ("acc", "shift"), ("group_names",)
 
     def __init__(self, acc, shift, group_names=None):
         self.acc, self.shift = acc, shift
@@ -1065,20 +1080,12 @@ class SobolAccumulator:
         """The accumulator of no family at all (the neutral element of ``merge``), NumPy."""
         return cls(np.zeros((steps, n_columns, SOBOL_FIELDS + 3 * n_groups)), np.asarray(shift, dtype=np.float64).reshape(steps, n_columns), group_names)
 
-    def numpy(self) -> "SobolAccumulator":
-        """Host NumPy copy (self when it is one already)."""
-        if not _is_tensor(self.acc):
-            return self
-        return SobolAccumulator(self.acc.detach().cpu().numpy(), self.shift.detach().cpu().numpy(), self.group_names)
-
     def merge(self, other: "SobolAccumulator") -> "SobolAccumulator":
         """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been taken
         with the same shift.  Works on NumPy arrays and on torch tensors alike."""
-        if tuple(self.acc.shape) != tuple(other.acc.shape):
+        if not _same_shape(self.acc, other.acc):
             raise ValueError("accumulators of different shapes")
-        xp = __import__("torch") if _is_tensor(self.acc) else np
-        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
-        if not bool(same):
+        if not _same_table(self.shift, other.shift):
             raise ValueError("accumulators taken with different shifts cannot be merged")
         return SobolAccumulator(self.acc + other.acc, self.shift, self.group_names)
 
@@ -1240,12 +1247,14 @@ class EnsembleSobolBootstrap:
         return lo, hi
 
 
-class SobolBootstrapAccumulator:
+class SobolBootstrapAccumulator(_Accumulator):
     """
     The raw tables of ``okx_ensemble_sobol_bootstrap``: ``acc [R, S, K, SOBOL_FIELDS + 3 D]`` float64 - replicate ``r`` holds the fields
     of a ``SobolAccumulator`` with every family's term multiplied by the family's weight - ``shift [S, K]`` and the ``seed`` of the
     weights; NumPy arrays or torch tensors (host or device).
     """
+
+    TABLES, CARRIED = ("acc", "shift"), ("seed", "group_names")
 
     def __init__(self, acc, shift, seed: int, group_names=None):
         self.acc, self.shift, self.seed = acc, shift, int(seed)
@@ -1262,22 +1271,14 @@ class SobolBootstrapAccumulator:
     def n_replicates(self) -> int:
         return int(self.acc.shape[0])
 
-    def numpy(self) -> "SobolBootstrapAccumulator":
-        """Host NumPy copy (self when it is one already)."""
-        if not _is_tensor(self.acc):
-            return self
-        return SobolBootstrapAccumulator(self.acc.detach().cpu().numpy(), self.shift.detach().cpu().numpy(), self.seed, self.group_names)
-
     def merge(self, other: "SobolBootstrapAccumulator") -> "SobolBootstrapAccumulator":
         """``self`` then ``other`` as one accumulator (a new one): additions only, which is why both must have been taken with the same
         shift and - the weights of a family are a function of the seed - the same seed."""
-        if tuple(self.acc.shape) != tuple(other.acc.shape):
+        if not _same_shape(self.acc, other.acc):
             raise ValueError("accumulators of different shapes")
         if self.seed != other.seed:
             raise ValueError("accumulators taken with different seeds cannot be merged")
-        xp = __import__("torch") if _is_tensor(self.acc) else np
-        same = self.shift is other.shift or (xp.equal(self.shift, other.shift) if xp is not np else np.array_equal(self.shift, other.shift))
-        if not bool(same):
+        if not _same_table(self.shift, other.shift):
             raise ValueError("accumulators taken with different shifts cannot be merged")
         return SobolBootstrapAccumulator(self.acc + other.acc, self.shift, self.seed, self.group_names)
 

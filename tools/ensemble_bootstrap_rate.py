@@ -21,16 +21,13 @@ ensemble_stats.sobol_bootstrap_host exactly in the integer fields and within 2 (
 
 from __future__ import annotations
 
-import argparse
-import json
 import math
-import os
 import statistics
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
+import ensemble_rate_common as common
+from ensemble_rate_common import timed
+
 
 U = 2.0 ** -53
 PEAK_FP64_VECTOR = 78.6e12   # MI355X datasheet, FLOP/s
@@ -52,32 +49,6 @@ def measure_one(args, by_point: bool, replicates: list) -> dict:
     g = n * m
     seed = fplan.plan.seed
 
-    def events(fn, count):
-        out = []
-        for _ in range(count):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def timed(passes):
-        for fn in passes.values():
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        runs = {name: [] for name in passes}
-        for _ in range(4):
-            for name, fn in passes.items():
-                runs[name] += events(fn, max(1, args.reps // 4))
-        out = {}
-        for name, r in runs.items():
-            q = statistics.quantiles(r, n=4)
-            out[name] = {"median": statistics.median(r), "interquartile": q[2] - q[0], "runs": r}
-        return out
-
     pipe = ShardedEnsemble(dp, fplan, rel, s, metric_columns=columns, reduce=True, sobol=True, chain_len=1, predictor=False)
     pipe.step()
     torch.cuda.synchronize()
@@ -91,7 +62,7 @@ def measure_one(args, by_point: bool, replicates: list) -> dict:
     for r in replicates:
         passes[f"bootstrap_R{r}"] = lambda r=r: dp.sobol_bootstrap_ensemble(table, n_replicates=r, seed=seed, out=boots[r], **table_kw)
         passes[f"weights_R{r}"] = lambda r=r: dp.bootstrap_weights(n, r, seed, out=weights[r])
-    times = timed(passes)
+    times = timed(passes, args.reps)
     torch.cuda.synchronize()
     copy_ms = []
     for _ in range(max(1, args.reps // 4)):
@@ -163,6 +134,15 @@ def measure_one(args, by_point: bool, replicates: list) -> dict:
     }
 
 
+def measure(args) -> list:
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this tool measures on the device and has no other path")
+    replicates = [int(r) for r in args.replicates.split(",")]
+    return [measure_one(args, by_point=which == "10", replicates=replicates) for which in args.groups.split(",")]
+
+
 def summary(results: list) -> str:
     lines = []
     for res in results:
@@ -181,30 +161,12 @@ def summary(results: list) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--families", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
+    ap = common.parser(families=4096, steps_per_geometry=256, rehearsal=False)
     ap.add_argument("--groups", default="10,30", help="which groupings to measure: 10 (by point) and / or 30 (by coordinate)")
     ap.add_argument("--replicates", default="64,256")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--check-families", type=int, default=16, help="families compared with the host definition")
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    import torch
-
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this tool measures on the device and has no other path")
-    replicates = [int(r) for r in args.replicates.split(",")]
-    results = [measure_one(args, by_point=which == "10", replicates=replicates) for which in args.groups.split(",")]
-    text = json.dumps(results, indent=1)
-    print(summary(results))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(results))
-    return 0
+    return common.run(ap.parse_args(), measure, summary, echo=False)
 
 
 if __name__ == "__main__":

@@ -21,20 +21,14 @@ entries (default: all).
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-from ensemble_reduce_rate import FP64_VECTOR_PEAK, HBM_PEAK, build  # noqa: E402
+import ensemble_rate_common as common
+from ensemble_rate_common import alternated, rank, spread, step_ms
+from ensemble_reduce_rate import FP64_VECTOR_PEAK, HBM_PEAK, build
 
 
 def subset(steps: int, n_columns: int, n_steps: int = 9) -> list:
@@ -45,44 +39,26 @@ def subset(steps: int, n_columns: int, n_steps: int = 9) -> list:
 
 def rank_main(args) -> None:
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
-    entries = [int(x) for x in args.entries.split(",")] if args.entries else True
-    pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True,
-                           covariance=entries, chain_len=1, predictor=False)
-    acc = pipe.step()
-    torch.cuda.synchronize()
-    merged, fin = pipe.covariance_accumulator, pipe.covariance()
-    torch.save({"gram": merged.gram.cpu(), "sum": merged.sum.cpu(), "counts": merged.counts.cpu(), "entries": merged.entries.cpu(),
-                "shift": acc.shift.cpu(), "covariance": fin.covariance, "count": fin.count, "used": pipe.covariance_local_used.cpu(),
-                "sent": pipe.covariance_exchange_bytes_per_rank, "range": pipe.geometry_range, "pieces": pipe.pieces},
-               os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
+        entries = [int(x) for x in args.entries.split(",")] if args.entries else True
+        pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True,
+                               covariance=entries, chain_len=1, predictor=False)
+        acc = pipe.step()
+        torch.cuda.synchronize()
+        merged, fin = pipe.covariance_accumulator, pipe.covariance()
+        torch.save({"gram": merged.gram.cpu(), "sum": merged.sum.cpu(), "counts": merged.counts.cpu(), "entries": merged.entries.cpu(),
+                    "shift": acc.shift.cpu(), "covariance": fin.covariance, "count": fin.count, "used": pipe.covariance_local_used.cpu(),
+                    "sent": pipe.covariance_exchange_bytes_per_rank, "range": pipe.geometry_range, "pieces": pipe.pieces},
+                   os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 38900 + os.getpid() % 1000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--geometries", str(args.geometries), "--steps-per-geometry", str(args.steps_per_geometry), "--chunks", str(args.chunks),
-                               "--entries", args.entries, "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 38900, ["--geometries", args.geometries, "--steps-per-geometry", args.steps_per_geometry,
+                                                        "--chunks", args.chunks, "--entries", args.entries], span=1000)
 
 
 def measure(args) -> dict:
@@ -106,21 +82,6 @@ def measure(args) -> dict:
     torch.cuda.synchronize()
     values, status, shift = covaried.metric_local, covaried.info_local[:, 32], covaried.local_accumulator.shift
     reps = args.reps
-
-    def events(fn, n=reps):
-        out = []
-        for _ in range(n):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
 
     # (a) the pass, (b) the torch formulation beside it - alternated block by block so that a drift hits all alike
     full = dp.covariance_ensemble(values, steps_per_geometry=s, status=status, shift=shift)
@@ -151,14 +112,7 @@ def measure(args) -> dict:
     fns = {"pass_1024": lambda: dp.covariance_ensemble(values, steps_per_geometry=s, status=status, out=full), "pass_1024_valu": valu_pass,
            "pass_36": lambda: dp.covariance_ensemble(values, steps_per_geometry=s, status=status, out=part),
            "torch_1024": torch_form(None), "torch_36": torch_form(index)}
-    for fn in fns.values():
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    runs = {name: [] for name in fns}
-    for _ in range(4):
-        for name, fn in fns.items():
-            runs[name] += events(fn, max(1, reps // 4))
+    runs = alternated(fns, reps)
     med = {name: statistics.median(r) for name, r in runs.items()}
     valu_gap = float(((full.gram - other.gram).abs() / torch.sqrt(torch.outer(torch.diag(full.gram), torch.diag(full.gram))).clamp_min(1e-300)).max())
     t_gram, t_sum, t_used = torch_form(None)()
@@ -184,14 +138,6 @@ def measure(args) -> dict:
                   and np.array_equal(got.used, want.used))
 
     # (d) the sharded ensemble's step with and without the covariance, alternated
-    def step_ms(fn, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / n * 1e3
-
     rounds = [(step_ms(reduced.step, args.steps), step_ms(covaried.step, args.steps)) for _ in range(5)]
     off, on = statistics.median(r[0] for r in rounds), statistics.median(r[1] for r in rounds)
 
@@ -248,36 +194,9 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--chunks", type=int, default=0)
+    ap = common.parser(geometries=4096, steps_per_geometry=256, steps=50, warmup=10, reps=20, chunks=0)
     ap.add_argument("--entries", default="")
-    ap.add_argument("--timeout", type=float, default=500.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    return common.run(ap.parse_args(), measure, summary, rank_main, rehearse)
 
 
 if __name__ == "__main__":

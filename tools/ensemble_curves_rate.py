@@ -21,20 +21,14 @@ tests/test_gpu_ensemble_curves.py compares.
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-from ensemble_reduce_rate import HBM_PEAK, build  # noqa: E402
+import ensemble_rate_common as common
+from ensemble_rate_common import alternated, rank, spread
+from ensemble_reduce_rate import HBM_PEAK, build
 
 STAT_FIELDS = ("count", "rejected", "mean", "variance", "std", "min", "max", "argmin", "argmax", "sensitivity", "intercept", "r2")
 
@@ -55,43 +49,25 @@ def rank_main(args) -> None:
     import dataclasses
 
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
-    pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True,
-                           factors="hardpoints" if args.geometries > 2 else None, curves=curve_arguments(rel), chain_len=1, predictor=False)
-    acc = pipe.step()
-    torch.cuda.synchronize()
-    stats, local = pipe.curve_stats(), pipe.curves_local()
-    torch.save({"stats": {f.name: getattr(stats, f.name) for f in dataclasses.fields(stats)}, "features": local.features.cpu(), "count": local.count.cpu(),
-                "acc": acc.acc.cpu(), "sent": pipe.exchange_bytes_per_rank, "curves_sent": pipe.curves_exchange_bytes_per_rank,
-                "range": pipe.geometry_range, "n_factors": pipe.n_factors},
-               os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
+        pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True,
+                               factors="hardpoints" if args.geometries > 2 else None, curves=curve_arguments(rel), chain_len=1, predictor=False)
+        acc = pipe.step()
+        torch.cuda.synchronize()
+        stats, local = pipe.curve_stats(), pipe.curves_local()
+        torch.save({"stats": {f.name: getattr(stats, f.name) for f in dataclasses.fields(stats)}, "features": local.features.cpu(), "count": local.count.cpu(),
+                    "acc": acc.acc.cpu(), "sent": pipe.exchange_bytes_per_rank, "curves_sent": pipe.curves_exchange_bytes_per_rank,
+                    "range": pipe.geometry_range, "n_factors": pipe.n_factors},
+                   os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 40500 + os.getpid() % 2000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--geometries", str(args.geometries), "--steps-per-geometry", str(args.steps_per_geometry), "--chunks", str(args.chunks),
-                               "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 40500, ["--geometries", args.geometries, "--steps-per-geometry", args.steps_per_geometry,
+                                                        "--chunks", args.chunks])
 
 
 def measure(args) -> dict:
@@ -112,21 +88,6 @@ def measure(args) -> dict:
     values, status = reduced.metric_local, reduced.info_local[:, 32]
     reps = args.reps
 
-    def events(fn, n):
-        out = []
-        for _ in range(n):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
-
     passes = {}
     outs = {}
     for degree in (1, 3):
@@ -140,14 +101,7 @@ def measure(args) -> dict:
     passes["screen"] = lambda: dp.screen_ensemble(values, steps_per_geometry=s, status=status, out=scr)
     acc = EnsembleAccumulator(torch.empty_like(reduced.local_accumulator.acc), reduced.local_accumulator.shift, None)
     passes["reduce"] = lambda: dp.reduce_ensemble(values, steps_per_geometry=s, status=status, out=acc)
-    for fn in passes.values():
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    runs = {name: [] for name in passes}
-    for _ in range(4):
-        for name, fn in passes.items():
-            runs[name] += events(fn, max(1, reps // 4))
+    runs = alternated(passes, reps)
     med = {name: statistics.median(r) for name, r in runs.items()}
 
     # (c) the host route: the copy alone, then curves_host on a slice of the geometries
@@ -203,34 +157,8 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--chunks", type=int, default=0)
-    ap.add_argument("--timeout", type=float, default=500.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    ap = common.parser(geometries=4096, steps_per_geometry=256, warmup=3, reps=20, chunks=0)
+    return common.run(ap.parse_args(), measure, summary, rank_main, rehearse)
 
 
 if __name__ == "__main__":

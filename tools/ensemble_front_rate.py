@@ -16,19 +16,14 @@ recorded, not a gate - was tens of microseconds.  The ratio to the screen pass i
 
 from __future__ import annotations
 
-import argparse
-import json
-import os
 import statistics
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-from ensemble_curves_rate import curve_arguments  # noqa: E402
-from ensemble_reduce_rate import build  # noqa: E402
+import ensemble_rate_common as common
+from ensemble_rate_common import alternated, spread
+from ensemble_curves_rate import curve_arguments
+from ensemble_reduce_rate import build
 
 
 def front_objectives(n_columns: int, m: int) -> list:
@@ -67,35 +62,13 @@ def measure(args) -> dict:
     scr = dp.screen_ensemble(features, steps_per_geometry=1, limits=limits)
     reps = args.reps
 
-    def events(fn, count):
-        out = []
-        for _ in range(count):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
-
     passes, outs = {}, {}
     for m in (2, 4, 8):
         out = dp.front_ensemble(features, steps_per_geometry=1, objectives=front_objectives(k, m), mask=scr.flags)
         outs[m] = out
         passes[f"front_m{m}"] = lambda out=out: dp.front_ensemble(features, steps_per_geometry=1, mask=scr.flags, out=out)
     passes["screen"] = lambda: dp.screen_ensemble(features, steps_per_geometry=1, out=scr)
-    for fn in passes.values():
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    runs = {name: [] for name in passes}
-    for _ in range(4):
-        for name, fn in passes.items():
-            runs[name] += events(fn, max(1, reps // 4))
+    runs = alternated(passes, reps)
     med = {name: statistics.median(r) for name, r in runs.items()}
 
     # (c) the host route: the copy alone, then front_host on the copied table
@@ -146,24 +119,8 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    ap = common.parser(geometries=4096, steps_per_geometry=256, warmup=3, reps=20, rehearsal=False)
+    return common.run(ap.parse_args(), measure, summary)
 
 
 if __name__ == "__main__":

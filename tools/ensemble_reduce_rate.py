@@ -16,16 +16,12 @@ What the on-device ensemble reduction costs (okx_ensemble_reduce, ShardedEnsembl
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
-import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import ensemble_rate_common as common
+from ensemble_rate_common import rank, step_ms
 
 HBM_PEAK = 6.3e12          # B/s (README roofline)
 FP64_VECTOR_PEAK = 78.6e12  # FLOP/s, MI355X vector fp64
@@ -49,39 +45,21 @@ def build(n_geom: int, steps: int, device):
 
 def rank_main(args) -> None:
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
-    pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, metric_columns=columns, reduce=True, factors="hardpoints",
-                           chain_len=1, predictor=False)
-    acc = pipe.step()
-    torch.cuda.synchronize()
-    torch.save({"acc": acc.acc.cpu(), "factor_acc": acc.factor_acc.cpu(), "shift": acc.shift.cpu(), "sent": pipe.exchange_bytes_per_rank,
-                "range": pipe.geometry_range}, os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
+        pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, metric_columns=columns, reduce=True, factors="hardpoints",
+                               chain_len=1, predictor=False)
+        acc = pipe.step()
+        torch.cuda.synchronize()
+        torch.save({"acc": acc.acc.cpu(), "factor_acc": acc.factor_acc.cpu(), "shift": acc.shift.cpu(), "sent": pipe.exchange_bytes_per_rank,
+                    "range": pipe.geometry_range}, os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 34500 + os.getpid() % 2000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--geometries", str(args.geometries), "--steps-per-geometry", str(args.steps_per_geometry), "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 34500, ["--geometries", args.geometries, "--steps-per-geometry", args.steps_per_geometry])
 
 
 def measure(args) -> dict:
@@ -98,14 +76,6 @@ def measure(args) -> dict:
     plain = ShardedEnsemble(dp, table, rel, s, metric_columns=columns, **kw)
     reduced = ShardedEnsemble(dp, table, rel, s, metric_columns=columns, reduce=True, factors="hardpoints", **kw)
     factors_host = reduced.my_factors.cpu().numpy()
-
-    def step_ms(fn, reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / reps * 1e3
 
     def host_statistics():
         full = plain.step()
@@ -168,31 +138,8 @@ def measure(args) -> dict:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--launches", type=int, default=4000)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--timeout", type=float, default=500.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-    return 0
+    ap = common.parser(geometries=4096, steps_per_geometry=256, steps=400, warmup=20, launches=4000)
+    return common.run(ap.parse_args(), measure, None, rank_main, rehearse)
 
 
 if __name__ == "__main__":

@@ -18,15 +18,12 @@ per second are in the output either way.  No test asserts a time.
 
 from __future__ import annotations
 
-import argparse
-import json
-import os
 import statistics
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import ensemble_rate_common as common
+from ensemble_rate_common import alternated, spread
 
 
 def host_route(program, plan, n_geometries: int, sigma: float, seed: int):
@@ -90,30 +87,8 @@ def measure(args) -> dict:
                     variants[name + ("_all_outputs" if full else "")] = (p, out)
     torch.cuda.synchronize()
 
-    def events(fn, count):
-        out = []
-        for _ in range(count):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
-
     passes = {name: (lambda p=p, out=out: dp.sample_ensemble(p, out=out)) for name, (p, out) in variants.items()}
-    for fn in passes.values():
-        for _ in range(max(1, args.warmup)):
-            fn()
-    torch.cuda.synchronize()
-    runs = {name: [] for name in passes}
-    for _ in range(4):
-        for name, fn in passes.items():
-            runs[name] += events(fn, max(1, reps // 4))
+    runs = alternated(passes, reps, warm=max(1, args.warmup))
     device_us = {}
     for name, (p, out) in variants.items():
         n = int(out.hardpoints.shape[0])
@@ -182,25 +157,13 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
+    ap = common.parser(rehearsal=False)
     ap.add_argument("--geometries", default="4096,262144")
     ap.add_argument("--sigma", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    return common.run(ap.parse_args(), measure, summary)
 
 
 if __name__ == "__main__":

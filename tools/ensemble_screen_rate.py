@@ -21,21 +21,15 @@ the fixed window.
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-from ensemble_reduce_rate import HBM_PEAK, build  # noqa: E402
-from ensemble_select_rate import window  # noqa: E402
+import ensemble_rate_common as common
+from ensemble_rate_common import alternated, rank, spread, step_ms
+from ensemble_reduce_rate import HBM_PEAK, build
+from ensemble_select_rate import window
 
 FIELDS = ("flags", "tally", "blame", "passed")
 
@@ -43,46 +37,28 @@ FIELDS = ("flags", "tally", "blame", "passed")
 def rank_main(args) -> None:
     import numpy as np
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
-    limits, scale = window(args.steps_per_geometry, len(columns)), None
-    if args.limits:
-        with np.load(args.limits) as fh:
-            limits, scale = fh["limits"], fh["scale"]
-    pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True, limits=limits,
-                           screen=True, screen_scale=scale, chain_len=1, predictor=False)
-    acc = pipe.step()
-    torch.cuda.synchronize()
-    got, local = pipe.screen(), pipe.screen_local()
-    torch.save({"screen": {f: getattr(got, f) for f in FIELDS}, "local": {k: v.cpu() for k, v in local.items()}, "acc": acc.acc.cpu(),
-                "sent": pipe.exchange_bytes_per_rank, "screen_sent": pipe.screen_exchange_bytes_per_rank, "range": pipe.geometry_range},
-               os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
+        limits, scale = window(args.steps_per_geometry, len(columns)), None
+        if args.limits:
+            with np.load(args.limits) as fh:
+                limits, scale = fh["limits"], fh["scale"]
+        pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, chunks=args.chunks or None, metric_columns=columns, reduce=True, limits=limits,
+                               screen=True, screen_scale=scale, chain_len=1, predictor=False)
+        acc = pipe.step()
+        torch.cuda.synchronize()
+        got, local = pipe.screen(), pipe.screen_local()
+        torch.save({"screen": {f: getattr(got, f) for f in FIELDS}, "local": {k: v.cpu() for k, v in local.items()}, "acc": acc.acc.cpu(),
+                    "sent": pipe.exchange_bytes_per_rank, "screen_sent": pipe.screen_exchange_bytes_per_rank, "range": pipe.geometry_range},
+                   os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 38500 + os.getpid() % 2000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--geometries", str(args.geometries), "--steps-per-geometry", str(args.steps_per_geometry), "--chunks", str(args.chunks),
-                               "--limits", args.limits, "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 38500, ["--geometries", args.geometries, "--steps-per-geometry", args.steps_per_geometry,
+                                                        "--chunks", args.chunks, "--limits", args.limits])
 
 
 def measure(args) -> dict:
@@ -115,22 +91,6 @@ def measure(args) -> dict:
     values, status = screened.metric_local, screened.info_local[:, 32]
     reps = args.reps
 
-    def events(fn, n=reps):
-        """Median and runs [us] of ``fn`` between device events, one pair per repetition."""
-        out = []
-        for _ in range(n):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return statistics.median(out), out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
-
     # (a) the pass alone, (b) the yardsticks beside it - alternated block by block so that a drift hits all three alike
     scr = dp.screen_ensemble(values, steps_per_geometry=s, status=status, limits=limits, scale=scale)
     one_screen = lambda: dp.screen_ensemble(values, steps_per_geometry=s, status=status, out=scr)  # noqa: E731
@@ -139,14 +99,7 @@ def measure(args) -> dict:
     run = dp.select_prepare(s, k, (0.5,), limits, rounds=True)
     dp.select_begin(run)
     one_count = lambda: dp.select_count(run, 0, values, steps_per_geometry=s, status=status)  # noqa: E731
-    for fn in (one_screen, one_reduce, one_count):
-        for _ in range(5):
-            fn()
-    torch.cuda.synchronize()
-    runs = {"screen": [], "reduce": [], "count": []}
-    for _ in range(4):
-        for name, fn in (("screen", one_screen), ("reduce", one_reduce), ("count", one_count)):
-            runs[name] += events(fn, max(1, reps // 4))[1]
+    runs = alternated({"screen": one_screen, "reduce": one_reduce, "count": one_count}, reps)
     med = {name: statistics.median(r) for name, r in runs.items()}
 
     # (c) what the user must otherwise do on one GPU
@@ -166,14 +119,6 @@ def measure(args) -> dict:
         bool(np.array_equal(got.margin.view(np.uint64), want.margin.view(np.uint64)))
 
     # (d) the sharded ensemble's step with and without the screen, alternated
-    def step_ms(fn, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / n * 1e3
-
     rounds = [(step_ms(reduced.step, args.steps), step_ms(screened.step, args.steps)) for _ in range(5)]
     off, on = statistics.median(r[0] for r in rounds), statistics.median(r[1] for r in rounds)
 
@@ -215,36 +160,9 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--chunks", type=int, default=0)
+    ap = common.parser(geometries=4096, steps_per_geometry=256, steps=50, warmup=10, reps=20, chunks=0)
     ap.add_argument("--limits", default="")
-    ap.add_argument("--timeout", type=float, default=500.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    return common.run(ap.parse_args(), measure, summary, rank_main, rehearse)
 
 
 if __name__ == "__main__":

@@ -16,20 +16,14 @@ the rehearsal tests/test_gpu_ensemble_select.py compares.
 
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-
-sys.path.insert(0, os.path.join(REPO, "tools"))
-
-from ensemble_reduce_rate import HBM_PEAK, build  # noqa: E402
+import ensemble_rate_common as common
+from ensemble_rate_common import events, rank, step_ms
+from ensemble_reduce_rate import HBM_PEAK, build
 
 PROBS = (0.00135, 0.5, 0.99865)
 FIELDS = ("count", "lower", "upper", "quantile", "below", "above", "yield_")
@@ -46,40 +40,22 @@ def window(steps: int, n_columns: int):
 
 def rank_main(args) -> None:
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
-    pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, metric_columns=columns, reduce=True, quantiles=PROBS,
-                           limits=window(args.steps_per_geometry, len(columns)), chain_len=1, predictor=False)
-    acc = pipe.step()
-    torch.cuda.synchronize()
-    q = pipe.quantiles()
-    torch.save({"q": {f: getattr(q, f) for f in FIELDS}, "acc": acc.acc.cpu(), "sent": pipe.exchange_bytes_per_rank,
-                "select_sent": pipe.select_exchange_bytes_per_rank, "range": pipe.geometry_range}, os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        dp, table, rel, columns = build(args.geometries, args.steps_per_geometry, device)
+        pipe = ShardedEnsemble(dp, table, rel, args.steps_per_geometry, metric_columns=columns, reduce=True, quantiles=PROBS,
+                               limits=window(args.steps_per_geometry, len(columns)), chain_len=1, predictor=False)
+        acc = pipe.step()
+        torch.cuda.synchronize()
+        q = pipe.quantiles()
+        torch.save({"q": {f: getattr(q, f) for f in FIELDS}, "acc": acc.acc.cpu(), "sent": pipe.exchange_bytes_per_rank,
+                    "select_sent": pipe.select_exchange_bytes_per_rank, "range": pipe.geometry_range}, os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 36500 + os.getpid() % 2000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--geometries", str(args.geometries), "--steps-per-geometry", str(args.steps_per_geometry), "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 36500, ["--geometries", args.geometries, "--steps-per-geometry", args.steps_per_geometry])
 
 
 def measure(args) -> dict:
@@ -104,24 +80,13 @@ def measure(args) -> dict:
     values, status = selected.metric_local, selected.info_local[:, 32]
     reps = args.reps
 
-    def events(fn, n=reps):
-        """Median and runs [us] of ``fn`` between device events, one pair per repetition."""
-        out = []
-        for _ in range(n):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return statistics.median(out), out
-
     # (a) the pass alone
     sel = dp.select_ensemble(values, steps_per_geometry=s, status=status, probs=PROBS, limits=limits)
     one_select = lambda: dp.select_ensemble(values, steps_per_geometry=s, status=status, out=sel)  # noqa: E731
     for _ in range(5):
         one_select()
-    select_us, select_runs = events(one_select)
+    select_runs = events(one_select, reps)
+    select_us = statistics.median(select_runs)
     run = dp.select_prepare(s, k, PROBS, limits, rounds=True)
     n_rounds = dp.select_rounds
     per_round = []
@@ -154,7 +119,8 @@ def measure(args) -> dict:
     one_reduce = lambda: dp.reduce_ensemble(values, steps_per_geometry=s, status=status, out=out)  # noqa: E731
     for _ in range(5):
         one_reduce()
-    reduce_us, reduce_runs = events(one_reduce)
+    reduce_runs = events(one_reduce, reps)
+    reduce_us = statistics.median(reduce_runs)
 
     # (c) what the user must otherwise do on one GPU
     copy_ms, host_ms = [], []
@@ -180,14 +146,6 @@ def measure(args) -> dict:
         bool(np.array_equal(below, got.below)) and bool(np.array_equal(above, got.above))
 
     # (d) the sharded ensemble's step with and without quantiles, alternated
-    def step_ms(fn, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / n * 1e3
-
     rounds = [(step_ms(reduced.step, args.steps), step_ms(selected.step, args.steps)) for _ in range(5)]
     off, on = statistics.median(r[0] for r in rounds), statistics.median(r[1] for r in rounds)
 
@@ -224,34 +182,8 @@ def summary(r: dict) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--geometries", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--timeout", type=float, default=500.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    result = measure(args)
-    text = json.dumps(result, indent=1)
-    print(text)
-    print(summary(result))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(result))
-    return 0
+    ap = common.parser(geometries=4096, steps_per_geometry=256, steps=50, warmup=10, reps=20)
+    return common.run(ap.parse_args(), measure, summary, rank_main, rehearse)
 
 
 if __name__ == "__main__":

@@ -21,17 +21,15 @@ Sobol stage fed an INTEGER table (``integer_rows``) in its place, whose sums are
 
 from __future__ import annotations
 
-import argparse
 import dataclasses
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import ensemble_rate_common as common
+from ensemble_rate_common import rank, timed
+
 
 U = 2.0 ** -53
 
@@ -65,56 +63,38 @@ def integer_rows(lo: int, hi: int, n_columns: int):
 def rank_main(args) -> None:
     import numpy as np
     import torch
-    import torch.distributed as dist
 
     from open_kinematics_amd.dist import ShardedEnsemble
 
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = str(args.port)
-    dist.init_process_group("gloo", rank=args.rank, world_size=args.rehearse)
-    device = torch.device("cuda:0")
-    s = args.steps_per_geometry
-    dp, fplan, rel, columns = build(args.families, s, device, n_points=args.points or None)
-    k = len(columns)
-    pipe = ShardedEnsemble(dp, fplan, rel, s, metric_columns=columns, reduce=True, sobol=True, chunks=2, shift=np.zeros((s, k)), chain_len=1,
-                           predictor=False)
-    pipe.step()
-    torch.cuda.synchronize()
-    real = pipe.sobol_accumulator.acc.cpu().clone()
-    # the Sobol stage once more, its chunks fed the integer table in place of the evaluated one
-    glo, ghi = pipe.geometry_range
-    values, status = integer_rows(glo * s, ghi * s, k)
-    pipe.metric_local.copy_(torch.as_tensor(values, device=device))
-    pipe.info_local[:, 32] = torch.as_tensor(status, device=device)
-    stage = pipe.stages["sobol"]
-    stage.begin_step()
-    for c in range(pipe.chunks):
-        a, b = pipe.pieces[c][pipe.rank]
-        if b > a:
-            stage.rows(a, b, slice((a - glo) * s, (b - glo) * s))
-    stage.end_step()
-    torch.cuda.synchronize()
-    torch.save({"acc": real, "integer_acc": pipe.sobol_accumulator.acc.cpu().clone(), "flags": pipe.sampled_flags.cpu(), "range": pipe.geometry_range,
-                "pieces": pipe.pieces, "sent": pipe.sobol_exchange_bytes_per_rank}, os.path.join(args.out, f"rank{args.rank}.pt"))
-    dist.barrier()
-    dist.destroy_process_group()
+    with rank(args) as device:
+        s = args.steps_per_geometry
+        dp, fplan, rel, columns = build(args.families, s, device, n_points=args.points or None)
+        k = len(columns)
+        pipe = ShardedEnsemble(dp, fplan, rel, s, metric_columns=columns, reduce=True, sobol=True, chunks=2, shift=np.zeros((s, k)), chain_len=1,
+                               predictor=False)
+        pipe.step()
+        torch.cuda.synchronize()
+        real = pipe.sobol_accumulator.acc.cpu().clone()
+        # the Sobol stage once more, its chunks fed the integer table in place of the evaluated one
+        glo, ghi = pipe.geometry_range
+        values, status = integer_rows(glo * s, ghi * s, k)
+        pipe.metric_local.copy_(torch.as_tensor(values, device=device))
+        pipe.info_local[:, 32] = torch.as_tensor(status, device=device)
+        stage = pipe.stages["sobol"]
+        stage.begin_step()
+        for c in range(pipe.chunks):
+            a, b = pipe.pieces[c][pipe.rank]
+            if b > a:
+                stage.rows(a, b, slice((a - glo) * s, (b - glo) * s))
+        stage.end_step()
+        torch.cuda.synchronize()
+        torch.save({"acc": real, "integer_acc": pipe.sobol_accumulator.acc.cpu().clone(), "flags": pipe.sampled_flags.cpu(), "range": pipe.geometry_range,
+                    "pieces": pipe.pieces, "sent": pipe.sobol_exchange_bytes_per_rank}, os.path.join(args.out, f"rank{args.rank}.pt"))
 
 
 def rehearse(args) -> int:
-    port = 36500 + os.getpid() % 2000
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rehearse", str(args.rehearse), "--rank", str(r), "--port", str(port),
-                               "--families", str(args.families), "--steps-per-geometry", str(args.steps_per_geometry), "--points", str(args.points),
-                               "--out", args.out])
-             for r in range(args.rehearse)]
-    codes = []
-    for p in procs:
-        try:
-            codes.append(p.wait(timeout=args.timeout))
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            return 124
-    return max(abs(c) for c in codes)
+    return common.rehearse(args, __file__, 36500, ["--families", args.families, "--steps-per-geometry", args.steps_per_geometry,
+                                                        "--points", args.points])
 
 
 def measure_one(args, by_point: bool) -> dict:
@@ -131,36 +111,10 @@ def measure_one(args, by_point: bool) -> dict:
     g = n * m
     reps = args.reps
 
-    def events(fn, count):
-        out = []
-        for _ in range(count):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append(a.elapsed_time(b) * 1e3)
-        return out
-
-    def spread(runs):
-        q = statistics.quantiles(runs, n=4)
-        return q[2] - q[0]
-
-    def timed(passes):
-        for fn in passes.values():
-            for _ in range(3):
-                fn()
-        torch.cuda.synchronize()
-        runs = {name: [] for name in passes}
-        for _ in range(4):
-            for name, fn in passes.items():
-                runs[name] += events(fn, max(1, reps // 4))
-        return {name: {"median": statistics.median(r), "interquartile": spread(r), "runs": r} for name, r in runs.items()}
-
     # (a) the draw
     plain = dataclasses.replace(fplan.plan, n_total=g)
     fam_out, plain_out = dp.sample_families(fplan), dp.sample_ensemble(plain)
-    draw = timed({"sample_families": lambda: dp.sample_families(fplan, out=fam_out), "sample_ensemble": lambda: dp.sample_ensemble(plain, out=plain_out)})
+    draw = timed(reps=reps, passes={"sample_families": lambda: dp.sample_families(fplan, out=fam_out), "sample_ensemble": lambda: dp.sample_ensemble(plain, out=plain_out)})
     del fam_out, plain_out
     # (b) the estimator over the evaluated table
     pipe = ShardedEnsemble(dp, fplan, rel, s, metric_columns=columns, reduce=True, sobol=True, chain_len=1, predictor=False)
@@ -176,7 +130,7 @@ def measure_one(args, by_point: bool) -> dict:
     shift = pipe.local_accumulator.shift
     acc = dp.sobol_ensemble(table, steps_per_geometry=s, n_groups=d, status=status, mask=flags, shift=shift)
     racc = dp.reduce_ensemble(table, steps_per_geometry=s, status=status, shift=shift)
-    est = timed({"sobol": lambda: dp.sobol_ensemble(table, steps_per_geometry=s, n_groups=d, status=status, mask=flags, out=acc),
+    est = timed(reps=reps, passes={"sobol": lambda: dp.sobol_ensemble(table, steps_per_geometry=s, n_groups=d, status=status, mask=flags, out=acc),
                  "reduce": lambda: dp.reduce_ensemble(table, steps_per_geometry=s, status=status, out=racc)})
     torch.cuda.synchronize()
     table_bytes = 8 * g * s * k
@@ -216,6 +170,10 @@ def measure_one(args, by_point: bool) -> dict:
     }
 
 
+def measure(args) -> list:
+    return [measure_one(args, by_point=which == "10") for which in args.groups.split(",")]
+
+
 def summary(results: list) -> str:
     lines = []
     for r in results:
@@ -233,34 +191,11 @@ def summary(results: list) -> str:
 
 
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--families", type=int, default=4096)
-    ap.add_argument("--steps-per-geometry", type=int, default=256)
+    ap = common.parser(families=4096, steps_per_geometry=256, timeout=600.0)
     ap.add_argument("--points", type=int, default=0, help="perturb the first POINTS authored points only (0: all)")
     ap.add_argument("--groups", default="10,30", help="which groupings to measure: 10 (by point) and / or 30 (by coordinate)")
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--rehearse", type=int, default=0)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--port", type=int, default=0)
-    ap.add_argument("--timeout", type=float, default=600.0)
-    args = ap.parse_args()
-    if args.rehearse and args.rank >= 0:
-        rank_main(args)
-        return 0
-    if args.rehearse:
-        return rehearse(args)
-    results = [measure_one(args, by_point=which == "10") for which in args.groups.split(",")]
-    text = json.dumps(results, indent=1)
-    print(text)
-    print(summary(results))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w", encoding="utf-8") as fh:
-            fh.write(text + "\n")
-        with open(os.path.splitext(args.out)[0] + ".txt", "w", encoding="utf-8") as fh:
-            fh.write(summary(results))
-    return 0
+    return common.run(ap.parse_args(), measure, summary, rank_main, rehearse)
 
 
 if __name__ == "__main__":
