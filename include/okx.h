@@ -1273,6 +1273,63 @@ int32_t okx_ensemble_sobol_bootstrap(int64_t n_families, int64_t family_offset, 
 size_t okx_ensemble_sobol_bootstrap_scratch_bytes(int64_t n_families, int32_t n_groups, int64_t steps, int32_t n_columns,
                                                   int32_t n_replicates);
 
+/*
+ * Main effects from given data on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): how every
+ * (step, column) entry of an evaluated ensemble depends on ONE factor beyond a straight line - its conditional moments over
+ * equal-probability bins of the factor (Plischke 2010), from the ordinary ensemble that is already in HBM, without a further
+ * solve.  Two passes: the factors are binned once (they do not change from step to step), the table is streamed per call.
+ *
+ * okx_ensemble_bin.  d_factors [n_geometries][ldf] doubles (n_factors <= ldf), d_edges [n_factors][n_bins - 1] the ascending
+ * interior edges of every factor's bins (the caller validates them: finite and non-decreasing), 1 <= n_bins <=
+ * OKX_ENS_EFFECTS_MAX_BINS, 1 <= n_factors <= OKX_ENS_EFFECTS_MAX_FACTORS.  Outputs:
+ *   d_bins    [n_geometries][n_factors] uint8   the bin of the geometry for the factor: the NUMBER OF EDGES <= x - comparisons
+ *             only, a value on an edge goes to the upper bin, -inf / +inf land in the end bins; OKX_ENS_EFFECTS_NO_BIN for a NaN
+ *             (the geometry is left out for that factor alone)
+ *   d_order   [n_factors][n_geometries] int32   per factor its binned geometries, bin by bin, ASCENDING geometry index inside a
+ *             bin; the slots behind the last binned geometry hold -1
+ *   d_offsets [n_factors][n_bins + 1] int64     where every bin starts in that list; the last entry is the binned count
+ * Positions come from ballots and prefix counts, no atomic decides a slot: the same bits every run.  Integers and comparisons
+ * only: the pass equals ensemble_stats.bin_factors_host byte for byte.
+ *
+ * okx_ensemble_effects.  Table, status bytes and counting rule are those of okx_ensemble_reduce (status & 7 == 1 and a finite
+ * value); with d_mask [n_geometries] uint8 a geometry counts only when bit 0 of its byte is clear (the sampler's d_flags).
+ * d_order / d_offsets are what okx_ensemble_bin made of the SAME geometries.  With d = value - d_shift[step][column],
+ *   d_acc [n_factors][n_bins][OKX_EFFECTS_FIELDS][steps * n_columns], every field a double, the entry fastest:
+ *   OKX_EFFECTS_COUNT, OKX_EFFECTS_SUM, OKX_EFFECTS_SUMSQ   the geometries of the bin that count at the entry, sum d, sum d d
+ * ROUNDING.  d is rounded, then d d, then each is added (no fused multiply-add).  Every cell is ONE chain of additions over the
+ * bin's geometries in ascending order, begun at 0 (accumulate = 0; a cell whose bin is empty gets zeros) or at what d_acc
+ * holds (accumulate = 1; all partials need ONE shift and the same edges): no slabs, no scratch, no floating-point atomic -
+ * bit-identical from run to run and from device to device, equal to ensemble_stats.effects_host on integer tables; chunks
+ * accumulated in ascending order carry the bits of the whole, accumulators merged by addition differ from it by the addition
+ * order only.  The table is read once per factor.  The host turns the fields into conditional means, within-bin spreads and
+ * the first-order indices (ensemble_stats.EffectsAccumulator.finalize).
+ * Both are launch-only, stream-ordered, without allocation and legal inside a stream capture; n_geometries = 0 is legal
+ * (offsets of zeros; zeros or, accumulating, what was there).  Errors (okx_last_error text): a negative count, n_factors or
+ * n_bins outside their caps, ld < n_columns / ldf < n_factors or a null table, more than 2^31 - 1 geometries or too many
+ * entries for one call.
+ */
+enum { OKX_ENS_EFFECTS_MAX_BINS = 64, OKX_ENS_EFFECTS_MAX_FACTORS = 288, OKX_ENS_EFFECTS_NO_BIN = 255 };
+enum { OKX_EFFECTS_COUNT = 0, OKX_EFFECTS_SUM = 1, OKX_EFFECTS_SUMSQ = 2, OKX_EFFECTS_FIELDS = 3 };
+
+int32_t okx_ensemble_bin(int64_t n_geometries, int32_t n_factors,
+                         const double* d_factors, int64_t ldf,              /* [n_geometries][ldf]                      */
+                         const double* d_edges, int32_t n_bins,             /* [n_factors][n_bins - 1]                  */
+                         uint8_t* d_bins,                                   /* [n_geometries][n_factors]                */
+                         int32_t* d_order,                                  /* [n_factors][n_geometries]                */
+                         int64_t* d_offsets,                                /* [n_factors][n_bins + 1]                  */
+                         void* stream);
+
+int32_t okx_ensemble_effects(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                             const double* d_values, int64_t ld,              /* [n_geometries * steps][ld]           */
+                             const uint8_t* d_status, int64_t status_stride,  /* or NULL                              */
+                             const uint8_t* d_mask,                           /* [n_geometries] or NULL               */
+                             int32_t n_factors, int32_t n_bins,
+                             const int32_t* d_order, const int64_t* d_offsets, /* of okx_ensemble_bin                 */
+                             const double* d_shift,                           /* [steps][n_columns]                   */
+                             int32_t accumulate,
+                             double* d_acc,                       /* [n_factors][n_bins][3][steps * n_columns]        */
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,10 @@ EVAL_RATE_WHEEL_CENTER_X, EVAL_RATE_WHEEL_CENTER_Z, EVAL_RATE_RACK_Y = 19, 21, 2
 EVAL_AXLE_COLUMNS = 64
 EVAL_AXLE_LEFT, EVAL_AXLE_RIGHT, EVAL_AXLE_METRICS, EVAL_AXLE_ROLES = 0, 24, 48, 56
 
+# okx_ensemble_bin / okx_ensemble_effects (include/okx.h OKX_ENS_EFFECTS_*, OKX_EFFECTS_*); ensemble_stats.py names them EFFECTS_*
+ENS_EFFECTS_MAX_BINS, ENS_EFFECTS_MAX_FACTORS, ENS_EFFECTS_NO_BIN = 64, 288, 255
+EFFECTS_COUNT, EFFECTS_SUM, EFFECTS_SUMSQ, EFFECTS_FIELDS = 0, 1, 2, 3
+
 INFO_CONVERGED = 1
 INFO_RESIDUAL_EXCEEDED = 2
 INFO_FAILED = 4

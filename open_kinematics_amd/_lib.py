@@ -90,6 +90,8 @@ EXPORTS = (
     "okx_ensemble_bootstrap_weights",
     "okx_ensemble_sobol_bootstrap",
     "okx_ensemble_sobol_bootstrap_scratch_bytes",
+    "okx_ensemble_bin",
+    "okx_ensemble_effects",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -306,6 +308,10 @@ def load() -> C.CDLL:
     lib.okx_ensemble_sobol_bootstrap.restype = i32
     lib.okx_ensemble_sobol_bootstrap_scratch_bytes.argtypes = [i64, i32, i64, i32, i32]
     lib.okx_ensemble_sobol_bootstrap_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_bin.argtypes = [i64, i32, vp, i64, vp, i32, vp, vp, vp, vp]
+    lib.okx_ensemble_bin.restype = i32
+    lib.okx_ensemble_effects.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp]
+    lib.okx_ensemble_effects.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

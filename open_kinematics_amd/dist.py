@@ -429,13 +429,25 @@ class ShardedEnsemble:
     ``ensemble_stats.EnsembleSobolBootstrap`` (the replicates' indices, their standard deviations and percentile intervals),
     ``sobol_bootstrap_accumulator`` the merged tables, ``sobol_bootstrap_exchange_bytes_per_rank`` what the rank sends.  Families are
     resampled as independent units; under ``LHS`` they are not quite, so the intervals are on the conservative side.
+
+    ``effects=n_bins`` or ``effects=dict(bins=B, edges=table)`` (with ``reduce=True`` and ``factors``) adds HOW an entry depends on each
+    single factor beyond a straight line (``okx_ensemble_bin`` / ``okx_ensemble_effects``): count, sum and sum of squares of every entry
+    over ``B`` equal-probability bins of every factor - the given-data estimator, from the ordinary ensemble and without a further
+    solve.  The edges ``[P, B - 1]`` carry the same bits on every rank: with ``factors="sampled"`` they are the plan's own inverse CDFs
+    at ``k / B`` (``ensemble_stats.effects_edges``), otherwise the order statistics of the factors of all geometries.  A chunk's factor
+    rows are binned once; right after the chunk's reduction its rows of ``metric_local`` are accumulated with the reduction's shift
+    and, when the ensemble was sampled, the sampler's flags as the mask.  ``step()`` then ends with one all-gather of the
+    accumulators, added on every rank in ascending rank order - the same bits on every rank; on the device a rank's chunks continue
+    every cell's chain, so chunkings of one rank carry the same bits; world sizes agree to rounding.  ``effects()`` returns the
+    ``ensemble_stats.EnsembleEffects`` (conditional mean and spread per bin, first-order index per factor and entry),
+    ``effects_accumulator`` the merged tables, ``effects_exchange_bytes_per_rank`` what the rank sends (``24 P B S K``).
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
                  covariance=None, curves=None, front=None, sobol: bool = False, bootstrap: int | None = None, bootstrap_seed: int | None = None,
-                 **solve_kw):
+                 effects=None, **solve_kw):
         from .ensemble_sample import FamilyPlan, SamplePlan
 
         self.plan = hardpoints if isinstance(hardpoints, (SamplePlan, FamilyPlan)) else None
@@ -465,6 +477,10 @@ class ShardedEnsemble:
             covariance = None
         if covariance is not None and not reduce:
             raise ValueError("covariance= accumulates the reduced ensemble: it needs reduce=True")
+        if effects is False:
+            effects = None
+        if effects is not None and (not reduce or factors is None):
+            raise ValueError("effects= bins the factors of the reduced ensemble: it needs reduce=True and factors")
         if curves is not None and not reduce:
             raise ValueError("curves= fits the reduced ensemble's columns: it needs reduce=True")
         if front is not None:
@@ -625,6 +641,8 @@ class ShardedEnsemble:
             if self.covarying:
                 stage = self.stages["covariance"] = stages.Covariance(self, covariance)
                 self.covariance_entries = stage.entries
+            if effects is not None:
+                self.stages["effects"] = stages.Effects(self, effects)
             if curves is not None:
                 self.stages["curves"] = stages.Curves(self, dict(curves))
             if front is not None:
@@ -632,6 +650,7 @@ class ShardedEnsemble:
         sent = {name: stage.bytes_per_rank for name, stage in self.stages.items()}
         self.select_exchange_bytes_per_rank, self.screen_exchange_bytes_per_rank = sent.get("select", 0), sent.get("screen", 0)
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
+        self.effects_exchange_bytes_per_rank = sent.get("effects", 0)
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
         self.front_exchange_bytes_per_rank = sent.get("front", 0)
         self.sobol_exchange_bytes_per_rank = sent.get("sobol", 0)
@@ -664,6 +683,16 @@ class ShardedEnsemble:
         if "sobol_bootstrap" not in self.stages:
             raise ValueError("sobol_bootstrap() needs sobol=True and bootstrap=R")
         return self.stages["sobol_bootstrap"].sobol_bootstrap(level)
+
+    effects_accumulator = property(lambda self: self.stages["effects"].merged,
+                                   doc="The merged main-effects accumulator of the last ``step()`` (``effects=``); None before.")
+
+    def effects(self):
+        """``ensemble_stats.EnsembleEffects`` of the WHOLE ensemble after the last ``step()`` (``effects=``): per factor, bin and entry the
+        conditional mean and spread, per factor and entry the first-order index.  The same bits on every rank."""
+        if "effects" not in self.stages:
+            raise ValueError("effects() needs effects=n_bins")
+        return self.stages["effects"].effects()
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""
@@ -952,7 +981,7 @@ class ShardedEnsemble:
             torch.cuda.current_stream(self.expand_stream.device).wait_stream(self.expand_stream)
         if self.reduce:
             # every rank, with or without a geometry, in this order: the accumulators' all-gather, the Sobol' accumulators' all-gather, the select rounds' all-reduces,
-            # the screen's all-reduce and all-gather, the covariance's all-gather, the curve features' all-gather, the front
+            # the screen's all-reduce and all-gather, the covariance's all-gather, the effects' all-gather, the curve features' all-gather, the front
             # rows' all-gather
             for stage in self.stages.values():
                 stage.end_step()

@@ -17,6 +17,7 @@ pass (``okx_ensemble_...``)    prepare call          result
 ``sobol_ensemble``             -                     ``ensemble_stats.SobolAccumulator``
 ``bootstrap_weights``          -                     ``uint8 [n_rows, R]`` tensor
 ``sobol_bootstrap_ensemble``   -                     ``ensemble_stats.SobolBootstrapAccumulator``
+``effects_ensemble``           ``bin_factors``       ``ensemble_stats.EffectsAccumulator``
 =============================  ====================  ==============================================
 
 Every pass takes ``out=``, the result of an earlier call or of its prepare call; the tables it holds are checked in one place
@@ -33,9 +34,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensemble_stats import (CURVE_FIELDS, ENS_FIELDS, FRONT_TARGET, SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS, CovarianceAccumulator,
-                             EnsembleAccumulator, EnsembleCurves, SobolAccumulator, SobolBootstrapAccumulator, _host_f64, broadcast_limits,
-                             broadcast_scale, check_covariance_arguments, check_front_arguments, check_replicates, factor_moment_count)
+from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS,
+                             CovarianceAccumulator, EffectsAccumulator, EnsembleAccumulator, EnsembleCurves, SobolAccumulator, SobolBootstrapAccumulator,
+                             _host_f64, broadcast_limits, broadcast_scale, check_covariance_arguments, check_effects_arguments, check_front_arguments,
+                             check_replicates, factor_moment_count)
 
 F64, I64, I32, U8 = torch.float64, torch.int64, torch.int32, torch.uint8
 
@@ -187,6 +189,22 @@ class EnsembleSample:
     delta: torch.Tensor | None
     flags: torch.Tensor | None
     lo: int = 0
+
+
+@dataclass
+class EffectBins:
+    """
+    What ``DeviceProgram.bin_factors`` returns and ``effects_ensemble`` takes, device tensors of ``G`` geometries and ``F`` factors:
+    ``bins [G, F]`` uint8 (the bin of the geometry for the factor, 255: the factor is NaN), ``order [F, G]`` int32 (per factor the
+    binned geometries bin by bin, ascending inside a bin; -1 behind them), ``offsets [F, n_bins + 1]`` int64 (where every bin starts)
+    and ``edges [F, n_bins - 1]`` float64 as uploaded.
+    """
+
+    bins: torch.Tensor
+    order: torch.Tensor
+    offsets: torch.Tensor
+    edges: torch.Tensor
+    n_bins: int
 
 
 def _ptr(t: torch.Tensor | None, row: int = 0) -> C.c_void_p:
@@ -831,4 +849,68 @@ class EnsembleReductions:
         scratch = self._ensemble_scratch("sobol_bootstrap", int(self.lib.okx_ensemble_sobol_bootstrap_scratch_bytes(n, d, s, k, r)))
         self._ensemble_call(who, n, first, d, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift), C.c_uint64(seed), r,
                             1 if accumulate else 0, _ptr(out.acc), _ptr(scratch), scratch.numel())
+        return out
+
+    # ---- okx_ensemble_bin / okx_ensemble_effects: conditional moments over the bins of every factor (ensemble_stats.EnsembleEffects) ----
+
+    def bin_factors(self, factors, edges=None, out=None) -> "EffectBins":
+        """
+        ``okx_ensemble_bin``: the bins of ``factors [G, F]`` (a float64 device tensor with unit column stride; rows may be strided) against
+        ``edges [F, B - 1]`` - ``ensemble_stats.effects_edges``; validated on the host (finite, non-decreasing) and uploaded - as an
+        ``EffectBins`` of device tensors: the bin bytes, per factor the list of its geometries bin by bin and where every bin starts.
+        Done ONCE for an ensemble: factors do not change from step to step.  ``out``: the ``EffectBins`` of an earlier call of the same
+        shape - it carries its own edges; with it the call uploads and allocates nothing and is legal inside a stream capture.
+        Integers and comparisons only: the bytes of ``ensemble_stats.bin_factors_host`` / ``bin_lists_host``, the same every run.
+        """
+        dev = self.device
+        if not isinstance(factors, torch.Tensor) or factors.dim() != 2 or factors.dtype != F64 or factors.device != dev \
+                or (factors.shape[1] > 1 and factors.stride(1) != 1):
+            raise ValueError("factors must be a float64 [G, F] device tensor with unit column stride")
+        g, f = factors.shape
+        ldf = factors.stride(0) if g > 1 else max(f, factors.stride(0))
+        if ldf < f:
+            raise ValueError("rows of factors overlap")
+        if self._new_result(out, (edges,), "edges"):
+            if edges is None:
+                raise ValueError("edges are needed (or out=, which carries its own)")
+            host = _host_f64(edges)
+            b = host.shape[1] + 1 if host.ndim == 2 else 0
+            b, host, _ = check_effects_arguments(b, f, host)
+            out = EffectBins(torch.empty((g, f), dtype=U8, device=dev), torch.empty((f, g), dtype=I32, device=dev),
+                             torch.empty((f, b + 1), dtype=I64, device=dev), torch.as_tensor(host, device=dev), b)
+        b = int(out.n_bins)
+        self._check_tables(f"out must hold contiguous device tables bins [{g}, {f}], order [{f}, {g}], offsets [{f}, {b + 1}] and edges [{f}, {b - 1}]",
+                           [(out.bins, (g, f), U8), (out.order, (f, g), I32), (out.offsets, (f, b + 1), I64), (out.edges, (f, b - 1), F64)])
+        self._ensemble_call("okx_ensemble_bin", g, f, _ptr(factors), ldf, _ptr(out.edges), b, _ptr(out.bins), _ptr(out.order), _ptr(out.offsets))
+        return out
+
+    def effects_ensemble(self, values, *, steps_per_geometry: int, bins, status=None, mask=None, shift=None, out=None, accumulate: bool = False,
+                         factor_names=None):
+        """
+        ``okx_ensemble_effects``: the main-effects accumulator (``ensemble_stats.EffectsAccumulator``, device tensors: ``acc [F, B, 3, S, K]``
+        = count, sum d, sum d^2 of every bin of every factor, ``shift [S, K]``, ``edges [F, B - 1]``) of a column table in HBM.  ``values``
+        and ``status`` as ``reduce_ensemble`` takes them (unit column stride; strided rows and a strided status byte are passed on,
+        nothing is copied); ``bins``: the ``EffectBins`` ``bin_factors`` made of the factors of THESE geometries; ``mask [G]`` contiguous
+        uint8, bit 0 set: the geometry does not count - the sampler's ``flags`` as they lie in HBM.  ``shift [S, K]`` the common shift
+        (None: the table's own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift, pass it or pass
+        ``out=``).  ``out``: the accumulator of an earlier call - it carries its own shift - to write (``accumulate=False``) or to go on
+        from (``True``); with it and a table shape seen before, the call allocates nothing and is legal inside a stream capture.
+        ``.finalize()`` copies to the host: conditional means, within-bin spreads, first-order indices.  Every cell is one chain of
+        additions in ascending geometry order: bit-identical from run to run, and chunks accumulated in ascending order carry the
+        bits of the whole table.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        if not isinstance(bins, EffectBins):
+            raise ValueError("bins must be the EffectBins of bin_factors")
+        f, b = _rows(bins.order), int(bins.n_bins)
+        self._check_tables(f"bins must hold contiguous device tables order [F, {g}] and offsets [F, {b + 1}] of the table's {g} geometries",
+                           [(bins.order, (f, g), I32), (bins.offsets, (f, b + 1), I64), (bins.edges, (f, b - 1), F64)])
+        if self._new_result(out, (shift,), "shift", accumulate):
+            out = EffectsAccumulator(torch.empty((f, b, EFFECTS_FIELDS, s, k), dtype=F64, device=self.device), self._ensemble_shift(shift, values, g, s, k),
+                                     bins.edges, factor_names)
+        self._check_tables(f"out must hold contiguous device tables acc [{f}, {b}, {EFFECTS_FIELDS}, S, K], shift [S, K] = [{s}, {k}] and edges [{f}, {b - 1}]",
+                           [(out.acc, (f, b, EFFECTS_FIELDS, s, k), F64), (out.shift, (s, k), F64), (out.edges, (f, b - 1), F64)])
+        self._check_mask(mask, g, contiguous=True)
+        self._ensemble_call("okx_ensemble_effects", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), f, b, _ptr(bins.order), _ptr(bins.offsets),
+                            _ptr(out.shift), 1 if accumulate else 0, _ptr(out.acc))
         return out

@@ -1,7 +1,7 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
 (moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``SobolBootstrap`` (``bootstrap=``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
-(``covariance=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+(``covariance=``), ``Effects`` (``effects=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
 * ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
@@ -437,6 +437,78 @@ class Covariance(_AccumulatorStage):
         self.merged = self.merged_over_ranks(mine, (mine.gram, mine.sum, mine.counts.view(torch.float64)), unpack)
 
     def covariance(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result
+
+
+class Effects(_AccumulatorStage):
+    """``effects=n_bins`` or ``effects=dict(bins=, edges=)``: the conditional moments of every entry over equal-probability bins of each of
+    the reduction's factors, chunk by chunk right after the reduction, with the reduction's shift and - when the ensemble was sampled -
+    the sampler's flag bytes as the mask.  The edges are the same bits on every rank: analytic from the plan for ``factors="sampled"``,
+    else the order statistics of the factors of ALL geometries.  A chunk's factor rows are binned once, the first time it is taken in:
+    factors do not change from step to step."""
+
+    def __init__(self, owner, effects):
+        super().__init__(owner)
+        o = owner
+        reduction = o.stages["reduce"]
+        edges = None
+        if isinstance(effects, dict):
+            unknown = set(effects) - {"bins", "edges"}
+            if unknown or "bins" not in effects:
+                raise ValueError(f"effects= takes an integer or dict(bins=, edges=) (got {sorted(effects)})")
+            effects, edges = effects["bins"], effects.get("edges")
+        p = reduction.n_factors
+        if not p:
+            raise ValueError("effects= bins the reduction's factors: it needs factors=")
+        n_bins = es.check_effects_arguments(effects, p)[0]
+        if edges is None:
+            if getattr(reduction, "_sampled", None) is not None:
+                edges = es.effects_edges(getattr(o.plan, "plan", o.plan), n_bins)  # (a FamilyPlan wraps the plan its rows are drawn from)
+            else:
+                edges = es.effects_edges(reduction.all_factors, n_bins)
+        elif isinstance(edges, torch.Tensor):
+            edges = edges.detach().cpu().numpy()
+        self.n_bins, self.edges, _ = es.check_effects_arguments(n_bins, p, edges)
+        self.factor_names = reduction.factor_names
+        self.factors = reduction.my_factors  # this rank's rows [n, P], where the ensemble lives
+        self.flags = o.sampled_flags.contiguous() if o.sampled_flags is not None else None
+        k = len(o.metric_index)
+        shift = o.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's (itself, no copy)
+        self.local = es.EffectsAccumulator(torch.zeros((p, self.n_bins, es.EFFECTS_FIELDS, o.steps, k), dtype=torch.float64, device=o.device), shift,
+                                           torch.as_tensor(self.edges, device=o.device), self.factor_names)
+        self.binned = {}  # (a, b) -> the bins of the chunk's rows
+        self.merged = self.result = None
+        self.allocate_exchange(self.local.acc.numel())
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        mask = None if self.flags is None else self.flags[a - glo : b - glo]
+        bins = self.binned.get((a, b))
+        if self.on_device:
+            if bins is None:
+                bins = self.binned[(a, b)] = o.dp.bin_factors(self.factors[a - glo : b - glo], self.edges)
+            o.dp.effects_ensemble(values, steps_per_geometry=o.steps, bins=bins, status=status, mask=mask, out=mine, accumulate=self.taken)
+            return
+        if bins is None:
+            bins = self.binned[(a, b)] = es.bin_factors_host(self.factors[a - glo : b - glo].cpu().numpy(), self.edges)
+        part = es.effects_host(*self.host_tables(a, b, values, status), None if mask is None else mask.cpu().numpy(), bins, self.n_bins,
+                               mine.shift.cpu().numpy(), self.edges)
+        if not self.taken:
+            mine.acc.zero_()
+        mine.acc += torch.from_numpy(part.acc)
+
+    def exchange(self) -> None:
+        mine = self.local
+        self.result = None
+        self.merged = self.merged_over_ranks(mine, (mine.acc,), lambda row: es.EffectsAccumulator(row.reshape(mine.acc.shape), mine.shift, mine.edges,
+                                                                                                  self.factor_names))
+
+    def effects(self):
         if self.merged is None:
             raise RuntimeError("no step() yet")
         if self.result is None:

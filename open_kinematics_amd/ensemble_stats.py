@@ -21,6 +21,9 @@ WHICH FACTOR GROUP explains the variance: the Sobol' accumulators of a pick-free
 their first-order and total-order indices (``sobol_host`` / ``SobolAccumulator`` / ``EnsembleSobol``, ``okx_ensemble_sobol``), and
 HOW FAR TO TRUST them: Poisson-bootstrap replicates of those accumulators, their standard deviations and percentile intervals
 (``bootstrap_weights`` / ``sobol_bootstrap_host`` / ``SobolBootstrapAccumulator`` / ``EnsembleSobolBootstrap``, ``okx_ensemble_sobol_bootstrap``).
+HOW an entry depends on ONE factor beyond a straight line, from the ordinary ensemble: its conditional moments over equal-probability
+bins of every factor and the first-order indices they give (``effects_edges`` / ``bin_factors_host`` / ``effects_host`` /
+``EffectsAccumulator`` / ``EnsembleEffects``, ``okx_ensemble_bin`` and ``okx_ensemble_effects``).
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -1348,3 +1351,242 @@ __all__ = ["EnsembleAccumulator", "EnsembleStats", "reduce_host", "hardpoint_fac
            "SOBOL_DROPPED", "SOBOL_SUM_A", "SOBOL_SUM_B", "SOBOL_SUMSQ_A", "SOBOL_SUMSQ_B", "SOBOL_FIELDS", "SOBOL_MAX_GROUPS", "EnsembleSobolBootstrap",
            "SobolBootstrapAccumulator", "sobol_bootstrap_host", "bootstrap_weights", "check_replicates", "BOOTSTRAP_MAX_REPLICATES", "BOOTSTRAP_THRESHOLDS",
            "BOOTSTRAP_MAX_WEIGHT"]
+
+
+# ---- main effects from given data: conditional moments over equal-probability bins of every factor (okx_ensemble_bin, okx_ensemble_effects) ----
+
+EFFECTS_COUNT, EFFECTS_SUM, EFFECTS_SUMSQ = range(3)
+EFFECTS_FIELDS = 3  # OKX_EFFECTS_FIELDS
+EFFECTS_MAX_BINS = 64  # OKX_ENS_EFFECTS_MAX_BINS
+EFFECTS_MAX_FACTORS = 288  # OKX_ENS_EFFECTS_MAX_FACTORS (as OKX_ENS_SAMPLE_MAX_LATENTS)
+EFFECTS_NO_BIN = 255  # OKX_ENS_EFFECTS_NO_BIN: the factor is NaN, the geometry is left out for that factor alone
+
+
+def check_effects_arguments(n_bins, n_factors, edges=None, bins=None):
+    """``(n_bins, edges [F, n_bins - 1] float64 or None, bins [G, F] uint8 or None)``, or ValueError in the words of
+    ``okx_ensemble_bin`` / ``okx_ensemble_effects``: the caps, edges finite and non-decreasing per factor, bin bytes below ``n_bins`` or
+    ``EFFECTS_NO_BIN``."""
+    who = "okx_ensemble_effects"
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 1 <= int(n_bins) <= EFFECTS_MAX_BINS:
+        raise ValueError(f"{who}: {n_bins} bins, 1 to {EFFECTS_MAX_BINS} allowed")
+    b, f = int(n_bins), int(n_factors)
+    if not 1 <= f <= EFFECTS_MAX_FACTORS:
+        raise ValueError(f"{who}: {f} factors, 1 to {EFFECTS_MAX_FACTORS} allowed")
+    if edges is not None:
+        edges = np.ascontiguousarray(_host_f64(edges))
+        if edges.shape != (f, b - 1):
+            raise ValueError(f"okx_ensemble_bin: edges must be [{f}, {b - 1}] (factors, bins - 1), got {list(edges.shape)}")
+        bad = np.argwhere(~np.isfinite(edges))
+        if bad.size:
+            j, i = (int(x) for x in bad[0])
+            raise ValueError(f"okx_ensemble_bin: edge {i} of factor {j} is {edges[j, i]:g}, not finite")
+        bad = np.argwhere(edges[:, 1:] < edges[:, :-1])
+        if bad.size:
+            j, i = (int(x) for x in bad[0])
+            raise ValueError(f"okx_ensemble_bin: the edges of factor {j} decrease at edge {i + 1} ({edges[j, i + 1]:g} < {edges[j, i]:g})")
+    if bins is not None:
+        bins = np.asarray(bins)
+        if bins.ndim != 2 or bins.shape[1] != f or bins.dtype != np.uint8:
+            raise ValueError(f"{who}: bins must be uint8 [G, {f}]")
+        bad = np.argwhere((bins >= b) & (bins != EFFECTS_NO_BIN))
+        if bad.size:
+            g, j = (int(x) for x in bad[0])
+            raise ValueError(f"{who}: the bin of geometry {g} for factor {j} is {int(bins[g, j])}, neither below {b} nor {EFFECTS_NO_BIN}")
+    return b, edges, bins
+
+
+def effects_edges(source, n_bins: int) -> np.ndarray:
+    """
+    ``[F, n_bins - 1]`` ascending interior edges of ``n_bins`` equal-probability bins of every factor.  ``source`` an
+    ``ensemble_sample.SamplePlan`` (the factors are its latents): the ANALYTIC edges, the plan's own inverse CDFs at ``k / n_bins``
+    through ``ensemble_sample.latents_from_units`` - every rank computes the same bits without seeing a sample.  ``source`` a table
+    ``[G, F]``: the exact order statistic ``sorted(column)[ceil(k G / n_bins) - 1]``, a member of the column, no interpolation.
+    """
+    from .ensemble_sample import SamplePlan, latents_from_units
+
+    if isinstance(source, SamplePlan):
+        b = check_effects_arguments(n_bins, source.n_latents)[0]
+        u = np.repeat((np.arange(1, b, dtype=np.float64) / float(b))[:, None], source.n_latents, axis=1)  # [B - 1, Z]
+        return np.ascontiguousarray(latents_from_units(source, u).T)
+    table = _host_f64(source)
+    if table.ndim != 2 or table.shape[0] < 1:
+        raise ValueError("okx_ensemble_bin: the edges of a table need factors [G, F] with G >= 1")
+    g, f = table.shape
+    b = check_effects_arguments(n_bins, f)[0]
+    at = np.asarray([(k * g + b - 1) // b - 1 for k in range(1, b)], dtype=np.int64)  # ceil(k G / B) - 1, in integers
+    return np.ascontiguousarray(np.sort(table, axis=0)[at].T.reshape(f, b - 1))
+
+
+def bin_factors_host(factors, edges) -> np.ndarray:
+    """
+    ``okx_ensemble_bin``'s bin bytes in NumPy: ``[G, F]`` uint8 of ``factors [G, F]`` against ``edges [F, B - 1]``.  The bin is the NUMBER
+    OF EDGES ``<= x`` - comparisons only: a value on an edge goes to the upper bin, ``-inf`` / ``+inf`` land in the end bins.  NaN gives
+    ``EFFECTS_NO_BIN``: the geometry is left out for that factor only.
+    """
+    x = np.asarray(factors, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("factors must be [G, F]")
+    edges = np.asarray(edges, dtype=np.float64).reshape(x.shape[1], -1)
+    _, edges, _ = check_effects_arguments(edges.shape[1] + 1, x.shape[1], edges)
+    with np.errstate(invalid="ignore"):
+        at = (edges[None, :, :] <= x[:, :, None]).sum(axis=2)
+    return np.where(np.isnan(x), EFFECTS_NO_BIN, at).astype(np.uint8)
+
+
+def bin_lists_host(bins, n_bins: int):
+    """``(order [F, G] int32, offsets [F, n_bins + 1] int64)`` of ``okx_ensemble_bin`` from the bin bytes ``[G, F]``: per factor the binned
+    geometries bin by bin, ascending geometry index inside a bin (the slots behind them -1), and where every bin starts."""
+    bins = np.asarray(bins)
+    b, _, bins = check_effects_arguments(n_bins, bins.shape[1] if bins.ndim == 2 else 0, None, bins)
+    g, f = bins.shape
+    order = np.full((f, g), -1, dtype=np.int32)
+    offsets = np.zeros((f, b + 1), dtype=np.int64)
+    for j in range(f):
+        ranked = np.argsort(bins[:, j], kind="stable")  # (255 sorts last)
+        n = int((bins[:, j] != EFFECTS_NO_BIN).sum())
+        order[j, :n] = ranked[:n]
+        offsets[j, 1:] = np.cumsum(np.bincount(bins[:, j], minlength=256)[:b])
+    return order, offsets
+
+
+@dataclass
+class EnsembleEffects:
+    """
+    What ``EffectsAccumulator.finalize`` returns (NumPy, host), the main effects of every factor on every (step, column) entry from
+    given data (Plischke 2010).  Per (factor, bin, entry) ``[F, B, S, K]``: ``count`` the geometries of the bin that count at the entry,
+    ``mean`` the conditional mean ``E[value | factor in bin]`` (NaN for an empty bin) and ``std`` the within-bin standard deviation
+    (unbiased; NaN for ``count < 2``).  Per (factor, entry) ``[F, S, K]``, from the bins' sums - a geometry whose factor is NaN is in no
+    bin, so these may differ from factor to factor: ``total_count``, ``total_mean``, ``total_variance`` (unbiased; NaN for ``total_count <
+    2``), ``first = SSB / SST`` with ``SSB = sum_b s_b^2 / n_b - s^2 / n`` and ``SST = q - s^2 / n``, the share of the variance the
+    conditional means explain, and ``first_corrected = (SSB - (B' - 1) MSW) / SST`` with ``MSW = (SST - SSB) / (n - B')`` and ``B'`` the
+    non-empty bins: ``first`` less its upward bias of about ``(B' - 1) / n`` (the one-way ANOVA correction; it may come out slightly
+    negative).  Both are NaN where ``SST <= 0`` or ``n <= B'``.  ``edges [F, B - 1]`` are the bins' interior edges.
+
+    ``first`` is the first-order Sobol' index of the factor only when the factors are INDEPENDENT.  That holds for the sampler's
+    latents (``factors="sampled"``); it does not hold for the mixed coordinates of a plan with ``mixing``, where a factor's bins also
+    sort the geometries by what correlates with it.
+    """
+
+    count: np.ndarray
+    mean: np.ndarray
+    std: np.ndarray
+    total_count: np.ndarray
+    total_mean: np.ndarray
+    total_variance: np.ndarray
+    first: np.ndarray
+    first_corrected: np.ndarray
+    edges: np.ndarray
+    factor_names: list | None = None
+
+
+class EffectsAccumulator(_Accumulator):
+    """
+    The raw tables of ``okx_ensemble_effects``: ``acc [F, B, EFFECTS_FIELDS, S, K]`` float64 (``COUNT``, ``SUM d``, ``SUMSQ d d`` of every
+    bin of every factor), ``shift [S, K]`` and ``edges [F, B - 1]`` - NumPy arrays or torch tensors (host or device), whatever produced
+    them.
+    """
+
+    TABLES, CARRIED = ("acc", "shift", "edges"), ("factor_names",)
+
+    def __init__(self, acc, shift, edges, factor_names=None):
+        self.acc, self.shift, self.edges = acc, shift, edges
+        self.factor_names = list(factor_names) if factor_names is not None else None
+        if acc.ndim != 5 or acc.shape[2] != EFFECTS_FIELDS or tuple(shift.shape) != tuple(acc.shape[3:]) \
+                or tuple(edges.shape) != (acc.shape[0], acc.shape[1] - 1):
+            raise ValueError("acc must be [F, B, EFFECTS_FIELDS, S, K], shift [S, K] and edges [F, B - 1]")
+
+    n_factors = property(lambda self: int(self.acc.shape[0]))
+    n_bins = property(lambda self: int(self.acc.shape[1]))
+
+    @classmethod
+    def empty(cls, steps: int, n_columns: int, shift, edges, factor_names=None) -> "EffectsAccumulator":
+        """The accumulator of no geometry at all (the neutral element of ``merge``), NumPy."""
+        edges = np.asarray(edges, dtype=np.float64)
+        return cls(np.zeros((edges.shape[0], edges.shape[1] + 1, EFFECTS_FIELDS, steps, n_columns)),
+                   np.asarray(shift, dtype=np.float64).reshape(steps, n_columns), edges, factor_names)
+
+    def merge(self, other: "EffectsAccumulator") -> "EffectsAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been taken
+        with the same shift and the same edges.  Works on NumPy arrays and on torch tensors alike."""
+        if not _same_shape(self.acc, other.acc):
+            raise ValueError("accumulators of different shapes")
+        if not _same_table(self.edges, other.edges):
+            raise ValueError("accumulators binned with different edges cannot be merged")
+        if not _same_table(self.shift, other.shift):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        return EffectsAccumulator(self.acc + other.acc, self.shift, self.edges, self.factor_names)
+
+    def finalize(self) -> EnsembleEffects:
+        """Conditional means, within-bin spreads and the first-order indices on the host in fp64."""
+        h = self.numpy()
+        acc, shift = np.asarray(h.acc, dtype=np.float64), np.asarray(h.shift, dtype=np.float64)
+        nb, sb, qb = acc[:, :, EFFECTS_COUNT], acc[:, :, EFFECTS_SUM], acc[:, :, EFFECTS_SUMSQ]  # [F, B, S, K]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_b = np.where(nb > 0, sb / nb, np.nan)
+            within_b = np.where(nb > 0, np.maximum(qb - sb * mean_b, 0.0), 0.0)  # sum (d - mean_b)^2 of the bin
+            std = np.sqrt(np.where(nb > 1, within_b / (nb - 1), np.nan))
+            n, s, q = nb.sum(axis=1), sb.sum(axis=1), qb.sum(axis=1)              # [F, S, K]
+            filled = (nb > 0).sum(axis=1).astype(np.float64)
+            mean_d = np.where(n > 0, s / n, np.nan)
+            sst = q - s * mean_d
+            ssb = np.where(nb > 0, sb * mean_b, 0.0).sum(axis=1) - s * mean_d
+            defined = (sst > 0.0) & (n > filled)
+            msw = (sst - ssb) / (n - filled)
+            first = np.where(defined, ssb / sst, np.nan)
+            corrected = np.where(defined, (ssb - (filled - 1.0) * msw) / sst, np.nan)
+            variance = np.where(n > 1, np.maximum(sst, 0.0) / (n - 1), np.nan)
+        return EnsembleEffects(nb.astype(np.int64), shift[None, None] + mean_b, std, n.astype(np.int64), shift[None] + mean_d, variance, first, corrected,
+                               np.asarray(h.edges, dtype=np.float64), self.factor_names)
+
+
+def effects_terms(values, status=None, mask=None, shift=None):
+    """The terms ``okx_ensemble_effects`` sums, per geometry: ``(counts [G, S, K] bool, d [G, S, K], shift [S, K])`` of ``values [G, S, K]``,
+    ``status [G, S]`` uint8 or None and ``mask [G]`` uint8 or None (bit 0 set: the geometry does not count); ``d = value - shift``, rounded,
+    0 where the geometry does not count."""
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    if shift is None:
+        shift = clean_shift(v[0]) if g else np.zeros((s, k))
+    shift = np.asarray(shift, dtype=np.float64).reshape(s, k)
+    if not np.all(np.isfinite(shift)):
+        raise ValueError("the shift must be finite (clean_shift replaces undefined entries)")
+    if mask is not None:
+        ok = ok & ((np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0)[:, None, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.where(ok, v - shift[None], 0.0)
+    return ok, d, shift
+
+
+def effects_host(values, status=None, mask=None, bins=None, n_bins: int = 1, shift=None, edges=None, factor_names=None) -> EffectsAccumulator:
+    """
+    The accumulator of ``okx_ensemble_effects`` in NumPy.  ``values [G, S, K]``; ``status [G, S]`` uint8 or None (every state accepted);
+    ``mask [G]`` uint8 or None (bit 0 set: the geometry does not count - the sampler's / screen's flag byte); ``bins [G, F]`` uint8 the
+    bin of every geometry for every factor (``bin_factors_host``; ``EFFECTS_NO_BIN``: in none); ``shift [S, K]`` (None: the values of
+    geometry 0, undefined entries 0); ``edges [F, n_bins - 1]`` what the bins were cut with (None: not recorded, NaN).  Cell (factor,
+    bin, entry) covers the geometries of that bin that count at the entry; every difference and product is rounded on its own and
+    the sums run over the bin's geometries in ascending order, one after the other.
+    """
+    ok, d, shift = effects_terms(values, status, mask, shift)
+    g, s, k = d.shape
+    if bins is None:
+        raise ValueError("okx_ensemble_effects: bins are needed (bin_factors_host)")
+    bins = np.asarray(bins)
+    b, edges, bins = check_effects_arguments(n_bins, bins.shape[1] if bins.ndim == 2 else 0, edges, bins)
+    if bins.shape[0] != g:
+        raise ValueError(f"okx_ensemble_effects: bins must be uint8 [{g}, F], one row per geometry")
+    f = bins.shape[1]
+    order, offsets = bin_lists_host(bins, b)
+    acc = np.zeros((f, b, EFFECTS_FIELDS, s, k))
+    with np.errstate(over="ignore", invalid="ignore"):
+        sq = d * d
+    for j in range(f):
+        lengths = np.diff(offsets[j])
+        for p in range(int(lengths.max()) if b else 0):  # the p-th geometry of every bin that has one: each cell's chain in ascending order
+            has = np.flatnonzero(lengths > p)
+            at = order[j, offsets[j, has] + p]
+            acc[j, has, EFFECTS_COUNT] += ok[at]
+            acc[j, has, EFFECTS_SUM] += d[at]
+            acc[j, has, EFFECTS_SUMSQ] += sq[at]
+    if edges is None:
+        edges = np.full((f, b - 1), np.nan)
+    return EffectsAccumulator(acc, shift, edges, factor_names)
