@@ -1330,6 +1330,75 @@ int32_t okx_ensemble_effects(int64_t n_geometries, int64_t steps, int32_t n_colu
                              double* d_acc,                       /* [n_factors][n_bins][3][steps * n_columns]        */
                              void* stream);
 
+/*
+ * Tolerance what-ifs by likelihood reweighting on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up):
+ * what the scatter and the yield of an evaluated ensemble BECOME when the law of some latents changes from p to q - a tolerance
+ * tightened, a nominal re-centred - from the ensemble that is already in HBM, without a further draw or solve.  A scenario is a
+ * per-geometry likelihood ratio w_g = q(z_g) / p(z_g) of the latents the sampler kept (okx_ensemble_sample's d_latents); every
+ * what-if statistic is a weighted sum over the evaluated table.
+ *
+ * okx_ensemble_tilt_weights.  d_latents [n_geometries][ldz] doubles (n_latents <= ldz), d_tilt [n_scenarios][n_latents]
+ * [OKX_TILT_PARAMS] = (a, b, c, lo, hi) per (scenario, latent) - ensemble_sample.tolerance_scenarios builds it -,
+ * 1 <= n_scenarios <= OKX_ENS_TILT_MAX_SCENARIOS, 1 <= n_latents <= OKX_ENS_SAMPLE_MAX_LATENTS.  Per (geometry, scenario), over
+ * the latents z in ascending order:
+ *   inside = lo <= z <= hi (comparisons: a NaN latent is outside), term = (c z + b) z + a, logw = 0.0 + term_0 + term_1 + ...
+ *   d_weights [n_geometries][ldw] double (n_scenarios <= ldw):  w = every latent inside ? exp_unit(logw) : 0.0
+ * exp_unit(x): k = rint(x * 1.4426950408889634), r = (x - k * LN2_HI) - k * LN2_LO with LN2_HI = 0x3fe62e42fee00000 and
+ * LN2_LO = 1.9082149292705877e-10, P = the Horner sum of r^n / n!, n = 0 .. 13, the result ldexp(P, k); x < -708 and NaN give
+ * 0.0, x > 708 is taken as 708.  Every operation is rounded on its own (contraction is off for the unit): the pass equals
+ * ensemble_sample.tilt_weights_host (NumPy) bit for bit.  The launch cannot read d_tilt on the host:
+ * okx_ensemble_tilt_check validates a HOST copy of it (a NaN, lo > hi, a non-finite a, b or c, the caps).
+ *
+ * okx_ensemble_reweigh.  Table, status bytes and counting rule are those of okx_ensemble_reduce (status & 7 == 1 and a finite
+ * value); with d_mask [n_geometries] uint8 a geometry counts only when bit 0 of its byte is clear (the sampler's d_flags).
+ * d_weights [n_geometries][ldw] the weights of n_scenarios scenarios (the pass above, or any doubles); d_limits
+ * [steps][n_columns][2] = (lo, hi) or NULL (nothing is outside); d_verdict [n_geometries] uint8, okx_ensemble_screen's d_flags, or
+ * NULL (every geometry passes).  With d = value - d_shift[step][column] and ww = w w:
+ *   d_acc [n_scenarios][OKX_REWEIGH_FIELDS][steps * n_columns], every field a double, the entry fastest, over the states that count:
+ *   OKX_REWEIGH_COUNT those with w > 0;  OKX_REWEIGH_W sum w;  OKX_REWEIGH_WW sum ww;  OKX_REWEIGH_WD sum w d;
+ *   OKX_REWEIGH_WDD sum (w d) d;  OKX_REWEIGH_WWD sum ww d;  OKX_REWEIGH_WWDD sum (ww d) d;  OKX_REWEIGH_OUT_LO sum w [value < lo];
+ *   OKX_REWEIGH_OUT_HI sum w [value > hi];  OKX_REWEIGH_WW_OUT sum ww [value < lo or value > hi]
+ *   d_joint [n_scenarios][OKX_REWEIGH_JOINT_FIELDS] over the geometries whose mask bit is clear:
+ *   OKX_REWEIGH_JOINT_SEEN sum w;  _SEEN_WW sum ww;  _PASS sum w [verdict == 0];  _PASS_WW;  _OUTSIDE sum w [verdict &
+ *   OKX_SCREEN_OUTSIDE];  _UNRESOLVED sum w [verdict & OKX_SCREEN_UNRESOLVED];  _GEOMETRIES their number (the same in every scenario)
+ * ROUNDING.  d, ww and every product are rounded on their own, then added (no fused multiply-add); a geometry whose weight is
+ * 0 in a scenario is skipped there.  Geometries ascend inside a slab, slab partials (d_scratch, okx_ensemble_reweigh_scratch_bytes)
+ * merge in ascending order after what d_acc / d_joint hold when accumulate = 1 (all partials need ONE shift and the same
+ * limits), the slab plan comes from the sizes alone and there is no floating-point atomic: bit-identical from run to run and
+ * from device to device; chunkings agree to rounding, exactly when the sums are exact.  The host turns the fields into
+ * self-normalised means, spreads, effective sample sizes, standard errors and yields (ensemble_stats.ReweighAccumulator.finalize).
+ * Both are launch-only, stream-ordered, without allocation and legal inside a stream capture; n_geometries = 0 is legal
+ * (no weights; zeros or, accumulating, what was there).  Errors (okx_last_error text): a negative count, n_scenarios or
+ * n_latents outside their caps, ld < n_columns / ldz < n_latents / ldw < n_scenarios or a null table, too many entries for one
+ * call, short or misaligned scratch.
+ */
+enum { OKX_ENS_TILT_MAX_SCENARIOS = 256, OKX_TILT_PARAMS = 5 };
+enum { OKX_REWEIGH_COUNT = 0, OKX_REWEIGH_W = 1, OKX_REWEIGH_WW = 2, OKX_REWEIGH_WD = 3, OKX_REWEIGH_WDD = 4, OKX_REWEIGH_WWD = 5,
+       OKX_REWEIGH_WWDD = 6, OKX_REWEIGH_OUT_LO = 7, OKX_REWEIGH_OUT_HI = 8, OKX_REWEIGH_WW_OUT = 9, OKX_REWEIGH_FIELDS = 10 };
+enum { OKX_REWEIGH_JOINT_SEEN = 0, OKX_REWEIGH_JOINT_SEEN_WW = 1, OKX_REWEIGH_JOINT_PASS = 2, OKX_REWEIGH_JOINT_PASS_WW = 3,
+       OKX_REWEIGH_JOINT_OUTSIDE = 4, OKX_REWEIGH_JOINT_UNRESOLVED = 5, OKX_REWEIGH_JOINT_GEOMETRIES = 6, OKX_REWEIGH_JOINT_FIELDS = 7 };
+
+int32_t okx_ensemble_tilt_weights(int64_t n_geometries,
+                                  const double* d_latents, int64_t ldz, int32_t n_latents,  /* [n_geometries][ldz]            */
+                                  const double* d_tilt, int32_t n_scenarios,                /* [n_scenarios][n_latents][5]    */
+                                  double* d_weights, int64_t ldw,                           /* [n_geometries][ldw]            */
+                                  void* stream);
+int32_t okx_ensemble_tilt_check(const double* tilt, int32_t n_scenarios, int32_t n_latents);
+
+int32_t okx_ensemble_reweigh(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                             const double* d_values, int64_t ld,              /* [n_geometries * steps][ld]           */
+                             const uint8_t* d_status, int64_t status_stride,  /* or NULL                              */
+                             const uint8_t* d_mask,                           /* [n_geometries] or NULL               */
+                             const double* d_shift,                           /* [steps][n_columns]                   */
+                             const double* d_weights, int64_t ldw, int32_t n_scenarios, /* [n_geometries][ldw]        */
+                             const double* d_limits,                          /* [steps][n_columns][2] or NULL        */
+                             const uint8_t* d_verdict,                        /* [n_geometries] or NULL               */
+                             int32_t accumulate,
+                             double* d_acc,                       /* [n_scenarios][10][steps * n_columns]             */
+                             double* d_joint,                     /* [n_scenarios][7]                                 */
+                             void* d_scratch, size_t scratch_bytes, void* stream);
+size_t okx_ensemble_reweigh_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_scenarios);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,13 @@ EVAL_AXLE_LEFT, EVAL_AXLE_RIGHT, EVAL_AXLE_METRICS, EVAL_AXLE_ROLES = 0, 24, 48,
 ENS_EFFECTS_MAX_BINS, ENS_EFFECTS_MAX_FACTORS, ENS_EFFECTS_NO_BIN = 64, 288, 255
 EFFECTS_COUNT, EFFECTS_SUM, EFFECTS_SUMSQ, EFFECTS_FIELDS = 0, 1, 2, 3
 
+# okx_ensemble_tilt_weights / okx_ensemble_reweigh (include/okx.h OKX_ENS_TILT_*, OKX_TILT_*, OKX_REWEIGH_*); ensemble_stats.py names them REWEIGH_*
+ENS_TILT_MAX_SCENARIOS, TILT_PARAMS = 256, 5
+(REWEIGH_COUNT, REWEIGH_W, REWEIGH_WW, REWEIGH_WD, REWEIGH_WDD, REWEIGH_WWD, REWEIGH_WWDD, REWEIGH_OUT_LO, REWEIGH_OUT_HI, REWEIGH_WW_OUT,
+ REWEIGH_FIELDS) = range(11)
+(REWEIGH_JOINT_SEEN, REWEIGH_JOINT_SEEN_WW, REWEIGH_JOINT_PASS, REWEIGH_JOINT_PASS_WW, REWEIGH_JOINT_OUTSIDE, REWEIGH_JOINT_UNRESOLVED,
+ REWEIGH_JOINT_GEOMETRIES, REWEIGH_JOINT_FIELDS) = range(8)
+
 INFO_CONVERGED = 1
 INFO_RESIDUAL_EXCEEDED = 2
 INFO_FAILED = 4

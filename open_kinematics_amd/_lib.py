@@ -92,6 +92,10 @@ EXPORTS = (
     "okx_ensemble_sobol_bootstrap_scratch_bytes",
     "okx_ensemble_bin",
     "okx_ensemble_effects",
+    "okx_ensemble_tilt_weights",
+    "okx_ensemble_tilt_check",
+    "okx_ensemble_reweigh",
+    "okx_ensemble_reweigh_scratch_bytes",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -312,6 +316,14 @@ def load() -> C.CDLL:
     lib.okx_ensemble_bin.restype = i32
     lib.okx_ensemble_effects.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp]
     lib.okx_ensemble_effects.restype = i32
+    lib.okx_ensemble_tilt_weights.argtypes = [i64, vp, i64, i32, vp, i32, vp, i64, vp]
+    lib.okx_ensemble_tilt_weights.restype = i32
+    lib.okx_ensemble_tilt_check.argtypes = [vp, i32, i32]
+    lib.okx_ensemble_tilt_check.restype = i32
+    lib.okx_ensemble_reweigh.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_reweigh.restype = i32
+    lib.okx_ensemble_reweigh_scratch_bytes.argtypes = [i64, i64, i32, i32]
+    lib.okx_ensemble_reweigh_scratch_bytes.restype = C.c_size_t
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -441,13 +441,24 @@ class ShardedEnsemble:
     every cell's chain, so chunkings of one rank carry the same bits; world sizes agree to rounding.  ``effects()`` returns the
     ``ensemble_stats.EnsembleEffects`` (conditional mean and spread per bin, first-order index per factor and entry),
     ``effects_accumulator`` the merged tables, ``effects_exchange_bytes_per_rank`` what the rank sends (``24 P B S K``).
+
+    ``whatif=scenarios`` (with ``reduce=True``, a ``SamplePlan`` and ``factors="sampled"``) adds WHAT THE SCATTER AND THE YIELD BECOME when
+    tolerances change (``okx_ensemble_tilt_weights`` / ``okx_ensemble_reweigh``): ``scenarios`` is the list of specs
+    ``ensemble_sample.tolerance_scenarios`` takes (or its table); every geometry gets the likelihood ratio of its latents under each
+    scenario - a chunk's weights are computed once - and right after the chunk's reduction (and screen) its rows of ``metric_local`` are
+    accumulated as weighted sums with the reduction's shift, the sampler's flags as the mask, ``limits=`` when given and, with
+    ``screen=True``, the screen's flag bytes as the verdict.  No further draw and no further solve.  ``step()`` then ends with one
+    all-gather of the accumulators, added on every rank in ascending rank order - the same bits on every rank; world sizes and
+    chunkings agree to rounding, exactly when the sums are exact.  ``whatif()`` returns the ``ensemble_stats.EnsembleWhatIf``,
+    ``whatif_accumulator`` the merged tables, ``whatif_exchange_bytes_per_rank`` what the rank sends (``8 N (10 S K + 7)``).  It is refused for a
+    ``FamilyPlan``, whose pick-freeze members are no draw of the plan's law.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
                  covariance=None, curves=None, front=None, sobol: bool = False, bootstrap: int | None = None, bootstrap_seed: int | None = None,
-                 effects=None, **solve_kw):
+                 effects=None, whatif=None, **solve_kw):
         from .ensemble_sample import FamilyPlan, SamplePlan
 
         self.plan = hardpoints if isinstance(hardpoints, (SamplePlan, FamilyPlan)) else None
@@ -471,7 +482,10 @@ class ShardedEnsemble:
             raise ValueError("reduce=True reduces metric columns: it needs metric_columns (and factors / shift need reduce=True)")
         if (screen or screen_scale is not None) and (not screen or not reduce or limits is None):
             raise ValueError("screen=True screens the reduced ensemble: it needs reduce=True and limits (and screen_scale needs screen=True)")
-        if (quantiles is not None or (limits is not None and not screen)) and (not reduce or quantiles is None):
+        if whatif is not None and (not reduce or isinstance(self.plan, FamilyPlan) or not (isinstance(factors, str) and factors == "sampled")):
+            raise ValueError("whatif= reweighs the ensemble of a SamplePlan by its latents: it needs reduce=True, factors='sampled' and no FamilyPlan "
+                             "(a pick-freeze family is not a draw of the plan's law)")
+        if (quantiles is not None or (limits is not None and not screen and whatif is None)) and (not reduce or quantiles is None):
             raise ValueError("quantiles / limits select over the reduced ensemble: they need reduce=True (and limits need quantiles)")
         if covariance is False:
             covariance = None
@@ -643,6 +657,8 @@ class ShardedEnsemble:
                 self.covariance_entries = stage.entries
             if effects is not None:
                 self.stages["effects"] = stages.Effects(self, effects)
+            if whatif is not None:
+                self.stages["whatif"] = stages.WhatIf(self, whatif, limits)
             if curves is not None:
                 self.stages["curves"] = stages.Curves(self, dict(curves))
             if front is not None:
@@ -651,6 +667,7 @@ class ShardedEnsemble:
         self.select_exchange_bytes_per_rank, self.screen_exchange_bytes_per_rank = sent.get("select", 0), sent.get("screen", 0)
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
         self.effects_exchange_bytes_per_rank = sent.get("effects", 0)
+        self.whatif_exchange_bytes_per_rank = sent.get("whatif", 0)
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
         self.front_exchange_bytes_per_rank = sent.get("front", 0)
         self.sobol_exchange_bytes_per_rank = sent.get("sobol", 0)
@@ -693,6 +710,17 @@ class ShardedEnsemble:
         if "effects" not in self.stages:
             raise ValueError("effects() needs effects=n_bins")
         return self.stages["effects"].effects()
+
+    whatif_accumulator = property(lambda self: self.stages["whatif"].merged,
+                                  doc="The merged what-if accumulator of the last ``step()`` (``whatif=``); None before.")
+
+    def whatif(self):
+        """``ensemble_stats.EnsembleWhatIf`` of the WHOLE ensemble after the last ``step()`` (``whatif=``): per scenario and entry the reweighted
+        mean, spread, effective sample size, standard error and yield; per scenario the joint yield and the mean weight.  The same bits on
+        every rank."""
+        if "whatif" not in self.stages:
+            raise ValueError("whatif() needs whatif=scenarios")
+        return self.stages["whatif"].whatif()
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""

@@ -18,6 +18,8 @@ pass (``okx_ensemble_...``)    prepare call          result
 ``bootstrap_weights``          -                     ``uint8 [n_rows, R]`` tensor
 ``sobol_bootstrap_ensemble``   -                     ``ensemble_stats.SobolBootstrapAccumulator``
 ``effects_ensemble``           ``bin_factors``       ``ensemble_stats.EffectsAccumulator``
+``tilt_weights``               ``tilt_prepare``      ``float64 [G, N]`` tensor
+``reweigh_ensemble``           ``tilt_weights``      ``ensemble_stats.ReweighAccumulator``
 =============================  ====================  ==============================================
 
 Every pass takes ``out=``, the result of an earlier call or of its prepare call; the tables it holds are checked in one place
@@ -34,10 +36,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS,
-                             CovarianceAccumulator, EffectsAccumulator, EnsembleAccumulator, EnsembleCurves, SobolAccumulator, SobolBootstrapAccumulator,
-                             _host_f64, broadcast_limits, broadcast_scale, check_covariance_arguments, check_effects_arguments, check_front_arguments,
-                             check_replicates, factor_moment_count)
+from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, REWEIGH_FIELDS, REWEIGH_JOINT_FIELDS, REWEIGH_MAX_SCENARIOS,
+                             SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS, CovarianceAccumulator, EffectsAccumulator, EnsembleAccumulator, EnsembleCurves,
+                             ReweighAccumulator, SobolAccumulator, SobolBootstrapAccumulator, _host_f64, broadcast_limits, broadcast_scale,
+                             check_covariance_arguments, check_effects_arguments, check_front_arguments, check_replicates, check_reweigh_limits, factor_moment_count)
 
 F64, I64, I32, U8 = torch.float64, torch.int64, torch.int32, torch.uint8
 
@@ -913,4 +915,94 @@ class EnsembleReductions:
         self._check_mask(mask, g, contiguous=True)
         self._ensemble_call("okx_ensemble_effects", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), f, b, _ptr(bins.order), _ptr(bins.offsets),
                             _ptr(out.shift), 1 if accumulate else 0, _ptr(out.acc))
+        return out
+
+    # ---- okx_ensemble_tilt_weights / okx_ensemble_reweigh: tolerance what-ifs by likelihood reweighting (ensemble_stats.EnsembleWhatIf) ----
+
+    def tilt_prepare(self, scenarios) -> torch.Tensor:
+        """
+        The scenario table ``[N, Z, 5]`` of ``ensemble_sample.tolerance_scenarios`` validated on the host (``okx_ensemble_tilt_check``: no NaN,
+        ``lo <= hi``, finite ``a, b, c``, the caps) and uploaded ONCE: the float64 device tensor ``tilt_weights`` takes.
+        """
+        host = np.ascontiguousarray(_host_f64(scenarios))
+        if host.ndim != 3 or host.shape[2] != 5:
+            raise ValueError("scenarios must be the [N, Z, 5] table of ensemble_sample.tolerance_scenarios")
+        rc = self.lib.okx_ensemble_tilt_check(host.ctypes.data_as(C.c_void_p), min(host.shape[0], REWEIGH_MAX_SCENARIOS + 1), min(host.shape[1], 1 << 20))
+        _lib.check(rc, "okx_ensemble_tilt_weights")
+        return torch.as_tensor(host, device=self.device)
+
+    def tilt_weights(self, latents, scenarios, out=None) -> torch.Tensor:
+        """
+        ``okx_ensemble_tilt_weights``: the likelihood ratios ``float64 [G, N]`` of the geometries whose latents are ``latents [G, Z]`` (a
+        float64 device tensor with unit column stride; rows may be strided - the sampler's ``latents`` as they lie in HBM) under the ``N``
+        scenarios of ``scenarios``: the table of ``ensemble_sample.tolerance_scenarios`` (validated and uploaded by this call) or the device
+        tensor ``tilt_prepare`` made of it (then the call uploads nothing).  The bits of ``ensemble_sample.tilt_weights_host``.  ``out``: a
+        ``[G, N]`` float64 device tensor with unit column stride to write into (rows may be strided); with it and a prepared table the call
+        allocates nothing and is legal inside a stream capture.
+        """
+        dev = self.device
+        if not isinstance(latents, torch.Tensor) or latents.dim() != 2 or latents.dtype != F64 or latents.device != dev \
+                or (latents.shape[1] > 1 and latents.stride(1) != 1):
+            raise ValueError("latents must be a float64 [G, Z] device tensor with unit column stride")
+        g, z = latents.shape
+        ldz = latents.stride(0) if g > 1 else max(z, latents.stride(0))
+        if ldz < z:
+            raise ValueError("rows of latents overlap")
+        table = scenarios if isinstance(scenarios, torch.Tensor) and scenarios.device == dev else self.tilt_prepare(scenarios)
+        n = _rows(table)
+        self._check_tables(f"scenarios must be a contiguous float64 [N, {z}, 5] table, one row per latent of the table", [(table, (n, z, 5), F64)])
+        if out is None:
+            out = torch.empty((g, n), dtype=F64, device=dev)
+        if not isinstance(out, torch.Tensor) or out.dtype != F64 or out.device != dev or tuple(out.shape) != (g, n) or (n > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be a float64 [{g}, {n}] device tensor with unit column stride")
+        ldw = out.stride(0) if g > 1 else max(n, out.stride(0))
+        if ldw < n:
+            raise ValueError("rows of out overlap")
+        self._ensemble_call("okx_ensemble_tilt_weights", g, _ptr(latents), ldz, z, _ptr(table), n, _ptr(out), ldw)
+        return out
+
+    def reweigh_ensemble(self, values, *, steps_per_geometry: int, weights, status=None, mask=None, shift=None, limits=None, verdict=None, out=None,
+                         accumulate: bool = False, scenario_names=None):
+        """
+        ``okx_ensemble_reweigh``: the what-if accumulator (``ensemble_stats.ReweighAccumulator``, device tensors: ``acc [N, 10, S, K]``,
+        ``joint [N, 7]``, ``shift [S, K]``, ``limits [S, K, 2]`` or None) of a column table in HBM under ``N`` scenarios.  ``values`` and ``status``
+        as ``reduce_ensemble`` takes them (unit column stride; strided rows and a strided status byte are passed on, nothing is copied);
+        ``weights [G, N]`` float64 with unit column stride, what ``tilt_weights`` made of the latents of THESE geometries (or any table of
+        doubles); ``mask [G]`` contiguous uint8, bit 0 set: the geometry does not count - the sampler's ``flags`` as they lie in HBM;
+        ``verdict [G]`` contiguous uint8, ``screen_ensemble``'s ``flags`` (None: every geometry passes); ``limits`` ``[S, K, 2]``, ``[K, 2]`` or
+        ``[2]`` = (lo, hi), validated on the host and uploaded (None: nothing is outside).  ``shift [S, K]`` the common shift (None: the table's
+        own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift, pass it or pass ``out=``).  ``out``: the
+        accumulator of an earlier call - it carries its own shift and limits - to write (``accumulate=False``) or add into (``True``); with
+        it and a table shape seen before, the call uploads and allocates nothing and is legal inside a stream capture.  ``.finalize()``
+        copies to the host: the reweighted mean, spread, effective sample size, standard errors and yields of every scenario.
+        Bit-identical from run to run; different chunkings agree to rounding, exactly when the sums are exact.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        dev = self.device
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.dtype != F64 or weights.device != dev or weights.shape[0] != g \
+                or (weights.shape[1] > 1 and weights.stride(1) != 1):
+            raise ValueError(f"weights must be a float64 [{g}, N] device tensor with unit column stride, one row per geometry of the table")
+        n = int(weights.shape[1])
+        if not 1 <= n <= REWEIGH_MAX_SCENARIOS:
+            raise ValueError(f"okx_ensemble_reweigh: {n} scenarios, 1 to {REWEIGH_MAX_SCENARIOS} allowed")
+        ldw = weights.stride(0) if g > 1 else max(n, weights.stride(0))
+        if ldw < n:
+            raise ValueError("rows of weights overlap")
+        if self._new_result(out, (shift, limits), "shift and limits", accumulate):
+            lim = None
+            if limits is not None:
+                lim = torch.as_tensor(check_reweigh_limits(limits, s, k), device=dev)
+            out = ReweighAccumulator(torch.empty((n, REWEIGH_FIELDS, s, k), dtype=F64, device=dev), torch.empty((n, REWEIGH_JOINT_FIELDS), dtype=F64, device=dev),
+                                     self._ensemble_shift(shift, values, g, s, k), lim, scenario_names)
+        self._check_tables(f"out must hold contiguous device tables acc [{n}, {REWEIGH_FIELDS}, S, K], joint [{n}, {REWEIGH_JOINT_FIELDS}], shift [S, K] = "
+                           f"[{s}, {k}] and limits [S, K, 2]",
+                           [(out.acc, (n, REWEIGH_FIELDS, s, k), F64), (out.joint, (n, REWEIGH_JOINT_FIELDS), F64), (out.shift, (s, k), F64)],
+                           [(out.limits, (s, k, 2), F64)])
+        self._check_mask(mask, g, contiguous=True)
+        if verdict is not None and (not isinstance(verdict, torch.Tensor) or verdict.dtype != U8 or tuple(verdict.shape) != (g,) or verdict.device != dev
+                                    or not verdict.is_contiguous()):
+            raise ValueError("verdict must be a contiguous uint8 [G] device tensor")
+        scratch = self._ensemble_scratch("reweigh", int(self.lib.okx_ensemble_reweigh_scratch_bytes(g, s, k, n)))
+        self._ensemble_call("okx_ensemble_reweigh", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift), _ptr(weights), ldw, n,
+                            _ptr(out.limits), _ptr(verdict), 1 if accumulate else 0, _ptr(out.acc), _ptr(out.joint), _ptr(scratch), scratch.numel())
         return out

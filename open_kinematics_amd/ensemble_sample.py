@@ -604,7 +604,180 @@ def group_by_point(plan: SamplePlan) -> tuple:
     return np.asarray([order.index(pt) for pt in points], dtype=np.int32), tuple(first[pt] for pt in order)
 
 
+# ---- tolerance what-ifs: likelihood reweighting of an ensemble that is already drawn (okx_ensemble_tilt_weights) ----
+
+TILT_MAX_SCENARIOS = 256  # OKX_ENS_TILT_MAX_SCENARIOS
+TILT_PARAMS = 5           # OKX_TILT_PARAMS: a, b, c, lo, hi per (scenario, latent)
+LOG2E = 1.4426950408889634
+LN2_HI = float.fromhex("0x1.62e42fee00000p-1")  # 0x3fe62e42fee00000: its low 21 bits are zero, k * LN2_HI is exact for |k| <= 1100
+LN2_LO = 1.9082149292705877e-10
+EXP_UNIT_MIN, EXP_UNIT_MAX = -708.0, 708.0
+_EXP = tuple(1.0 / math.factorial(n) for n in range(14))  # 1 / n!, n = 0 .. 13 (n! is exact in fp64, the quotient correctly rounded)
+
+
+def exp_unit(x):
+    """``exp(x)`` by ``+ - *``, ``rint`` and ``ldexp`` alone - ``log_unit``'s counterpart, written out so that host and device agree bit
+    for bit (``np.exp`` is libm's): ``k = rint(x LOG2E)``, ``r = (x - k LN2_HI) - k LN2_LO`` (|r| <= 0.35), ``P`` the Horner sum of ``r^n / n!``,
+    n = 0 .. 13, the result ``ldexp(P, k)``; within 1e-14 relative of ``exp`` on [-708, 708].  ``x < -708`` and a NaN give 0.0; ``x > 708``
+    is taken as 708 (the callers' checks keep a log-weight far below it)."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        live = x >= EXP_UNIT_MIN
+        xs = np.where(live, np.minimum(x, EXP_UNIT_MAX), 0.0)
+        k = np.rint(xs * LOG2E)
+        r = (xs - k * LN2_HI) - k * LN2_LO
+        return np.where(live, np.ldexp(_horner(_EXP, r), k.astype(np.int32)), 0.0)
+
+
+def _phi_between(lo: float, hi: float) -> float:
+    """``Phi(hi) - Phi(lo)`` of the standard normal by the host's ``erfc``, taken in the tail both bounds lie in."""
+    root = math.sqrt(2.0)
+    if lo >= 0.0:
+        return 0.5 * (math.erfc(lo / root) - math.erfc(hi / root))
+    if hi <= 0.0:
+        return 0.5 * (math.erfc(-hi / root) - math.erfc(-lo / root))
+    return (1.0 - 0.5 * math.erfc(hi / root)) - 0.5 * math.erfc(-lo / root)
+
+
+def _tilt_peak(a: float, b: float, c: float, lo: float, hi: float) -> float:
+    """The largest value of ``(c z + b) z + a`` a latent inside ``[lo, hi]`` can give (a sampled latent lies within +-9)."""
+    lo, hi = max(lo, -9.0), min(hi, 9.0)
+    at = [lo, hi] + ([-b / (2.0 * c)] if c < 0.0 and lo < -b / (2.0 * c) < hi else [])
+    return max((c * z + b) * z + a for z in at)
+
+
+def tolerance_scenarios(plan: SamplePlan, specs) -> np.ndarray:
+    """
+    The scenario table ``tilt [S, Z, 5]`` = ``(a, b, c, lo, hi)`` per (scenario, latent) that ``tilt_weights_host`` and
+    ``okx_ensemble_tilt_weights`` read.  A scenario changes the LAW of some latents of ``plan``; ``specs`` is a sequence of dicts, one
+    per scenario, ``{name: dict(ratio=t, shift=m, window=(lo, hi))}`` (every key optional: ``ratio`` 1, ``shift`` 0, ``window`` the
+    kind's own).  ``name`` is one of ``plan.factor_names()``, or a point name (``"point7"``) for its three coordinates.  By kind:
+
+    * ``NORMAL``: ``N(0, 1) -> N(m, t^2)``, ``c = (1 - 1 / t^2) / 2``, ``b = m / t^2``, ``a = -ln t - m^2 / (2 t^2)``; with a ``window`` the
+      new law is truncated to it and ``a`` also takes ``-ln(Phi((hi - m) / t) - Phi((lo - m) / t))``;
+    * ``TRUNCATED(k)``: the same ``a, b, c``; ``a`` also takes ``ln[(Phi(k) - Phi(-k)) / (Phi((hi - m) / t) - Phi((lo - m) / t))]``, the window
+      ``[lo, hi]`` inside ``[-k, k]`` (default: ``[-k, k]``);
+    * ``UNIFORM``: uniform on ``[m - t, m + t]`` inside ``[-1, 1]``: ``a = ln(1 / t)``, ``b = c = 0``, the window ``[m - t, m + t]``.
+
+    An untouched latent is ``(0, 0, 0, -inf, +inf)``, so the empty spec is the identity scenario (every weight exactly 1).  The
+    normalisers come from the host's ``erfc`` once, as ``SamplePlan.bound_table``'s: they are part of the table.  The new law must be
+    dominated by the drawn one (a window inside the support) and - ``NORMAL`` / ``TRUNCATED`` without a window - ``t < sqrt(2)``: at
+    ``t >= sqrt(2)`` the weights of a normal latent have infinite variance.
+    """
+    who = "okx_ensemble_tilt_weights"
+    specs = list(specs)
+    z = plan.n_latents
+    if not 1 <= len(specs) <= TILT_MAX_SCENARIOS:
+        raise ValueError(f"{who}: {len(specs)} scenarios, 1 to {TILT_MAX_SCENARIOS} allowed")
+    if not 1 <= z <= MAX_LATENTS:
+        raise ValueError(f"{who}: {z} latents, 1 to {MAX_LATENTS} allowed")
+    names = plan.factor_names()
+    bounds = plan.bound_table()
+    tilt = np.zeros((len(specs), z, TILT_PARAMS))
+    tilt[:, :, 3], tilt[:, :, 4] = -np.inf, np.inf
+    for s, spec in enumerate(specs):
+        for name, change in dict(spec).items():
+            hit = [i for i, n in enumerate(names) if n == name] or [i for i, n in enumerate(names) if n.startswith(f"{name}.")]
+            if not hit:
+                raise ValueError(f"{who}: scenario {s} names {name!r}, which is no latent of the plan and no point of one")
+            change = dict(change)
+            unknown = set(change) - {"ratio", "shift", "window"}
+            if unknown:
+                raise ValueError(f"{who}: scenario {s}, {name!r}: a change takes ratio, shift and window (got {sorted(unknown)})")
+            t, m, window = float(change.get("ratio", 1.0)), float(change.get("shift", 0.0)), change.get("window")
+            if not (math.isfinite(t) and t > 0.0) or not math.isfinite(m):
+                raise ValueError(f"{who}: scenario {s}, {name!r}: ratio {t:g} and shift {m:g} must be finite and the ratio greater than 0")
+            if window is not None:
+                window = (float(window[0]), float(window[1]))
+                if not window[0] < window[1]:  # (also a NaN)
+                    raise ValueError(f"{who}: scenario {s}, {name!r}: the window ({window[0]:g}, {window[1]:g}) must have lo < hi")
+            for i in hit:
+                kind = int(plan.kind[i])
+                if kind == UNIFORM:
+                    lo, hi = m - t, m + t
+                    if window is not None:
+                        raise ValueError(f"{who}: scenario {s}, {names[i]!r}: a uniform latent takes ratio and shift, its window is [shift - ratio, shift + ratio]")
+                    if lo < -1.0 or hi > 1.0:
+                        raise ValueError(f"{who}: scenario {s}, {names[i]!r}: the window [{lo:g}, {hi:g}] leaves the support [-1, 1] of the drawn law")
+                    tilt[s, i] = math.log(1.0 / t), 0.0, 0.0, lo, hi
+                    continue
+                k = float(bounds[i, 0]) if kind == TRUNCATED else math.inf
+                if window is None and t >= math.sqrt(2.0):
+                    raise ValueError(f"{who}: scenario {s}, {names[i]!r}: ratio {t:g} >= sqrt(2) without a window - the weights of a normal latent then "
+                                     f"have infinite variance")
+                lo, hi = (-k, k) if window is None else window
+                if lo < -k or hi > k:
+                    raise ValueError(f"{who}: scenario {s}, {names[i]!r}: the window [{lo:g}, {hi:g}] leaves the support [{-k:g}, {k:g}] of the drawn law")
+                a = -math.log(t) - m * m / (2.0 * t * t)
+                if math.isfinite(lo) or math.isfinite(hi):
+                    mass = _phi_between((lo - m) / t, (hi - m) / t)
+                    if not mass > 0.0:
+                        raise ValueError(f"{who}: scenario {s}, {names[i]!r}: the new law has no mass in the window [{lo:g}, {hi:g}]")
+                    a += math.log((float(bounds[i, 2]) if kind == TRUNCATED else 1.0) / mass)
+                tilt[s, i] = a, m / (t * t), 0.5 * (1.0 - 1.0 / (t * t)), lo, hi
+        peak = sum(_tilt_peak(*tilt[s, i]) for i in range(z))  # (an untouched latent adds 0)
+        if not peak <= 700.0:
+            raise ValueError(f"{who}: scenario {s}: a log-weight may reach {peak:g}, beyond what exp_unit takes (700)")
+    check_tilt(tilt)
+    return tilt
+
+
+def check_tilt(tilt) -> np.ndarray:
+    """``tilt`` as a contiguous float64 ``[S, Z, 5]`` table, or ValueError in the words of ``okx_ensemble_tilt_check``."""
+    who = "okx_ensemble_tilt_weights"
+    table = np.ascontiguousarray(np.asarray(tilt, dtype=np.float64))
+    if table.ndim != 3 or table.shape[2] != TILT_PARAMS:
+        raise ValueError(f"{who}: the scenario table must be [S, Z, {TILT_PARAMS}] (a, b, c, lo, hi)")
+    s, z = table.shape[:2]
+    if not 1 <= s <= TILT_MAX_SCENARIOS:
+        raise ValueError(f"{who}: {s} scenarios, 1 to {TILT_MAX_SCENARIOS} allowed")
+    if not 1 <= z <= MAX_LATENTS:
+        raise ValueError(f"{who}: {z} latents, 1 to {MAX_LATENTS} allowed")
+    bad = np.argwhere(~np.isfinite(table[:, :, :3]).all(axis=2))
+    if bad.size:
+        raise ValueError(f"{who}: scenario {int(bad[0, 0])}, latent {int(bad[0, 1])}: a, b or c is not finite")
+    with np.errstate(invalid="ignore"):
+        bad = np.argwhere(~(table[:, :, 3] <= table[:, :, 4]))
+    if bad.size:
+        raise ValueError(f"{who}: scenario {int(bad[0, 0])}, latent {int(bad[0, 1])}: the window is NaN or has lo > hi")
+    return table
+
+
+def tilt_weights_host(latents, tilt) -> np.ndarray:
+    """
+    The definition of ``okx_ensemble_tilt_weights``: the likelihood ratios ``w [G, S]`` of ``latents [G, Z]`` (what the sampler kept,
+    ``sample_host(plan)[1]``) under the scenarios ``tilt [S, Z, 5]`` (``tolerance_scenarios``).  Per (geometry, scenario), over the
+    latents in ascending order::
+
+        inside_z = lo <= z <= hi                 (comparisons: a NaN latent is outside)
+        term_z   = (c * z + b) * z + a           (every operation rounded on its own, no fused multiply-add)
+        logw     = 0.0 + term_0 + term_1 + ...   (every add rounded)
+        w        = exp_unit(logw) if every latent is inside, else 0.0
+
+    The device pass equals this bit for bit.  GUARDS AND REDRAWS need no special case: the drawn law is ``p`` conditioned on the
+    guards, the target law is ``q`` under the same guards, and their ratio is ``q / p`` times a constant that the self-normalised
+    estimates (``ensemble_stats.ReweighAccumulator.finalize`` divides every sum by the sum of the weights) divide out.  Under ``LHS``
+    the geometries are not independent draws: the estimates stay consistent, but the effective sample size ``(sum w)^2 / sum w^2`` and
+    the standard errors built on it are a heuristic there (on the conservative side for the strata's own latents).
+    """
+    x = np.asarray(latents, dtype=np.float64)
+    table = check_tilt(tilt)
+    if x.ndim != 2 or x.shape[1] != table.shape[1]:
+        raise ValueError(f"okx_ensemble_tilt_weights: latents must be [G, {table.shape[1]}], one column per latent of the scenario table")
+    g, s = x.shape[0], table.shape[0]
+    logw = np.zeros((g, s))
+    inside = np.ones((g, s), dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(table.shape[1]):
+            a, b, c, lo, hi = (table[None, :, i, j] for j in range(TILT_PARAMS))
+            col = x[:, i, None]
+            inside &= (lo <= col) & (col <= hi)
+            logw = logw + ((c * col + b) * col + a)
+        return np.where(inside, exp_unit(logw), 0.0)
+
+
 __all__ = ["SamplePlan", "sample_host", "hardpoint_plan", "FamilyPlan", "families_host", "check_families", "group_by_point",
+           "tolerance_scenarios", "tilt_weights_host", "check_tilt", "exp_unit", "TILT_MAX_SCENARIOS", "TILT_PARAMS",
            "SOBOL_MAX_GROUPS", "philox4x32_10", "draw_bits", "unit_from_bits", "stratum", "strata_bits", "strata_keys",
            "ppnd16", "log_unit", "units", "stratified_unit", "latents_from_units", "contract", "guards_hold", "check_arguments", "check_plan",
            "NORMAL", "UNIFORM", "TRUNCATED", "IID", "LHS", "GUARD_SIGN", "GUARD_DISTINCT", "GUARD_OFF_LINE", "PURPOSE_DRAW", "PURPOSE_STRATA", "PURPOSE_BOOTSTRAP",

@@ -1,7 +1,7 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
 (moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``SobolBootstrap`` (``bootstrap=``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
-(``covariance=``), ``Effects`` (``effects=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+(``covariance=``), ``Effects`` (``effects=``), ``WhatIf`` (``whatif=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
 * ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
@@ -509,6 +509,83 @@ class Effects(_AccumulatorStage):
                                                                                                   self.factor_names))
 
     def effects(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result
+
+
+class WhatIf(_AccumulatorStage):
+    """``whatif=scenarios`` (with ``factors="sampled"``): what every entry's scatter and yield become under each tolerance scenario, chunk
+    by chunk right after the reduction (and the screen), with the reduction's shift, the sampler's flag bytes as the mask, ``limits=``
+    when given and - with ``screen=True`` - the screen's flag bytes as the verdict.  ``scenarios`` is the list of specs
+    ``ensemble_sample.tolerance_scenarios`` takes, or the table it returns.  A chunk's weights are computed once, the first time it is
+    taken in: latents do not change from step to step."""
+
+    def __init__(self, owner, whatif, limits):
+        super().__init__(owner)
+        from .ensemble_sample import check_tilt, tolerance_scenarios
+
+        o = owner
+        reduction = o.stages["reduce"]
+        if isinstance(whatif, (np.ndarray, torch.Tensor)):
+            whatif = whatif.detach().cpu().numpy() if isinstance(whatif, torch.Tensor) else whatif
+            self.tilt = check_tilt(whatif)
+            if self.tilt.shape[1] != o.plan.n_latents:
+                raise ValueError(f"whatif=: the scenario table has {self.tilt.shape[1]} latents, the plan {o.plan.n_latents}")
+        else:
+            self.tilt = tolerance_scenarios(o.plan, whatif)
+        n, k = int(self.tilt.shape[0]), len(o.metric_index)
+        self.limits = None if limits is None else es.check_reweigh_limits(limits, o.steps, k)
+        self.latents = reduction.my_factors  # this rank's rows [n, Z] of the plan's latents, where the ensemble lives
+        self.flags = o.sampled_flags.contiguous()
+        shift = o.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's (itself, no copy)
+        self.local = es.ReweighAccumulator(torch.zeros((n, es.REWEIGH_FIELDS, o.steps, k), dtype=torch.float64, device=o.device),
+                                           torch.zeros((n, es.REWEIGH_JOINT_FIELDS), dtype=torch.float64, device=o.device), shift,
+                                           None if self.limits is None else torch.as_tensor(self.limits, device=o.device))
+        self.table = o.dp.tilt_prepare(self.tilt) if self.on_device else None
+        self.weights = {}  # (a, b) -> the weights of the chunk's rows
+        self.merged = self.result = None
+        self.allocate_exchange(self.local.acc.numel() + self.local.joint.numel())
+
+    def take(self, a: int, b: int, values, status) -> None:
+        from .ensemble_sample import tilt_weights_host
+
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        rows = slice(a - glo, b - glo)
+        mask, weights, verdict = self.flags[rows], self.weights.get((a, b)), None
+        screen = o.stages.get("screen")
+        if self.on_device:
+            if weights is None:
+                weights = self.weights[(a, b)] = o.dp.tilt_weights(self.latents[rows], self.table)
+            if screen is not None:
+                verdict = screen.run.flags[rows]
+            o.dp.reweigh_ensemble(values, steps_per_geometry=o.steps, weights=weights, status=status, mask=mask, verdict=verdict, out=mine,
+                                  accumulate=self.taken)
+            return
+        if weights is None:
+            weights = self.weights[(a, b)] = tilt_weights_host(self.latents[rows].cpu().numpy(), self.tilt)
+        if screen is not None:
+            verdict = np.ascontiguousarray(screen.part.flags[rows])
+        part = es.reweigh_host(*self.host_tables(a, b, values, status), mask.cpu().numpy(), weights, mine.shift.cpu().numpy(), self.limits, verdict)
+        if not self.taken:
+            mine.acc.zero_(), mine.joint.zero_()
+        mine.acc += torch.from_numpy(part.acc)
+        mine.joint += torch.from_numpy(part.joint)
+
+    def exchange(self) -> None:
+        mine = self.local
+        n_acc = mine.acc.numel()
+        self.result = None
+
+        def unpack(row):
+            return es.ReweighAccumulator(row[:n_acc].reshape(mine.acc.shape), row[n_acc:].reshape(mine.joint.shape), mine.shift, mine.limits)
+
+        self.merged = self.merged_over_ranks(mine, (mine.acc, mine.joint), unpack)
+
+    def whatif(self):
         if self.merged is None:
             raise RuntimeError("no step() yet")
         if self.result is None:

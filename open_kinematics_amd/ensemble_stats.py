@@ -1590,3 +1590,218 @@ def effects_host(values, status=None, mask=None, bins=None, n_bins: int = 1, shi
     if edges is None:
         edges = np.full((f, b - 1), np.nan)
     return EffectsAccumulator(acc, shift, edges, factor_names)
+
+
+# ---- tolerance what-ifs: the evaluated table under likelihood weights, scenario by scenario (okx_ensemble_reweigh) ----
+
+(REWEIGH_COUNT, REWEIGH_W, REWEIGH_WW, REWEIGH_WD, REWEIGH_WDD, REWEIGH_WWD, REWEIGH_WWDD, REWEIGH_OUT_LO, REWEIGH_OUT_HI,
+ REWEIGH_WW_OUT) = range(10)
+REWEIGH_FIELDS = 10  # OKX_REWEIGH_FIELDS
+(REWEIGH_JOINT_SEEN, REWEIGH_JOINT_SEEN_WW, REWEIGH_JOINT_PASS, REWEIGH_JOINT_PASS_WW, REWEIGH_JOINT_OUTSIDE, REWEIGH_JOINT_UNRESOLVED,
+ REWEIGH_JOINT_GEOMETRIES) = range(7)
+REWEIGH_JOINT_FIELDS = 7  # OKX_REWEIGH_JOINT_FIELDS
+REWEIGH_MAX_SCENARIOS = 256  # OKX_ENS_TILT_MAX_SCENARIOS
+
+
+def check_reweigh_limits(limits, steps: int, n_columns: int) -> np.ndarray:
+    """``limits`` as a contiguous float64 ``[S, K, 2]`` table without NaN and with ``lo <= hi``, or ValueError."""
+    who = "okx_ensemble_reweigh"
+    limits = broadcast_limits(limits, steps, n_columns)
+    if np.isnan(limits).any():
+        raise ValueError(f"{who}: a limit is NaN (an open side is -inf / +inf)")
+    if np.any(limits[..., 0] > limits[..., 1]):
+        raise ValueError(f"{who}: a limit has lo > hi")
+    return limits
+
+
+def check_reweigh_arguments(weights, n_geometries: int, limits=None, verdict=None, steps: int | None = None, n_columns: int | None = None):
+    """``(weights [G, S] float64, limits [S, K, 2] or None, verdict [G] uint8 or None)``, or ValueError in the words of
+    ``okx_ensemble_reweigh``: the scenario cap, one weight row and one verdict byte per geometry, limits without NaN and with lo <= hi."""
+    who = "okx_ensemble_reweigh"
+    w = np.asarray(weights.detach().cpu().numpy() if _is_tensor(weights) else weights, dtype=np.float64)
+    if w.ndim != 2 or w.shape[0] != n_geometries:
+        raise ValueError(f"{who}: weights must be [{n_geometries}, S], one row per geometry")
+    if not 1 <= w.shape[1] <= REWEIGH_MAX_SCENARIOS:
+        raise ValueError(f"{who}: {w.shape[1]} scenarios, 1 to {REWEIGH_MAX_SCENARIOS} allowed")
+    if limits is not None:
+        limits = check_reweigh_limits(limits, steps, n_columns)
+    if verdict is not None:
+        verdict = np.asarray(verdict.detach().cpu().numpy() if _is_tensor(verdict) else verdict)
+        if verdict.shape != (n_geometries,) or verdict.dtype != np.uint8:
+            raise ValueError(f"{who}: verdict must be uint8 [{n_geometries}], the screen's flag byte of every geometry")
+    return w, limits, verdict
+
+
+@dataclass
+class EnsembleWhatIf:
+    """
+    What ``ReweighAccumulator.finalize`` returns (NumPy, host): what the scatter and the yield of every (step, column) entry BECOME
+    under every scenario, from the ensemble as it was drawn.  Per (scenario, entry) ``[N, S, K]``, self-normalised (every sum divided
+    by the sum of the weights, so a constant factor of the weights - the guards' acceptance rate - drops out): ``count`` the states
+    that count with a weight above 0, ``mean = shift + WD / W``, ``variance = WDD / W - (WD / W)^2`` (not below 0), ``std``,
+    ``ess = W^2 / WW`` the effective sample size, ``mean_se = sqrt(WWDD - 2 mu WWD + mu^2 WW) / W`` with ``mu = WD / W`` the standard
+    error of the mean (the delta method of a ratio estimator), ``yield_ = 1 - (OUT_LO + OUT_HI) / W`` and ``yield_se`` by the same pattern
+    from ``WW_OUT`` (both None without limits), ``below`` / ``above`` the weighted shares under ``lo`` / over ``hi``.  Per scenario ``[N]``,
+    over the geometries the mask leaves: ``joint_yield = PASS / SEEN`` with ``joint_yield_se`` (the verdict is the screen's flag byte; without
+    one every geometry passes), ``outside`` / ``unresolved`` the weighted shares of those flags, ``ess_all = SEEN^2 / SEEN_WW`` and
+    ``mean_weight = SEEN / geometries`` - NEAR 1 when the draw supports the scenario; far from 1 the scenario asks for geometries the
+    ensemble does not hold, and none of the above is to be trusted.  Entries and scenarios without weight are NaN.
+
+    Under ``LHS`` the geometries are not independent: ``ess`` and the standard errors are a heuristic there.
+    """
+
+    count: np.ndarray
+    mean: np.ndarray
+    variance: np.ndarray
+    std: np.ndarray
+    ess: np.ndarray
+    mean_se: np.ndarray
+    yield_: np.ndarray | None
+    yield_se: np.ndarray | None
+    below: np.ndarray | None
+    above: np.ndarray | None
+    joint_yield: np.ndarray
+    joint_yield_se: np.ndarray
+    outside: np.ndarray
+    unresolved: np.ndarray
+    ess_all: np.ndarray
+    mean_weight: np.ndarray
+    geometries: int = 0
+    scenario_names: list | None = None
+
+
+class ReweighAccumulator(_Accumulator):
+    """
+    The raw tables of ``okx_ensemble_reweigh``: ``acc [N, REWEIGH_FIELDS, S, K]`` float64 (scenario, field, entry), ``joint [N,
+    REWEIGH_JOINT_FIELDS]``, ``shift [S, K]`` and ``limits [S, K, 2]`` or None - NumPy arrays or torch tensors (host or device), whatever
+    produced them.  Accumulators of disjoint geometries merge by addition.
+    """
+
+    TABLES, CARRIED = ("acc", "joint", "shift", "limits"), ("scenario_names",)
+
+    def __init__(self, acc, joint, shift, limits=None, scenario_names=None):
+        self.acc, self.joint, self.shift, self.limits = acc, joint, shift, limits
+        self.scenario_names = list(scenario_names) if scenario_names is not None else None
+        if acc.ndim != 4 or acc.shape[1] != REWEIGH_FIELDS or tuple(shift.shape) != tuple(acc.shape[2:]) \
+                or tuple(joint.shape) != (acc.shape[0], REWEIGH_JOINT_FIELDS) or (limits is not None and tuple(limits.shape) != tuple(acc.shape[2:]) + (2,)):
+            raise ValueError("acc must be [N, REWEIGH_FIELDS, S, K], joint [N, REWEIGH_JOINT_FIELDS], shift [S, K] and limits [S, K, 2]")
+
+    n_scenarios = property(lambda self: int(self.acc.shape[0]))
+
+    @classmethod
+    def empty(cls, n_scenarios: int, steps: int, n_columns: int, shift, limits=None, scenario_names=None) -> "ReweighAccumulator":
+        """The accumulator of no geometry at all (the neutral element of ``merge``), NumPy."""
+        return cls(np.zeros((n_scenarios, REWEIGH_FIELDS, steps, n_columns)), np.zeros((n_scenarios, REWEIGH_JOINT_FIELDS)),
+                   np.asarray(shift, dtype=np.float64).reshape(steps, n_columns), limits, scenario_names)
+
+    def merge(self, other: "ReweighAccumulator") -> "ReweighAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been taken
+        with the same shift and the same limits.  Works on NumPy arrays and on torch tensors alike."""
+        if not _same_shape(self.acc, other.acc):
+            raise ValueError("accumulators of different shapes")
+        if not _same_table(self.shift, other.shift):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        if (self.limits is None) != (other.limits is None) or (self.limits is not None and not _same_table(self.limits, other.limits)):
+            raise ValueError("accumulators taken with different limits cannot be merged")
+        return ReweighAccumulator(self.acc + other.acc, self.joint + other.joint, self.shift, self.limits, self.scenario_names)
+
+    def finalize(self) -> EnsembleWhatIf:
+        """The self-normalised estimates on the host in fp64."""
+        h = self.numpy()
+        acc, joint, shift = (np.asarray(t, dtype=np.float64) for t in (h.acc, h.joint, h.shift))
+        w, ww = acc[:, REWEIGH_W], acc[:, REWEIGH_WW]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            some = w > 0.0
+            mu = np.where(some, acc[:, REWEIGH_WD] / w, np.nan)
+            variance = np.maximum(acc[:, REWEIGH_WDD] / w - mu * mu, 0.0)
+            variance = np.where(some, variance, np.nan)
+            ess = np.where(some, w * w / ww, np.nan)
+            mean_se = np.sqrt(np.maximum(acc[:, REWEIGH_WWDD] - 2.0 * mu * acc[:, REWEIGH_WWD] + mu * mu * ww, 0.0)) / w
+            yield_ = yield_se = below = above = None
+            if h.limits is not None:
+                below, above = np.where(some, acc[:, REWEIGH_OUT_LO] / w, np.nan), np.where(some, acc[:, REWEIGH_OUT_HI] / w, np.nan)
+                out = below + above
+                yield_ = 1.0 - out
+                yield_se = np.sqrt(np.maximum(acc[:, REWEIGH_WW_OUT] - 2.0 * out * acc[:, REWEIGH_WW_OUT] + out * out * ww, 0.0)) / w
+            seen, seen_ww = joint[:, REWEIGH_JOINT_SEEN], joint[:, REWEIGH_JOINT_SEEN_WW]
+            any_seen = seen > 0.0
+            p = np.where(any_seen, joint[:, REWEIGH_JOINT_PASS] / seen, np.nan)
+            p_ww = joint[:, REWEIGH_JOINT_PASS_WW]
+            p_se = np.sqrt(np.maximum(p_ww - 2.0 * p * p_ww + p * p * seen_ww, 0.0)) / seen
+            geometries = joint[:, REWEIGH_JOINT_GEOMETRIES]
+            return EnsembleWhatIf(acc[:, REWEIGH_COUNT].astype(np.int64), shift[None] + mu, variance, np.sqrt(variance), ess, np.where(some, mean_se, np.nan),
+                                  yield_, yield_se, below, above, p, np.where(any_seen, p_se, np.nan),
+                                  np.where(any_seen, joint[:, REWEIGH_JOINT_OUTSIDE] / seen, np.nan),
+                                  np.where(any_seen, joint[:, REWEIGH_JOINT_UNRESOLVED] / seen, np.nan),
+                                  np.where(any_seen, seen * seen / seen_ww, np.nan), np.where(geometries > 0, seen / geometries, np.nan),
+                                  int(geometries.max()) if geometries.size else 0, self.scenario_names)
+
+
+def reweigh_terms(values, status=None, mask=None, shift=None, limits=None):
+    """What ``okx_ensemble_reweigh`` forms per geometry before a weight comes in: ``(counts [G, S, K] bool, d [G, S, K], below, above
+    [G, S, K] bool, shift [S, K])`` of ``values [G, S, K]``, ``status [G, S]`` uint8 or None, ``mask [G]`` uint8 or None (bit 0 set: the
+    geometry does not count) and ``limits [S, K, 2]`` or None; ``d = value - shift``, rounded, 0 where the state does not count;
+    ``below`` / ``above``: the state counts and its value lies strictly under ``lo`` / over ``hi``."""
+    ok, d, shift = effects_terms(values, status, mask, shift)
+    v = np.asarray(values, dtype=np.float64)
+    if limits is None:
+        below = above = np.zeros(v.shape, dtype=bool)
+    else:
+        with np.errstate(invalid="ignore"):
+            below, above = ok & (v < limits[None, ..., 0]), ok & (v > limits[None, ..., 1])
+    return ok, d, below, above, shift
+
+
+def reweigh_scenario_terms(ok, d, below, above, w):
+    """The ten terms ``[REWEIGH_FIELDS, G', S, K]`` of ONE scenario with the weights ``w [G']``: every product rounded on its own, in the
+    order the device forms them - ``wl = w`` where the state counts else 0, ``wwl = w w`` likewise, ``wl d``, ``(wl d) d``, ``wwl d``,
+    ``(wwl d) d``, and ``wl`` / ``wwl`` where the value is outside."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.asarray(w, dtype=np.float64)[:, None, None]
+        wl, wwl = np.where(ok, w, 0.0), np.where(ok, w * w, 0.0)
+        wd, wwd = wl * d, wwl * d
+        return np.stack([(ok & (w > 0.0)).astype(np.float64), wl, wwl, wd, wd * d, wwd, wwd * d, np.where(below, wl, 0.0), np.where(above, wl, 0.0),
+                         np.where(below | above, wwl, 0.0)])
+
+
+def reweigh_host(values, status=None, mask=None, weights=None, shift=None, limits=None, verdict=None, scenario_names=None) -> ReweighAccumulator:
+    """
+    The accumulator of ``okx_ensemble_reweigh`` in NumPy.  ``values [G, S, K]``; ``status [G, S]`` uint8 or None (every state accepted);
+    ``mask [G]`` uint8 or None (bit 0 set: the geometry does not count - the sampler's flag byte); ``weights [G, N]`` the likelihood
+    ratios of N scenarios (``ensemble_sample.tilt_weights_host``, or any table of doubles); ``shift [S, K]`` (None: the values of
+    geometry 0, undefined entries 0); ``limits`` ``[S, K, 2]``, ``[K, 2]`` or ``[2]`` = (lo, hi) or None (nothing is outside); ``verdict [G]``
+    uint8 the screen's flag byte of every geometry (0 passes) or None (every geometry passes).  With ``d = value - shift`` and
+    ``ww = w w``, per (scenario, entry) over the states that count: ``COUNT`` those with ``w > 0``, ``W``, ``WW``, ``WD = sum w d``,
+    ``WDD = sum (w d) d``, ``WWD``, ``WWDD``, ``OUT_LO = sum w [v < lo]``, ``OUT_HI = sum w [v > hi]``, ``WW_OUT``; per scenario over the geometries
+    whose mask bit is clear: ``SEEN = sum w``, ``SEEN_WW``, ``PASS = sum w [verdict == 0]``, ``PASS_WW``, ``OUTSIDE = sum w [verdict & 1]``,
+    ``UNRESOLVED = sum w [verdict & 2]`` and ``GEOMETRIES``, their number.  A geometry whose weight is 0 adds nothing.
+    """
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim != 3:
+        raise ValueError("values must be [G, S, K]")
+    g, s, k = v.shape
+    if weights is None:
+        raise ValueError("okx_ensemble_reweigh: weights are needed (tilt_weights_host)")
+    w, limits, verdict = check_reweigh_arguments(weights, g, limits, verdict, s, k)
+    ok, d, below, above, shift = reweigh_terms(v, status, mask, shift, limits)
+    n = w.shape[1]
+    acc = np.zeros((n, REWEIGH_FIELDS, s, k))
+    rows = max(1, (1 << 21) // max(1, s * k))  # geometries per block: the ten term tables of a block stay near 160 MB
+    for i in range(n):
+        for a in range(0, g, rows):
+            live = np.flatnonzero(w[a : a + rows, i] != 0.0) + a  # (a weight of 0 adds nothing, and the device skips it)
+            if live.size:
+                acc[i] += reweigh_scenario_terms(ok[live], d[live], below[live], above[live], w[live, i]).sum(axis=1)
+    seen = np.ones(g, dtype=bool) if mask is None else (np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0
+    flag = np.zeros(g, dtype=np.uint8) if verdict is None else verdict
+    joint = np.zeros((n, REWEIGH_JOINT_FIELDS))
+    with np.errstate(invalid="ignore", over="ignore"):
+        wl = np.where(seen[:, None], w, 0.0)
+        wwl = np.where(seen[:, None], w * w, 0.0)
+        passed = (flag == 0)[:, None]
+        joint[:, REWEIGH_JOINT_SEEN], joint[:, REWEIGH_JOINT_SEEN_WW] = wl.sum(axis=0), wwl.sum(axis=0)
+        joint[:, REWEIGH_JOINT_PASS], joint[:, REWEIGH_JOINT_PASS_WW] = np.where(passed, wl, 0.0).sum(axis=0), np.where(passed, wwl, 0.0).sum(axis=0)
+        joint[:, REWEIGH_JOINT_OUTSIDE] = np.where((flag & SCREEN_OUTSIDE != 0)[:, None], wl, 0.0).sum(axis=0)
+        joint[:, REWEIGH_JOINT_UNRESOLVED] = np.where((flag & SCREEN_UNRESOLVED != 0)[:, None], wl, 0.0).sum(axis=0)
+    joint[:, REWEIGH_JOINT_GEOMETRIES] = float(seen.sum())
+    return ReweighAccumulator(acc, joint, shift, limits, scenario_names)
