@@ -1399,6 +1399,81 @@ int32_t okx_ensemble_reweigh(int64_t n_geometries, int64_t steps, int32_t n_colu
                              void* d_scratch, size_t scratch_bytes, void* stream);
 size_t okx_ensemble_reweigh_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_scenarios);
 
+/*
+ * Polynomial response surface on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): a regression of
+ * selected entries of the evaluated table on products of orthonormal polynomials of per-geometry factors (a polynomial chaos
+ * expansion of total degree <= 3 with pairwise products) - which PAIRS of factors act together, a model of the table that
+ * predicts an entry at a perturbed geometry without a solve, and first-order / pairwise / total variance shares from ONE fit on
+ * the ORDINARY ensemble.  The device forms the normal equations; the host solves them (ensemble_stats.SurfaceAccumulator.finalize).
+ *
+ * okx_ensemble_basis.  d_factors [n_geometries][ld] doubles (n_factors <= ld, 1 <= n_factors <= OKX_ENS_SAMPLE_MAX_LATENTS); d_law
+ * [n_factors][3] doubles = (kind, centre, scale), kind OKX_SURFACE_MONOMIAL / _HERMITE / _LEGENDRE; d_terms [n_terms][4] int32 =
+ * (a, da, b, db): the term is psi_da(u_a) psi_db(u_b), a factor index -1 (with degree 0) where there is no factor; term 0 is the
+ * constant (-1, 0, -1, 0); 1 <= n_terms <= OKX_ENS_SURFACE_MAX_TERMS, degrees 1 .. OKX_ENS_SURFACE_MAX_DEGREE.  Per (geometry, term):
+ *   u = (x - centre) * scale, psi_0 = 1, and for degrees 1, 2, 3
+ *   monomial  u, u u, (u u) u
+ *   Hermite   u, (u u - 1) * 0.7071067811865476, ((u u - 3) * u) * 0.408248290463863
+ *   Legendre  u * 1.7320508075688772, (3 (u u) - 1) * 1.118033988749895, ((5 (u u) - 3) * u) * 1.3228756555322954
+ *   d_phi   [n_geometries][ld_phi] double (n_terms <= ld_phi): the product of the term's two psi
+ *   d_valid [n_geometries] uint8: 0 where ANY of the row's n_factors factors is not finite - that row of d_phi is then 0
+ * Every operation is rounded on its own (contraction is off for the unit): the pass equals ensemble_stats.basis_host (NumPy) bit
+ * for bit.  The launch cannot read d_law / d_terms on the host: okx_ensemble_basis_check validates HOST copies (counts outside
+ * their caps, a kind that is none of the three, a centre or scale that is not finite, a missing constant term, a factor index or
+ * degree out of range); on the device a factor index out of range reads as "no factor".
+ *
+ * okx_ensemble_surface.  Table, status bytes, entry list and shift are those of okx_ensemble_covariance, with a limit of its own:
+ * 1 <= n_entries <= OKX_ENS_SURFACE_MAX_ENTRIES.  COMPLETE CASES: a geometry is USED when every selected entry of it counts
+ * (status & 7 == 1 and a finite value), bit 0 of its d_mask byte is clear (d_mask [n_geometries] uint8 or NULL: the sampler's
+ * d_flags) and its d_valid byte is set.  With phi = d_phi's row (the basis pass, or any doubles), d = value - d_shift[entry] over
+ * the used geometries, T = n_terms, N = n_entries:
+ *   d_gram   [T][T] double  sum phi_t phi_t', the full square; gram[t][t'] and gram[t'][t] are the same bits
+ *   d_cross  [T][N] double  sum phi_t d_n
+ *   d_sumsq  [N]    double  sum d_n d_n (the product rounded, then added)
+ *   d_counts [2]    int64   geometries used, dropped
+ *   d_used   [n_geometries] uint8 or NULL: 1 where geometry g of THIS call is used
+ * d_valid says that the FACTORS of a row are finite, not that its basis values are: a finite factor whose u u overflows, or a table
+ * of the caller's own with a NaN or inf in a used row, is summed as it lies and leaves inf / NaN in d_gram and d_cross - the row is not
+ * dropped.  accumulate = 0 overwrites gram, cross, sumsq and counts; accumulate = 1 adds this call after what they hold - additions only,
+ * so it needs the same shift, entries and basis as the calls before.  Launch-only, stream-ordered, no host read-back, no
+ * allocation, legal inside a stream capture (one chain of three launches); n_geometries = 0 is legal.  No floating-point
+ * atomics (no atomics on device memory at all): the geometries are cut into slabs by a plan that is a function of
+ * (n_geometries, n_terms, n_entries) alone and never looks at the device, a slab is summed in ascending geometry order, four at a
+ * time in v_mfma_f64_16x16x4_f64, and the slabs are added in ascending order per output element - two runs, or two devices, give
+ * the same bits.  DIFFERENT CHUNKINGS of the same geometries agree to rounding only: |result - exact| <= (G + 2) u sum |term| each
+ * (exactly where every product and sum is representable).  d_scratch: okx_ensemble_surface_scratch_bytes.  The launch cannot read
+ * d_entries on the host: okx_ensemble_surface_check validates a HOST copy (okx_ensemble_covariance_check's rules and words under
+ * this pass's name and limits) before it is uploaded; on the device an index out of range is never dereferenced - its entry never
+ * counts, every geometry is dropped.
+ */
+enum { OKX_ENS_SURFACE_MAX_TERMS = 1024, OKX_ENS_SURFACE_MAX_ENTRIES = 2048, OKX_ENS_SURFACE_MAX_DEGREE = 3 };
+enum { OKX_SURFACE_MONOMIAL = 0, OKX_SURFACE_HERMITE = 1, OKX_SURFACE_LEGENDRE = 2 };
+
+int32_t okx_ensemble_basis(int64_t n_geometries,
+                           const double* d_factors, int64_t ld, int32_t n_factors,  /* [n_geometries][ld]                    */
+                           const double* d_law,                                     /* [n_factors][3]                        */
+                           const int32_t* d_terms, int32_t n_terms,                 /* [n_terms][4]                          */
+                           double* d_phi, int64_t ld_phi,                           /* [n_geometries][ld_phi]                */
+                           uint8_t* d_valid,                                        /* [n_geometries]                        */
+                           void* stream);
+int32_t okx_ensemble_basis_check(const double* law, int32_t n_factors, const int32_t* terms, int32_t n_terms);
+
+int32_t okx_ensemble_surface(int64_t n_geometries, int64_t steps, int32_t n_columns,
+                             const double* d_values, int64_t ld,              /* [n_geometries * steps][ld]           */
+                             const uint8_t* d_status, int64_t status_stride,  /* or NULL                              */
+                             const uint8_t* d_mask,                           /* [n_geometries] or NULL               */
+                             const double* d_phi, int64_t ld_phi,             /* [n_geometries][ld_phi]               */
+                             const uint8_t* d_valid,                          /* [n_geometries]                       */
+                             int32_t n_terms,
+                             const int32_t* d_entries, int32_t n_entries,     /* or NULL: all, n_entries = steps * n_columns */
+                             const double* d_shift,
+                             int32_t accumulate,
+                             double* d_gram, double* d_cross, double* d_sumsq, int64_t* d_counts,
+                             uint8_t* d_used,                                 /* or NULL                              */
+                             void* d_scratch, size_t scratch_bytes, void* stream);
+/* host only */
+size_t okx_ensemble_surface_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_terms, int32_t n_entries);
+int32_t okx_ensemble_surface_check(const int32_t* entries /* or NULL */, int32_t n_entries, int64_t n_table_entries, int32_t n_terms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,10 @@ ENS_TILT_MAX_SCENARIOS, TILT_PARAMS = 256, 5
 (REWEIGH_JOINT_SEEN, REWEIGH_JOINT_SEEN_WW, REWEIGH_JOINT_PASS, REWEIGH_JOINT_PASS_WW, REWEIGH_JOINT_OUTSIDE, REWEIGH_JOINT_UNRESOLVED,
  REWEIGH_JOINT_GEOMETRIES, REWEIGH_JOINT_FIELDS) = range(8)
 
+# okx_ensemble_basis / okx_ensemble_surface (include/okx.h OKX_ENS_SURFACE_*, OKX_SURFACE_*); ensemble_stats.py names them SURFACE_*
+ENS_SURFACE_MAX_TERMS, ENS_SURFACE_MAX_ENTRIES, ENS_SURFACE_MAX_DEGREE = 1024, 2048, 3
+SURFACE_MONOMIAL, SURFACE_HERMITE, SURFACE_LEGENDRE = 0, 1, 2
+
 INFO_CONVERGED = 1
 INFO_RESIDUAL_EXCEEDED = 2
 INFO_FAILED = 4

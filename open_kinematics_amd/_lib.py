@@ -96,6 +96,11 @@ EXPORTS = (
     "okx_ensemble_tilt_check",
     "okx_ensemble_reweigh",
     "okx_ensemble_reweigh_scratch_bytes",
+    "okx_ensemble_basis",
+    "okx_ensemble_basis_check",
+    "okx_ensemble_surface",
+    "okx_ensemble_surface_scratch_bytes",
+    "okx_ensemble_surface_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -324,6 +329,16 @@ def load() -> C.CDLL:
     lib.okx_ensemble_reweigh.restype = i32
     lib.okx_ensemble_reweigh_scratch_bytes.argtypes = [i64, i64, i32, i32]
     lib.okx_ensemble_reweigh_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_basis.argtypes = [i64, vp, i64, i32, vp, vp, i32, vp, i64, vp, vp]
+    lib.okx_ensemble_basis.restype = i32
+    lib.okx_ensemble_basis_check.argtypes = [vp, i32, vp, i32]
+    lib.okx_ensemble_basis_check.restype = i32
+    lib.okx_ensemble_surface.argtypes = [i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.okx_ensemble_surface.restype = i32
+    lib.okx_ensemble_surface_scratch_bytes.argtypes = [i64, i64, i32, i32, i32]
+    lib.okx_ensemble_surface_scratch_bytes.restype = C.c_size_t
+    lib.okx_ensemble_surface_check.argtypes = [vp, i32, i64, i32]
+    lib.okx_ensemble_surface_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

@@ -33,6 +33,7 @@
 
 #include "../../include/okx.h"
 #include "okx_enstable.hpp"
+#include "okx_gramtile.hpp"
 #include "okx_program.hpp"
 #include "okx_quad.hpp"
 
@@ -65,11 +66,7 @@ inline Plan plan_for(long long n_geom, long long n) {
   Plan p;
   p.tiles = (int)((n + kTile - 1) / kTile);
   p.pairs = (long long)p.tiles * (p.tiles + 1) / 2;
-  long long want = kWantGroups / (p.pairs > 0 ? p.pairs : 1);
-  if (want < 1) want = 1;
-  long long len = (n_geom + want - 1) / want;
-  len = (len + kBlock - 1) / kBlock * kBlock;
-  p.slab_len = len < kMinSlab ? kMinSlab : len;
+  p.slab_len = gramtile::slab_length(n_geom, p.pairs, kWantGroups, kBlock, kMinSlab);
   p.slabs = n_geom > 0 ? (n_geom + p.slab_len - 1) / p.slab_len : 0;
   p.gpb = enstable::geometries_per_group(n_geom, kWantGroups, kWaves);
   p.ugroups = n_geom > 0 ? (n_geom + p.gpb - 1) / p.gpb : 0;
@@ -145,13 +142,7 @@ __global__ __launch_bounds__(kThreads) void okx_cov_used(UsedArgs a) {
   if (threadIdx.x == 0) a.totals[blockIdx.x] = (long long)n_used;
 }
 
-// pair p of the lower triangle, row by row: (0,0) (1,0) (1,1) (2,0) ...
-__device__ inline void pair_of(long long p, int* ti, int* tj) {
-  int i = 0;
-  while ((long long)(i + 1) * (i + 2) / 2 <= p) ++i;
-  *ti = i;
-  *tj = (int)(p - (long long)i * (i + 1) / 2);
-}
+using gramtile::pair_of;  // pair p of the lower triangle, row by row: (0,0) (1,0) (1,1) (2,0) ...
 
 struct GramArgs {
   const double* values;
@@ -351,32 +342,7 @@ size_t okx_ensemble_covariance_scratch_bytes(int64_t n_geometries, int64_t steps
 }
 
 int32_t okx_ensemble_covariance_check(const int32_t* entries, int32_t n_entries, int64_t n_table_entries) {
-  const char* who = "okx_ensemble_covariance";
-  if (n_entries < 1 || n_entries > OKX_ENS_COV_MAX_ENTRIES)
-    return fail(OKX_ERR_INVALID, "%s: %lld entries selected, 1 to %d allowed", who, (long long)n_entries, (int)OKX_ENS_COV_MAX_ENTRIES);
-  if (!entries) {
-    if (n_entries != n_table_entries)
-      return fail(OKX_ERR_INVALID, "%s: without an entry list all %lld entries are selected, not %lld", who, (long long)n_table_entries, (long long)n_entries);
-    return OKX_OK;
-  }
-  for (int32_t i = 0; i < n_entries; ++i)
-    if (entries[i] < 0 || entries[i] >= n_table_entries)
-      return fail(OKX_ERR_INVALID, "%s: entry %lld is %lld, outside [0, %lld)", who, (long long)i, (long long)entries[i], (long long)n_table_entries);
-  // the first position that repeats an earlier one
-  std::vector<std::pair<int32_t, int32_t>> order((size_t)n_entries);
-  for (int32_t i = 0; i < n_entries; ++i) order[(size_t)i] = {entries[i], i};
-  std::sort(order.begin(), order.end());
-  int32_t at = -1, before = -1;
-  for (size_t i = 1; i < order.size(); ++i)
-    if (order[i].first == order[i - 1].first && (at < 0 || order[i].second < at)) {
-      at = order[i].second;
-      size_t j = i;
-      while (j > 0 && order[j - 1].first == order[i].first) --j;
-      before = order[j].second;
-    }
-  if (at >= 0)
-    return fail(OKX_ERR_INVALID, "%s: entry %lld repeats entry %lld (index %lld)", who, (long long)at, (long long)before, (long long)entries[at]);
-  return OKX_OK;
+  return okx::gramtile::check_entry_list("okx_ensemble_covariance", entries, n_entries, n_table_entries, OKX_ENS_COV_MAX_ENTRIES);
 }
 
 int32_t okx_ensemble_covariance(int64_t n_geometries, int64_t steps, int32_t n_columns, const double* d_values, int64_t ld, const uint8_t* d_status,

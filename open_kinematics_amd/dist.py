@@ -452,13 +452,25 @@ class ShardedEnsemble:
     chunkings agree to rounding, exactly when the sums are exact.  ``whatif()`` returns the ``ensemble_stats.EnsembleWhatIf``,
     ``whatif_accumulator`` the merged tables, ``whatif_exchange_bytes_per_rank`` what the rank sends (``8 N (10 S K + 7)``).  It is refused for a
     ``FamilyPlan``, whose pick-freeze members are no draw of the plan's law.
+
+    ``surface=True`` or ``surface=dict(degree=, interactions=, entries=, factors=)`` (with ``reduce=True`` and ``factors``) adds a POLYNOMIAL
+    RESPONSE SURFACE of the selected entries on the factors (``okx_ensemble_basis`` / ``okx_ensemble_surface``): which pairs of factors act
+    together, a model that predicts an entry at a perturbed geometry without a solve, and first-order, pairwise and total variance shares
+    from one fit on the ordinary ensemble.  The basis comes from the plan's laws for ``factors="sampled"`` (orthonormal Hermite / Legendre
+    polynomials of the latents), otherwise from the factor table of all geometries (standardised monomials; no variance shares).  A chunk's
+    basis rows are built once, and right after the chunk's reduction its rows of ``metric_local`` are accumulated into the normal equations
+    with the reduction's shift and the sampler's flags as the mask.  Default entries: all ``S K`` when that is at most 2048, else ``entries=``
+    is asked for.  ``step()`` then ends with one all-gather of the accumulators, added on every rank in ascending rank order - the same bits
+    on every rank; world sizes and chunkings agree to rounding, exactly when the sums are exact.  ``surface()`` returns the
+    ``ensemble_stats.EnsembleSurface``, ``surface_accumulator`` the merged tables, ``surface_exchange_bytes_per_rank`` what the rank sends
+    (``8 (T^2 + T N + N + 2)``).  It is refused for a ``FamilyPlan``: the pick-freeze rows are not an independent sample.
     """
 
     def __init__(self, device_program, hardpoints, targets, steps_per_geometry: int, *, group=None, chunks: int | None = None,
                  records: bool = True, relative_targets: bool = True, info: str = "full", direct: bool | None = None,
                  metric_columns=None, reduce: bool = False, factors=None, shift=None, quantiles=None, limits=None, screen: bool = False, screen_scale=None,
                  covariance=None, curves=None, front=None, sobol: bool = False, bootstrap: int | None = None, bootstrap_seed: int | None = None,
-                 effects=None, whatif=None, **solve_kw):
+                 effects=None, whatif=None, surface=None, **solve_kw):
         from .ensemble_sample import FamilyPlan, SamplePlan
 
         self.plan = hardpoints if isinstance(hardpoints, (SamplePlan, FamilyPlan)) else None
@@ -495,6 +507,11 @@ class ShardedEnsemble:
             effects = None
         if effects is not None and (not reduce or factors is None):
             raise ValueError("effects= bins the factors of the reduced ensemble: it needs reduce=True and factors")
+        if surface is False:
+            surface = None
+        if surface is not None and (not reduce or factors is None or isinstance(self.plan, FamilyPlan)):
+            raise ValueError("surface= regresses the reduced ensemble on its factors: it needs reduce=True, factors and no FamilyPlan "
+                             "(the pick-freeze rows are not an independent sample)")
         if curves is not None and not reduce:
             raise ValueError("curves= fits the reduced ensemble's columns: it needs reduce=True")
         if front is not None:
@@ -659,6 +676,8 @@ class ShardedEnsemble:
                 self.stages["effects"] = stages.Effects(self, effects)
             if whatif is not None:
                 self.stages["whatif"] = stages.WhatIf(self, whatif, limits)
+            if surface is not None:
+                self.stages["surface"] = stages.Surface(self, surface)
             if curves is not None:
                 self.stages["curves"] = stages.Curves(self, dict(curves))
             if front is not None:
@@ -668,6 +687,7 @@ class ShardedEnsemble:
         self.covariance_exchange_bytes_per_rank = sent.get("covariance", 0)
         self.effects_exchange_bytes_per_rank = sent.get("effects", 0)
         self.whatif_exchange_bytes_per_rank = sent.get("whatif", 0)
+        self.surface_exchange_bytes_per_rank = sent.get("surface", 0)
         self.curves_exchange_bytes_per_rank = sent.get("curves", 0)
         self.front_exchange_bytes_per_rank = sent.get("front", 0)
         self.sobol_exchange_bytes_per_rank = sent.get("sobol", 0)
@@ -721,6 +741,17 @@ class ShardedEnsemble:
         if "whatif" not in self.stages:
             raise ValueError("whatif() needs whatif=scenarios")
         return self.stages["whatif"].whatif()
+
+    surface_accumulator = property(lambda self: self.stages["surface"].merged,
+                                   doc="The merged response-surface accumulator of the last ``step()`` (``surface=``); None before.")
+
+    def surface(self):
+        """``ensemble_stats.EnsembleSurface`` of the WHOLE ensemble after the last ``step()`` (``surface=``): per entry the coefficients of the
+        basis terms, R^2 and the residual spread; with an orthonormal basis the first-order, pairwise and total variance shares.  The same
+        bits on every rank."""
+        if "surface" not in self.stages:
+            raise ValueError("surface() needs surface=True or surface=dict(...)")
+        return self.stages["surface"].surface()
 
     def quantiles(self):
         """``ensemble_stats.EnsembleQuantiles`` of the last ``step()`` (``quantiles=...``): the same bits on every rank."""

@@ -20,6 +20,7 @@ pass (``okx_ensemble_...``)    prepare call          result
 ``effects_ensemble``           ``bin_factors``       ``ensemble_stats.EffectsAccumulator``
 ``tilt_weights``               ``tilt_prepare``      ``float64 [G, N]`` tensor
 ``reweigh_ensemble``           ``tilt_weights``      ``ensemble_stats.ReweighAccumulator``
+``surface_ensemble``           ``basis_factors``     ``ensemble_stats.SurfaceAccumulator``
 =============================  ====================  ==============================================
 
 Every pass takes ``out=``, the result of an earlier call or of its prepare call; the tables it holds are checked in one place
@@ -38,8 +39,9 @@ import torch
 from . import _lib
 from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, REWEIGH_FIELDS, REWEIGH_JOINT_FIELDS, REWEIGH_MAX_SCENARIOS,
                              SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS, CovarianceAccumulator, EffectsAccumulator, EnsembleAccumulator, EnsembleCurves,
-                             ReweighAccumulator, SobolAccumulator, SobolBootstrapAccumulator, _host_f64, broadcast_limits, broadcast_scale,
-                             check_covariance_arguments, check_effects_arguments, check_front_arguments, check_replicates, check_reweigh_limits, factor_moment_count)
+                             ReweighAccumulator, SobolAccumulator, SobolBootstrapAccumulator, SurfaceAccumulator, SurfaceBasis, _host_f64, broadcast_limits,
+                             broadcast_scale, check_covariance_arguments, check_effects_arguments, check_front_arguments, check_replicates, check_reweigh_limits,
+                             check_surface_arguments, check_surface_basis, factor_moment_count)
 
 F64, I64, I32, U8 = torch.float64, torch.int64, torch.int32, torch.uint8
 
@@ -207,6 +209,19 @@ class EffectBins:
     offsets: torch.Tensor
     edges: torch.Tensor
     n_bins: int
+
+
+@dataclass
+class SurfaceBasisTable:
+    """What ``basis_factors`` returns, device tensors: ``phi [G, T]`` float64 with unit column stride (rows may be strided: a view of a wider
+    table), the basis rows of the geometries; ``valid [G]`` uint8, 0 where a factor of the geometry is not finite (its row of ``phi`` is then 0);
+    ``law [P, 3]`` and ``terms [T, 4]``, the uploaded tables of ``basis`` (``ensemble_stats.SurfaceBasis``, host)."""
+
+    phi: torch.Tensor
+    valid: torch.Tensor
+    law: torch.Tensor
+    terms: torch.Tensor
+    basis: SurfaceBasis
 
 
 def _ptr(t: torch.Tensor | None, row: int = 0) -> C.c_void_p:
@@ -1006,3 +1021,110 @@ class EnsembleReductions:
         self._ensemble_call("okx_ensemble_reweigh", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(out.shift), _ptr(weights), ldw, n,
                             _ptr(out.limits), _ptr(verdict), 1 if accumulate else 0, _ptr(out.acc), _ptr(out.joint), _ptr(scratch), scratch.numel())
         return out
+
+    # ---- okx_ensemble_basis / okx_ensemble_surface: the normal equations of a polynomial response surface (ensemble_stats.EnsembleSurface) ----
+
+    def _strided_rows(self, t, what: str, letters: str, rows: int | None = None) -> tuple:
+        """``(G, columns, ld)`` of ``t``, a float64 ``[G, columns]`` device tensor with unit column stride whose rows may be strided."""
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != F64 or t.device != self.device or (t.shape[1] > 1 and t.stride(1) != 1) \
+                or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"{what} must be a float64 {letters} device tensor with unit column stride")
+        g, c = t.shape
+        ld = t.stride(0) if g > 1 else max(c, t.stride(0))
+        if ld < c:
+            raise ValueError(f"rows of {what} overlap")
+        return g, c, ld
+
+    def basis_factors(self, factors, basis=None, out=None) -> "SurfaceBasisTable":
+        """
+        ``okx_ensemble_basis``: the basis rows of ``factors [G, P]`` (a float64 device tensor with unit column stride; rows may be strided - the
+        sampler's ``latents`` as they lie in HBM) under ``basis`` (``ensemble_stats.surface_terms``; validated on the host and uploaded) as a
+        ``SurfaceBasisTable``: ``phi [G, T]`` and ``valid [G]``.  Done ONCE for an ensemble: factors do not change from step to step.  ``out``: the
+        ``SurfaceBasisTable`` of an earlier call of the same shape - it carries its own basis (``basis`` may then be None); its ``phi`` may be a
+        view with strided rows; with it the call uploads and allocates nothing and is legal inside a stream capture.  The bits of
+        ``ensemble_stats.basis_host``.
+        """
+        g, p, ld = self._strided_rows(factors, "factors", "[G, P]")
+        dev = self.device
+        if out is None:
+            if not isinstance(basis, SurfaceBasis):
+                raise ValueError("basis must be the SurfaceBasis of ensemble_stats.surface_terms (or out=, which carries its own)")
+            law, terms = check_surface_basis(basis.law, basis.terms)
+            rc = self.lib.okx_ensemble_basis_check(law.ctypes.data_as(C.c_void_p), min(law.shape[0], 1 << 20), terms.ctypes.data_as(C.c_void_p), terms.shape[0])
+            _lib.check(rc, "okx_ensemble_basis")
+            out = SurfaceBasisTable(torch.empty((g, terms.shape[0]), dtype=F64, device=dev), torch.empty(g, dtype=U8, device=dev),
+                                    torch.as_tensor(law, device=dev), torch.as_tensor(terms, device=dev), basis)
+        elif basis is not None and not basis.same(out.basis):
+            raise ValueError("out= carries its own basis")
+        t = out.basis.n_terms
+        if out.basis.n_factors != p:
+            raise ValueError(f"factors must be [G, {out.basis.n_factors}], one column per factor of the basis")
+        _, _, ld_phi = self._strided_rows(out.phi, f"out.phi [{g}, {t}]", "[G, T]", rows=g)
+        if out.phi.shape[1] != t:
+            raise ValueError(f"out.phi must be [{g}, {t}]")
+        self._check_tables(f"out must hold contiguous device tables valid [{g}], law [{p}, 3] and terms [{t}, 4]",
+                           [(out.valid, (g,), U8), (out.law, (p, 3), F64), (out.terms, (t, 4), I32)])
+        self._ensemble_call("okx_ensemble_basis", g, _ptr(factors), ld, p, _ptr(out.law), _ptr(out.terms), t, _ptr(out.phi), ld_phi, _ptr(out.valid))
+        return out
+
+    def surface_ensemble(self, values, *, steps_per_geometry: int, basis_table, status=None, mask=None, entries=None, shift=None, out=None,
+                         accumulate: bool = False):
+        """
+        ``okx_ensemble_surface``: the response-surface accumulator (``ensemble_stats.SurfaceAccumulator``, device tensors: ``gram [T, T]``,
+        ``cross [T, N]``, ``sumsq [N]``, ``counts [2]`` = used, dropped, ``used [G]`` uint8) of ``entries`` - N distinct indices ``s K + k``, None: all
+        ``S K`` - of a column table in HBM over its COMPLETE geometries: every selected entry counts, bit 0 of the mask byte is clear and the
+        basis row is valid.  ``values`` and ``status`` as ``reduce_ensemble`` takes them (unit column stride; strided rows and a strided status
+        byte are passed on, nothing is copied); ``basis_table``: the ``SurfaceBasisTable`` ``basis_factors`` made of the factors of THESE
+        geometries; ``mask [G]`` contiguous uint8 - the sampler's ``flags`` as they lie in HBM.  ``shift [S, K]`` the common shift (None: the
+        table's own geometry 0, undefined entries 0 - chunks that are accumulated need ONE shift, pass it or pass ``out=``).  ``out``: the
+        accumulator of an earlier call - it carries its own shift, entries and basis - to write (``accumulate=False``) or add into (``True``);
+        with it and a table shape seen before, the call uploads and allocates nothing and is legal inside a stream capture (``out.used`` is
+        written when it holds a byte per geometry of the call).  ``.finalize()`` copies to the host and solves: coefficients, R^2, variance
+        shares.  Bit-identical from run to run; different chunkings agree to rounding.
+        """
+        g, s, k, ld, stride = self._ensemble_table(values, status, steps_per_geometry)
+        dev = self.device
+        if not isinstance(basis_table, SurfaceBasisTable):
+            raise ValueError("basis_table must be the SurfaceBasisTable of basis_factors")
+        t = basis_table.basis.n_terms
+        _, _, ld_phi = self._strided_rows(basis_table.phi, f"basis_table.phi [{g}, {t}] (one row per geometry of the table)", "[G, T]", rows=g)
+        if basis_table.phi.shape[1] != t:
+            raise ValueError(f"basis_table.phi must be [{g}, {t}]")
+        self._check_tables(f"basis_table must hold a contiguous device table valid [{g}]", [(basis_table.valid, (g,), U8)])
+        if self._new_result(out, (shift, entries), "shift and entries", accumulate):
+            host = None if entries is None else np.ascontiguousarray(check_surface_arguments(
+                entries.detach().cpu().numpy() if isinstance(entries, torch.Tensor) else entries, s * k, t))
+            n = s * k if host is None else host.size
+            rc = self.lib.okx_ensemble_surface_check(None if host is None else host.ctypes.data_as(C.c_void_p), min(n, 1 << 30), s * k, t)
+            _lib.check(rc, "okx_ensemble_surface")
+            shift = self._ensemble_shift(shift, values, g, s, k)
+            index = torch.arange(n, dtype=torch.int32, device=dev) if host is None else torch.as_tensor(host, device=dev)
+            out = SurfaceAccumulator(torch.empty((t, t), dtype=F64, device=dev), torch.empty((t, n), dtype=F64, device=dev), torch.empty(n, dtype=F64, device=dev),
+                                     torch.empty(2, dtype=I64, device=dev), shift, index, torch.empty(g, dtype=U8, device=dev), basis=basis_table.basis,
+                                     natural=host is None)  # (all entries in natural order: the call passes no entry list)
+        elif not out.basis.same(basis_table.basis):
+            raise ValueError("out= was taken with another basis")
+        n = _rows(out.entries)
+        self._check_tables(f"out must hold contiguous device tables gram [{t}, {t}], cross [{t}, N], sumsq [N], counts [2], entries [N] and shift [S, K] = [{s}, {k}]",
+                           [(out.gram, (t, t), F64), (out.cross, (t, n), F64), (out.sumsq, (n,), F64), (out.counts, (2,), I64), (out.shift, (s, k), F64),
+                            (out.entries, (n,), I32)])
+        self._check_mask(mask, g, contiguous=True)
+        used = out.used  # (written when it holds a byte per geometry of the call)
+        if used is not None and (used.dtype != U8 or used.shape[0] < g or not used.is_contiguous() or used.device != dev):
+            used = None
+        scratch = self._ensemble_scratch("surface", int(self.lib.okx_ensemble_surface_scratch_bytes(g, s, k, t, n)))
+        index = None if out.natural and n == s * k else _ptr(out.entries)
+        self._ensemble_call("okx_ensemble_surface", g, s, k, _ptr(values), ld, _ptr(status), stride, _ptr(mask), _ptr(basis_table.phi), ld_phi,
+                            _ptr(basis_table.valid), t, index, n, _ptr(out.shift), 1 if accumulate else 0, _ptr(out.gram), _ptr(out.cross), _ptr(out.sumsq),
+                            _ptr(out.counts), _ptr(used), _ptr(scratch), scratch.numel())
+        return out
+
+    def predict_surface(self, surface, factors) -> torch.Tensor:
+        """
+        The fitted entries ``float64 [G, N]`` of ``surface`` (``ensemble_stats.EnsembleSurface``, host) at ``factors [G, P]`` on the device, without
+        a solve: the basis pass, then ``shift + phi @ coefficients`` (``torch.matmul``); NaN where a factor is not finite.  Host form:
+        ``EnsembleSurface.predict``.
+        """
+        table = self.basis_factors(factors, surface.basis)
+        out = torch.as_tensor(surface.shift, device=self.device)[None, :] + torch.matmul(table.phi, torch.as_tensor(surface.coefficients, device=self.device))
+        return torch.where(table.valid[:, None] != 0, out, torch.full_like(out, float("nan")))

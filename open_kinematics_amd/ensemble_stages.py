@@ -1,7 +1,7 @@
 """
 The stages ``dist.ShardedEnsemble(reduce=True)`` runs over every rank's own shard of an evaluated ensemble: ``Reduction``
 (moments, extremes, sensitivities), ``Sobol`` (``sobol=True``), ``SobolBootstrap`` (``bootstrap=``), ``Selection`` (``quantiles=``), ``Screening`` (``screen=True``), ``Covariance``
-(``covariance=``), ``Effects`` (``effects=``), ``WhatIf`` (``whatif=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
+(``covariance=``), ``Effects`` (``effects=``), ``WhatIf`` (``whatif=``), ``Surface`` (``surface=``), ``Curves`` (``curves=``) and ``Front`` (``front=``).  One protocol, which ``ShardedEnsemble`` drives over the stages that are switched on, in this order:
 
 * the constructor takes the owning ensemble and the stage's own arguments: it validates, allocates and sets ``bytes_per_rank``;
 * ``begin_step()``; ``rows(a, b, local)``: geometries ``[a, b)`` of this rank (rows ``local`` of its tables) are taken in - the
@@ -586,6 +586,92 @@ class WhatIf(_AccumulatorStage):
         self.merged = self.merged_over_ranks(mine, (mine.acc, mine.joint), unpack)
 
     def whatif(self):
+        if self.merged is None:
+            raise RuntimeError("no step() yet")
+        if self.result is None:
+            self.result = self.merged.finalize()
+        return self.result
+
+
+class Surface(_AccumulatorStage):
+    """``surface=True`` or ``surface=dict(degree=, interactions=, entries=, factors=)``: the normal equations of a polynomial response surface
+    of the selected entries on the reduction's factors, chunk by chunk right after the reduction, with the reduction's shift and - when the
+    ensemble was sampled - the sampler's flag bytes as the mask.  The basis is the same bits on every rank: from the plan's laws for
+    ``factors="sampled"``, else from the factor table of ALL geometries.  A chunk's basis rows are built once, the first time it is taken
+    in: factors do not change from step to step."""
+
+    def __init__(self, owner, surface):
+        super().__init__(owner)
+        o = owner
+        reduction = o.stages["reduce"]
+        options = {} if surface is True else dict(surface)
+        unknown = set(options) - {"degree", "interactions", "entries", "factors"}
+        if unknown:
+            raise ValueError(f"surface= takes True or dict(degree=, interactions=, entries=, factors=) (got {sorted(options)})")
+        if not reduction.n_factors:
+            raise ValueError("surface= regresses on the reduction's factors: it needs factors=")
+        k, device = len(o.metric_index), o.device
+        entries = options.get("entries")
+        if entries is None and o.steps * k > es.SURFACE_MAX_ENTRIES:
+            raise ValueError(f"surface=: the table has {o.steps * k} entries, more than {es.SURFACE_MAX_ENTRIES}: choose some with entries=")
+        source = o.plan if getattr(reduction, "_sampled", None) is not None else reduction.all_factors
+        self.basis = es.surface_terms(source, options.get("degree", 2), options.get("interactions", True), options.get("factors"))
+        if self.basis.factor_names is None and reduction.factor_names is not None:
+            self.basis.factor_names = tuple(reduction.factor_names)
+        t = self.basis.n_terms
+        self.entries = es.check_surface_arguments(entries.detach().cpu().numpy() if isinstance(entries, torch.Tensor) else entries, o.steps * k, t)
+        n = int(self.entries.size)
+        glo, ghi = o.geometry_range
+        self.factors = reduction.my_factors  # this rank's rows [n, P], where the ensemble lives
+        self.flags = o.sampled_flags.contiguous() if o.sampled_flags is not None else None
+        shift = o.local_accumulator.shift  # ONE table for every partial that is ever merged: the reduction's (itself, no copy)
+        self.local = es.SurfaceAccumulator(torch.zeros((t, t), dtype=torch.float64, device=device), torch.zeros((t, n), dtype=torch.float64, device=device),
+                                           torch.zeros(n, dtype=torch.float64, device=device), torch.zeros(2, dtype=torch.int64, device=device), shift,
+                                           torch.as_tensor(self.entries, device=device), torch.zeros(ghi - glo, dtype=torch.uint8, device=device),
+                                           basis=self.basis, natural=entries is None)
+        self.rows_of = {}  # (a, b) -> the basis rows of the chunk
+        self.merged = self.result = None
+        self.allocate_exchange(t * t + t * n + n + 2)
+
+    def take(self, a: int, b: int, values, status) -> None:
+        o, mine = self.owner, self.local
+        glo = o.geometry_range[0]
+        rows = slice(a - glo, b - glo)
+        mask = None if self.flags is None else self.flags[rows]
+        table = self.rows_of.get((a, b))
+        if self.on_device:
+            if table is None:
+                table = self.rows_of[(a, b)] = o.dp.basis_factors(self.factors[rows], self.basis)
+            view = es.SurfaceAccumulator(mine.gram, mine.cross, mine.sumsq, mine.counts, mine.shift, mine.entries, mine.used[a - glo :], basis=self.basis,
+                                         natural=mine.natural)
+            o.dp.surface_ensemble(values, steps_per_geometry=o.steps, basis_table=table, status=status, mask=mask, out=view, accumulate=self.taken)
+            return
+        if table is None:
+            table = self.rows_of[(a, b)] = es.basis_host(self.factors[rows].cpu().numpy(), self.basis)
+        part = es.surface_host(*self.host_tables(a, b, values, status), None if mask is None else mask.cpu().numpy(), table[0], table[1], self.entries,
+                               mine.shift.cpu().numpy(), basis=self.basis)
+        if not self.taken:
+            mine.gram.zero_(), mine.cross.zero_(), mine.sumsq.zero_(), mine.counts.zero_()
+        mine.gram += torch.from_numpy(part.gram)
+        mine.cross += torch.from_numpy(part.cross)
+        mine.sumsq += torch.from_numpy(part.sumsq)
+        mine.counts += torch.from_numpy(part.counts)
+        mine.used[rows] = torch.from_numpy(part.used)
+
+    def exchange(self) -> None:
+        """(the counts travel as their int64 bits)"""
+        mine = self.local
+        t, n = self.basis.n_terms, int(mine.entries.shape[0])
+        self.result = None
+
+        def unpack(row):
+            at = (t * t, t * t + t * n, t * t + t * n + n)
+            return es.SurfaceAccumulator(row[: at[0]].reshape(t, t), row[at[0] : at[1]].reshape(t, n), row[at[1] : at[2]], row[at[2] :].view(torch.int64),
+                                         mine.shift, mine.entries, basis=self.basis)
+
+        self.merged = self.merged_over_ranks(mine, (mine.gram, mine.cross, mine.sumsq, mine.counts.view(torch.float64)), unpack)
+
+    def surface(self):
         if self.merged is None:
             raise RuntimeError("no step() yet")
         if self.result is None:

@@ -24,6 +24,9 @@ HOW FAR TO TRUST them: Poisson-bootstrap replicates of those accumulators, their
 HOW an entry depends on ONE factor beyond a straight line, from the ordinary ensemble: its conditional moments over equal-probability
 bins of every factor and the first-order indices they give (``effects_edges`` / ``bin_factors_host`` / ``effects_host`` /
 ``EffectsAccumulator`` / ``EnsembleEffects``, ``okx_ensemble_bin`` and ``okx_ensemble_effects``).
+WHICH PAIRS of factors act together, and a model of the table: a polynomial response surface - orthonormal Hermite / Legendre polynomials
+of the sampler's latents with pairwise products, fitted by least squares from the normal equations the device accumulates (``surface_terms`` /
+``basis_host`` / ``surface_host`` / ``SurfaceAccumulator`` / ``EnsembleSurface``, ``okx_ensemble_basis`` and ``okx_ensemble_surface``).
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -1805,3 +1808,356 @@ def reweigh_host(values, status=None, mask=None, weights=None, shift=None, limit
         joint[:, REWEIGH_JOINT_UNRESOLVED] = np.where((flag & SCREEN_UNRESOLVED != 0)[:, None], wl, 0.0).sum(axis=0)
     joint[:, REWEIGH_JOINT_GEOMETRIES] = float(seen.sum())
     return ReweighAccumulator(acc, joint, shift, limits, scenario_names)
+
+
+# ---- polynomial response surface with pairwise interactions: a regression on orthonormal polynomials of the factors (okx_ensemble_basis, okx_ensemble_surface) ----
+
+SURFACE_MONOMIAL, SURFACE_HERMITE, SURFACE_LEGENDRE = 0, 1, 2  # OKX_SURFACE_*
+SURFACE_MAX_TERMS = 1024    # OKX_ENS_SURFACE_MAX_TERMS: 1024 terms with 2048 entries keep every table below 16 MB
+SURFACE_MAX_ENTRIES = 2048  # OKX_ENS_SURFACE_MAX_ENTRIES
+SURFACE_MAX_DEGREE = 3      # OKX_ENS_SURFACE_MAX_DEGREE
+SURFACE_MAX_FACTORS = 288   # OKX_ENS_SAMPLE_MAX_LATENTS
+SURFACE_PIVOT = CURVE_PIVOT  # a fit is refused when a Cholesky pivot of the Gram matrix scaled to a unit diagonal is not greater than this
+_SURFACE_KINDS = ("monomial", "Hermite", "Legendre")
+
+
+@dataclass
+class SurfaceBasis:
+    """
+    The terms of a response surface (``surface_terms``): ``law [P, 3]`` float64 = (kind, centre, scale) per factor, kind ``SURFACE_MONOMIAL`` /
+    ``SURFACE_HERMITE`` / ``SURFACE_LEGENDRE``; ``terms [T, 4]`` int32 = (a, da, b, db): the term is ``psi_da(u_a) psi_db(u_b)`` with
+    ``u = (x - centre) * scale``, ``b = -1, db = 0`` without a second factor; term 0 is the constant ``(-1, 0, -1, 0)``.  ``orthonormal``: the
+    terms are orthonormal under the law the factors were drawn from, so the squared coefficients are variance shares (the indices of
+    ``SurfaceAccumulator.finalize``).  ``factor_names``: one per factor, or None.
+    """
+
+    law: np.ndarray
+    terms: np.ndarray
+    orthonormal: bool = False
+    factor_names: tuple | None = None
+
+    n_factors = property(lambda self: int(self.law.shape[0]))
+    n_terms = property(lambda self: int(self.terms.shape[0]))
+
+    def same(self, other: "SurfaceBasis") -> bool:
+        return self is other or (np.array_equal(self.law, other.law) and np.array_equal(self.terms, other.terms) and self.orthonormal == other.orthonormal)
+
+    def term_name(self, t: int) -> str:
+        """Term ``t`` in words: ``"1"``, ``"psi2(point3.z)"``, ``"psi1(point3.z) psi1(point4.z)"``."""
+        name = (lambda p: self.factor_names[p] if self.factor_names is not None else f"factor{p}")
+        a, da, b, db = (int(x) for x in self.terms[t])
+        parts = [f"psi{d}({name(p)})" for p, d in ((a, da), (b, db)) if p >= 0]
+        return " ".join(parts) if parts else "1"
+
+
+def check_surface_basis(law, terms) -> tuple:
+    """``(law [P, 3] float64, terms [T, 4] int32)``, contiguous, or ValueError in the words of ``okx_ensemble_basis_check``."""
+    who = "okx_ensemble_basis"
+    law, raw = np.asarray(law, dtype=np.float64), np.asarray(terms)
+    if law.ndim != 2 or law.shape[1] != 3 or raw.ndim != 2 or raw.shape[1] != 4:
+        raise ValueError("law must be [P, 3] = (kind, centre, scale) and terms [T, 4] = (a, da, b, db)")
+    if raw.size and not np.issubdtype(raw.dtype, np.integer):
+        raise ValueError("terms must be integers (a, da, b, db)")
+    p, t = law.shape[0], raw.shape[0]
+    if not 1 <= t <= SURFACE_MAX_TERMS:
+        raise ValueError(f"{who}: {t} terms, 1 to {SURFACE_MAX_TERMS} allowed")
+    if not 1 <= p <= SURFACE_MAX_FACTORS:
+        raise ValueError(f"{who}: {p} factors, 1 to {SURFACE_MAX_FACTORS} allowed")
+    for i in range(p):
+        if law[i, 0] not in (SURFACE_MONOMIAL, SURFACE_HERMITE, SURFACE_LEGENDRE):
+            raise ValueError(f"{who}: factor {i} has kind {law[i, 0]:g}, not 0 (monomial), 1 (Hermite) or 2 (Legendre)")
+        if not np.all(np.isfinite(law[i, 1:])):
+            raise ValueError(f"{who}: factor {i} has a centre or scale that is not finite")
+    raw = raw.astype(np.int64)
+    if tuple(raw[0]) != (-1, 0, -1, 0):
+        raise ValueError(f"{who}: term 0 must be the constant (-1, 0, -1, 0)")
+    for i in range(t):
+        for f, d in ((raw[i, 0], raw[i, 1]), (raw[i, 2], raw[i, 3])):
+            if f < -1 or f >= p:
+                raise ValueError(f"{who}: term {i} names factor {int(f)}, outside [-1, {p})")
+            if (d != 0) if f < 0 else not 1 <= d <= SURFACE_MAX_DEGREE:
+                raise ValueError(f"{who}: term {i} has degree {int(d)} of factor {int(f)} (0 without a factor, else 1 to {SURFACE_MAX_DEGREE})")
+    return np.ascontiguousarray(law), np.ascontiguousarray(raw.astype(np.int32))
+
+
+def surface_terms(source, degree: int = 2, interactions: bool = True, factors=None) -> SurfaceBasis:
+    """
+    The basis of a response surface of total degree ``degree`` (1 to 3) over the factors of ``source``:
+
+    * an ``ensemble_sample.SamplePlan``: its LATENTS are the factors (also with ``mixing``).  An untruncated normal latent gives Hermite with
+      (0, 1), a uniform latent on ``[lo, hi] = [-1, 1]`` Legendre with centre ``(lo + hi) / 2`` and scale ``2 / (hi - lo)``, a truncated normal
+      Hermite with (0, 1) - its polynomials are then not orthonormal under the law, which clears ``orthonormal``;
+    * a factor table ``[G, P]`` of ALL geometries (every rank then gets the same bits): monomials of the standardised column, centre = the
+      column mean, scale = 1 / the column standard deviation (1 where that is 0), over the finite values; ``orthonormal`` is cleared.
+
+    Term 0 is the constant; then every factor's degree 1, then every factor's degree 2 (and 3), then with ``interactions`` the products
+    ``psi_1(u_a) psi_1(u_b)`` for ``a > b``.  ``factors``: the indices of the factors to take (None: all), in the order wanted.
+    """
+    degree = int(degree)
+    if not 1 <= degree <= SURFACE_MAX_DEGREE:
+        raise ValueError(f"the degree of a response surface is 1 to {SURFACE_MAX_DEGREE}, not {degree}")
+    orthonormal, names = True, None
+    if hasattr(source, "kind") and hasattr(source, "n_latents"):
+        from .ensemble_sample import NORMAL, TRUNCATED, UNIFORM
+
+        p = source.n_latents
+        law = np.zeros((p, 3))
+        for i, kind in enumerate(source.kind):
+            if kind == UNIFORM:
+                lo, hi = -1.0, 1.0  # ensemble_sample.latents_from_units: 2 u - 1
+                law[i] = SURFACE_LEGENDRE, (lo + hi) / 2.0, 2.0 / (hi - lo)
+            elif kind in (NORMAL, TRUNCATED):
+                law[i] = SURFACE_HERMITE, 0.0, 1.0
+                orthonormal = orthonormal and kind == NORMAL
+            else:
+                raise ValueError(f"latent {i} has kind {int(kind)}: no polynomial family is known for it")
+        names = tuple(source.factor_names())
+    else:
+        table = np.asarray(source, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] < 1:
+            raise ValueError("the source of a basis is a SamplePlan or a factor table [G, P]")
+        p = table.shape[1]
+        law = np.zeros((p, 3))
+        law[:, 0], law[:, 2] = SURFACE_MONOMIAL, 1.0
+        for i in range(p):
+            x = table[:, i][np.isfinite(table[:, i])]
+            if x.size:
+                law[i, 1] = np.mean(x)
+                sd = float(np.std(x))
+                law[i, 2] = 1.0 / sd if sd > 0.0 and np.isfinite(1.0 / sd) else 1.0
+        orthonormal = False
+    take = np.arange(p) if factors is None else np.atleast_1d(np.asarray(factors)).reshape(-1)
+    if take.size and not np.issubdtype(take.dtype, np.integer):
+        raise ValueError("factors= takes factor indices")
+    take = take.astype(np.int64)
+    if take.size < 1 or np.any(take < 0) or np.any(take >= p) or np.unique(take).size != take.size:
+        raise ValueError(f"factors= must be distinct indices in [0, {p})")
+    f = take.size
+    t = 1 + degree * f + (f * (f - 1) // 2 if interactions and degree >= 2 else 0)
+    if t > SURFACE_MAX_TERMS:
+        raise ValueError(f"okx_ensemble_basis: {t} terms, 1 to {SURFACE_MAX_TERMS} allowed")
+    rows = [(-1, 0, -1, 0)]
+    for d in range(1, degree + 1):
+        rows += [(int(a), d, -1, 0) for a in take]
+    if interactions and degree >= 2:
+        rows += [(int(take[i]), 1, int(take[j]), 1) for i in range(f) for j in range(i)]
+    law, terms = check_surface_basis(law, np.array(rows, dtype=np.int32))
+    return SurfaceBasis(law, terms, orthonormal, names)
+
+
+def _surface_psi(kind, u):
+    """``[4, G]``: psi_0 .. psi_3 of ``u [G]`` for one factor; every operation rounded on its own, as the device does them."""
+    uu = u * u
+    if kind == SURFACE_HERMITE:
+        return np.stack([np.ones_like(u), u, (uu - 1.0) * 0.7071067811865476, ((uu - 3.0) * u) * 0.408248290463863])
+    if kind == SURFACE_LEGENDRE:
+        return np.stack([np.ones_like(u), u * 1.7320508075688772, (3.0 * uu - 1.0) * 1.118033988749895, ((5.0 * uu - 3.0) * u) * 1.3228756555322954])
+    return np.stack([np.ones_like(u), u, uu, uu * u])
+
+
+def basis_host(factors, basis: SurfaceBasis):
+    """
+    ``okx_ensemble_basis`` in NumPy: ``(phi [G, T] float64, valid [G] uint8)`` of ``factors [G, P]``.  ``valid`` is 0 where any factor of the
+    row is not finite, and that row of ``phi`` is then 0.  No fused multiply-add anywhere: the device gives the same bits.
+    """
+    x = np.asarray(factors, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != basis.n_factors:
+        raise ValueError(f"factors must be [G, {basis.n_factors}], one column per factor of the basis")
+    g = x.shape[0]
+    valid = np.isfinite(x).all(axis=1)
+    one = np.ones((4, g))
+    with np.errstate(invalid="ignore", over="ignore"):
+        psi = {}
+        for p in np.unique(basis.terms[:, (0, 2)]):
+            if p >= 0:
+                psi[int(p)] = _surface_psi(int(basis.law[p, 0]), (x[:, p] - basis.law[p, 1]) * basis.law[p, 2])
+        phi = np.empty((g, basis.n_terms))
+        for t, (a, da, b, db) in enumerate(basis.terms):
+            phi[:, t] = (psi[int(a)] if a >= 0 else one)[da] * (psi[int(b)] if b >= 0 else one)[db]
+    phi[~valid] = 0.0
+    return phi, valid.astype(np.uint8)
+
+
+def check_surface_arguments(entries, n_table_entries: int, n_terms: int | None = None) -> np.ndarray:
+    """``entries [N]`` as int32 (None: all ``n_table_entries`` in natural order) by ``check_covariance_arguments``' rules with the surface pass's
+    own limit, or ValueError in the words of ``okx_ensemble_surface_check``."""
+    who = "okx_ensemble_surface"
+    if n_terms is not None and not 1 <= int(n_terms) <= SURFACE_MAX_TERMS:
+        raise ValueError(f"{who}: {int(n_terms)} terms, 1 to {SURFACE_MAX_TERMS} allowed")
+    n_table = int(n_table_entries)
+    n = n_table if entries is None else np.atleast_1d(np.asarray(entries)).size
+    if not 1 <= n <= SURFACE_MAX_ENTRIES:
+        raise ValueError(f"{who}: {n} entries selected, 1 to {SURFACE_MAX_ENTRIES} allowed")
+    try:  # (SURFACE_MAX_ENTRIES <= COV_MAX_ENTRIES: the count has passed, the other rules are the covariance pass's)
+        return check_covariance_arguments(entries, n_table)
+    except ValueError as err:
+        raise ValueError(str(err).replace("okx_ensemble_covariance", who)) from None
+
+
+@dataclass
+class EnsembleSurface:
+    """
+    What ``SurfaceAccumulator.finalize`` returns (NumPy, host), for the ``N`` selected entries in the caller's order and the ``T`` terms of
+    ``basis``: ``entries [N]``, ``count`` the geometries used and ``dropped`` the others, ``shift [N]`` (of the entries), ``coefficients [T, N]``
+    so that ``value ~ shift + sum_t c_t psi_t``, ``r2 [N]`` (NaN where the entry does not vary), ``residual_std [N]`` (``count - T`` degrees of
+    freedom).  With an orthonormal basis the variance shares of the fit: ``variance [N] = sum_{t > 0} c_t^2``, ``first [P, N]`` from the terms
+    of factor p alone, ``interaction [P, P, N]`` (symmetric, zero diagonal) from the product terms, ``total [P, N]`` from every term that contains
+    p - each divided by ``variance`` (NaN where that is 0); otherwise None.
+    """
+
+    entries: np.ndarray
+    count: int
+    dropped: int
+    basis: SurfaceBasis
+    shift: np.ndarray
+    coefficients: np.ndarray
+    r2: np.ndarray
+    residual_std: np.ndarray
+    variance: np.ndarray | None = None
+    first: np.ndarray | None = None
+    interaction: np.ndarray | None = None
+    total: np.ndarray | None = None
+
+    def predict(self, factors) -> np.ndarray:
+        """``[G, N]``: the fitted entries at ``factors [G, P]`` - ``shift + basis_host(factors) @ coefficients``; NaN where a factor is not finite."""
+        phi, valid = basis_host(factors, self.basis)
+        out = self.shift[None, :] + phi @ self.coefficients
+        out[valid == 0] = np.nan
+        return out
+
+
+class SurfaceAccumulator(_Accumulator):
+    """
+    The raw tables of ``okx_ensemble_surface``: ``gram [T, T]``, ``cross [T, N]`` and ``sumsq [N]`` float64, ``counts [2]`` int64 (used, dropped),
+    ``shift [S, K]`` and ``entries [N]`` int32 - NumPy arrays or torch tensors (host or device), whatever produced them -, and the
+    ``SurfaceBasis`` the rows of Phi were made with.  ``used [G]`` uint8 (or None) is the per-geometry byte of the LAST call that filled it.
+    """
+
+    TABLES, CARRIED, DEVICE_ONLY = ("gram", "cross", "sumsq", "counts", "shift", "entries", "used"), ("basis", "natural"), ("natural",)
+
+    def __init__(self, gram, cross, sumsq, counts, shift, entries, used=None, *, basis: SurfaceBasis, natural: bool = False):
+        self.gram, self.cross, self.sumsq, self.counts, self.shift, self.entries, self.used = gram, cross, sumsq, counts, shift, entries, used
+        self.basis, self.natural = basis, bool(natural)
+        t, n = basis.n_terms, int(entries.shape[0])
+        if tuple(gram.shape) != (t, t) or tuple(cross.shape) != (t, n) or tuple(sumsq.shape) != (n,) or tuple(counts.shape) != (2,) or shift.ndim != 2:
+            raise ValueError("gram must be [T, T], cross [T, N], sumsq [N], counts [2], shift [S, K] and entries [N]")
+
+    @classmethod
+    def empty(cls, shift, basis: SurfaceBasis, entries=None) -> "SurfaceAccumulator":
+        """The accumulator of no geometry at all (the neutral element of ``merge``), NumPy."""
+        shift = np.asarray(shift, dtype=np.float64)
+        e = check_surface_arguments(entries, shift.size, basis.n_terms)
+        t = basis.n_terms
+        return cls(np.zeros((t, t)), np.zeros((t, e.size)), np.zeros(e.size), np.zeros(2, dtype=np.int64), shift, e, basis=basis)
+
+    def merge(self, other: "SurfaceAccumulator") -> "SurfaceAccumulator":
+        """``self`` then ``other`` as one accumulator (a new one; both stay): additions only, which is why both must have been taken with the
+        same shift, entries and basis.  Works on NumPy arrays and on torch tensors alike."""
+        if not self.basis.same(other.basis):
+            raise ValueError("accumulators of different bases cannot be merged")
+        if not (_same_shape(self.entries, other.entries) and _same_table(self.entries, other.entries)):
+            raise ValueError("accumulators of different entries cannot be merged")
+        if not (_same_shape(self.shift, other.shift) and _same_table(self.shift, other.shift)):
+            raise ValueError("accumulators taken with different shifts cannot be merged")
+        return SurfaceAccumulator(self.gram + other.gram, self.cross + other.cross, self.sumsq + other.sumsq, self.counts + other.counts, self.shift,
+                                  self.entries, basis=self.basis)
+
+    def finalize(self) -> EnsembleSurface:
+        """The least-squares fit on the host in fp64: the Gram matrix scaled to a unit diagonal, Cholesky, two triangular solves.  ValueError
+        when fewer than ``T + 2`` geometries were used, or naming the first term whose pivot is ``<= 2^-40`` (it is not independent of the
+        terms before it)."""
+        h = self.numpy()
+        basis = h.basis
+        gram, cross, sumsq = (np.asarray(x, dtype=np.float64) for x in (h.gram, h.cross, h.sumsq))
+        entries = np.asarray(h.entries, dtype=np.int64)
+        shift = np.asarray(h.shift, dtype=np.float64).reshape(-1)[entries]
+        n, dropped = int(h.counts[0]), int(h.counts[1])
+        t = basis.n_terms
+        if n < t + 2:
+            raise ValueError(f"the response surface is refused: {n} geometries used, a fit of {t} terms needs at least T + 2 = {t + 2}")
+        diag = np.diag(gram)
+        s = 1.0 / np.sqrt(np.where(diag > 0.0, diag, 1.0))  # (a term that is 0 in every used geometry keeps its 0 diagonal: refused below)
+        a = gram * np.outer(s, s)
+        lower = np.zeros((t, t))
+        for j in range(t):
+            pivot = a[j, j] - lower[j, :j] @ lower[j, :j]
+            if not pivot > SURFACE_PIVOT:
+                raise ValueError(f"the response surface is refused: term {j} ({basis.term_name(j)}) is rank-deficient - not independent of the terms "
+                                 f"before it (pivot {pivot:.3g} <= 2^-40 of its diagonal entry)")
+            lower[j, j] = np.sqrt(pivot)
+            lower[j + 1:, j] = (a[j + 1:, j] - lower[j + 1:, :j] @ lower[j, :j]) / lower[j, j]
+        y = cross * s[:, None]
+        for j in range(t):  # L z = y
+            y[j] = (y[j] - lower[j, :j] @ y[:j]) / lower[j, j]
+        for j in range(t - 1, -1, -1):  # L^T c' = z
+            y[j] = (y[j] - lower[j + 1:, j] @ y[j + 1:]) / lower[j, j]
+        c = y * s[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            # term 0 separates as _fit separates the intercept: sum (phi_t - mean phi_t) d = cross_t - gram[t][0] cross_0 / n
+            centred = cross[1:] - np.outer(gram[1:, 0], cross[0]) / n
+            total_ss = sumsq - cross[0] * cross[0] / n
+            explained = np.einsum("tn,tn->n", c[1:], centred)
+            r2 = np.where(total_ss > 0.0, explained / total_ss, np.nan)
+            residual_std = np.sqrt(np.maximum(total_ss - explained, 0.0) / (n - t))
+        out = EnsembleSurface(entries, n, dropped, basis, shift, c, r2, residual_std)
+        if basis.orthonormal:
+            p, cc = basis.n_factors, c * c
+            variance = cc[1:].sum(axis=0)
+            first, total, inter = np.zeros((p, c.shape[1])), np.zeros((p, c.shape[1])), np.zeros((p, p, c.shape[1]))
+            for i in range(1, t):
+                a_, _, b_, _ = (int(x) for x in basis.terms[i])
+                if b_ < 0 or a_ < 0 or a_ == b_:
+                    f = a_ if a_ >= 0 else b_
+                    first[f] += cc[i]
+                    total[f] += cc[i]
+                else:
+                    inter[a_, b_] += cc[i]
+                    inter[b_, a_] += cc[i]
+                    total[a_] += cc[i]
+                    total[b_] += cc[i]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                share = np.where(variance > 0.0, 1.0 / variance, np.nan)
+                out.variance, out.first, out.interaction, out.total = variance, first * share, inter * share, total * share
+        return out
+
+
+def surface_host(values, status=None, mask=None, phi=None, valid=None, entries=None, shift=None, basis: SurfaceBasis | None = None) -> SurfaceAccumulator:
+    """
+    The accumulator of ``okx_ensemble_surface`` in NumPy.  ``values [G, S, K]``; ``status [G, S]`` uint8 or None (every state accepted); ``mask [G]``
+    uint8 or None, bit 0 set: the geometry does not count; ``phi [G, T]`` and ``valid [G]`` from ``basis_host``; ``entries [N]`` distinct ``s K + k``
+    (None: all, natural order); ``shift [S, K]`` (None: the values of geometry 0, undefined entries 0); ``basis`` the ``SurfaceBasis`` of ``phi``
+    (``finalize`` needs it).  COMPLETE CASES: a geometry is USED when every selected entry of it counts (``status & 7 == 1`` and a finite
+    value), bit 0 of its mask byte is clear and ``valid`` is set.  The sums run over the used geometries in ascending order, one after the
+    other; every product is rounded before its addition.
+    """
+    v, ok = _accepted(values, status)
+    g, s, k = v.shape
+    phi = np.asarray(phi, dtype=np.float64)
+    if phi.ndim != 2 or phi.shape[0] != g:
+        raise ValueError(f"phi must be [G, T] = [{g}, T], one row per geometry of the table")
+    t = phi.shape[1]
+    e = check_surface_arguments(entries, s * k, t)
+    if basis is not None and basis.n_terms != t:
+        raise ValueError(f"phi has {t} columns, the basis {basis.n_terms} terms")
+    if shift is None:
+        shift = clean_shift(v[0]) if g else np.zeros((s, k))
+    shift = np.asarray(shift, dtype=np.float64).reshape(s, k)
+    if not np.all(np.isfinite(shift)):
+        raise ValueError("the shift must be finite (clean_shift replaces undefined entries)")
+    at = e.astype(np.int64)
+    used = ok.reshape(g, s * k)[:, at].all(axis=1)
+    if mask is not None:
+        used &= (np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0
+    if valid is not None:
+        used &= np.asarray(valid).reshape(g) != 0
+    with np.errstate(invalid="ignore"):
+        d = np.where(used[:, None], v.reshape(g, s * k)[:, at] - shift.reshape(-1)[at][None], 0.0)
+    gram, cross, sumsq = np.zeros((t, t)), np.zeros((t, e.size)), np.zeros(e.size)
+    for i in np.flatnonzero(used):  # ascending geometry order, as the device walks a slab
+        gram += np.outer(phi[i], phi[i])
+        cross += np.outer(phi[i], d[i])
+        sumsq += d[i] * d[i]
+    counts = np.array([int(used.sum()), g - int(used.sum())], dtype=np.int64)
+    if basis is None:  # (a table of doubles without a law: the terms are anonymous monomials of nothing; finalize solves, names by number)
+        basis = SurfaceBasis(np.array([[0.0, 0.0, 1.0]]), np.array([[-1, 0, -1, 0]] + [[0, 1, -1, 0]] * (t - 1), dtype=np.int32))
+    return SurfaceAccumulator(gram, cross, sumsq, counts, shift, e, used.astype(np.uint8), basis=basis)
