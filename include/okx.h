@@ -1474,6 +1474,56 @@ int32_t okx_ensemble_surface(int64_t n_geometries, int64_t steps, int32_t n_colu
 size_t okx_ensemble_surface_scratch_bytes(int64_t n_geometries, int64_t steps, int32_t n_columns, int32_t n_terms, int32_t n_entries);
 int32_t okx_ensemble_surface_check(const int32_t* entries /* or NULL */, int32_t n_entries, int64_t n_table_entries, int32_t n_terms);
 
+/*
+ * Evaluation of a response surface on device (ADDED UNDER ABI 6 - nothing existing changed; look the symbols up): the fitted
+ * model as a column table that every ensemble pass reads, without the basis table [G][T] ever lying in memory.
+ *
+ * okx_ensemble_predict.  d_factors, ld, n_factors, d_law, d_terms and n_terms exactly as okx_ensemble_basis takes them, under the
+ * same limits; d_coefficients [n_terms][ld_c] doubles with 1 <= n_entries <= OKX_ENS_SURFACE_MAX_ENTRIES columns (n_entries <=
+ * ld_c); d_shift [n_entries] doubles or NULL (zeros); d_mask [n_geometries] uint8 or NULL, bit 0 set drops the row (the sampler's
+ * d_flags).  With psi_t the basis value of term t (the bits of okx_ensemble_basis), N = n_entries:
+ *   mode OKX_PREDICT_VALUE     d_out[g][n] = shift[n] + sum_t psi_t c[t][n]
+ *   mode OKX_PREDICT_RESIDUAL  d_out[g][n] = value[g][entry n] - (shift[n] + sum_t psi_t c[t][n])
+ *   d_out   [n_geometries][ld_out] double (N <= ld_out); columns at and beyond N are not touched
+ *   d_valid [n_geometries] uint8: 0 where ANY of the row's n_factors factors is not finite or bit 0 of its mask byte is set -
+ *           that row of d_out is then NaN in every column
+ * RESIDUAL mode reads the table the way every ensemble pass takes it (steps, n_columns, d_values, ld_values, d_status,
+ * status_stride; d_entries [N] int32 = s * n_columns + k, or NULL: all steps * n_columns = N entries in natural order); an entry
+ * that does not count (status & 7 != 1 or a value that is not finite) is NaN.  VALUE mode ignores those seven arguments.
+ *
+ * THE BITS.  ROW-PURE: the row of a geometry is a function of its factor row, the basis, the coefficients and the shift alone.
+ * The sum over the terms starts at 0 and takes the terms in ascending panels of 32 (the terms beyond T are zeros), four at a time in
+ * v_mfma_f64_16x16x4_f64 - an order that depends on n_terms only: not on n_geometries, not on where the row lies in the call,
+ * not on ld, ld_c, ld_out or n_entries, not on what else runs.  Then the shift is added in ONE rounded addition, then (RESIDUAL)
+ * the difference is taken in ONE rounded subtraction.  So every chunking, every device and every rank gives a geometry the same
+ * bits, and a chunk that is drawn and predicted again is the same chunk.  Against exact arithmetic:
+ * |out - exact| <= (T + 4) u (|shift| + sum_t |psi_t c_t|) + 2 u |value|, u = 2^-53, with psi_t the basis values as rounded.
+ * One launch on the given stream, no scratch, no atomics, no allocation, no host read-back: legal inside a stream capture;
+ * n_geometries = 0 is legal.  The launch cannot read d_entries on the host: okx_ensemble_predict_check validates a HOST copy
+ * (the counts; with n_table_entries > 0 the entry list by okx_ensemble_surface_check's rules and words under this pass's name);
+ * the law and the terms are validated by okx_ensemble_basis_check.  On the device an entry index out of range is never
+ * dereferenced (its column is NaN) and a factor index out of range reads as "no factor".
+ */
+enum { OKX_PREDICT_VALUE = 0, OKX_PREDICT_RESIDUAL = 1 };
+
+int32_t okx_ensemble_predict(int64_t n_geometries, int32_t mode,
+                             const double* d_factors, int64_t ld, int32_t n_factors,  /* [n_geometries][ld]                    */
+                             const double* d_law,                                     /* [n_factors][3]                        */
+                             const int32_t* d_terms, int32_t n_terms,                 /* [n_terms][4]                          */
+                             const double* d_coefficients, int64_t ld_c, int32_t n_entries, /* [n_terms][ld_c]                 */
+                             const double* d_shift,                                   /* [n_entries] or NULL                   */
+                             const uint8_t* d_mask,                                   /* [n_geometries] or NULL                */
+                             int64_t steps, int32_t n_columns,                        /* RESIDUAL: the table ...               */
+                             const double* d_values, int64_t ld_values,               /* [n_geometries * steps][ld_values]     */
+                             const uint8_t* d_status, int64_t status_stride,          /* or NULL                               */
+                             const int32_t* d_entries,                                /* [n_entries] or NULL                   */
+                             double* d_out, int64_t ld_out,                           /* [n_geometries][ld_out]                */
+                             uint8_t* d_valid,                                        /* [n_geometries]                        */
+                             void* stream);
+/* host only */
+int32_t okx_ensemble_predict_check(const int32_t* entries /* or NULL */, int32_t n_entries, int64_t n_table_entries, int32_t n_terms,
+                                   int32_t n_factors);
+
 #ifdef __cplusplus
 }
 #endif

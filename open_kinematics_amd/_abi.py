@@ -125,6 +125,9 @@ ENS_TILT_MAX_SCENARIOS, TILT_PARAMS = 256, 5
 ENS_SURFACE_MAX_TERMS, ENS_SURFACE_MAX_ENTRIES, ENS_SURFACE_MAX_DEGREE = 1024, 2048, 3
 SURFACE_MONOMIAL, SURFACE_HERMITE, SURFACE_LEGENDRE = 0, 1, 2
 
+# okx_ensemble_predict (include/okx.h OKX_PREDICT_*)
+PREDICT_VALUE, PREDICT_RESIDUAL = 0, 1
+
 INFO_CONVERGED = 1
 INFO_RESIDUAL_EXCEEDED = 2
 INFO_FAILED = 4

@@ -101,6 +101,8 @@ EXPORTS = (
     "okx_ensemble_surface",
     "okx_ensemble_surface_scratch_bytes",
     "okx_ensemble_surface_check",
+    "okx_ensemble_predict",
+    "okx_ensemble_predict_check",
 )
 
 # include/okx_debug.h: test hooks and profiling aids, not part of the drop-in boundary
@@ -339,6 +341,10 @@ def load() -> C.CDLL:
     lib.okx_ensemble_surface_scratch_bytes.restype = C.c_size_t
     lib.okx_ensemble_surface_check.argtypes = [vp, i32, i64, i32]
     lib.okx_ensemble_surface_check.restype = i32
+    lib.okx_ensemble_predict.argtypes = [i64, i32, vp, i64, i32, vp, vp, i32, vp, i64, i32, vp, vp, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp]
+    lib.okx_ensemble_predict.restype = i32
+    lib.okx_ensemble_predict_check.argtypes = [vp, i32, i64, i32, i32]
+    lib.okx_ensemble_predict_check.restype = i32
     if lib.okx_abi_version() != ABI_VERSION:
         raise RuntimeError("libokx.so ABI version mismatch")
     _lib = lib

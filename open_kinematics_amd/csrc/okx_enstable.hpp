@@ -1,5 +1,6 @@
-// okx_enstable.hpp — what the eleven passes over an ensemble table [G * S][ld] share (okx_ensemble.hip, okx_select.hip,
-// okx_screen.hip, okx_covariance.hip, okx_curves.hip, okx_front.hip, okx_sobol.hip, okx_bootstrap.hip, okx_effects.hip, okx_tilt.hip, okx_surface.hip; okx_sample.hip draws tables and reads
+// okx_enstable.hpp — what the twelve passes over an ensemble table [G * S][ld] share (okx_ensemble.hip, okx_select.hip,
+// okx_screen.hip, okx_covariance.hip, okx_curves.hip, okx_front.hip, okx_sobol.hip, okx_bootstrap.hip, okx_effects.hip, okx_tilt.hip, okx_surface.hip,
+// okx_predict.hip in its RESIDUAL mode; okx_sample.hip draws tables and reads
 // none, so it stays out).  Host side: the view of the table's seven arguments, the argument checks (each with the calling entry point's name
 // for the message; a pass calls them where the order of its own checks wants them), the launch plans' common arithmetic and
 // the launch helper.  Device side (kernel units only): the acceptance rule, the view's two walks, the workgroup sum and the

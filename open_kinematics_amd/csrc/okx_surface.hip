@@ -29,6 +29,7 @@
 #include "okx_enstable.hpp"
 #include "okx_gramtile.hpp"
 #include "okx_program.hpp"
+#include "okx_surfbasis.hpp"  // psi
 
 #pragma clang fp contract(off)
 
@@ -48,25 +49,6 @@ constexpr int kMaxFactors = OKX_ENS_SAMPLE_MAX_LATENTS;
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 // ---- basis ----
-
-// psi_degree of u by the factor's kind; every operation rounded (ensemble_stats._surface_psi)
-__device__ inline double psi(int kind, int degree, double u) {
-  if (degree == 0) return 1.0;
-  const double uu = u * u;
-  if (kind == OKX_SURFACE_HERMITE) {
-    if (degree == 1) return u;
-    if (degree == 2) return (uu - 1.0) * 0.7071067811865476;
-    return ((uu - 3.0) * u) * 0.408248290463863;
-  }
-  if (kind == OKX_SURFACE_LEGENDRE) {
-    if (degree == 1) return u * 1.7320508075688772;
-    if (degree == 2) return (3.0 * uu - 1.0) * 1.118033988749895;
-    return ((5.0 * uu - 3.0) * u) * 1.3228756555322954;
-  }
-  if (degree == 1) return u;
-  if (degree == 2) return uu;
-  return uu * u;
-}
 
 struct BasisArgs {
   const double* factors;   // [n_geom][ld]

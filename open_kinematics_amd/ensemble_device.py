@@ -21,6 +21,8 @@ pass (``okx_ensemble_...``)    prepare call          result
 ``tilt_weights``               ``tilt_prepare``      ``float64 [G, N]`` tensor
 ``reweigh_ensemble``           ``tilt_weights``      ``ensemble_stats.ReweighAccumulator``
 ``surface_ensemble``           ``basis_factors``     ``ensemble_stats.SurfaceAccumulator``
+``predict_ensemble``           ``upload_surface``    ``(out [G, N], valid [G])`` tensors
+``validate_surface``           ``upload_surface``    ``ensemble_stats.SurfaceValidation``
 =============================  ====================  ==============================================
 
 Every pass takes ``out=``, the result of an earlier call or of its prepare call; the tables it holds are checked in one place
@@ -37,11 +39,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, REWEIGH_FIELDS, REWEIGH_JOINT_FIELDS, REWEIGH_MAX_SCENARIOS,
+from .ensemble_stats import (CURVE_FIELDS, EFFECTS_FIELDS, ENS_FIELDS, FRONT_TARGET, PREDICT_RESIDUAL, PREDICT_VALUE, REWEIGH_FIELDS, REWEIGH_JOINT_FIELDS, REWEIGH_MAX_SCENARIOS,
                              SELECT_MAX_PROBS, SOBOL_FIELDS, SOBOL_MAX_GROUPS, CovarianceAccumulator, EffectsAccumulator, EnsembleAccumulator, EnsembleCurves,
-                             ReweighAccumulator, SobolAccumulator, SobolBootstrapAccumulator, SurfaceAccumulator, SurfaceBasis, _host_f64, broadcast_limits,
+                             ReweighAccumulator, SobolAccumulator, SobolBootstrapAccumulator, SurfaceAccumulator, SurfaceBasis, SurfaceValidation, _host_f64, broadcast_limits,
                              broadcast_scale, check_covariance_arguments, check_effects_arguments, check_front_arguments, check_replicates, check_reweigh_limits,
-                             check_surface_arguments, check_surface_basis, factor_moment_count)
+                             check_predict_arguments, check_surface_arguments, check_surface_basis, factor_moment_count, validation_from_terms)
 
 F64, I64, I32, U8 = torch.float64, torch.int64, torch.int32, torch.uint8
 
@@ -222,6 +224,22 @@ class SurfaceBasisTable:
     law: torch.Tensor
     terms: torch.Tensor
     basis: SurfaceBasis
+
+
+@dataclass
+class SurfaceModel:
+    """What ``upload_surface`` returns and ``predict_ensemble`` / ``validate_surface`` take, device tensors of a fitted surface of ``T`` terms,
+    ``P`` factors and ``N`` entries: ``law [P, 3]``, ``terms [T, 4]`` int32, ``coefficients [T, N]``, ``shift [N]``, ``entries [N]`` int32 and
+    ``whitener [T, T]`` (None when the fit carries none); ``basis`` and ``entries_host`` are the host forms the checks read."""
+
+    law: torch.Tensor
+    terms: torch.Tensor
+    coefficients: torch.Tensor
+    shift: torch.Tensor
+    entries: torch.Tensor
+    whitener: torch.Tensor | None
+    basis: SurfaceBasis
+    entries_host: np.ndarray
 
 
 def _ptr(t: torch.Tensor | None, row: int = 0) -> C.c_void_p:
@@ -1123,8 +1141,122 @@ class EnsembleReductions:
         """
         The fitted entries ``float64 [G, N]`` of ``surface`` (``ensemble_stats.EnsembleSurface``, host) at ``factors [G, P]`` on the device, without
         a solve: the basis pass, then ``shift + phi @ coefficients`` (``torch.matmul``); NaN where a factor is not finite.  Host form:
-        ``EnsembleSurface.predict``.
+        ``EnsembleSurface.predict``.  ``predict_ensemble`` gives the same table from one launch, without the basis table in memory and with
+        defined bits.
         """
         table = self.basis_factors(factors, surface.basis)
         out = torch.as_tensor(surface.shift, device=self.device)[None, :] + torch.matmul(table.phi, torch.as_tensor(surface.coefficients, device=self.device))
         return torch.where(table.valid[:, None] != 0, out, torch.full_like(out, float("nan")))
+
+    # ---- okx_ensemble_predict: the fitted surface as a column table (ensemble_stats.predict_host), and its leave-one-out error ----
+
+    def upload_surface(self, surface) -> "SurfaceModel":
+        """
+        The tables of ``surface`` (``ensemble_stats.EnsembleSurface``, host) on the device as a ``SurfaceModel``: validated on the host
+        (``okx_ensemble_basis_check``, ``okx_ensemble_predict_check``) and uploaded ONCE, so that ``predict_ensemble`` uploads nothing.
+        """
+        basis = surface.basis
+        if not isinstance(basis, SurfaceBasis):
+            raise ValueError("surface must be an EnsembleSurface (SurfaceAccumulator.finalize)")
+        law, terms = check_surface_basis(basis.law, basis.terms)
+        rc = self.lib.okx_ensemble_basis_check(law.ctypes.data_as(C.c_void_p), min(law.shape[0], 1 << 20), terms.ctypes.data_as(C.c_void_p), terms.shape[0])
+        _lib.check(rc, "okx_ensemble_basis")
+        c, shift, _ = check_predict_arguments(basis, surface.coefficients, surface.shift)
+        entries = np.ascontiguousarray(np.asarray(surface.entries).reshape(-1).astype(np.int32))
+        if entries.size != c.shape[1]:
+            raise ValueError(f"surface.entries must be [N] = [{c.shape[1]}]")
+        rc = self.lib.okx_ensemble_predict_check(None, min(c.shape[1], 1 << 30), 0, terms.shape[0], min(law.shape[0], 1 << 20))
+        _lib.check(rc, "okx_ensemble_predict")
+        dev = self.device
+        whitener = getattr(surface, "whitener", None)
+        return SurfaceModel(torch.as_tensor(law, device=dev), torch.as_tensor(terms, device=dev), _as_f64(c, dev), _as_f64(shift, dev),
+                            torch.as_tensor(entries, device=dev), None if whitener is None else _as_f64(whitener, dev), basis, entries)
+
+    def predict_ensemble(self, model, factors, *, mask=None, values=None, status=None, steps_per_geometry=None, coefficients=None, out=None,
+                         valid=None) -> tuple:
+        """
+        ``okx_ensemble_predict``: ``(out [G, N], valid [G])``, the surface of ``model`` (``upload_surface``) at ``factors [G, P]`` (a float64
+        device tensor with unit column stride; rows may be strided - the sampler's ``latents`` as they lie in HBM) as a column table that
+        every ensemble pass reads with ``steps_per_geometry=1`` - one launch, the basis table never lies in memory.  ``mask [G]`` contiguous
+        uint8 (the sampler's ``flags``): bit 0 set drops the row.  A dropped row, or one with a factor that is not finite, is NaN in every
+        column and has ``valid = 0``.  With ``values`` (and ``status``, ``steps_per_geometry``, as ``reduce_ensemble`` takes them) the call
+        runs RESIDUAL mode: ``value - prediction`` of the model's entries, NaN where the entry does not count.  ``coefficients``: another
+        ``[T, N']`` device matrix (unit column stride) in the place of the model's, with a zero shift - how the whitener goes through.
+        ``out`` (``[G, N]``, rows may be strided: columns of a wider table) and ``valid`` (``[G]`` uint8): with both the call allocates and
+        uploads nothing and is legal inside a stream capture.  ROW-PURE: a geometry's row has the same bits in every chunking, on every
+        device and in every call (``include/okx.h``); ``ensemble_stats.predict_host`` within the bound stated there.
+        """
+        if not isinstance(model, SurfaceModel):
+            raise ValueError("model must be the SurfaceModel of upload_surface")
+        g, p, ld = self._strided_rows(factors, "factors", "[G, P]")
+        t = model.basis.n_terms
+        if model.basis.n_factors != p:
+            raise ValueError(f"factors must be [G, {model.basis.n_factors}], one column per factor of the basis")
+        self._check_tables(f"model must hold contiguous device tables law [{p}, 3] and terms [{t}, 4]", [(model.law, (p, 3), F64), (model.terms, (t, 4), I32)])
+        shift = None
+        if coefficients is None:
+            coefficients, shift = model.coefficients, model.shift
+        _, n, ld_c = self._strided_rows(coefficients, f"coefficients [{t}, N]", "[T, N]", rows=t)
+        self._check_tables(f"model must hold a contiguous device table shift [{n}]", [], [(shift, (n,), F64)])
+        self._check_mask(mask, g, contiguous=True)
+        mode, s, k, ld_v, stride, index = PREDICT_VALUE, 0, 0, 0, 0, None
+        if values is not None:
+            if steps_per_geometry is None:
+                raise ValueError("steps_per_geometry is needed with values=")
+            gv, s, k, ld_v, stride = self._ensemble_table(values, status, steps_per_geometry)
+            if gv != g:
+                raise ValueError(f"values must hold {g} geometries, one per factor row")
+            host = model.entries_host
+            if host.size != n:
+                raise ValueError(f"okx_ensemble_predict: {host.size} entries of the table for {n} columns of the coefficients")
+            self._check_tables(f"model must hold a contiguous device table entries [{n}]", [(model.entries, (n,), I32)])
+            rc = self.lib.okx_ensemble_predict_check(host.ctypes.data_as(C.c_void_p), min(host.size, 1 << 30), s * k, t, p)
+            _lib.check(rc, "okx_ensemble_predict")
+            mode, index = PREDICT_RESIDUAL, model.entries
+        elif status is not None:
+            raise ValueError("status= goes with values=")
+        dev = self.device
+        if out is None:
+            out = torch.empty((g, n), dtype=F64, device=dev)
+        _, _, ld_out = self._strided_rows(out, f"out [{g}, {n}]", "[G, N]", rows=g)
+        if out.shape[1] != n:
+            raise ValueError(f"out must be [{g}, {n}]")
+        if valid is None:
+            valid = torch.empty(g, dtype=U8, device=dev)
+        self._check_tables(f"valid must be a contiguous uint8 [{g}] device tensor", [(valid, (g,), U8)])
+        self._ensemble_call("okx_ensemble_predict", g, mode, _ptr(factors), ld, p, _ptr(model.law), _ptr(model.terms), t, _ptr(coefficients), ld_c, n,
+                            _ptr(shift), _ptr(mask), s, k, _ptr(values), ld_v, _ptr(status), stride, _ptr(index), _ptr(out), ld_out, _ptr(valid))
+        return out, valid
+
+    def validate_surface(self, model, surface, factors, values, *, steps_per_geometry: int, status=None, mask=None, used=None, chunk: int = 16384):
+        """
+        The leave-one-out error of a fit over the geometries it was fitted on (``ensemble_stats.SurfaceValidation``; the definition is
+        ``ensemble_stats.surface_validate_host``): one RESIDUAL call of ``predict_ensemble`` for ``e``, one VALUE call with the whitener per
+        ``chunk`` geometries for the leverage ``h = |phi_g whitener|^2`` (``[chunk, T]`` bounds the memory), then ``e_loo = e / (1 - h)`` and
+        its sums with torch's elementwise operations on the device.  ``used [G]``: the used bytes of the fit (``SurfaceAccumulator.used``);
+        None: the rows whose residuals are all defined - the complete cases.  NOT bit-defined: the row norms and the sums are torch's.
+        """
+        if model.whitener is None or getattr(surface, "total_ss", None) is None:
+            raise ValueError("the surface carries no whitener (SurfaceAccumulator.finalize fills it)")
+        e, _ = self.predict_ensemble(model, factors, mask=mask, values=values, status=status, steps_per_geometry=steps_per_geometry)
+        g = e.shape[0]
+        keep = torch.isfinite(e).all(dim=1) if used is None else torch.as_tensor(used, device=self.device).reshape(-1) != 0
+        if keep.shape[0] != g:
+            raise ValueError(f"used must be [G] = [{g}]")
+        h = torch.empty(g, dtype=F64, device=self.device)
+        step = max(1, int(chunk))
+        for a in range(0, g, step):
+            z, _ = self.predict_ensemble(model, factors[a:a + step], coefficients=model.whitener)
+            h[a:a + step] = (z * z).sum(dim=1)
+        count = int(keep.sum().item())
+        if count == 0:
+            return validation_from_terms(np.zeros((0, e.shape[1])), np.zeros(0), np.zeros(0), np.asarray(surface.total_ss, dtype=np.float64))
+        loo = torch.where(keep[:, None], e / (1.0 - h)[:, None], torch.zeros((), dtype=F64, device=self.device))
+        ss = (loo * loo).sum(dim=0).cpu().numpy()
+        worst, at = loo.abs().max(dim=0)
+        total_ss = np.asarray(surface.total_ss, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            q2 = np.where(total_ss > 0.0, 1.0 - ss / total_ss, np.nan)
+        zero, low = torch.zeros((), dtype=F64, device=self.device), torch.full((), float("-inf"), dtype=F64, device=self.device)
+        return SurfaceValidation(np.sqrt(ss / count), q2, worst.cpu().numpy(), at.cpu().numpy().astype(np.int64), float(torch.where(keep, h, low).max().item()),
+                                 float(torch.where(keep, h, zero).sum().item()) / count, count)

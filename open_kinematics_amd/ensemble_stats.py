@@ -27,6 +27,9 @@ bins of every factor and the first-order indices they give (``effects_edges`` / 
 WHICH PAIRS of factors act together, and a model of the table: a polynomial response surface - orthonormal Hermite / Legendre polynomials
 of the sampler's latents with pairwise products, fitted by least squares from the normal equations the device accumulates (``surface_terms`` /
 ``basis_host`` / ``surface_host`` / ``SurfaceAccumulator`` / ``EnsembleSurface``, ``okx_ensemble_basis`` and ``okx_ensemble_surface``).
+THE MODEL IN USE AND UNDER TEST: the fitted surface evaluated as a column table, or the table's residuals against it (``predict_host``,
+``okx_ensemble_predict``; ``ensemble_virtual.virtual_ensemble`` counts millions of drawn geometries through it), and its leave-one-out
+error from residuals and leverages without a refit (``surface_loo_host`` / ``surface_validate_host`` / ``SurfaceValidation``).
 
 ``EnsembleAccumulator`` holds the raw tables; partial accumulators taken with THE SAME shift merge by additions and
 comparisons (``merge``), ``finalize`` turns one into ``EnsembleStats``.
@@ -2002,7 +2005,9 @@ class EnsembleSurface:
     so that ``value ~ shift + sum_t c_t psi_t``, ``r2 [N]`` (NaN where the entry does not vary), ``residual_std [N]`` (``count - T`` degrees of
     freedom).  With an orthonormal basis the variance shares of the fit: ``variance [N] = sum_{t > 0} c_t^2``, ``first [P, N]`` from the terms
     of factor p alone, ``interaction [P, P, N]`` (symmetric, zero diagonal) from the product terms, ``total [P, N]`` from every term that contains
-    p - each divided by ``variance`` (NaN where that is 0); otherwise None.
+    p - each divided by ``variance`` (NaN where that is 0); otherwise None.  For ``surface_validate_host`` / ``DeviceProgram.validate_surface``
+    the fit also carries ``whitener [T, T]`` = ``S L^-T`` of its own scaled Cholesky factor (``Phi @ whitener`` has orthonormal columns over the
+    used geometries, so a row's squared norm there is its leverage) and ``total_ss [N]``, the centred sum of squares of the entries.
     """
 
     entries: np.ndarray
@@ -2017,6 +2022,8 @@ class EnsembleSurface:
     first: np.ndarray | None = None
     interaction: np.ndarray | None = None
     total: np.ndarray | None = None
+    whitener: np.ndarray | None = None
+    total_ss: np.ndarray | None = None
 
     def predict(self, factors) -> np.ndarray:
         """``[G, N]``: the fitted entries at ``factors [G, P]`` - ``shift + basis_host(factors) @ coefficients``; NaN where a factor is not finite."""
@@ -2100,6 +2107,11 @@ class SurfaceAccumulator(_Accumulator):
             r2 = np.where(total_ss > 0.0, explained / total_ss, np.nan)
             residual_std = np.sqrt(np.maximum(total_ss - explained, 0.0) / (n - t))
         out = EnsembleSurface(entries, n, dropped, basis, shift, c, r2, residual_std)
+        inverse = np.zeros((t, t))  # L^-1 by forward substitution, row by row
+        for j in range(t):
+            inverse[j, :j] = -(lower[j, :j] @ inverse[:j, :j]) / lower[j, j]
+            inverse[j, j] = 1.0 / lower[j, j]
+        out.whitener, out.total_ss = s[:, None] * inverse.T, total_ss
         if basis.orthonormal:
             p, cc = basis.n_factors, c * c
             variance = cc[1:].sum(axis=0)
@@ -2161,3 +2173,138 @@ def surface_host(values, status=None, mask=None, phi=None, valid=None, entries=N
     if basis is None:  # (a table of doubles without a law: the terms are anonymous monomials of nothing; finalize solves, names by number)
         basis = SurfaceBasis(np.array([[0.0, 0.0, 1.0]]), np.array([[-1, 0, -1, 0]] + [[0, 1, -1, 0]] * (t - 1), dtype=np.int32))
     return SurfaceAccumulator(gram, cross, sumsq, counts, shift, e, used.astype(np.uint8), basis=basis)
+
+
+# ---- evaluation of a response surface: the model as a column table, and its leave-one-out error (okx_ensemble_predict) ----
+
+PREDICT_VALUE, PREDICT_RESIDUAL = 0, 1  # OKX_PREDICT_*
+
+
+def check_predict_arguments(basis: SurfaceBasis, coefficients, shift=None, entries=None, n_table_entries: int = 0):
+    """``(coefficients [T, N] float64, shift [N] float64 or None, entries [N] int32 or None)`` or ValueError in the words of
+    ``okx_ensemble_predict`` / ``okx_ensemble_predict_check``.  ``n_table_entries > 0``: the RESIDUAL table has that many entries."""
+    who = "okx_ensemble_predict"
+    c = np.asarray(coefficients, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != basis.n_terms:
+        raise ValueError(f"coefficients must be [T, N] = [{basis.n_terms}, N], one row per term of the basis")
+    n = c.shape[1]
+    if not 1 <= n <= SURFACE_MAX_ENTRIES:
+        raise ValueError(f"{who}: {n} entries, 1 to {SURFACE_MAX_ENTRIES} allowed")
+    if shift is not None:
+        shift = np.asarray(shift, dtype=np.float64).reshape(-1)
+        if shift.size != n:
+            raise ValueError(f"shift must be [N] = [{n}], one per column of the coefficients")
+    e = None
+    if n_table_entries > 0:
+        count = int(n_table_entries) if entries is None else np.atleast_1d(np.asarray(entries)).size
+        if count != n:
+            raise ValueError(f"{who}: {count} entries of the table for {n} columns of the coefficients"
+                             if entries is not None else f"{who}: without an entry list all {int(n_table_entries)} entries are selected, not {n}")
+        try:
+            e = check_covariance_arguments(entries, int(n_table_entries))
+        except ValueError as err:
+            raise ValueError(str(err).replace("okx_ensemble_covariance", who)) from None
+    return c, shift, e
+
+
+def predict_host(factors, basis: SurfaceBasis, coefficients, shift=None, mask=None, values=None, status=None, entries=None):
+    """
+    ``okx_ensemble_predict`` in NumPy, the definition of both modes: ``(out [G, N] float64, valid [G] uint8)``.  ``factors [G, P]``;
+    ``coefficients [T, N]``; ``shift [N]`` or None (zeros); ``mask [G]`` uint8 or None, bit 0 set drops the row.  VALUE mode (``values`` None):
+    ``out = shift + basis_host(factors) @ coefficients``.  RESIDUAL mode: ``values [G, S, K]`` (``status [G, S]`` uint8 or None: every state
+    accepted; ``entries [N]`` distinct ``s K + k``, None: all ``S K = N`` in natural order) gives ``out = value - (shift + ...)``, NaN where the
+    entry does not count (``status & 7 != 1`` or a value that is not finite).  ``valid`` is 0 where a factor of the row is not finite or its mask
+    bit is set, and that row is NaN in every column.  The device sums the terms in another order (``include/okx.h``): it agrees within
+    ``(T + 4) u (|shift| + sum |psi_t c_t|) + 2 u |value|`` each side, not bit for bit.
+    """
+    n_table = 0
+    if values is not None:
+        v, ok = _accepted(values, status)
+        n_table = v.shape[1] * v.shape[2]
+    c, shift, e = check_predict_arguments(basis, coefficients, shift, entries, n_table)
+    phi, valid = basis_host(factors, basis)
+    g = phi.shape[0]
+    if mask is not None:
+        valid = valid & ((np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0).astype(np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = phi @ c
+        if shift is not None:
+            out = shift[None, :] + out
+        if values is not None:
+            if v.shape[0] != g:
+                raise ValueError(f"values must be [G, S, K] with G = {g}, one geometry per factor row")
+            at = e.astype(np.int64)
+            out = np.where(ok.reshape(g, n_table)[:, at], v.reshape(g, n_table)[:, at] - out, np.nan)
+    out[valid == 0] = np.nan
+    return out, valid.astype(np.uint8)
+
+
+@dataclass
+class SurfaceValidation:
+    """
+    The leave-one-out check of a fitted surface (``surface_validate_host``, ``DeviceProgram.validate_surface``) over the ``count`` used
+    geometries, per entry ``[N]``: ``loo_rms`` = sqrt(mean e_loo^2), ``q2`` = 1 - sum e_loo^2 / total_ss (NaN where the entry does not vary; the
+    out-of-sample counterpart of ``r2``, never above it), ``loo_max`` = max |e_loo| and ``loo_max_geometry`` where it is; per fit
+    ``max_leverage`` and ``mean_leverage`` (T / count for a fit over exactly these geometries).  ``e_loo = e / (1 - h)``: the error of the fit
+    WITHOUT geometry g AT geometry g, from the residual ``e`` and the leverage ``h`` of the fit with it - no refit.
+    """
+
+    loo_rms: np.ndarray
+    q2: np.ndarray
+    loo_max: np.ndarray
+    loo_max_geometry: np.ndarray
+    max_leverage: float
+    mean_leverage: float
+    count: int
+
+
+def surface_used_host(surface: "EnsembleSurface", factors, values, status=None, mask=None) -> np.ndarray:
+    """``[G]`` bool: the complete cases of ``surface_host`` for the entries of ``surface``."""
+    v, ok = _accepted(values, status)
+    g = v.shape[0]
+    used = ok.reshape(g, -1)[:, np.asarray(surface.entries, dtype=np.int64)].all(axis=1)
+    used &= np.isfinite(np.asarray(factors, dtype=np.float64)).all(axis=1)
+    if mask is not None:
+        used &= (np.asarray(mask).reshape(g).astype(np.uint8) & 1) == 0
+    return used
+
+
+def validation_from_terms(e, h, used, total_ss) -> SurfaceValidation:
+    """``SurfaceValidation`` from the residuals ``e [G, N]``, the leverages ``h [G]`` and ``used [G]`` (NumPy); rows that are not used do not count."""
+    used = np.asarray(used).reshape(-1) != 0
+    count = int(used.sum())
+    n = e.shape[1]
+    if count == 0:
+        nan = np.full(n, np.nan)
+        return SurfaceValidation(nan, nan.copy(), nan.copy(), np.full(n, -1, dtype=np.int64), float("nan"), float("nan"), 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        loo = np.where(used[:, None], e / (1.0 - h)[:, None], 0.0)
+        ss = (loo * loo).sum(axis=0)
+        q2 = np.where(np.asarray(total_ss) > 0.0, 1.0 - ss / np.asarray(total_ss), np.nan)
+    at = np.abs(loo).argmax(axis=0)
+    return SurfaceValidation(np.sqrt(ss / count), q2, np.abs(loo)[at, np.arange(n)], at.astype(np.int64), float(h[used].max()), float(h[used].mean()), count)
+
+
+def surface_loo_host(surface: "EnsembleSurface", factors, values, status=None, mask=None, used=None) -> tuple:
+    """``(e [G, N], h [G], used [G] bool)`` of ``surface_validate_host``: the residuals ``predict_host(RESIDUAL)``, the leverages
+    ``|phi_g whitener|^2`` and the used geometries; ``e_loo = e / (1 - h)`` on the used rows."""
+    if surface.whitener is None or surface.total_ss is None:
+        raise ValueError("the surface carries no whitener (SurfaceAccumulator.finalize fills it)")
+    if used is None:
+        used = surface_used_host(surface, factors, values, status, mask)
+    used = np.asarray(used).reshape(-1) != 0
+    e, _ = predict_host(factors, surface.basis, surface.coefficients, surface.shift, mask, values, status, surface.entries)
+    z, _ = predict_host(factors, surface.basis, surface.whitener)
+    with np.errstate(invalid="ignore"):
+        h = (z * z).sum(axis=1)
+    return e, h, used
+
+
+def surface_validate_host(surface: "EnsembleSurface", factors, values, status=None, mask=None, used=None) -> SurfaceValidation:
+    """
+    The leave-one-out error of ``surface`` (a finalized fit with its ``whitener`` and ``total_ss``) over the geometries it was fitted on:
+    ``factors [G, P]``, ``values [G, S, K]``, ``status`` and ``mask`` as ``surface_host`` took them; ``used [G]`` the used bytes of the fit
+    (None: the complete cases are found again).  ``e = predict_host(RESIDUAL)``, ``h = |phi_g whitener|^2``, ``e_loo = e / (1 - h)``.
+    """
+    e, h, used = surface_loo_host(surface, factors, values, status, mask, used)
+    return validation_from_terms(e, h, used, surface.total_ss)
